@@ -1,23 +1,27 @@
 #!/usr/bin/env python
 """bench.py — BASELINE.json metric: training slices/sec (256x256x3, B=16) of PnP-AdaNet's segmenter+GAN step on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...)
 
 Headline workload (default, BASELINE.json configs[3]): the JOINT step of `train_gan.py --phase train-gan` — one discriminator
 update on B MR + B CT slices (both critics, RMSProp, weight clip; adversarial.py:839-862) followed by one generator update on the
 B CT slices (adversarial.py:866-882) — B=16 slices of each domain per GPU, fp32, dropout keep 0.75, synthetic N(0,1) slices already
 resident in HBM; B slices are counted per step.  Weak scaling: every rank processes its own 16+16 slices, gradients are
-all-reduced (RCCL).  Rank 0 prints, as the LAST line of stdout, ONE compact JSON record (< 2 KB: the driver parses the tail of
-stdout; round 3's 20 KB line arrived unparsed) carrying
-  * `roofline`          the kernel symbol with the largest share of the timed region's convolution time, timed live with HIP
-                        events recorded by libpnp_hip.so around each of its launches (pnp_prof_*), against the fp32-MFMA peak;
+all-reduced (RCCL).  A plain run sets up, warms up, times the K steps, writes the last timed step's outputs (--dump-outputs DIR:
+its losses and the trainable variables it updated, as .npy) and prints, on rank 0, as the LAST line of stdout, ONE compact JSON
+record (< 2 KB: the driver parses the tail of stdout; round 3's 20 KB line arrived unparsed).  `--full` measures, after that, what
+the headline does not need and adds it to the record:
+  * `roofline`          the kernel symbol with the largest share of the step's convolution time, timed live with HIP events recorded
+                        by libpnp_hip.so around each of its launches (pnp_prof_*) in probed steps of their own, against the MFMA peak;
   * `roofline_all_mfma_convs`  the aggregate over every MFMA convolution symbol of the step;
   * `segmenter_step`    BASELINE configs[1] (source segmenter fwd + bwd + Adam, source_segmenter.py:484-489) timed the same way;
+  * `fp32_mfma_step`, `bf16_step`  the headline step on the fp32 matrix pipe / in configs[4]'s arithmetic;
+  * `config.comm`       (N > 1) what the all-reduce moved and how much of it one more step waited for;
   * `cpu_baseline`      the CPU oracle's joint step (oracle/nets_adv.py, torch-CPU fp32) on this host's cores AT THE GPU LINE'S BATCH
                         (B = 16: 1 warm-up + 2 timed steps), with the B = 2 figure as a second field.
 The per-symbol table (`roofline_kernels`: forward, data gradient, filter gradient of every convolution symbol) goes to a side file,
-`bench_kernels_<workload>_<dtype>.json` under gpurun_out/ (on a GPU box) or profiles/, and its path is named in the record.
+`bench_kernels_<workload>_<dtype>.json` (side_file_path), and its path is named in the record.
 `--workload segmenter` makes configs[1] the headline line instead (same contract); `--dtype bf16` runs configs[4]'s arithmetic (a
 separate line, never the headline).  The joint workload starts from BN moving statistics calibrated on the synthetic batches (40
 untimed training-mode forwards) — the phase itself starts from a trained baseline checkpoint; with un-calibrated statistics the
@@ -244,14 +248,11 @@ def side_file_path(workload, dtype, world):
     return os.path.join(d, "bench_kernels_%s_%s%s.json" % (workload, dtype, "" if world == 1 else "_n%d" % world))
 
 
-PROBE_STEPS = 2      # timed steps whose convolution launches carry HIP events (see timed_loop)
+PROBE_STEPS = 2      # --full: steps whose convolution launches carry HIP events (see probed_steps)
 
 
-def timed_loop(step_fn, warmup, steps, world, dev, prof=None):
-    """W untimed + K timed steps bracketed by barrier + synchronize; returns (seconds = max over ranks, last loss).
-    prof: the per-kernel HIP events are recorded during the FIRST PROBE_STEPS steps of the timed region only — an event pair around
-    each of the ~560 convolution launches of a joint step costs ~9 ms per step (measured: 117.3 vs 108.4 ms), which would otherwise
-    be charged to `value`; with 2 probed steps out of K the perturbation of the reported time is below 1 % at the driver's K = 20."""
+def timed_loop(step_fn, warmup, steps, world, dev):
+    """W untimed + K timed steps bracketed by barrier + synchronize; returns (seconds = max over ranks, last loss)."""
     def barrier():
         if world > 1:
             torch.distributed.barrier()
@@ -261,23 +262,50 @@ def timed_loop(step_fn, warmup, steps, world, dev, prof=None):
         step_fn(k)
         k += 1
     barrier()
-    if prof is not None:
-        prof(True)
     t0 = time.perf_counter()
     for i in range(steps):
-        if prof is not None and i == PROBE_STEPS:
-            prof(False)
         loss = step_fn(k)
         k += 1
     barrier()
     el = time.perf_counter() - t0
-    if prof is not None:
-        prof(False)
     if world > 1:
         el = importlib.import_module(PKG + ".parallel").all_max_scalar(el, dev)
     lossv = float(loss)
     assert np.isfinite(lossv), "training diverged: loss=%r" % lossv
     return el, lossv
+
+
+def probed_steps(step_fn, first, prof):
+    """--full: PROBE_STEPS more steps (indices first, first + 1, ...) with HIP events around every convolution launch, after the timed
+    region — an event pair around each of the ~560 convolution launches of a joint step costs ~9 ms per step (measured: 117.3 vs
+    108.4 ms), which would otherwise be charged to `value`.  Returns the per-symbol rows of pnp_prof_summary."""
+    torch.cuda.synchronize()
+    prof(True)
+    try:
+        for i in range(PROBE_STEPS):
+            step_fn(first + i)
+        torch.cuda.synchronize()
+    finally:
+        prof(False)
+    return importlib.import_module(PKG + "._lib").prof_summary()
+
+
+DUMP_MAX_VALUES = 1 << 23     # --dump-outputs: trainable values written at most (32 MB of float32; the joint step trains 28 M)
+
+
+def dump_outputs(out_dir, losses, store):
+    """--dump-outputs DIR: what a caller of the timed step holds after its last run — the losses it returned (<name>.npy, float64) and
+    the trainable variables it updated (trainable_variables.npy, float32, flattened in the store's order; a fixed, seeded sample of
+    DUMP_MAX_VALUES of them, in that order, when there are more)"""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in losses.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(float(v), np.float64))
+    with torch.no_grad():
+        flat = torch.cat([v.tensor.detach().reshape(-1) for v in store.trainable()])
+        if flat.numel() > DUMP_MAX_VALUES:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_VALUES, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(out_dir, "trainable_variables.npy"), flat.float().cpu().numpy())
 
 
 def roofline_records(rows, peak):
@@ -318,14 +346,18 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=16, help="slices per GPU (of each domain for the joint step)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs (losses, updated trainable variables) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the roofline objects, the sub-runs (secondary workload, fp32 pipe, bf16), "
+                         "the all-reduce record (N > 1) and the cpu_baseline, and write the side file")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline")
     ap.add_argument("--cpu-batch", type=int, default=16, help="slices per domain of the cpu_baseline sample (default: the GPU line's B = 16)")
     ap.add_argument("--cpu-steps", type=int, default=2, help="timed steps of the cpu_baseline sample (after --cpu-warmup)")
     ap.add_argument("--cpu-warmup", type=int, default=1)
     ap.add_argument("--cpu-small-batch", type=int, default=2, help="second, small cpu_baseline sample (0: none)")
-    ap.add_argument("--no-probe", action="store_true", help="no per-kernel HIP events (no roofline objects)")
+    ap.add_argument("--no-probe", action="store_true", help="--full without per-kernel HIP events (no roofline objects)")
     ap.add_argument("--no-overlap", action="store_true")
-    ap.add_argument("--no-sub", action="store_true", help="skip the secondary workload's sub-record")
+    ap.add_argument("--no-sub", action="store_true", help="--full without the sub-runs' records")
     ap.add_argument("--dtype", choices=["f32", "bf16"], default="f32",
                     help="bf16: BASELINE configs[4] arithmetic (bf16 MFMA conv operands, fp32 accumulation / master weights / BN); a separate "
                          "line, never the headline")
@@ -407,7 +439,14 @@ def main():
         y = torch.from_numpy(one_hot(blob_labels(rng, B))).to(dev)
         if use_graph:
             try_capture(lambda: tr.capture_step(x, y, 0.75))
-        return eager_while_probing(tr, lambda i: tr.train_step(x, y, 0.75, i * world + rank))
+        last = {}
+
+        def step(i):
+            last["loss"] = tr.train_step(x, y, 0.75, i * world + rank)
+            return last["loss"]
+        fn = eager_while_probing(tr, step)
+        fn.outputs = lambda: (last, net.store)
+        return fn
 
     def make_joint():
         adv = importlib.import_module(PKG + ".adversarial")
@@ -431,11 +470,14 @@ def main():
         if use_graph:
             try_capture(lambda: tr.capture_steps(x, ct, 0.75))
 
+        last = {}
+
         def step(i):
-            tr.dis_step(x, ct, 0.75, 2 * (i * world + rank) + 1)
+            last["dis_loss"] = tr.dis_step(x, ct, 0.75, 2 * (i * world + rank) + 1)
             if reducer is not None:
                 step.comm_dis = (reducer.bytes_step, list(reducer.launch_log), reducer.exposed_time_ms() if reducer.measure_exposed else None)
-            return tr.gen_step(ct, 0.75, 2 * (i * world + rank) + 2)
+            last["gen_loss"] = tr.gen_step(ct, 0.75, 2 * (i * world + rank) + 2)
+            return last["gen_loss"]
         inner = eager_while_probing(tr, step)
 
         def outer(i):
@@ -443,6 +485,7 @@ def main():
             if hasattr(step, "comm_dis"):
                 outer.comm_dis = step.comm_dis
             return r
+        outer.outputs = lambda: (last, net.store)
         return outer
 
     names = {
@@ -466,15 +509,22 @@ def main():
             L.prof_enable((L.PROF_CONV_FWD | L.PROF_CONV_DGRAD | L.PROF_CONV_WGRAD) if on else 0)
 
     step_fn = makers[args.workload]()
-    el, lossv = timed_loop(step_fn, args.warmup, args.steps, world, dev, prof)
-    rows = [] if args.no_probe else L.prof_summary()
+    el, lossv = timed_loop(step_fn, args.warmup, args.steps, world, dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *step_fn.outputs())
+    # everything from here to the record is --full only: untimed steps of the headline's model, then runs of their own
+    k_next = args.warmup + args.steps
+    rows = []
+    if args.full and not args.no_probe:
+        rows = probed_steps(step_fn, k_next, prof)
+        k_next += PROBE_STEPS
     comm = None
-    if world > 1:
+    if args.full and world > 1:
         # what the all-reduce moved and how much of it the step had to wait for: ONE extra, untimed step with an event pair around the
         # compute stream's wait on the side stream (GradReducer.measure_exposed)
         red = reducers[args.workload]
         red.measure_exposed = True
-        step_fn(args.warmup + args.steps)
+        step_fn(k_next)
         torch.cuda.synchronize()
         nc = par.native_comm()
         comm = {"transport": par.transport(), "rccl_version": nc.version if nc is not None else None, "overlap": bool(red.overlap),
@@ -492,9 +542,9 @@ def main():
         red.measure_exposed = False
     del step_fn
     sub = None
-    if not args.no_sub:
+    if args.full and not args.no_sub:
         sub_steps, sub_warm = max(5, min(args.steps, 10)), 2
-        el2, loss2 = timed_loop(makers[other](), sub_warm, sub_steps, world, dev, None)
+        el2, loss2 = timed_loop(makers[other](), sub_warm, sub_steps, world, dev)
         sub = {"workload": names[other][1], "value": world * B * sub_steps / el2, "unit": "slices/s", "ms_per_step": 1e3 * el2 / sub_steps,
                "steps": sub_steps, "warmup": sub_warm, "final_loss": loss2}
 
@@ -503,13 +553,13 @@ def main():
     # same step with every GEMM on the native fp32 MFMA pipe (PNP_WINOGRAD_X3=0 PNP_X3_DIRECT=0, round 5's arithmetic) stays selectable and is reported
     # beside the headline: 2 warm-up + 8 timed steps
     sub_fp32 = None
-    if not args.no_sub and args.dtype == "f32" and world == 1 and K.wino_x3(-1) != 0:
+    if args.full and not args.no_sub and args.dtype == "f32" and world == 1 and K.wino_x3(-1) != 0:
         prev_x3 = K.wino_x3(0)
         prev_x3d = K.x3_direct(0)        # (and the narrow layers back on the fp32-pipe routes: nothing of this sub-run touches the bf16 pipe)
         try:
             K.weights_changed()
             nf = 8
-            el4, loss4 = timed_loop(makers[args.workload](), 2, nf, world, dev, None)
+            el4, loss4 = timed_loop(makers[args.workload](), 2, nf, world, dev)
             sub_fp32 = {"workload": "the headline step with every convolution on the fp32 matrix pipe (PNP_WINOGRAD_X3=0 PNP_X3_DIRECT=0)", "value": world * B * nf / el4,
                         "unit": "slices/s", "ms_per_step": 1e3 * el4 / nf, "steps": nf, "warmup": 2, "final_loss": loss4}
         finally:
@@ -520,11 +570,11 @@ def main():
     # BASELINE configs[4] arithmetic (bf16 MFMA operands, fp32 accumulation / master weights / BN) on the headline workload, as a
     # sub-record of the driver's own line: same step definition, 2 warm-up + 10 timed steps
     sub_bf16 = None
-    if not args.no_sub and args.dtype == "f32" and args.workload == "joint" and world == 1:      # (N = 1 only: the scaling runs stay what they were)
+    if args.full and not args.no_sub and args.dtype == "f32" and args.workload == "joint" and world == 1:      # (N = 1 only: the scaling runs stay what they were)
         Fn.set_conv_dtype("bf16")
         try:
             nb = 10
-            el3, loss3 = timed_loop(make_joint(), 2, nb, world, dev, None)
+            el3, loss3 = timed_loop(make_joint(), 2, nb, world, dev)
             sub_bf16 = {"workload": "BASELINE configs[4] arithmetic on the joint step: bf16 MFMA conv operands (resident bf16 activations / filter shadows), "
                                     "fp32 accumulation, master weights and BN; B=%d/GPU" % B,
                         "value": world * B * nb / el3, "unit": "slices/s", "ms_per_step": 1e3 * el3 / nb, "steps": nb, "warmup": 2, "final_loss": loss3}
@@ -546,9 +596,9 @@ def main():
             if recs:
                 top = dict(recs[0])
                 res["roofline"] = top
-                res["roofline_note"] = ("roofline = the kernel symbol with the largest share of the timed region's convolution time; `achieved` = sum of "
+                res["roofline_note"] = ("roofline = the kernel symbol with the largest share of the step's convolution time; `achieved` = sum of "
                                         "algorithmic FLOP (2*N*OH*OW*R*S*C*K) / sum of launch durations, HIP events recorded by libpnp_hip.so on the "
-                                        "launch stream around every launch of the symbol in the first %d steps of the timed region; `traffic` = HBM-side "
+                                        "launch stream around every launch of the symbol in %d probed steps after the timed region; `traffic` = HBM-side "
                                         "bytes per launch from the committed rocprofv3 PMC passes (2*FETCH_SIZE + WRITE_SIZE, separate passes; "
                                         "`traffic_source` names the file), null if absent.  Symbols of the Winograd route (csrc/conv_wino.hip): `wino_gemm_kernel` / "
                                         "`wino_wgrad_gemm_kernel` are priced at the flops they EXECUTE (`flops_counted`: 2*P^2*T*C*K, T = tiles of MxM outputs, "
@@ -562,12 +612,12 @@ def main():
                 # `achieved`: flops the kernels EXECUTE / all convolution kernel time (Winograd transforms included: time, no flops);
                 # `achieved_algorithmic`: SURVEY.md §8(d) convolution flops of the step / the same time — comparable across rounds whatever
                 # the route (it exceeds the fp32 MFMA peak when the Winograd routes skip enough multiplications)
-                alg = ALG_GFLOP_PER_SLICE[args.workload] * B * min(PROBE_STEPS, args.steps) * 1e9
+                alg = ALG_GFLOP_PER_SLICE[args.workload] * B * PROBE_STEPS * 1e9
                 res["roofline_all_mfma_convs"] = {"achieved": fl / (ms * 1e-3) / 1e12, "peak": peak, "frac": fl / (ms * 1e-3) / 1e12 / peak,
                                                   "achieved_algorithmic": alg / (ms * 1e-3) / 1e12,
-                                                  "unit": "TFLOP/s", "ms_per_step": ms / min(PROBE_STEPS, args.steps),
-                                                  "launches_per_step": sum(r["launches"] for r in rows) / min(PROBE_STEPS, args.steps),
-                                                  "probed_steps": min(PROBE_STEPS, args.steps)}
+                                                  "unit": "TFLOP/s", "ms_per_step": ms / PROBE_STEPS,
+                                                  "launches_per_step": sum(r["launches"] for r in rows) / PROBE_STEPS,
+                                                  "probed_steps": PROBE_STEPS}
         tfl = ALG_GFLOP_PER_SLICE[args.workload] * B * 1e-3                      # TFLOP per step per GPU
         res["step_algorithmic"] = {"tflop_per_step": tfl, "achieved": tfl / (el / args.steps), "frac_of_mfma_peak": tfl / (el / args.steps) / peak}
         if sub is not None:
@@ -576,24 +626,25 @@ def main():
             res["fp32_mfma_step"] = sub_fp32
         if sub_bf16 is not None:
             res["bf16_step"] = sub_bf16
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(args.workload, args.cpu_batch, args.cpu_steps, args.cpu_warmup)
             if args.cpu_small_batch and args.cpu_small_batch != args.cpu_batch:
                 small = cpu_baseline(args.workload, args.cpu_small_batch, 2, 1)
                 cb["value_B%d" % args.cpu_small_batch] = small["value"]
                 cb["sample_B%d" % args.cpu_small_batch] = small["sample_detail"]
             res["cpu_baseline"] = cb
-        # what the host side of the library holds on to between steps (workspaces per slot and stream, transformed filters, bf16 shadows) and
-        # what torch's allocator has reserved at the end of the run: side file only
-        res["device_memory"] = dict(K.memory_report(), torch_reserved=int(torch.cuda.memory_reserved(dev)), torch_peak_allocated=int(torch.cuda.max_memory_allocated(dev)))
-        # the per-symbol table and the full-precision record: side file (and stderr); the LAST stdout line is the compact record
-        try:
-            path = side_file_path(args.workload, args.dtype, world)
-            with open(path, "w") as f:
-                json.dump(res, f, indent=1)
-            res["kernels_file"] = os.path.relpath(path, ROOT)
-        except OSError:
-            pass
+        if args.full:
+            # what the host side of the library holds on to between steps (workspaces per slot and stream, transformed filters, bf16 shadows) and
+            # what torch's allocator has reserved at the end of the run: side file only
+            res["device_memory"] = dict(K.memory_report(), torch_reserved=int(torch.cuda.memory_reserved(dev)), torch_peak_allocated=int(torch.cuda.max_memory_allocated(dev)))
+            # the per-symbol table and the full-precision record: side file (and stderr); the LAST stdout line is the compact record
+            try:
+                path = side_file_path(args.workload, args.dtype, world)
+                with open(path, "w") as f:
+                    json.dump(res, f, indent=1)
+                res["kernels_file"] = os.path.relpath(path, ROOT)
+            except OSError:
+                pass
         sys.stderr.write(json.dumps(res) + "\n")
         sys.stderr.flush()
         line = json.dumps(compact_record(res))

@@ -60,19 +60,26 @@ def test_native_rccl_two_ranks(dev):
     assert p.stdout.count(" ok ") == 2
 
 
-def test_bench_two_rank_launch_line(dev):
+def test_bench_two_rank_launch_line(dev, tmp_path):
+    """the plain line: the timed steps, rank 0's --dump-outputs, the record — none of what --full adds"""
+    import numpy as np
+    out = str(tmp_path / "outputs")
     p = _run([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "4", "--no-cpu-baseline", "--workload", "segmenter",
-              "--no-sub"],
+              "--no-sub", "--dump-outputs", out],
              {"PNP_DIST_BACKEND": "gloo", "PNP_SAME_DEVICE": "1"})
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
     r = json.loads(line)
     assert r["n_gpus"] == 2 and r["config"]["global_batch"] == 8 and r["scaling"] == "weak" and r["value"] > 0
+    assert r["steps"] == 2 and r["ms_per_step"] > 0 and "roofline" not in r and "kernels_file" not in r and r["config"]["comm"] is None
+    assert sorted(os.listdir(out)) == ["loss.npy", "trainable_variables.npy"]
+    loss, v = np.load(os.path.join(out, "loss.npy")), np.load(os.path.join(out, "trainable_variables.npy"))
+    assert loss.dtype == np.float64 and np.isclose(float(loss), r["config"]["final_loss"], rtol=1e-3) and v.dtype == np.float32 and np.isfinite(v).all()
 
 
 def test_bench_two_rank_gan_workload(dev):
     """config 4 launch line: joint dis + gen step, 2 ranks, gradient buckets of the frozen groups skipped"""
-    p = _run([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "2", "--workload", "gan"],
+    p = _run([os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--batch", "2", "--workload", "gan", "--full"],
              {"PNP_DIST_BACKEND": "gloo", "PNP_SAME_DEVICE": "1"})
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     last = p.stdout.rstrip("\n").splitlines()[-1]              # the driver parses the LAST stdout line (out of a ~2000-character tail)

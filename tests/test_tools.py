@@ -166,3 +166,26 @@ def test_bench_prices_the_winograd_transforms_against_the_hbm_roof():
                                 "config": {"workload": "w"}, "roofline": dict(recs[0])})
     back = json.loads(json.dumps(rec))
     assert back["roofline"]["bound"] == "hbm" and back["roofline"]["unit"] == "GB/s"
+
+
+def test_bench_dump_outputs_float_files_within_budget(tmp_path, monkeypatch):
+    """--dump-outputs: losses as float64 scalars, the trainable variables as ONE float32 vector in the store's order — a fixed, seeded
+    sample of DUMP_MAX_VALUES of them when there are more (the same one from run to run), never more than 64 MB in all"""
+    import types
+
+    import numpy as np
+    import torch
+    import bench
+    assert bench.DUMP_MAX_VALUES * 4 <= 64 << 20
+    a, b = torch.arange(6, dtype=torch.float32).reshape(2, 3), torch.arange(6, 10, dtype=torch.float32)
+    store = types.SimpleNamespace(trainable=lambda: [types.SimpleNamespace(tensor=a), types.SimpleNamespace(tensor=b)])
+    bench.dump_outputs(str(tmp_path / "all"), {"dis_loss": torch.tensor(0.5), "gen_loss": 1.25}, store)
+    d = tmp_path / "all"
+    assert sorted(os.listdir(d)) == ["dis_loss.npy", "gen_loss.npy", "trainable_variables.npy"]
+    assert np.load(d / "dis_loss.npy").dtype == np.float64 and float(np.load(d / "gen_loss.npy")) == 1.25
+    assert np.array_equal(np.load(d / "trainable_variables.npy"), np.arange(10, dtype=np.float32))
+    monkeypatch.setattr(bench, "DUMP_MAX_VALUES", 4)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), {}, store)
+    s1, s2 = (np.load(tmp_path / r / "trainable_variables.npy") for r in ("s1", "s2"))
+    assert s1.dtype == np.float32 and len(s1) == 4 and np.array_equal(s1, s2) and np.all(np.diff(s1) > 0)

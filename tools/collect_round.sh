@@ -8,10 +8,11 @@ R=${R:-r6z}; O=gpurun_out/$R; mkdir -p $O
 PART=${PART:-AB}
 if [[ $PART == *A* ]]; then
 timeout 300 python __graft_entry__.py --smoke > $O/smoke.log 2>&1; tail -3 $O/smoke.log
-timeout 900 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; tail -c 600 $O/bench_n1.json; cp gpurun_out/bench_kernels_joint_f32.json $O/ 2>/dev/null
-timeout 300 python bench.py --workload segmenter --no-sub --no-cpu-baseline > $O/bench_segmenter_n1.json 2>/dev/null; cp gpurun_out/bench_kernels_segmenter_f32.json $O/ 2>/dev/null
-timeout 300 python bench.py --dtype bf16 --no-cpu-baseline > $O/bench_bf16_n1.json 2>/dev/null
-timeout 300 python bench.py --dtype bf16 --batch 32 --no-cpu-baseline --no-sub > $O/bench_bf16_B32_n1.json 2>/dev/null
+# (bench.py --full writes its per-symbol side file next to $O, into its parent directory: bench.side_file_path)
+timeout 900 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; tail -c 600 $O/bench_n1.json; cp $(dirname $O)/bench_kernels_joint_f32.json $O/ 2>/dev/null
+timeout 300 python bench.py --full --workload segmenter --no-sub --no-cpu-baseline > $O/bench_segmenter_n1.json 2>/dev/null; cp $(dirname $O)/bench_kernels_segmenter_f32.json $O/ 2>/dev/null
+timeout 300 python bench.py --full --dtype bf16 --no-cpu-baseline > $O/bench_bf16_n1.json 2>/dev/null
+timeout 300 python bench.py --full --dtype bf16 --batch 32 --no-cpu-baseline --no-sub > $O/bench_bf16_B32_n1.json 2>/dev/null
 # recorded steps at B = 16 (round 6: the bf16 one used to fault on replay) — slower than eager there, which is why --graph auto records at B <= 4 only
 for dt in bf16 f32; do timeout 300 python bench.py --dtype $dt --graph on --no-cpu-baseline --no-sub --no-probe 2>/dev/null | tail -1; done > $O/bench_graph_on_B16_n1.json
 B="python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-sub --graph off"
@@ -42,7 +43,7 @@ PMC_NOTE="collected with --kernel-include-regex '$RX' (the joint step segfaults 
 rm -rf $O/pmc_fetch $O/pmc_write $O/pmc_sq
 for sc in weak strong; do
   bt=2; [ $sc = strong ] && bt=16
-  PNP_DIST_BACKEND=gloo PNP_SAME_DEVICE=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 8 --batch $bt --steps 2 --warmup 1 --no-cpu-baseline --scaling $sc > $O/dp8_same_device_$sc.json 2> $O/dp8_same_device_$sc.err; echo "dp8 $sc rc=$?"; tail -c 300 $O/dp8_same_device_$sc.json
+  PNP_DIST_BACKEND=gloo PNP_SAME_DEVICE=1 timeout 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 8 --batch $bt --steps 2 --warmup 1 --no-cpu-baseline --scaling $sc > $O/dp8_same_device_$sc.json 2> $O/dp8_same_device_$sc.err; echo "dp8 $sc rc=$?"; tail -c 300 $O/dp8_same_device_$sc.json
 done
 # per-GPU batch sweep (strong-scaling operating points): eager / captured wall time against the sum of kernel durations, launches per step
 R=$R bash tools/batch_sweep.sh f32 > $O/batch_sweep.log 2>&1; tail -8 $O/batch_sweep.log
@@ -53,6 +54,6 @@ grep -E "passed|failed|FAILED" $O/pytest_gpu.log | tail -6
 fi
 if [[ $PART == *C* ]]; then
 # SURVEY 8(d)'s cpu_baseline sample in full: 2 warm-ups + the median of 5 timed oracle steps at B = 16 (about 9 minutes of host time)
-timeout 1500 python bench.py --cpu-steps 5 --cpu-warmup 2 --cpu-small-batch 0 --no-sub > $O/bench_cpu_median5_n1.json 2> $O/bench_cpu_median5_n1.err; tail -c 500 $O/bench_cpu_median5_n1.json
+timeout 1500 python bench.py --full --cpu-steps 5 --cpu-warmup 2 --cpu-small-batch 0 --no-sub > $O/bench_cpu_median5_n1.json 2> $O/bench_cpu_median5_n1.err; tail -c 500 $O/bench_cpu_median5_n1.json
 fi
 du -sh $O

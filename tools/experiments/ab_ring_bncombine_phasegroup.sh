@@ -6,7 +6,7 @@ for d in 1 2 3; do PNP_WGRAD_DEPTH=$d python tools/bench_conv.py 2>/dev/null | s
 paste -d'\n' $O/conv_depth1.txt $O/conv_depth2.txt $O/conv_depth3.txt | cut -c1-40,92-112
 run() { # label, env...
   L=$1; shift
-  env "$@" python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$L', round(r['value'],2), round(r['ms_per_step'],2), round(r['segmenter_step']['value'],1))" | tee -a $O/ab.txt
 }
 run base PNP_WGRAD_DEPTH=1 PNP_BN_FINAL_1STAGE=1 PNP_CONV_NOPHASEGROUP=1

@@ -10,8 +10,8 @@ done; done
 sort -k2,3 -s $O/ab.txt
 for v in v0 "" v3 v4 "" v3; do
 L=$P/libpnp_hip${v:+_$v}.so
-PNP_LIB=$L python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+PNP_LIB=$L python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('${v:-v2}', r['value'], r['ms_per_step'], r['segmenter_step']['value'])"
 done
-PNP_FUSE_BN_STATS=0 python bench.py --no-cpu-baseline 2>/dev/null | python -c "
+PNP_FUSE_BN_STATS=0 python bench.py --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys; r=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('v2 no epilogue stats', r['value'], r['ms_per_step'], r['segmenter_step']['value'])"
