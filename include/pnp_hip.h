@@ -300,6 +300,20 @@ int pnp_label_decomp(const float* label, float* onehot, int64_t P, int32_t ncls,
  * tf.confusion_matrix(compact_y, compact_pred, num_classes) (source_segmenter.py:85; rows = ground truth, columns = prediction) in one
  * pass.  compact_y [P] (nullable), pred [P] / cm [ncls*ncls] int64 (both or neither). */
 int pnp_confusion_matrix(const float* y, const int64_t* pred, int64_t* compact_y, int64_t* cm, int64_t P, int32_t ncls, void* stream);
+/* Surface distances of label volumes for volume evaluation (the reference's README points to SIFA's evaluate.py, which scores with
+ * medpy.metric.binary asd / assd / hd / hd95; connectivity 1).  Volumes [X, Y, Z] int32, z fastest, each extent in [1, 1024];
+ * (sx, sy, sz) = spacing per array axis, finite and > 0.  border(A) = voxels of A with a face neighbour outside A (outside the volume
+ * counts as outside A); a label outside [0, ncls) is in no class.
+ * pnp_edt3d_sq: exact squared Euclidean distance (physical units) to the nearest voxel with mask != 0, +inf everywhere if there is
+ * none; bit-exact for unit spacing; no workspace.
+ * pnp_surface_distances: out [ncls, 7] double = n_border_pred, n_border_gt, sum pred->gt, sum gt->pred, max pred->gt, max gt->pred,
+ * hd95 (numpy.percentile 95, linear, of the pooled distances of both directions).  Row 0 (background) is NaN; a class whose border is
+ * empty on either side keeps its counts and has NaN distances.  2 <= ncls <= 32.  Run-to-run bitwise deterministic.
+ * workspace: pnp_surface_workspace_bytes (0 for unsupported arguments). */
+int pnp_edt3d_sq(const uint8_t* mask, float* dist_sq, int64_t X, int64_t Y, int64_t Z, float sx, float sy, float sz, void* stream);
+size_t pnp_surface_workspace_bytes(int64_t X, int64_t Y, int64_t Z, int32_t ncls);
+int pnp_surface_distances(const int32_t* pred, const int32_t* gt, int64_t X, int64_t Y, int64_t Z, int32_t ncls, float sx, float sy,
+                          float sz, double* out, void* workspace, size_t workspace_bytes, void* stream);
 /* Synchronised batch statistics (data-parallel replicas of equally many rows): moments[0..C) = mean, moments[C..2C) = var + mean^2 in
  * double; the caller sums `moments` over the replicas (pnp_comm_allreduce, PNP_DTYPE_F64) and converts back with the replica count. */
 int pnp_bn_moments(const float* mean, const float* var, double* moments, int32_t C, void* stream);

@@ -124,6 +124,10 @@ PROTOTYPES = {
     "pnp_fill": (c_int, [_F, c_size_t, c_float, c_void_p]),
     "pnp_label_decomp": (c_int, [_F, _F, c_int64, c_int32, c_void_p]),
     "pnp_confusion_matrix": (c_int, [_F, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "pnp_edt3d_sq": (c_int, [c_void_p, _F, c_int64, c_int64, c_int64, c_float, c_float, c_float, c_void_p]),
+    "pnp_surface_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
+    "pnp_surface_distances": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_float, c_float, c_float, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]),
     "pnp_bn_moments": (c_int, [_F, _F, c_void_p, c_int32, c_void_p]),
     "pnp_bn_from_moments": (c_int, [c_void_p, c_int32, _F, _F, c_int32, c_void_p]),
     "pnp_cast_bf16": (c_int, [_F, c_void_p, c_size_t, c_void_p]),

@@ -736,14 +736,22 @@ class Trainer(object):
         pred, cm = self.net.predict_ct(torch.from_numpy(vol).to(dev), y)
         return pred.cpu().numpy(), cm
 
-    def test_eval(self, sess=None, output_path=".", flip_correction=True):
-        """adversarial.py:993-1052: CT test volumes through adapt_* front + shared second half; writes cm.csv"""
+    def test_eval(self, sess=None, output_path=".", flip_correction=True, surface=False, spacing="unit"):
+        """adversarial.py:993-1052: CT test volumes through adapt_* front + shared second half; writes cm.csv
+
+        surface=True (opt-in; the return value and the shuffled frame order are the same — the scoring draws no random numbers): each
+        subject is also scored with surface distances (surface.py) on the reassembled prediction against the flipped ground truth with
+        labels >= num_cls set to 0; frames the shuffled loop never predicts stay background.  spacing: "unit" or "header" (the label
+        NIfTI's affine).  Results: self.surface_eval_list and <output_path>/surface.csv; a per-organ mean +- std is printed when verbose."""
         from . import volume_eval as ve
         os.makedirs(os.path.join(output_path, "dense_pred"), exist_ok=True)
         self.test_pair_list = list(zip(self.test_label_list, self.test_nii_list))
+        slog = ve.surface_log(surface, self.num_cls, contour_map, spacing)
         sample_eval_list, all_cm = ve.test_eval(self._predict_batch, self.test_label_list, self.test_nii_list, self.net.batch_size,
-                                                self.num_cls, flip_correction, shuffle=True)
+                                                self.num_cls, flip_correction, shuffle=True, surface_log=slog)
         np.savetxt(os.path.join(output_path, "cm.csv"), all_cm)
+        if slog is not None:
+            self.surface_eval_list = ve.finish_surface_log(slog, output_path, verbose)
         return self.sample_metric_stddev(sample_eval_list)
 
     def test_model(self, this_model, output_path):

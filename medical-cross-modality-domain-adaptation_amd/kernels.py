@@ -751,6 +751,55 @@ def confusion_matrix(y, pred=None, want_compact=True):
     return cy, cm
 
 
+def _spacing3(spacing):
+    s = (1.0, 1.0, 1.0) if spacing is None else tuple(float(v) for v in spacing)
+    if len(s) != 3:
+        raise ValueError("spacing: 3 values (one per array axis) expected, got %r" % (spacing,))
+    return s
+
+
+def _labels_i32(t, what):
+    if not t.is_cuda:
+        raise _lib.PnpError("%s: pnp kernels need CUDA/HIP tensors (got a CPU tensor) — there is no CPU fallback" % what)
+    if t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 3:
+        raise _lib.PnpError("%s: a contiguous int32 [X, Y, Z] CUDA tensor expected, got %s %s contiguous=%s" % (what, t.dtype, tuple(t.shape),
+                                                                                                              t.is_contiguous()))
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def edt_sq(mask_u8, spacing=None):
+    """exact squared Euclidean distance transform (physical units) of a uint8 [X, Y, Z] mask to its non-zero voxels (pnp_edt3d_sq);
+    +inf everywhere when the mask is empty"""
+    if not mask_u8.is_cuda:
+        raise _lib.PnpError("edt_sq: pnp kernels need CUDA/HIP tensors (got a CPU tensor) — there is no CPU fallback")
+    if mask_u8.dtype != torch.uint8 or not mask_u8.is_contiguous() or mask_u8.dim() != 3:
+        raise _lib.PnpError("edt_sq: a contiguous uint8 [X, Y, Z] CUDA tensor expected, got %s %s" % (mask_u8.dtype, tuple(mask_u8.shape)))
+    sx, sy, sz = _spacing3(spacing)
+    out = torch.empty(mask_u8.shape, dtype=torch.float32, device=mask_u8.device)
+    X, Y, Z = mask_u8.shape
+    check(_lib.load().pnp_edt3d_sq(ctypes.c_void_p(mask_u8.data_ptr()), _p(out), X, Y, Z, sx, sy, sz, _stream()), "pnp_edt3d_sq")
+    return out
+
+
+def surface_distances(pred_i32, gt_i32, ncls, spacing=None):
+    """per-class surface-distance rows of two int32 [X, Y, Z] label volumes (pnp_surface_distances) -> float64 [ncls, 7] device tensor:
+    n_border_pred, n_border_gt, sum pred->gt, sum gt->pred, max pred->gt, max gt->pred, hd95"""
+    pp, gp = _labels_i32(pred_i32, "surface_distances"), _labels_i32(gt_i32, "surface_distances")
+    if tuple(pred_i32.shape) != tuple(gt_i32.shape):
+        raise _lib.PnpError("surface_distances: prediction %s and ground truth %s differ in shape" % (tuple(pred_i32.shape), tuple(gt_i32.shape)))
+    sx, sy, sz = _spacing3(spacing)
+    X, Y, Z = pred_i32.shape
+    lib = _lib.load()
+    need = lib.pnp_surface_workspace_bytes(X, Y, Z, int(ncls))
+    if need == 0:
+        raise _lib.PnpError("surface_distances: unsupported volume %s / ncls %d (extents <= 1024, 2 <= ncls <= 32)" % ((X, Y, Z), ncls))
+    out = torch.empty((int(ncls), 7), dtype=torch.float64, device=pred_i32.device)
+    ws = workspace(need, pred_i32.device, slot="surface")
+    check(lib.pnp_surface_distances(pp, gp, X, Y, Z, int(ncls), sx, sy, sz, ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                    ws.numel(), _stream()), "pnp_surface_distances")
+    return out
+
+
 def bn_moments(mean, var):
     C = mean.numel()
     mom = torch.empty(2 * C, dtype=torch.float64, device=mean.device)

@@ -568,19 +568,28 @@ class Trainer(object):
         self.net.evaluate(x, y, keep_prob=1.0, main_bn=False, adapt_bn=False, want_confusion=True)
         return self.net.compact_pred.cpu().numpy(), self.net.confusion_matrix
 
-    def test_eval(self, sess=None, output_path=".", flip_correction=True, save_result=False):
-        """source_segmenter.py:572-632: inference on the .nii test volumes -> (per-class mean Dice, see volume_eval for the 2nd value)"""
+    def test_eval(self, sess=None, output_path=".", flip_correction=True, save_result=False, surface=False, spacing="unit"):
+        """source_segmenter.py:572-632: inference on the .nii test volumes -> (per-class mean Dice, see volume_eval for the 2nd value)
+
+        surface=True (opt-in; the return value is the same): each subject is also scored with surface distances (surface.py: ASD,
+        ASSD, HD, HD95) on the pair of volumes _save_nii_prediction writes — the reassembled prediction and the flipped ground truth with
+        labels >= num_cls set to 0.  Slices the loop never predicts (the first and last, and those past the last whole batch) stay
+        background in the prediction.  spacing: "unit" (voxel units) or "header" (surface.spacing_of the label NIfTI's affine).
+        Results: self.surface_eval_list and <output_path>/surface.csv; a per-organ mean +- std is printed when verbose."""
         from . import volume_eval as ve
         pred_folder = os.path.join(output_path, "test_pred")
         os.makedirs(pred_folder, exist_ok=True)
         self.test_pair_list = list(zip(self.test_label_list, self.test_nii_list))
+        slog = ve.surface_log(surface, self.num_cls, contour_map, spacing)
 
         def on_sample(raw_y, tmp_y, nii_fid):
             if save_result is True:
                 lib._save_nii_prediction(raw_y, tmp_y, nii_fid, pred_folder, out_bname="dense_pred_" + os.path.basename(nii_fid),
                                          num_cls=self.num_cls)
         sample_eval_list, _ = ve.test_eval(self._predict_batch, self.test_label_list, self.test_nii_list, self.net.batch_size, self.num_cls,
-                                           flip_correction, shuffle=False, on_sample=on_sample)
+                                           flip_correction, shuffle=False, on_sample=on_sample, surface_log=slog)
+        if slog is not None:
+            self.surface_eval_list = ve.finish_surface_log(slog, output_path, verbose)
         return self.sample_metric_stddev(sample_eval_list)
 
     def test_choose_model(self, this_model, output_path):

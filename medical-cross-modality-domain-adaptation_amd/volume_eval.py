@@ -49,8 +49,11 @@ def eval_volume(predict, raw, raw_y, batch_size, num_cls, shuffle=True, rng=None
     return tmp_y, cm
 
 
-def test_eval(predict, label_list, nii_list, batch_size, num_cls, flip_correction=True, shuffle=True, rng=None, on_sample=None):
-    """the per-sample loop shared by both trainers -> (sample_eval_list [(dice, jaccard)], summed confusion matrix)"""
+def test_eval(predict, label_list, nii_list, batch_size, num_cls, flip_correction=True, shuffle=True, rng=None, on_sample=None,
+              surface_log=None):
+    """the per-sample loop shared by both trainers -> (sample_eval_list [(dice, jaccard)], summed confusion matrix).
+    surface_log (surface.SurfaceLog, optional): each subject's prediction is scored against its ground truth with labels >= num_cls
+    set to 0 — the pair lib._save_nii_prediction writes."""
     all_cm = np.zeros([num_cls, num_cls])
     sample_eval_list = []
     for idx_file, (label_fid, nii_fid) in enumerate(zip(label_list, nii_list)):
@@ -67,7 +70,27 @@ def test_eval(predict, label_list, nii_list, batch_size, num_cls, flip_correctio
         sample_eval_list.append((_dice(sample_cm), _jaccard(sample_cm)))
         if on_sample is not None:
             on_sample(raw_y, tmp_y, nii_fid)
+        if surface_log is not None:
+            gth = np.array(raw_y)
+            gth[gth > num_cls - 1] = 0
+            surface_log.add(os.path.basename(nii_fid), tmp_y, gth, label_fid)
     return sample_eval_list, all_cm
+
+
+def surface_log(enabled, num_cls, contour_map, spacing):
+    """Trainer.test_eval(surface=...): a surface.SurfaceLog, or None when the scoring is off"""
+    if not enabled:
+        return None
+    from .surface import SurfaceLog
+    return SurfaceLog(num_cls, contour_map, spacing)
+
+
+def finish_surface_log(slog, output_path, verbose=True):
+    """writes <output_path>/surface.csv, prints the per-organ summary when verbose -> the per-subject metric dicts"""
+    slog.write_csv(os.path.join(output_path, "surface.csv"))
+    if verbose:
+        slog.print_summary()
+    return slog.entries
 
 
 def sample_metric_stddev(sample_eval_list, num_cls, contour_map, quiet=False):
