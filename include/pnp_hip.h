@@ -314,6 +314,26 @@ int pnp_edt3d_sq(const uint8_t* mask, float* dist_sq, int64_t X, int64_t Y, int6
 size_t pnp_surface_workspace_bytes(int64_t X, int64_t Y, int64_t Z, int32_t ncls);
 int pnp_surface_distances(const int32_t* pred, const int32_t* gt, int64_t X, int64_t Y, int64_t Z, int32_t ncls, float sx, float sy,
                           float sz, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* WGAN-GP gradient penalty of the critics (gradient_penalty.py).  Per sample i of a [B, n] pair of critic inputs:
+ * pnp_gp_interpolate: out = eps_i * a + (1 - eps_i) * b with eps_i in [0, 1) drawn from (seed, stream_id, i) by the dropout counter hash;
+ * eps [B] receives the values used.
+ * pnp_gp_penalty: norms[i] = |g_i| (fp64 accumulation), penalty[0] = coef * mean_i (|g_i| - 1)^2, then g is scaled IN PLACE into the
+ * penalty's adjoint gscale * dP/dg (zero for a sample with |g_i| = 0).  workspace: pnp_gp_workspace_bytes (0 for bad arguments).
+ * pnp_bn_dbl_bwd: double backward of conv -> dropout(keep, seed, stream_id) -> BN(train, eps) [-> + pad(shortcut)] -> leaky(alpha; < 0:
+ * none) with respect to its input-gradient pass.  In: gc_bar = adjoint of the conv-accumulator gradient, d = BN input (post dropout),
+ * y = unit output (sign of the activation), gy = gradient at the unit output, the batch mean / biased var, gamma; sc_bar [P, Cs] = adjoint
+ * arriving at the shortcut gradient (Cs = 0: none; zero-padded (C - Cs) / 2 each side).  Out: gy_bar [P, C], xc_bar [P, C] = adjoint of d
+ * times mask / keep, gamma_bar [C] += (nullable).  workspace: pnp_bn_dbl_bwd_workspace_bytes.  All three run-to-run deterministic. */
+int pnp_gp_interpolate(const float* a, const float* b, float* out, float* eps, int64_t B, int64_t n, uint64_t seed, uint32_t stream_id,
+                       void* stream);
+size_t pnp_gp_workspace_bytes(int64_t B, int64_t n);
+int pnp_gp_penalty(float* g, int64_t B, int64_t n, float coef, float gscale, float* norms, float* penalty, void* workspace,
+                   size_t workspace_bytes, void* stream);
+size_t pnp_bn_dbl_bwd_workspace_bytes(int64_t P, int32_t C);
+int pnp_bn_dbl_bwd(const float* gc_bar, const float* d, const float* y, const float* gy, const float* mean, const float* var,
+                   const float* gamma, const float* sc_bar, int32_t Cs, float* gy_bar, float* xc_bar, float* gamma_bar, int64_t P, int32_t C,
+                   float eps, float alpha, float keep, uint64_t seed, uint32_t stream_id, void* workspace, size_t workspace_bytes,
+                   void* stream);
 /* Synchronised batch statistics (data-parallel replicas of equally many rows): moments[0..C) = mean, moments[C..2C) = var + mean^2 in
  * double; the caller sums `moments` over the replicas (pnp_comm_allreduce, PNP_DTYPE_F64) and converts back with the replica count. */
 int pnp_bn_moments(const float* mean, const float* var, double* moments, int32_t C, void* stream);

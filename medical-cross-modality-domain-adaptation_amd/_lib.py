@@ -128,6 +128,12 @@ PROTOTYPES = {
     "pnp_surface_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
     "pnp_surface_distances": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_float, c_float, c_float, c_void_p, c_void_p,
                                       c_size_t, c_void_p]),
+    "pnp_gp_interpolate": (c_int, [_F, _F, _F, _F, c_int64, c_int64, c_uint64, c_uint32, c_void_p]),
+    "pnp_gp_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "pnp_gp_penalty": (c_int, [_F, c_int64, c_int64, c_float, c_float, _F, _F, c_void_p, c_size_t, c_void_p]),
+    "pnp_bn_dbl_bwd_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "pnp_bn_dbl_bwd": (c_int, [_F, _F, _F, _F, _F, _F, _F, _F, c_int32, _F, _F, _F, c_int64, c_int32, c_float, c_float, c_float, c_uint64,
+                               c_uint32, c_void_p, c_size_t, c_void_p]),
     "pnp_bn_moments": (c_int, [_F, _F, c_void_p, c_int32, c_void_p]),
     "pnp_bn_from_moments": (c_int, [c_void_p, c_int32, _F, _F, c_int32, c_void_p]),
     "pnp_cast_bf16": (c_int, [_F, c_void_p, c_size_t, c_void_p]),

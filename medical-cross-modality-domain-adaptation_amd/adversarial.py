@@ -20,6 +20,7 @@ import torch
 
 from . import kernels as K
 from .functional import Conv2dDropFn, CriticInputFn, WganLossFn, fan_out, wgrad_overlap
+from .gradient_penalty import critic_gradient_penalty, critic_table
 from .layers import (DR_block, conv2d, conv_bn_relu2d, max_pool2d, residual_block, sharable_weight_variable, weight_variable)
 from .lib import _dice_eval, _label_decomp
 from .ops import PS
@@ -73,6 +74,10 @@ class Full_DRN(object):
         self.lambda_mask_loss = 1.0 if lam is None else float(lam)
         self.reg_coeff = ck.pop("regularizer", 1.0e-4)
         self.gan_reg_coeff = ck.pop("gan_regularizer", 1.0e-4)
+        # opt-in WGAN-GP penalty of the critics (gradient_penalty.py; not in the reference): 0 = the reference's weight clip
+        self.gp_weight = float(ck.pop("gp_weight", 0.0) or 0.0)
+        if not self.gp_weight >= 0.0:
+            raise ValueError("cost_kwargs gp_weight must be >= 0, got %r" % (self.gp_weight,))
 
     def _fc(self, x, w):
         """tf.matmul(tf.reshape(x, [-1, D]), w) (adversarial.py:395-397, 438-440) as a 1x1 'convolution' on the MFMA kernel"""
@@ -195,8 +200,6 @@ class Full_DRN(object):
                           cls_bn=True, cls_trainable=True):
         st = self.store
         fb = feature_base
-        sw = lambda shape, name: sharable_weight_variable(shape=shape, trainable=cls_trainable, name=name)
-        wl = self._lists["cls_weights"]
         with st.variable_scope('cls_0'):
             f4 = PS(input_conv4, r=8, n_channel=2, batch_size=self.batch_size)
             f6 = PS(input_conv6, r=8, n_channel=4, batch_size=self.batch_size)
@@ -207,66 +210,38 @@ class Full_DRN(object):
                 input_comp = torch.empty(tuple(seg_logits.shape[:3]) + (2 * 3 + 4 + 8 + 8 + seg_logits.shape[3] + 1,), device="meta")
             else:
                 input_comp = CriticInputFn.apply(f4, f6, f7, f9, seg_logits, 3)
-        spec = [(1, fb * 2, fb * 4, 3, 2, True), (2, fb * 4, fb * 8, 5, 2, True), (3, fb * 8, fb * 16, 3, 2, True),
-                (4, fb * 16, fb * 32, 3, 2, True), (5, fb * 32, fb * 32, 5, 4, False)]
-        h = input_comp
-        for k, cin, cout, kd, sd, inc in spec:
-            with st.variable_scope('cls_%d' % k):
-                wa, wb = sw([3, 3, cin, cout], "Variable"), sw([3, 3, cout, cout], "Variable_1")
-                blk = residual_block(h, wa, wb, keep_prob=keep_prob, inc_dim=inc, is_train=cls_bn, bn_trainable=cls_trainable,
-                                     scope='cls_%d' % k, leak=True)
-                wd = sw([kd, kd, cout, cout], "Variable_2")
-                h = conv_bn_relu2d(blk, wd, keep_prob, strides=[1, sd, sd, 1], is_train=cls_bn, bn_trainable=cls_trainable,
-                                   scope='cls_%d_3' % k, leak=True)
-                wl += [wa, wb, wd]
-        with st.variable_scope('cls_6'):
-            wr6_1c = sw([3, 3, fb * 32, fb * 32], "Variable")
-            conv_6c = conv_bn_relu2d(h, wr6_1c, strides=[1, 2, 2, 1], keep_prob=keep_prob, padding="SYMMETRIC", scope='cls_6',
-                                     is_train=cls_bn, bn_trainable=cls_trainable, leak=True)
-            wl.append(wr6_1c)
-        with st.variable_scope('cls_out'):
-            wc_out = sw([fb * 32 * 4, 1], "Variable")
-            cls_logits = self._fc(conv_6c, wc_out)
-            wl.append(wc_out)
-        return cls_logits
+        self._critic_input = input_comp
+        return self._critic_body(critic_table("cls", fb), input_comp, keep_prob, cls_bn, cls_trainable, self._lists["cls_weights"])
+
+    def _critic_body(self, table, h, keep_prob, bn, trainable, wl):
+        """the critics' layers from their ONE table (gradient_penalty.critic_table), in the builders' variable-creation order"""
+        sw = lambda shape, name: sharable_weight_variable(shape=shape, trainable=trainable, name=name)
+        for scope, layers in table:
+            with self.store.variable_scope(scope):
+                ws = []
+                for L in layers:
+                    if L[0] == "rb":
+                        _, bns, cin, cout, inc = L
+                        wa, wb = sw([3, 3, cin, cout], "Variable"), sw([3, 3, cout, cout], "Variable_1")
+                        h = residual_block(h, wa, wb, keep_prob=keep_prob, inc_dim=inc, is_train=bn, bn_trainable=trainable, scope=bns, leak=True)
+                        ws += [wa, wb]
+                    elif L[0] == "cbr":
+                        _, leaf, bns, k, cin, cout, sd, pad = L
+                        w = sw([k, k, cin, cout], leaf)
+                        h = conv_bn_relu2d(h, w, keep_prob, padding=pad, strides=[1, sd, sd, 1], is_train=bn, bn_trainable=trainable, scope=bns,
+                                           leak=True)
+                        ws.append(w)
+                    else:
+                        w = sw([L[1], 1], "Variable")
+                        h = self._fc(h, w)
+                        ws.append(w)
+                wl += ws
+        return h
 
     # ---- adversarial.py:402-443 ------------------------------------------------------------------------------------------
     def create_mask_critic(self, input_mask, feature_base=16, keep_prob=CRITIC_KEEP_PROB, num_cls=5, m_cls_bn=True, m_cls_trainable=True):
-        st = self.store
-        fb = feature_base
-        sw = lambda shape, name: sharable_weight_variable(shape=shape, trainable=m_cls_trainable, name=name)
-        wl = self._lists["m_cls_weights"]
-        with st.variable_scope('mask_cls_1'):
-            wr1_1m = sw([3, 3, num_cls, fb], "Variable")
-            out1m = conv_bn_relu2d(input_mask, wr1_1m, keep_prob, strides=[1, 2, 2, 1], is_train=m_cls_bn, bn_trainable=m_cls_trainable,
-                                   scope='mask_cls_1', leak=True)
-            wl.append(wr1_1m)
-        with st.variable_scope('mask_cls_2'):
-            wa, wb = sw([3, 3, fb, fb], "Variable"), sw([3, 3, fb, fb], "Variable_1")
-            blk = residual_block(out1m, wa, wb, keep_prob=keep_prob, inc_dim=False, is_train=m_cls_bn, bn_trainable=m_cls_trainable,
-                                 scope='m_cls_2', leak=True)
-            wd = sw([5, 5, fb, fb * 2], "Variable_2")
-            out2m = conv_bn_relu2d(blk, wd, keep_prob, strides=[1, 4, 4, 1], is_train=m_cls_bn, bn_trainable=m_cls_trainable,
-                                   scope='m_cls_2_3', leak=True)
-            wl += [wa, wb, wd]
-        with st.variable_scope('mask_cls_3'):
-            wa, wb = sw([3, 3, fb * 2, fb * 4], "Variable"), sw([3, 3, fb * 4, fb * 4], "Variable_1")
-            blk = residual_block(out2m, wa, wb, keep_prob=keep_prob, inc_dim=True, is_train=m_cls_bn, bn_trainable=m_cls_trainable,
-                                 scope='m_cls_3', leak=True)
-            wd = sw([5, 5, fb * 4, fb * 8], "Variable_2")
-            out3m = conv_bn_relu2d(blk, wd, keep_prob, strides=[1, 4, 4, 1], is_train=m_cls_bn, bn_trainable=m_cls_trainable,
-                                   scope='m_cls_3_3', leak=True)
-            wl += [wa, wb, wd]
-        with st.variable_scope('mask_cls_4'):
-            wr4_1m = sw([5, 5, fb * 8, fb * 16], "Variable")
-            conv_4m = conv_bn_relu2d(out3m, wr4_1m, strides=[1, 4, 4, 1], keep_prob=keep_prob, padding="SYMMETRIC", scope='m_cls_4',
-                                     is_train=m_cls_bn, bn_trainable=m_cls_trainable, leak=True)
-            wl.append(wr4_1m)
-        with st.variable_scope('m_cls_out'):
-            wm_out = sw([fb * 16 * 4, 1], "Variable")
-            m_cls_logits = self._fc(conv_4m, wm_out)
-            wl.append(wm_out)
-        return m_cls_logits
+        return self._critic_body(critic_table("mask", feature_base, num_cls), input_mask, keep_prob, m_cls_bn, m_cls_trainable,
+                                 self._lists["m_cls_weights"])
 
     # ---- the graph of adversarial.py:82-119, executed eagerly ---------------------------------------------------------------
     def _graph(self, mr, ct, keep_prob, mr_front_bn, joint_bn, ct_front_bn, record=False, segmenter_no_grad=False, drop_seed=0, critics=True, critic_keep=None):
@@ -303,6 +278,9 @@ class Full_DRN(object):
                         out[br + "_cls"] = self.create_classifier(z[br + "_c4"], z[br + "_c6"], b7, c9, lg_cls, feature_base=self.feature_base,
                                                                   cls_trainable=self.cls_trainable, **ckw)
                         out[br + "_logits"] = lg
+                        if self.gp_weight > 0:      # the penalty's interpolation end points (constants of the dis step)
+                            out[br + "_critic_input"] = self._critic_input.detach()
+                        self._critic_input = None
             with st.variable_scope("mask_cls_scope"):
                 for br in ("ct", "mr"):
                     if br in feats:
@@ -353,12 +331,37 @@ class Full_DRN(object):
         use_mask = lam != 0.0
         loss = WganLossFn.apply(o["ct_cls"], o["mr_cls"], o["ct_mask"] if use_mask else None, o["mr_mask"] if use_mask else None,
                                 (mu, -mu, lam * mu, -lam * mu), 1.0 / self.world_size)
+        # the penalty runs BEFORE the WGAN backward: it adds into the gradient arena on the compute stream, ahead of any bucket
+        # all-reduce that the backward's gradient sinks launch
+        pen = self.gradient_penalty(o, drop_seed) if self.gp_weight > 0 else None
         with wgrad_overlap():
             loss.backward(self.store.unit_grad(1))
-        self.dis_loss = loss.detach()
+        self.dis_loss = loss.detach() if pen is None else K.add(loss.detach(), pen)
         self.ct_logits, self.mr_logits = o["ct_logits"], o["mr_logits"]
         self.critic_scores = {k: o[k].detach() for k in ("ct_cls", "mr_cls", "ct_mask", "mr_mask") if o.get(k) is not None}
         return self.dis_loss
+
+    def gradient_penalty(self, o, drop_seed):
+        """gp_weight * [GP(cls) + lambda_mask_loss * GP(mask)] of the dis step's graph `o` (gradient_penalty.py): gradients into the arena,
+        -> the penalty [1].  Dropout / eps stream ids start right after the dis graph's own (self.gp_stream0 = the feature critic's first
+        unit; the mask critic's follow the feature critic's eps id).  Exposes gp_value, gp_norms {critic: mean |grad f|}, gp_eps."""
+        st = self.store
+        s0 = st.peek_drop_stream()
+        self.gp_stream0 = {}
+        self.gp_norms, self.gp_eps = {}, {}
+        ends = {"cls": ("mr_critic_input", "ct_critic_input"), "mask": ("mr_logits", "ct_logits")}
+        total = None
+        for critic, coef in (("cls", self.gp_weight), ("mask", self.gp_weight * self.lambda_mask_loss)):
+            if coef == 0.0:
+                continue
+            self.gp_stream0[critic] = s0
+            a, b = (o[k].detach().contiguous() for k in ends[critic])
+            pen, norms, eps, s0 = critic_gradient_penalty(self, critic, a, b, coef, drop_seed, s0)
+            self.gp_norms[critic] = norms.mean()
+            self.gp_eps[critic] = eps
+            total = pen if total is None else K.add(total, pen)
+        self.gp_value = total
+        return total
 
     def gen_loss_and_grads(self, ct, keep_prob, drop_seed=0):
         """generator step graph (adversarial.py:875-881): CT front in BN-training mode, gradients to `adapt_*` only."""
@@ -451,6 +454,10 @@ verbose = True
 
 def _host(t):
     return None if t is None else float(t)
+
+
+def _gp_weight(net):
+    return getattr(net, "gp_weight", 0.0)      # (networks without the cost key: stand-ins of the schedule tests)
 
 
 class _Null(object):
@@ -594,6 +601,9 @@ class Trainer(object):
         steps per graph are real updates.  Not under data parallelism."""
         if self.reducer is not None:
             raise RuntimeError("capture_steps: not under data parallelism (the bucketed all-reduce runs on a side stream)")
+        if _gp_weight(self.net) > 0:
+            raise RuntimeError("capture_steps: the gradient-penalty dis step (gp_weight = %g > 0) is not captured; run it eagerly"
+                               % _gp_weight(self.net))
         from .step_capture import CapturedStep
         if self.dis_optimizer is None:
             self._get_optimizer()
@@ -632,7 +642,8 @@ class Trainer(object):
         if self.reducer is not None:
             self.reducer.allreduce()
         self.dis_optimizer.step()
-        K.clip(self.net.store.arena, self.clip_mask, -0.03, 0.03, ranges=self._clip_ranges)
+        if _gp_weight(self.net) == 0:           # with the gradient penalty on, the penalty replaces the +-0.03 clip
+            K.clip(self.net.store.arena, self.clip_mask, -0.03, 0.03, ranges=self._clip_ranges)
         self.global_step += 1
         return loss
 
@@ -722,9 +733,15 @@ class Trainer(object):
         from .lib import _indicator_eval
         ct_d, mr_d = self.net.evaluate(ct_batch, ct_batch_y, mr_batch, mr_batch_y, detail=detail)
         self.loss_dict["val" if detail else "train"] = (step, ct_d, mr_d)
+        gp = {}
+        if _gp_weight(self.net) > 0 and getattr(self.net, "gp_value", None) is not None:
+            gp = {"gp": _host(self.net.gp_value)}
+            gp.update(("gp_norm_" + k, _host(v)) for k, v in self.net.gp_norms.items())
+            logging.info("step %d gradient penalty %.6g, mean critic-gradient norms %s" % (
+                step, gp["gp"], ", ".join("%s %.4g" % (k[8:], v) for k, v in gp.items() if k != "gp")))
         if getattr(self, "scalars", None) is not None:      # evaluate() has just synchronised: the last losses cost nothing to read here
             self.scalars.write("val_eval" if detail else "train_eval", step=step, ct_dice=ct_d, mr_dice=mr_d,
-                               dis_loss=_host(getattr(self.net, "dis_loss", None)), gen_loss=_host(getattr(self.net, "ct_gen_loss", None)))
+                               dis_loss=_host(getattr(self.net, "dis_loss", None)), gen_loss=_host(getattr(self.net, "ct_gen_loss", None)), **gp)
         if detail:
             _indicator_eval(self.net.confusion_matrix, verbose=verbose)
 

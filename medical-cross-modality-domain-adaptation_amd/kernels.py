@@ -800,6 +800,48 @@ def surface_distances(pred_i32, gt_i32, ncls, spacing=None):
     return out
 
 
+def gp_interpolate(a, b, seed, stream_id):
+    """WGAN-GP interpolation x_hat = eps_i * a + (1 - eps_i) * b per sample i of the leading dim (pnp_gp_interpolate) -> (x_hat, eps [B])"""
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError("gp_interpolate: %s vs %s" % (tuple(a.shape), tuple(b.shape)))
+    B = a.shape[0]
+    out = torch.empty_like(a)
+    eps = torch.empty(B, dtype=torch.float32, device=a.device)
+    check(_lib.load().pnp_gp_interpolate(_p(a), _p(b), _p(out), _p(eps), B, a.numel() // B, int(seed), int(stream_id), _stream()),
+          "pnp_gp_interpolate")
+    return out, eps
+
+
+def gp_penalty_(g, coef, gscale=1.0):
+    """per-sample norms of g [B, ...], penalty coef * mean_i (|g_i| - 1)^2; g is overwritten by gscale * dP/dg (pnp_gp_penalty)
+    -> (penalty [1], norms [B])"""
+    lib = _lib.load()
+    B = g.shape[0]
+    n = g.numel() // B
+    norms = torch.empty(B, dtype=torch.float32, device=g.device)
+    pen = torch.empty(1, dtype=torch.float32, device=g.device)
+    ws = workspace(lib.pnp_gp_workspace_bytes(B, n), g.device)
+    check(lib.pnp_gp_penalty(_p(g), B, n, float(coef), float(gscale), _p(norms), _p(pen), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                             _stream()), "pnp_gp_penalty")
+    return pen, norms
+
+
+def bn_dbl_bwd(gc_bar, d, y, gy, mean, var, gamma, sc_bar=None, eps=1e-3, alpha=0.2, keep_prob=1.0, seed=0, stream_id=0, gamma_bar=None):
+    """double backward of conv -> dropout -> BN(train) [-> + pad(shortcut)] -> leaky (pnp_bn_dbl_bwd) -> (gy_bar, xc_bar); gamma_bar
+    ([C], e.g. the variable's gradient slot) is ADDED to"""
+    lib = _lib.load()
+    C = d.shape[-1]
+    P = d.numel() // C
+    gy_bar = torch.empty_like(d)
+    xc_bar = torch.empty_like(d)
+    Cs = sc_bar.shape[-1] if sc_bar is not None else 0
+    ws = workspace(lib.pnp_bn_dbl_bwd_workspace_bytes(P, C), d.device)
+    check(lib.pnp_bn_dbl_bwd(_p(gc_bar), _p(d), _p(y), _p(gy), _p(mean), _p(var), _p(gamma), _p(sc_bar), Cs, _p(gy_bar), _p(xc_bar),
+                             _p(gamma_bar), P, C, float(eps), float(alpha), float(keep_prob), int(seed), int(stream_id),
+                             ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()), "pnp_bn_dbl_bwd")
+    return gy_bar, xc_bar
+
+
 def bn_moments(mean, var):
     C = mean.numel()
     mom = torch.empty(2 * C, dtype=torch.float64, device=mean.device)

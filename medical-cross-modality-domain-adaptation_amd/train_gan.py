@@ -2,7 +2,8 @@
   --phase pre-train : warm up the feature critic (dis only, 1 sub-iteration, lambda_mask_loss = 0, CT front frozen)
   --phase train-gan : joint training (20 dis : 1 gen, lambda_mask_loss = rate, dis_sub_iter += 1 every 300 steps)
   --phase fine-tune : continue from a breakpoint (the reference's `training_config` NameError at train_gan.py:121 is fixed)
-Extra flags: --synthetic N, --batch-size, --iters, --epochs, --output, --baseline (source-segmenter .npz for the pre-train hand-off).
+Extra flags: --synthetic N, --batch-size, --iters, --epochs, --output, --baseline (source-segmenter .npz for the pre-train hand-off),
+--gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference).
 """
 import argparse
 import datetime
@@ -50,7 +51,7 @@ def configure(phase):
     return ck, nc, tc
 
 
-def main(phase, argv=None):
+def parse_args(phase, argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--phase", default=phase)
     ap.add_argument("--synthetic", type=int, default=0)
@@ -64,10 +65,32 @@ def main(phase, argv=None):
                     "(exactly the single-GPU step on the concatenated batch; ~2 tiny collectives per BN layer per pass)")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="arithmetic of the convolution operands: f32 = the reference's "
                     "(default); bf16 = BASELINE configs[4]: bf16 MFMA operands, fp32 accumulation / master weights / BN")
+    ap.add_argument("--gp-weight", type=float, default=0.0, help="WGAN-GP gradient penalty weight of the critics (f = miu_dis * D; 10 = "
+                    "the WGAN-GP paper's value); > 0 replaces the +-0.03 weight clip.  fp32, without --sync-stats; default 0")
     args = ap.parse_args(argv)
+    if not args.gp_weight >= 0.0:
+        ap.error("--gp-weight must be >= 0, got %r" % args.gp_weight)
+    if args.gp_weight > 0 and args.dtype != "f32":
+        ap.error("--gp-weight > 0 runs fp32 convolutions only: the gradient penalty is not implemented for --dtype %s" % args.dtype)
+    if args.gp_weight > 0 and args.sync_stats:
+        ap.error("--gp-weight > 0 with --sync-stats: the gradient penalty's pass uses per-replica batch statistics and is not "
+                 "implemented with synchronised ones")
+    return args
+
+
+def configure_args(args):
+    """configure(args.phase) plus the flags that change the cost: gp_weight enters cost_kwargs only when it is > 0"""
+    ck, nc, tc = configure(args.phase)
+    if args.gp_weight > 0:
+        ck["gp_weight"] = float(args.gp_weight)
+    return ck, nc, tc
+
+
+def main(phase, argv=None):
+    args = parse_args(phase, argv)
     from .functional import set_conv_dtype
     set_conv_dtype(args.dtype)
-    ck, nc, tc = configure(args.phase)
+    ck, nc, tc = configure_args(args)
     num_cls, batch_size = 5, args.batch_size
     output_path = args.output
     rank, local, world = init_distributed()     # >1 only under torch.distributed.run: data-parallel, --batch-size slices per rank

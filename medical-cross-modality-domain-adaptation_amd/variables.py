@@ -106,6 +106,10 @@ class VariableStore(object):
         self._drop_stream += 1
         return s
 
+    def peek_drop_stream(self):
+        """the id the next next_drop_stream() hands out (the gradient penalty's ids follow the graph's)"""
+        return self._drop_stream
+
     def _prefix(self, var_scope):
         return "/".join(s for s in (self._vscope if var_scope else self._nscope) if s)
 
