@@ -138,6 +138,11 @@ int32_t pnp_conv2d_wino_x3(int32_t mode);
  * critics' 64-channel blocks at 256^2 / 128^2).  0: off, 1 (default): where a launch fills the chip (>= 256 tile x filter-block items), 2: wherever the
  * shapes allow (environment PNP_X3_DIRECT); mode < 0: read only.  Returns the previous mode. */
 int32_t pnp_conv2d_x3_direct(int32_t mode);
+/* The strided layers on the same kernels (stride 2..4, zero padding, dilation 1, C % 32 == 0 input and K % 64 == 0 output channels of the
+ * computed convolution, every output or stride-phase grid a multiple of 16 x 16, sub-filters of at most 3 x 3): the forward as a sum of
+ * stride-1 convolutions over the input's stride phases, the data gradient as all output stride phases in one persistent launch.  Taken under
+ * pnp_conv2d_x3_direct's mode (1: >= 256 items) while this switch is 1 (default; environment PNP_X3_STRIDED); 0: off.  Returns the previous value. */
+int32_t pnp_conv2d_x3_strided(int32_t mode);
 /* Transformed-filter cache of the route.  U = G g G^T (36 C K values per filter and pass: fp32, or three bf16 planes) only changes when the filter does: the caller
  * lends one buffer per (filter, pass) and reports weight writes; a launch whose filter has a valid entry skips wino_filter_kernel (the
  * frozen source segmenter / shared half of adversarial.py:839-882 never pay it again, a trained layer once per update instead of once per

@@ -388,6 +388,11 @@ bool x3d_chosen(const ConvArgs& a);
 int x3d_stats_parts(const pnp_conv_geom* g);
 size_t x3d_filter_bytes(int C, int K);
 int launch_x3_direct(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st);
+// ... and its strided layers (stride 2..4, zero padding): the forward (kind 0) as a sum over the input's stride phases, the data gradient
+// (kind 1) as all output stride phases in one launch; g = the FORWARD geometry.  x3s_chosen: the one predicate of workspace, partials and launch
+bool x3s_chosen(const pnp_conv_geom* g, int kind);
+size_t x3s_filter_bytes(const pnp_conv_geom* g);
+int launch_x3_strided(const ConvArgs& a, const pnp_conv_geom* g, int kind, void* ws, size_t ws_bytes, hipStream_t st);
 bool wino_chosen(const pnp_conv_geom* g);
 int wino_tile(const pnp_conv_geom* g);
 size_t wino_workspace_bytes(const pnp_conv_geom* g);

@@ -2175,6 +2175,17 @@ int launch_phase_group(const float* dy, const float* wt, float* outp, const pnp_
 
 }  // namespace
 
+// the forward on the direct split-bf16 kernels (conv_x3_direct.hip) — THE predicate of the workspace, the partial count and the launches:
+// 0 no; 1 the stride-1 kernel; 2 the strided one
+static int fwd_x3_route(const pnp_conv_geom* g) {
+    if (wino_chosen(g) || n16_geom_ok(g) || narrow_fwd_ok(g, nullptr)) return 0;
+    if (x3d_chosen(g)) return 1;
+    return x3s_chosen(g, 0) ? 2 : 0;
+}
+static size_t fwd_x3_bytes(const pnp_conv_geom* g, int route) {
+    return route == 1 ? x3d_filter_bytes(g->C, g->K) : (route == 2 ? x3s_filter_bytes(g) : 0);
+}
+
 extern "C" {
 
 // forward: only layers that leave at least 3/4 of the workgroup slots empty — at half a dispatch round the extra pass over the partials
@@ -2194,7 +2205,7 @@ size_t pnp_conv2d_fwd_workspace_bytes(const pnp_conv_geom* g) {
     const int ns = fwd_split(g);
     const size_t split = ns > 1 ? (size_t)ns * g->N * g->OH * g->OW * g->K * sizeof(float) : 0;
     // direct split-bf16 convolution of a narrow layer the Winograd planner leaves alone (conv_x3_direct.hip): its filter image
-    const size_t x3d = x3d_chosen(g) ? x3d_filter_bytes(g->C, g->K) : 0;
+    const size_t x3d = fwd_x3_bytes(g, fwd_x3_route(g));
     return split > x3d ? split : x3d;
 }
 
@@ -2222,8 +2233,11 @@ int pnp_conv2d_fwd_ws(const float* x, const float* w, float* y, const pnp_conv_g
         if (workspace && workspace_bytes >= wino_workspace_bytes(g)) return launch_wino(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream);
         return launch_fwd<0>(a, (hipStream_t)stream, nullptr);
     }
-    if (x3d_chosen(a) && workspace && workspace_bytes >= x3d_filter_bytes(a.C, a.K))
-        return launch_x3_direct(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream);
+    if (const int x3 = fwd_x3_route(g)) {
+        if (workspace && workspace_bytes >= fwd_x3_bytes(g, x3))
+            return x3 == 1 ? launch_x3_direct(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream)
+                           : launch_x3_strided(a, g, 0, workspace, workspace_bytes, (hipStream_t)stream);
+    }
     float* split_ws = (workspace && workspace_bytes >= pnp_conv2d_fwd_workspace_bytes(g) && pnp_conv2d_fwd_workspace_bytes(g) > 0)
                           ? (float*)workspace : nullptr;
     return launch_fwd<0>(a, (hipStream_t)stream, split_ws);
@@ -2255,7 +2269,7 @@ int pnp_conv2d_fwd_stats(const float* x, const float* w, float* y, const pnp_con
 int32_t pnp_conv2d_fwd_stats_ws_parts(const pnp_conv_geom* g) {
     if (!g || check_geom(g, "pnp_conv2d_fwd_stats_ws_parts") != PNP_OK) return 0;
     if (wino_chosen(g)) return wino_stats_parts(g);
-    if (x3d_chosen(g) && !n16_geom_ok(g) && !narrow_fwd_ok(g, nullptr)) return x3d_stats_parts(g);
+    if (fwd_x3_route(g)) return x3d_stats_parts(g);             // (one partial per 64 output pixels on both kernels)
     return pnp_conv2d_fwd_stats_parts(g);
 }
 
@@ -2273,8 +2287,9 @@ static int fwd_stats_impl(const float* x, const float* w, float* y, const pnp_co
     PNP_REQUIRE(keep_prob > 0.f, "pnp_conv2d_fwd_stats: keep_prob must be > 0");
     const bool wino = with_ws && wino_chosen(g);
     if (wino) PNP_REQUIRE(workspace && workspace_bytes >= wino_workspace_bytes(g), "pnp_conv2d_fwd_stats_ws: workspace too small (pnp_conv2d_fwd_workspace_bytes)");
-    const bool x3d = with_ws && !wino && x3d_chosen(g) && !n16_geom_ok(g) && !narrow_fwd_ok(g, nullptr);
-    if (x3d) PNP_REQUIRE(workspace && workspace_bytes >= x3d_filter_bytes(g->C, g->K), "pnp_conv2d_fwd_stats_ws: workspace too small (pnp_conv2d_fwd_workspace_bytes)");
+    const int x3 = (with_ws && !wino) ? fwd_x3_route(g) : 0;
+    const bool x3d = x3 != 0;
+    if (x3d) PNP_REQUIRE(workspace && workspace_bytes >= fwd_x3_bytes(g, x3), "pnp_conv2d_fwd_stats_ws: workspace too small (pnp_conv2d_fwd_workspace_bytes)");
     const int nparts = wino ? wino_stats_parts(g) : (x3d ? x3d_stats_parts(g) : pnp_conv2d_fwd_stats_parts(g));
     PNP_REQUIRE(nparts > 0, "pnp_conv2d_fwd_stats: no epilogue statistics for this geometry (pnp_conv2d_fwd_stats_parts == 0)");
     if (parts_bytes < (size_t)nparts * 2 * g->K * sizeof(float)) {
@@ -2292,7 +2307,8 @@ static int fwd_stats_impl(const float* x, const float* w, float* y, const pnp_co
     a.stat_ws = parts;
     a.stat_shift = shift;
     if (wino) return launch_wino(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream);
-    if (x3d) return launch_x3_direct(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream);
+    if (x3d) return x3 == 1 ? launch_x3_direct(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream)
+                            : launch_x3_strided(a, g, 0, workspace, workspace_bytes, (hipStream_t)stream);
     return launch_fwd<0>(a, (hipStream_t)stream);
 }
 
@@ -2388,6 +2404,10 @@ size_t pnp_conv2d_dgrad_workspace_bytes(const pnp_conv_geom* g) {
         const size_t f = x3d_filter_bytes(d.C, d.K);
         return b > f ? b : f;
     }
+    if (x3s_chosen(g, 1)) {                              // strided: the split filter image of every stride phase
+        const size_t f = x3s_filter_bytes(g);
+        return b > f ? b : f;
+    }
     return b;
 }
 
@@ -2460,6 +2480,11 @@ static int dgrad_impl(const float* dy, const float* w, float* dx, const pnp_conv
         size_t poff = woff;
         if (symp) poff += ((size_t)g->N * Ho * Wo * g->C * sizeof(float) + 255) & ~(size_t)255;
         float* split_ws = (workspace_bytes > poff) ? (float*)((char*)workspace + poff) : nullptr;
+        if (x3s_chosen(g, 1)) {              // every phase on the direct split-bf16 kernel, one launch (its filter image flips per phase)
+            ConvArgs a = make_args(dy, w, dx, g);
+            if (int e = launch_x3_strided(a, g, 1, workspace, workspace_bytes, st)) return e;
+            return add_residual(dx, residual);
+        }
         dim3 tgp((unsigned)pnp_cdiv(g->K, 32), (unsigned)pnp_cdiv(g->C, 32), (unsigned)(g->R * g->S));
         hipLaunchKernelGGL(flip_transpose_phase_kernel, tgp, dim3(256), 0, st, w, wt, g->R, g->S, g->C, g->K, g->stride);
         PNP_CHECK_LAUNCH("flip_transpose_phase_kernel");

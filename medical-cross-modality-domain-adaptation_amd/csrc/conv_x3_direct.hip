@@ -21,6 +21,8 @@
 // chain of 9 C terms — 8e-7 of max|ref| on 64 -> 64 (the direct fp32 kernel 2.9e-6, F(4x4) 1.2e-6 .. 8e-6).
 // Entry: launch_wino() hands the layers x3d_chosen() takes to launch_x3_direct() (they are layers the Winograd planner owns: workspace and
 // partial-count queries go through the same functions).  PNP_X3_DIRECT / pnp_conv2d_x3_direct(): 0 off, 1 where a launch fills the chip, 2 wherever the shapes allow.
+// The strided layers (conv_x3_direct_kernel_strided below, PNP_X3_STRIDED): forward and stride-phase data gradient as sums of stride-1
+// sub-convolutions on the same LDS layout, MFMA order and epilogue; entered from pnp_conv2d_fwd* / dgrad_impl through x3s_chosen().
 #include <atomic>
 #include <cstdlib>
 #include "conv_common.h"
@@ -367,6 +369,382 @@ __global__ void __launch_bounds__(256) x3d_filter_kernel(const float* __restrict
     w3[base + 2 * (size_t)KW * 32] = __builtin_bit_cast(unsigned short, b2);
 }
 
+// ============================ strided layers: sums of stride-1 sub-convolutions over the input's stride phases ============================
+// A stride-s convolution is the sum over the s x s input phases x_ab[i][j] = x[s i + a][s j + b] of stride-1 convolutions with the
+// sub-filters w[a + s t][b + s u]; a stride-phase data gradient is, per output phase, ONE stride-1 correlation of dy with a flipped sub-filter
+// whose outputs land s pixels apart (plan_phases).  Both are GROUPS of PHASES here: an item (group, 16 x 16 tile of the group's output grid,
+// 64 filters) accumulates over channel half x phase x the phase's T x U taps, one patch per (half, phase), the taps LDS offsets into it.
+// The forward is one group of s^2 phases; the data gradient s^2 groups of one phase each (all in one persistent launch).  Same LDS layout,
+// MFMA order, filter stages (of FSTG bytes, now from a [group][filter block][half][stage][plane][64][32] image) and epilogue as above; the
+// stage schedule is a run-time loop (channel halves and phases vary per layer and, for the data gradient, per item).
+constexpr int X3S_MAXPH = 16;
+
+struct X3sPhase {
+    int T, U;              // taps (rows, columns): 1..3
+    int ih0, iw0;          // input pixel of patch (0, 0) for the grid origin: patch (pr, pc) of the tile at (oh0, ow0) = si (oh0 + pr) + ih0, ...
+};
+struct X3sGroup {
+    int first_item, tiles_x, tiles_y;
+    int ph0, nph, nst;     // phases [ph0, ph0 + nph); nst = stages per channel half (sum of T U)
+    int o_h0, o_w0;        // output pixel of grid point (i, j) = (o_h0 + o_s i, o_w0 + o_s j)
+    int fbase;             // first stage of the group in the filter image
+};
+struct X3sArgs {
+    const float* x;               // [N][H][W][C]
+    const unsigned short* w3;     // filter image
+    float* y;                     // [N][OHt][OWt][K]
+    int N, H, W, C, K, NH, si;
+    int OHt, OWt, o_s;
+    int ngroups, nitems;
+    unsigned w3_bytes;
+    X3sGroup grp[X3S_MAXPH];
+    X3sPhase ph[X3S_MAXPH];
+    int do_drop;
+    uint32_t drop_thresh, drop_key;
+    float drop_keep;
+    const pnp_step_params* sp;
+    uint32_t drop_sid;
+    float* stat_ws;               // (one group only) [parts][2][K]; part = 4 tile + consumer wave
+    const float* stat_shift;
+};
+
+__device__ __forceinline__ int x3s_group(const X3sArgs& a, int id) {
+    int gi = 0;
+    for (int i = 1; i < a.ngroups; ++i)
+        if (id >= a.grp[i].first_item) gi = i;
+    return gi;
+}
+
+// KIND 0 / 1 only names the symbol (forward / data gradient)
+template <int KIND>
+__global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel_strided(X3sArgs a) {
+    constexpr int KW = 64, TN = 2;
+    constexpr int PLANE_F = KW * ROWB, FSTG = 3 * PLANE_F, NPC = FSTG / 1024;
+    __shared__ __attribute__((aligned(256))) unsigned char lds[LDS_BYTES];
+    unsigned char* const patch0 = lds;
+    unsigned char* const filt0 = lds + 2 * PATCH;
+    const int t = threadIdx.x, lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int KB = a.K / KW, NH = a.NH;
+    int myitems = 0, gstages = 0, nslots = 0;
+    for (int i = blockIdx.x; i < a.nitems; i += gridDim.x) {
+        const X3sGroup& G = a.grp[x3s_group(a, i)];
+        ++myitems;
+        gstages += NH * G.nst;
+        nslots += NH * G.nph;
+    }
+    if (myitems == 0) return;                       // (uniform for the workgroup)
+    // item -> (group, filter block, group-local tile, image, tile origin in the group's grid)
+    auto item_origin = [&](int it, int& gi, int& kb, int& tile, int& n, int& oh0, int& ow0) {
+        const int id = blockIdx.x + it * gridDim.x;
+        gi = x3s_group(a, id);
+        const X3sGroup& G = a.grp[gi];
+        const int loc = id - G.first_item;
+        tile = loc / KB;
+        kb = loc - tile * KB;
+        n = tile / (G.tiles_x * G.tiles_y);
+        const int r = tile - n * G.tiles_x * G.tiles_y;
+        oh0 = (r / G.tiles_x) * TH;
+        ow0 = (r % G.tiles_x) * TW;
+    };
+    // (item, half, phase index in the group) cursor over the patch slots / (item, half, stage) cursor over the filter stages
+    struct Cur { int it, hh, k; };
+
+    if (wave == 4) {
+        // ============================ filter loader: one 12 KB stage per barrier, LDS-DMA ============================
+        const __amdgpu_buffer_rsrc_t rw = make_rsrc(reinterpret_cast<const float*>(a.w3), a.w3_bytes);
+        const int lrow = lane >> 2, lchk = lane & 3;
+        constexpr int PPP = KW / 16;
+        unsigned vo[NPC];
+#pragma unroll
+        for (int i = 0; i < NPC; ++i) {
+            const int row = (i % PPP) * 16 + lrow;
+            vo[i] = (unsigned)((i / PPP) * PLANE_F + row * ROWB + ((lchk ^ swz(row)) << 4));
+        }
+        Cur c{0, 0, 0};
+        int gi, kb, tile, n, oh0, ow0;
+        item_origin(0, gi, kb, tile, n, oh0, ow0);
+        auto issue = [&](int g) {
+            const X3sGroup& G = a.grp[gi];
+            const int stg = G.fbase + (kb * NH + c.hh) * G.nst + c.k;
+            unsigned char* bp = filt0 + (g % NF) * FSTG;
+#pragma unroll
+            for (int i = 0; i < NPC; ++i) dma16(rw, (lds_void*)(bp + i * 1024), vo[i], stg * FSTG);
+            if (++c.k == G.nst) {
+                c.k = 0;
+                if (++c.hh == NH) {
+                    c.hh = 0;
+                    if (++c.it < myitems) item_origin(c.it, gi, kb, tile, n, oh0, ow0);
+                }
+            }
+        };
+#pragma unroll
+        for (int b = 0; b < NF - 1; ++b)
+            if (b < gstages) issue(b);
+        for (int g = 0; g < gstages; ++g) {
+            if (g + NF - 2 < gstages) wait_vm<NPC * (NF - 2)>();
+            else wait_vm0();
+            __builtin_amdgcn_s_barrier();
+            if (g + NF - 1 < gstages) issue(g + NF - 1);
+        }
+        wait_vm0();
+        return;
+    }
+    if (wave > 4) {
+        // ============================ patch loaders: global fp32 -> three bf16 planes -> LDS ============================
+        // slot k + 1 is split and stored during the LAST stage of slot k (its buffer was slot k - 1's), and slot k + 2's global loads
+        // are issued right behind: every load has at least one full stage of MFMA work to land in
+        const int pl = (wave - 5) * 64 + lane;
+        f32x4 st[NPI];
+        Cur lc{0, 0, 0};                             // the slot whose data the registers hold / will hold
+        auto load = [&]() {
+            int gi, kb, tile, n, oh0, ow0;
+            item_origin(lc.it, gi, kb, tile, n, oh0, ow0);
+            const X3sPhase P = a.ph[a.grp[gi].ph0 + lc.k];
+            const int rmax = TH - 1 + P.T, cmax = TW - 1 + P.U;       // patch rows / columns the phase's taps read
+#pragma unroll
+            for (int i = 0; i < NPI; ++i) {
+                const int e = pl + i * NPL;
+                const int q = e >> 3, j = e & 7;
+                const int pr = q / PW, pc = q - pr * PW;
+                const int ih = a.si * (oh0 + pr) + P.ih0, iw = a.si * (ow0 + pc) + P.iw0;
+                const bool ok = (e < NPX * 8) & (pr < rmax) & (pc < cmax) & ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+                if (ok) v = *reinterpret_cast<const f32x4*>(a.x + (((size_t)n * a.H + ih) * a.W + iw) * a.C + lc.hh * 32 + j * 4);
+                st[i] = v;
+            }
+        };
+        auto advance = [&](Cur& c) {
+            const int id = blockIdx.x + c.it * gridDim.x;
+            if (++c.k == a.grp[x3s_group(a, id)].nph) {
+                c.k = 0;
+                if (++c.hh == NH) { c.hh = 0; ++c.it; }
+            }
+        };
+        auto store = [&](int slot) {
+            unsigned char* pb = patch0 + (slot & 1) * PATCH;
+#pragma unroll
+            for (int i = 0; i < NPI; ++i) {
+                const int e = pl + i * NPL;
+                if (e >= NPX * 8) continue;
+                const int q = e >> 3, j = e & 7;
+                bf16x4 hi, mi, lo;
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    const float v = st[i][c];
+                    const __bf16 h = (__bf16)v;
+                    const float r1 = v - (float)h;
+                    const __bf16 m = (__bf16)r1;
+                    const float r2 = r1 - (float)m;
+                    hi[c] = h; mi[c] = m; lo[c] = (__bf16)r2;
+                }
+                const int off = q * ROWB + (((j >> 1) ^ swz(q)) << 4) + (j & 1) * 8;
+                *reinterpret_cast<bf16x4*>(pb + off) = hi;
+                *reinterpret_cast<bf16x4*>(pb + PLANE_P + off) = mi;
+                *reinterpret_cast<bf16x4*>(pb + 2 * PLANE_P + off) = lo;
+            }
+        };
+        auto taps_of = [&](const Cur& c) {
+            const int id = blockIdx.x + c.it * gridDim.x;
+            const X3sPhase& P = a.ph[a.grp[x3s_group(a, id)].ph0 + c.k];
+            return P.T * P.U;
+        };
+        load();
+        wait_vm0();
+        store(0);
+        advance(lc);
+        if (nslots > 1) load();
+        Cur sc{0, 0, 0};                             // the slot the consumers are on
+        int k = 0, j = 0, ns = taps_of(sc);
+        for (int g = 0; g < gstages; ++g) {
+            if (j == 0) wait_lgkm0();                // this slot's patch is in LDS
+            __builtin_amdgcn_s_barrier();
+            if (j == ns - 1) {
+                if (k + 1 < nslots) {
+                    wait_vm0();
+                    store(k + 1);
+                    advance(lc);
+                    if (k + 2 < nslots) load();
+                }
+                ++k;
+                j = 0;
+                advance(sc);
+                if (k < nslots) ns = taps_of(sc);
+            } else {
+                ++j;
+            }
+        }
+        return;
+    }
+    // ============================ consumers: 64 pixels (4 output rows x 16) x 64 filters per wave ============================
+    const int l31 = lane & 31, h = lane >> 5;
+    const int prow = l31 >> 4, pcol = (l31 < 16) ? l31 : ((l31 - 16 + 14) & 15);
+    int aq[2];
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm) aq[tm] = (4 * wave + 2 * tm + prow) * PW + pcol;
+    int woff[TN][2];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) woff[tn][ks] = (tn * 32 + l31) * ROWB + (((2 * ks + h) ^ swz(tn * 32 + l31)) << 4);
+    constexpr int kTermX[6] = {2, 1, 0, 1, 0, 0}, kTermW[6] = {0, 1, 2, 0, 1, 0};
+    f32x16 acc[2][TN];
+    bf16x8 xf[2][3][2];
+    bf16x8 xn[3][2];
+    auto x_frag = [&](const unsigned char* A, int dq, int ks, int p, int tm) {
+        const int q = aq[tm] + dq;
+        return *reinterpret_cast<const bf16x8*>(A + p * PLANE_P + q * ROWB + (((2 * ks + h) ^ swz(q)) << 4));
+    };
+    const uint32_t dkey = a.do_drop ? pnp_eff_drop_key(a.drop_key, a.sp, a.drop_sid) : 0u;
+    int g = 0, slot = 0;
+    for (int it = 0; it < myitems; ++it) {
+        int gi, kb, tile, n, oh0, ow0;
+        item_origin(it, gi, kb, tile, n, oh0, ow0);
+        const X3sGroup& G = a.grp[gi];
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) acc[tm][tn][e] = 0.f;
+        for (int hh = 0; hh < NH; ++hh) {
+            for (int pk = 0; pk < G.nph; ++pk, ++slot) {
+                const X3sPhase P = a.ph[G.ph0 + pk];
+                const unsigned char* A = patch0 + (slot & 1) * PATCH;
+                for (int tap = 0, ntap = P.T * P.U; tap < ntap; ++tap, ++g) {
+                    const int tr = tap / P.U, tc = tap - tr * P.U;
+                    const int dq = tr * PW + tc;
+                    wait_lgkm0();
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+                    if (tap == 0) {
+#pragma unroll
+                        for (int p = 0; p < 3; ++p)
+#pragma unroll
+                            for (int tm = 0; tm < 2; ++tm) xf[0][p][tm] = x_frag(A, 0, 0, p, tm);
+                    } else {
+#pragma unroll
+                        for (int p = 0; p < 3; ++p)
+#pragma unroll
+                            for (int tm = 0; tm < 2; ++tm) xf[0][p][tm] = xn[p][tm];
+                    }
+                    const unsigned char* B = filt0 + (g % NF) * FSTG;
+                    bf16x8 wf[2][3][TN];
+#pragma unroll
+                    for (int p = 0; p < 3; ++p)
+#pragma unroll
+                        for (int tn = 0; tn < TN; ++tn) wf[0][p][tn] = *reinterpret_cast<const bf16x8*>(B + p * PLANE_F + woff[tn][0]);
+#pragma unroll
+                    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+                        for (int tm = 0; tm < 2; ++tm) xf[1][p][tm] = x_frag(A, dq, 1, p, tm);
+#pragma unroll
+                        for (int tn = 0; tn < TN; ++tn) wf[1][p][tn] = *reinterpret_cast<const bf16x8*>(B + p * PLANE_F + woff[tn][1]);
+                    }
+                    if (tap + 1 < ntap) {                // the next tap's first slice: same patch, no barrier in between
+                        const int nr = (tap + 1) / P.U, nc = tap + 1 - nr * P.U;
+#pragma unroll
+                        for (int p = 0; p < 3; ++p)
+#pragma unroll
+                            for (int tm = 0; tm < 2; ++tm) xn[p][tm] = x_frag(A, nr * PW + nc, 0, p, tm);
+                    }
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+                        for (int trm = 0; trm < 6; ++trm)
+#pragma unroll
+                            for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                                for (int tn = 0; tn < TN; ++tn)
+                                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[ks][kTermX[trm]][tm], wf[ks][kTermW[trm]][tn], acc[tm][tn], 0, 0, 0);
+                }
+            }
+        }
+        // ---------------- epilogue: as conv_x3_direct_kernel's, the output pixel scattered by the group's (o_s, o_h0, o_w0)
+        auto mlin_of = [&](int tm, int i) {
+            const int r = (i & 3) + 8 * (i >> 2) + 4 * h;
+            const int orow = oh0 + 4 * wave + 2 * tm + (r >> 4);
+            const int ocol = ow0 + ((r < 16) ? r : ((r - 16 + 14) & 15));
+            return (n * a.OHt + G.o_h0 + a.o_s * orow) * a.OWt + G.o_w0 + a.o_s * ocol;
+        };
+        int ncol[TN];
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) ncol[tn] = kb * KW + tn * 32 + l31;
+#define X3S_FOR                                                      \
+    _Pragma("unroll") for (int tm = 0; tm < 2; ++tm)                 \
+        _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)            \
+            _Pragma("unroll") for (int i = 0; i < 16; ++i)
+        if (a.do_drop) {
+            X3S_FOR {
+                const uint32_t idx = (uint32_t)((size_t)mlin_of(tm, i) * a.K + ncol[tn]);
+                acc[tm][tn][i] = pnp_drop_keep(idx, dkey, a.drop_thresh) ? acc[tm][tn][i] / a.drop_keep : 0.f;
+            }
+        }
+        if (a.stat_ws) {
+            const int part = tile * 4 + wave;
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn) {
+                const float shift = a.stat_shift ? a.stat_shift[ncol[tn]] : 0.f;
+                float ssum = 0.f, ssq = 0.f;
+#pragma unroll
+                for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const float d = acc[tm][tn][i] - shift;
+                        ssum += d;
+                        ssq = fmaf(d, d, ssq);
+                    }
+                const float s_ = ssum + __shfl_xor(ssum, 32, 64);
+                const float q_ = ssq + __shfl_xor(ssq, 32, 64);
+                if (h == 0) {
+                    a.stat_ws[((size_t)part * 2 + 0) * a.K + ncol[tn]] = s_;
+                    a.stat_ws[((size_t)part * 2 + 1) * a.K + ncol[tn]] = q_;
+                }
+            }
+        }
+        const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.y, (unsigned)((size_t)a.N * a.OHt * a.OWt * a.K * 4));
+        X3S_FOR bstore1(ry, (unsigned)(mlin_of(tm, i) * a.K + ncol[tn]) * 4u, acc[tm][tn][i]);
+#undef X3S_FOR
+    }
+}
+
+// the strided layers' filter image: [group][K / 64][C / 32][stage of the group][plane][64 filters][32 channels] bf16.  Stage e of the flat
+// list (groups in order) is forward filter tap (tr[e], tc[e]); FLIP = false: w is [R][S][C][K] (forward); true: w is the forward filter
+// [R][S][K][C] of a data gradient computed as a correlation of dy (C = the forward's K), roles transposed (the flip is in the tap list)
+struct X3sTaps {
+    int ngroups, R, S;
+    int st0[X3S_MAXPH + 1];       // first flat stage of each group
+    int tr[64], tc[64];
+};
+template <bool FLIP>
+__global__ void __launch_bounds__(256) x3s_filter_kernel(const float* __restrict__ w, unsigned short* __restrict__ w3, int C, int K, X3sTaps tp) {
+    const int NH = C >> 5, KB = K / 64;
+    const long long total = (long long)KB * NH * tp.st0[tp.ngroups] * 64 * 32;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= total) return;
+    const int i = (int)(e & 31), o = (int)((e >> 5) & 63);
+    const int simg = (int)(e >> 11);                 // stage of the image
+    int gi = 0;
+    for (int q = 1; q < tp.ngroups; ++q)
+        if (simg >= KB * NH * tp.st0[q]) gi = q;
+    const int nst = tp.st0[gi + 1] - tp.st0[gi];
+    const int loc = simg - KB * NH * tp.st0[gi];
+    const int s = loc % nst, khh = loc / nst;
+    const int hf = khh % NH, kb = khh / NH;
+    const int r = tp.tr[tp.st0[gi] + s], c = tp.tc[tp.st0[gi] + s];
+    const int ic = hf * 32 + i, oc = kb * 64 + o;
+    const float v = FLIP ? w[(((size_t)r * tp.S + c) * K + oc) * C + ic] : w[(((size_t)r * tp.S + c) * C + ic) * K + oc];
+    const __bf16 b0 = (__bf16)v;
+    const float r1 = v - (float)b0;
+    const __bf16 b1 = (__bf16)r1;
+    const float r2 = r1 - (float)b1;
+    const __bf16 b2 = (__bf16)r2;
+    const size_t base = (size_t)simg * 3 * 64 * 32 + (size_t)o * 32 + i;
+    w3[base] = __builtin_bit_cast(unsigned short, b0);
+    w3[base + 64 * 32] = __builtin_bit_cast(unsigned short, b1);
+    w3[base + 2 * 64 * 32] = __builtin_bit_cast(unsigned short, b2);
+}
+
 std::atomic<int> g_x3d_mode{-1};
 
 int x3d_mode() {
@@ -387,9 +765,144 @@ bool dims_ok(int R, int S, int stride, int dil, int C, int K, int OH, int OW, lo
     return x3d_mode() >= 2 || (M / (TH * TW)) * (K == 32 ? 1 : K / 64) >= 256;
 }
 
+std::atomic<int> g_x3s_mode{-1};
+
+int x3s_mode() {
+    int m = g_x3s_mode.load(std::memory_order_relaxed);
+    if (m < 0) {
+        m = getenv("PNP_X3_STRIDED") ? atoi(getenv("PNP_X3_STRIDED")) : 1;
+        g_x3s_mode.store(m, std::memory_order_relaxed);
+    }
+    return m;
+}
+
+// a strided layer's groups, phases and filter stages (kind 0: the forward of g; 1: its data gradient); false: not this route
+struct X3sPlan {
+    int ngroups, nitems, stride;
+    X3sGroup grp[X3S_MAXPH];
+    X3sPhase ph[X3S_MAXPH];
+    X3sTaps taps;
+};
+
+bool x3s_plan(const pnp_conv_geom* g, int kind, X3sPlan* pl) {
+    if (x3d_mode() <= 0 || x3s_mode() <= 0 || g->dtype != PNP_DTYPE_F32 || g->pad_mode != PNP_PAD_ZERO || g->dil != 1) return false;
+    const int s = g->stride;
+    if (s < 2 || s > 4 || g->R < s || g->S < s || g->R > 3 * s || g->S > 3 * s) return false;
+    const int Cin = kind == 0 ? g->C : g->K, Kout = kind == 0 ? g->K : g->C;      // channels of the convolution this kernel computes
+    if ((Cin % 32) != 0 || (Kout % 64) != 0) return false;
+    const long long out_elems = kind == 0 ? (long long)g->N * g->OH * g->OW * g->K : (long long)g->N * g->H * g->W * g->C;
+    if (out_elems >= (1ll << 30) || (long long)g->R * g->S > 64) return false;
+    X3sPlan p{};
+    p.stride = s;
+    int ns = 0, items = 0;
+    auto add_group = [&](int GH, int GW, int o_h0, int o_w0) -> bool {
+        if (GH <= 0 || GW <= 0 || (GH % TH) != 0 || (GW % TW) != 0) return false;
+        X3sGroup& G = p.grp[p.ngroups++];
+        G.first_item = items;
+        G.tiles_x = GW / TW; G.tiles_y = GH / TH;
+        G.o_h0 = o_h0; G.o_w0 = o_w0;
+        G.fbase = (Kout / 64) * (Cin / 32) * ns;          // (stages of the groups before this one; ns = their taps)
+        items += g->N * G.tiles_x * G.tiles_y * (Kout / 64);
+        return true;
+    };
+    if (kind == 0) {
+        if (!add_group(g->OH, g->OW, 0, 0)) return false;
+        X3sGroup& G = p.grp[0];
+        G.ph0 = 0; G.nph = s * s; G.nst = g->R * g->S;
+        p.taps.st0[0] = 0;
+        for (int ra = 0; ra < s; ++ra)
+            for (int cb = 0; cb < s; ++cb) {
+                X3sPhase& P = p.ph[ra * s + cb];
+                P.T = (g->R - ra + s - 1) / s; P.U = (g->S - cb + s - 1) / s;
+                P.ih0 = ra - g->pad_t; P.iw0 = cb - g->pad_l;
+                for (int t = 0; t < P.T; ++t)
+                    for (int u = 0; u < P.U; ++u) { p.taps.tr[ns] = ra + s * t; p.taps.tc[ns] = cb + s * u; ++ns; }
+            }
+        p.taps.st0[1] = ns;
+    } else {
+        DgradPhase dp[16];
+        const int nph = plan_phases(g, dp);
+        if (nph != s * s) return false;
+        for (int i = 0; i < nph; ++i) {
+            const DgradPhase& q = dp[i];
+            if (q.T > 3 || q.U > 3) return false;
+            p.taps.st0[i] = ns;
+            if (!add_group(q.I, q.J, q.h0, q.w0)) return false;
+            X3sGroup& G = p.grp[i];
+            G.ph0 = i; G.nph = 1; G.nst = q.T * q.U;
+            X3sPhase& P = p.ph[i];
+            P.T = q.T; P.U = q.U; P.ih0 = -q.pad_t; P.iw0 = -q.pad_l;
+            for (int t = 0; t < q.T; ++t)                 // correlation tap (t, u) = forward tap (pa + s (T-1-t), pb + s (U-1-u))
+                for (int u = 0; u < q.U; ++u) { p.taps.tr[ns] = q.pa + s * (q.T - 1 - t); p.taps.tc[ns] = q.pb + s * (q.U - 1 - u); ++ns; }
+        }
+        p.taps.st0[nph] = ns;
+    }
+    if (ns != g->R * g->S) return false;
+    p.nitems = items;
+    p.taps.ngroups = p.ngroups; p.taps.R = g->R; p.taps.S = g->S;
+    // mode 1: at least one item per CU (a persistent launch of fewer leaves CUs idle), and only where it measured faster than the fp32-pipe
+    // kernels — phase patches that serve >= 4 taps on average (k5s2: 25 taps over 4 patches), or data gradients of <= 64 dy channels (k3s2
+    // 64@256, whose 1x1 / 1x2 phases run at 40-65 TF/s on the fp32 pipe); k3s2 with 2.25 taps per patch is bound by its patch loads
+    // elsewhere (256@64, 512@32: 0.8-0.9x).  Mode 2: wherever the shapes allow (tests)
+    if (x3d_mode() < 2 && (items < 256 || !(g->R * g->S >= 4 * s * s || (kind == 1 && Cin <= 64)))) return false;
+    if (pl) *pl = p;
+    return true;
+}
+
 }  // namespace
 
 namespace pnpconv {
+
+bool x3s_chosen(const pnp_conv_geom* g, int kind) { return x3s_plan(g, kind, nullptr); }
+
+size_t x3s_filter_bytes(const pnp_conv_geom* g) { return (size_t)g->R * g->S * g->C * g->K * 6; }
+
+// forward (kind 0: a = make_args(x, w, y, g)) or stride-phase data gradient (kind 1: a = make_args(dy, w, dx, g), w the FORWARD filter) of a
+// strided layer x3s_chosen() takes; g = the forward geometry
+int launch_x3_strided(const ConvArgs& a, const pnp_conv_geom* g, int kind, void* ws, size_t ws_bytes, hipStream_t st) {
+    X3sPlan pl;
+    if (!x3s_plan(g, kind, &pl)) {
+        pnp_set_error("launch_x3_strided: layer not on this route");
+        return PNP_EINVAL;
+    }
+    const size_t fbytes = x3s_filter_bytes(g);
+    if (!ws || ws_bytes < fbytes) {
+        pnp_set_error("launch_x3_strided: workspace too small (%zu < %zu)", ws_bytes, fbytes);
+        return PNP_EWORKSPACE;
+    }
+    unsigned short* w3 = (unsigned short*)ws;
+    const int cls = prof_class(kind);
+    const int Cin = kind == 0 ? g->C : g->K, Kout = kind == 0 ? g->K : g->C;
+    {
+        const long long total = (long long)g->R * g->S * g->C * g->K;
+        PnpProfScope ps(cls, st, 0.0, 4.0 * total + 6.0 * total, "x3s_filter_kernel<%s>", kind ? "true" : "false");
+        const unsigned blocks = (unsigned)pnp_cdiv(total, 256);
+        if (kind) hipLaunchKernelGGL((x3s_filter_kernel<true>), dim3(blocks), dim3(256), 0, st, a.w, w3, Cin, Kout, pl.taps);
+        else hipLaunchKernelGGL((x3s_filter_kernel<false>), dim3(blocks), dim3(256), 0, st, a.w, w3, Cin, Kout, pl.taps);
+        PNP_CHECK_LAUNCH("x3s_filter_kernel");
+    }
+    X3sArgs x{};
+    x.x = a.x; x.w3 = w3; x.y = a.y;
+    x.N = g->N; x.C = Cin; x.K = Kout; x.NH = Cin / 32;
+    if (kind == 0) { x.H = g->H; x.W = g->W; x.si = g->stride; x.OHt = g->OH; x.OWt = g->OW; x.o_s = 1; }
+    else { x.H = g->OH; x.W = g->OW; x.si = 1; x.OHt = g->H; x.OWt = g->W; x.o_s = g->stride; }
+    x.ngroups = pl.ngroups; x.nitems = pl.nitems;
+    x.w3_bytes = (unsigned)fbytes;
+    for (int i = 0; i < pl.ngroups; ++i) x.grp[i] = pl.grp[i];
+    for (int i = 0; i < X3S_MAXPH; ++i) x.ph[i] = pl.ph[i];
+    x.do_drop = a.do_drop; x.drop_thresh = a.drop_thresh; x.drop_key = a.drop_key; x.drop_keep = a.drop_keep; x.sp = a.sp; x.drop_sid = a.drop_sid;
+    x.stat_ws = kind == 0 ? a.stat_ws : nullptr; x.stat_shift = a.stat_shift;
+    const dim3 grid((unsigned)(pl.nitems > 256 ? 256 : pl.nitems));
+    // flops = the bf16 MFMA flops the kernel EXECUTES: six plane products per useful fp32 multiply-add (every forward tap exactly once per
+    // output pixel of the forward, or per input pixel of the data gradient)
+    const double fl = 6.0 * 2.0 * (double)g->N * g->OH * g->OW * g->R * g->S * g->C * g->K;
+    const double by = 4.0 * ((double)g->N * x.H * x.W * Cin + (double)g->N * x.OHt * x.OWt * Kout) + 6.0 * g->R * g->S * g->C * g->K;
+    PnpProfScope ps(cls, st, fl, by, "conv_x3_direct_kernel_strided<%d>", kind);
+    if (kind) hipLaunchKernelGGL((conv_x3_direct_kernel_strided<1>), grid, dim3(512), 0, st, x);
+    else hipLaunchKernelGGL((conv_x3_direct_kernel_strided<0>), grid, dim3(512), 0, st, x);
+    PNP_CHECK_LAUNCH("conv_x3_direct_kernel_strided");
+    return PNP_OK;
+}
 
 bool x3d_chosen(const pnp_conv_geom* g) {
     return x3d_mode() > 0 && g->dtype == PNP_DTYPE_F32 && (g->pad_mode == PNP_PAD_ZERO || (g->pad_t == 0 && g->pad_l == 0)) && dims_ok(g->R, g->S, g->stride, g->dil, g->C, g->K, g->OH, g->OW, (long long)g->N * g->OH * g->OW);
@@ -450,5 +963,12 @@ int launch_x3_direct(const ConvArgs& a, int kind, bool flip_transpose, void* ws,
 extern "C" int32_t pnp_conv2d_x3_direct(int32_t mode) {
     const int prev = x3d_mode();
     if (mode >= 0) g_x3d_mode.store(mode > 2 ? 2 : mode, std::memory_order_relaxed);
+    return prev;
+}
+
+// the strided layers' share of that route (PNP_X3_STRIDED): 0 off, 1 on (where pnp_conv2d_x3_direct's mode allows)
+extern "C" int32_t pnp_conv2d_x3_strided(int32_t mode) {
+    const int prev = x3s_mode();
+    if (mode >= 0) g_x3s_mode.store(mode > 0 ? 1 : 0, std::memory_order_relaxed);
     return prev;
 }
