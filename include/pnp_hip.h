@@ -143,6 +143,14 @@ int32_t pnp_conv2d_x3_direct(int32_t mode);
  * stride-1 convolutions over the input's stride phases, the data gradient as all output stride phases in one persistent launch.  Taken under
  * pnp_conv2d_x3_direct's mode (1: >= 256 items) while this switch is 1 (default; environment PNP_X3_STRIDED); 0: off.  Returns the previous value. */
 int32_t pnp_conv2d_x3_strided(int32_t mode);
+/* The FILTER GRADIENT of the stride-1 layers on the same arithmetic (csrc/conv_x3_wgrad.hip: 3x3, dilation 1, zero padding, fp32 geometry, 32
+ * or 64 input channels, 64 filters, output a multiple of 16 x 16): x patches and dy tiles split into three bf16 planes in the loaders,
+ * transposed on the way out of LDS, six plane products per fragment pair, the whole [9][C][64] gradient in registers for the launch; one
+ * partial sum per persistent workgroup (two with 32 channels) through pnp_conv2d_wgrad_workspace_bytes(g) of workspace, summed in a fixed
+ * order (deterministic; pnp_conv2d_wgrad_acc adds into dw there).  Asked after the Winograd filter-gradient planner, before the fp32-pipe
+ * kernels.  Taken under pnp_conv2d_x3_direct's mode (1: >= 256 tiles) while this switch is 1 (default; environment PNP_X3_WGRAD); 0: off.
+ * Returns the previous value (mode < 0: read only). */
+int32_t pnp_conv2d_x3_wgrad(int32_t mode);
 /* Transformed-filter cache of the route.  U = G g G^T (36 C K values per filter and pass: fp32, or three bf16 planes) only changes when the filter does: the caller
  * lends one buffer per (filter, pass) and reports weight writes; a launch whose filter has a valid entry skips wino_filter_kernel (the
  * frozen source segmenter / shared half of adversarial.py:839-882 never pay it again, a trained layer once per update instead of once per

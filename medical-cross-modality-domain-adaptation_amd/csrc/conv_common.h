@@ -393,6 +393,12 @@ int launch_x3_direct(const ConvArgs& a, int kind, bool flip_transpose, void* ws,
 bool x3s_chosen(const pnp_conv_geom* g, int kind);
 size_t x3s_filter_bytes(const pnp_conv_geom* g);
 int launch_x3_strided(const ConvArgs& a, const pnp_conv_geom* g, int kind, void* ws, size_t ws_bytes, hipStream_t st);
+// ... and the filter gradient of its stride-1 layers with 64 filters (conv_x3_wgrad.hip, PNP_X3_WGRAD).  x3w_chosen: the one predicate of the
+// workspace query and the launch; the partial sums pass through x3w_workspace_bytes(g) of workspace.  x3d_route_mode: PNP_X3_DIRECT's mode
+int x3d_route_mode();
+bool x3w_chosen(const pnp_conv_geom* g);
+size_t x3w_workspace_bytes(const pnp_conv_geom* g);
+int launch_x3_wgrad(const float* x, const float* dy, float* dw, const pnp_conv_geom* g, int accumulate, void* ws, size_t ws_bytes, hipStream_t st);
 bool wino_chosen(const pnp_conv_geom* g);
 int wino_tile(const pnp_conv_geom* g);
 size_t wino_workspace_bytes(const pnp_conv_geom* g);

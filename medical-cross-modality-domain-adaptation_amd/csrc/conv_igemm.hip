@@ -2055,6 +2055,7 @@ int launch_wgd(const WgdArgs& a, const WgdPlan& pl, hipStream_t st) {
 
 size_t wgrad_ws(const pnp_conv_geom* g) {
     if (wino_wgrad_chosen(g)) return wino_wgrad_workspace_bytes(g);         // Winograd route (conv_wino.hip)
+    if (x3w_chosen(g)) return x3w_workspace_bytes(g);                       // direct split-bf16 route (conv_x3_wgrad.hip)
     const size_t nout = (size_t)g->R * g->S * g->C * g->K;
     if (n16_wgrad_ok(g)) return (size_t)n16_wgrad_blocks(g) * nout * sizeof(float);
     const long long P = (long long)g->N * g->OH * g->OW;
@@ -2586,6 +2587,8 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, const pnp_conv
     if (!ws) workspace_bytes = 0;
     if (wino_wgrad_chosen(g) && workspace_bytes >= wino_wgrad_workspace_bytes(g))
         return launch_wino_wgrad(a, dw, accumulate, workspace, workspace_bytes, st);
+    if (x3w_chosen(g) && workspace_bytes >= x3w_workspace_bytes(g))
+        return launch_x3_wgrad(x, dy, dw, g, accumulate, workspace, workspace_bytes, st);
     if (n16_wgrad_ok(g) && workspace_bytes >= wgrad_ws(g)) {
         if (int e = launch_n16_wgrad(a, ws, st)) return e;
         const size_t nout = (size_t)a.Kred * a.K;

@@ -23,6 +23,7 @@
 // partial-count queries go through the same functions).  PNP_X3_DIRECT / pnp_conv2d_x3_direct(): 0 off, 1 where a launch fills the chip, 2 wherever the shapes allow.
 // The strided layers (conv_x3_direct_kernel_strided below, PNP_X3_STRIDED): forward and stride-phase data gradient as sums of stride-1
 // sub-convolutions on the same LDS layout, MFMA order and epilogue; entered from pnp_conv2d_fwd* / dgrad_impl through x3s_chosen().
+// The FILTER gradient of the stride-1 layers with 64 filters is conv_x3_wgrad.hip (PNP_X3_WGRAD), under this file's mode (x3d_route_mode()).
 #include <atomic>
 #include <cstdlib>
 #include "conv_common.h"
@@ -852,6 +853,8 @@ bool x3s_plan(const pnp_conv_geom* g, int kind, X3sPlan* pl) {
 }  // namespace
 
 namespace pnpconv {
+
+int x3d_route_mode() { return x3d_mode(); }
 
 bool x3s_chosen(const pnp_conv_geom* g, int kind) { return x3s_plan(g, kind, nullptr); }
 

@@ -169,6 +169,12 @@ def x3_strided(mode=-1):
     return int(_lib.load().pnp_conv2d_x3_strided(int(mode)))
 
 
+def x3_wgrad(mode=-1):
+    """the filter gradient of the stride-1 3x3 layers with 32 / 64 input channels and 64 filters on the direct split-bf16 kernel
+    (csrc/conv_x3_wgrad.hip), under x3_direct's mode: 0 off, 1 on; returns the previous value (mode < 0: read only)"""
+    return int(_lib.load().pnp_conv2d_x3_wgrad(int(mode)))
+
+
 def wino_chosen(g, kind=0):
     """pnp_conv2d_fwd* (kind 0) / pnp_conv2d_dgrad* (kind 1) / pnp_conv2d_wgrad* (kind 2) of this layer (g = the forward geometry): 0 = the
     direct kernels, else the output tile edge of the Winograd route (2 or 4) — truthy exactly when the layer is on the route"""

@@ -108,6 +108,8 @@ def main():
         tot["dgrad"] += td * cnt
         tot["wgrad"] += tw * cnt
         totflop += flop * cnt
+    if tot["fwd"] <= 0.0:                           # (ONLY= picked layers the segmenter does not have)
+        return
     print("segmenter conv totals (ms): fwd %.2f dgrad %.2f wgrad %.2f ; fwd GFLOP %.1f -> %.1f TF/s (%.1f%% of %.1f)" % (
         tot["fwd"], tot["dgrad"], tot["wgrad"], totflop / 1e9, totflop / tot["fwd"] / 1e9, 100 * totflop / tot["fwd"] / 1e9 / PEAK, PEAK))
 
