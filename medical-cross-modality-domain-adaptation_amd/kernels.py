@@ -345,6 +345,7 @@ _filter_cache = {}
 CAST_COUNT = [0]          # on-demand casts since the last reset (tests / profiling: how many producers still lack a bf16 output)
 
 
+RECORDING = [None]        # token of the hipGraph recording in progress (step_capture.CapturedStep): filter_shadows casts once per recording
 PINNED = [0]              # live CapturedStep objects: their hipGraphs hold the ADDRESSES of filter shadows — nothing may be freed under them
 
 
@@ -424,14 +425,21 @@ def filter_shadows(w):
     # valid: same weight epoch (kernels that write weights), same torch version counter (an in-place torch op on the filter or the arena
     # it is a view of), same owner object (a new tensor on a recycled address is another filter)
     owner = w._base if w._base is not None else w
-    if ent is None or ent[3] != w._version or ent[4]() is not owner or (ent[0] != _WEIGHT_EPOCH[0] and _changed_since(ent[0], key[0], key[0] + 4 * w.numel())):
+    # While a hipGraph is being recorded the refresh is ALWAYS taken once per recording (as bf16_of does): a shadow that happens to be
+    # fresh at capture time would leave its cast out of the graph, and every replay would then read the copy of whatever the filter held
+    # when it was recorded — the filters another graph updates (the generator's, read by the dis graph) or a state_dict loaded after the
+    # recording.  (Once: RECORDING names the recording; a second read of the same filter in it follows the ordinary staleness rule.)
+    # The other way round, a cast that was only RECORDED has not run: outside that recording its entry counts as stale.
+    rec = (RECORDING[0] if RECORDING[0] is not None else object()) if torch.cuda.is_current_stream_capturing() else None
+    if ent is None or ent[5] is not rec or ent[3] != w._version or ent[4]() is not owner or \
+            (ent[0] != _WEIGHT_EPOCH[0] and _changed_since(ent[0], key[0], key[0] + 4 * w.numel())):
         if ent is None:
             w_io, w_oi = filter_bf16(w)
         else:                   # refresh in place: same buffers, no allocation in the steady state
             w_io, w_oi = ent[1], ent[2]
             R, S, C, Kc = w.shape
             check(_lib.load().pnp_filter_bf16(_p(w), _ph(w_io), _ph(w_oi), R, S, C, Kc, _stream()), "pnp_filter_bf16")
-        ent = (_WEIGHT_EPOCH[0], w_io, w_oi, w._version, weakref.ref(owner))
+        ent = (_WEIGHT_EPOCH[0], w_io, w_oi, w._version, weakref.ref(owner), rec)
         _filter_cache[key] = ent
     return ent[1], ent[2]
 

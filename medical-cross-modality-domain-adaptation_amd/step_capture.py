@@ -57,10 +57,12 @@ class CapturedStep(object):
         self.graph = torch.cuda.CUDAGraph()
         _lib.check(lib.pnp_step_params_bind(self._bp), "pnp_step_params_bind")
         t0 = adam.t if adam is not None else 0
+        K.RECORDING[0] = object()                        # every filter shadow the step reads is cast inside the recording, once
         try:
             with torch.cuda.graph(self.graph):
                 self.out = fn(*self.static)
         finally:
+            K.RECORDING[0] = None
             _lib.check(lib.pnp_step_params_bind(None), "pnp_step_params_bind")
             if adam is not None:
                 adam.t = t0                              # recording executes nothing: the counter moved, the weights did not

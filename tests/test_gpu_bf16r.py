@@ -98,6 +98,41 @@ def test_resident_fwd_dgrad_wgrad_vs_rounded_oracle(dev, case):
     assert all(e < 2e-5 for e in errs.values()), errs
 
 
+def test_resident_256x128_tile_data_gradient_vs_rounded_oracle(dev):
+    """the 256x128 tile (8 waves, 3 LDS stages: plan_tile 0, taken at cdiv(M, 256) * (K / 128) >= 256) as a DATA GRADIENT — the dominant
+    symbol of the bf16 joint step, which the table above reaches for one forward only (group_10).  (16, 64, 64, 128 -> 128) is the
+    cheapest layer whose data gradient meets the predicate (M = 65536 pixels of dx, 128 output channels: exactly 256 tiles).  The tile
+    is asserted from the symbol: <BM, BN, WM, WN, BKC, KIND, R, S, NBUF, 1>."""
+    K, L = pkg("kernels"), pkg("_lib")
+    N, H, C, Kf = 16, 64, 128, 128
+    assert -(-(N * H * H) // 256) * (C // 128) >= 256           # the predicate of conv_bf16r.hip's plan_tile, for the data gradient
+    rng = np.random.default_rng(N + H + C + Kf)
+    x = rng.standard_normal((N, H, H, C)).astype(np.float32)
+    w = (rng.standard_normal((3, 3, C, Kf)) * np.sqrt(2.0 / (9 * C))).astype(np.float32)
+    dy = rng.standard_normal((N, H, H, Kf)).astype(np.float32)
+    res = rng.standard_normal(x.shape).astype(np.float32)
+    g = K.conv_geom(x.shape, w.shape, 1, 1, "SAME", dtype=L.DTYPE_BF16)
+    assert K.bf16r_served(g, 0) and K.bf16r_served(g, 1)
+    xd, wd, dyd, resd = (torch.from_numpy(a).to(dev) for a in (x, w, dy, res))
+    xh, dyh = K.cast_bf16(xd), K.cast_bf16(dyd)
+    w_io, w_oi = K.filter_bf16(wd)
+    rb = lambda a: T.round_bf16(torch.from_numpy(a)).double()
+    xg = rb(x).requires_grad_(True)
+    yo = T.conv2d(xg, rb(w), 1, 1, "SAME")
+    yo.backward(rb(dy))
+    (dx, dxh), names = _ran(L, lambda: K.conv2d_dgrad_bf16r(dyh, w_io, g, want_h=True), L.PROF_CONV_DGRAD)
+    assert names == ["conv_bf16r_kernel<256, 128, 4, 2, 64, 1, 3, 3, 3, 1>"], names
+    (dx2, _), names_r = _ran(L, lambda: K.conv2d_dgrad_bf16r(dyh, w_io, g, residual=resd), L.PROF_CONV_DGRAD)
+    assert names_r == names, names_r
+    (y, _, _), names_f = _ran(L, lambda: K.conv2d_fwd_bf16r(xh, w_oi, g), L.PROF_CONV_FWD)
+    assert names_f == ["conv_bf16r_kernel<256, 128, 4, 2, 64, 0, 3, 3, 3, 1>"], names_f
+    errs = {"dx": _rel(dx, xg.grad), "dx+res": _rel(dx2, xg.grad + torch.from_numpy(res).double()), "y": _rel(y, yo)}
+    print("resident bf16 256x128 tile (%d, %d, %d, %d->%d): %s; ran %s" % (N, H, H, C, Kf, {k_: "%.2e" % e for k_, e in errs.items()},
+                                                                         names + names_f))
+    assert torch.equal(dxh.float(), dx.bfloat16().float())
+    assert all(e < 2e-5 for e in errs.values()), errs
+
+
 def test_resident_forward_epilogues_statistics_dropout_fused_bn(dev):
     """the resident forward shares conv_epilogue with the fp32 kernels: dropout mask stream, BN-statistics partials (its OWN tile
     geometry: pnp_conv2d_fwd_bf16r_stats_parts) and the fused inference BN + shortcut + leaky-ReLU — held to the separate kernels"""

@@ -77,8 +77,21 @@ def _segmenter_capture_case(dev):
     assert tr_c._cap["step"].replays == n0
 
 
-def test_captured_gan_steps_equal_eager_bit_for_bit(dev):
-    adv = pkg("adversarial")
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_captured_gan_steps_equal_eager_bit_for_bit(dev, dtype):
+    """bf16: the recordings must hold the casts of every filter shadow they read (kernels.filter_shadows) — the dis graph convolves with
+    the generator filters the gen graph has just updated, and a load_state_dict after capture_steps must reach the next replay."""
+    F = pkg("functional")
+    F.set_conv_dtype(dtype)
+    try:
+        _gan_capture_case(dev, dtype)
+    finally:
+        pkg("_lib").prof_enable(0)
+        F.set_conv_dtype("f32")
+
+
+def _gan_capture_case(dev, dtype):
+    adv, L = pkg("adversarial"), pkg("_lib")
     from test_gpu_adversarial import COST as GCOST, NETCFG, he_state
     B = 2
     rng = np.random.default_rng(0)
@@ -101,7 +114,16 @@ def test_captured_gan_steps_equal_eager_bit_for_bit(dev):
             out.append(float(tr.dis_step(mr, ct, 0.75, 2 * i + 1)))
             out.append(float(tr.gen_step(ct, 0.75, 2 * i + 2)))
         return out
+    L.prof_summary()
+    L.prof_enable(L.PROF_CONV_FWD | L.PROF_CONV_DGRAD | L.PROF_CONV_WGRAD)
     le = run(tr_e)
+    torch.cuda.synchronize()
+    L.prof_enable(0)
+    names = [r_["name"] for r_ in L.prof_summary() for _ in range(r_["launches"])]
+    share = sum("bf16" in n for n in names) / float(len(names))
+    print("captured GAN steps (%s): %.0f %% of the eager trainer's %d conv launches on bf16 kernels" % (dtype, 100 * share, len(names)))
+    # (a silent float32 run would pass the comparison below for the wrong reason; the bar is test_joint_step_bf16_within_budget's)
+    assert share > 0.5 if dtype == "bf16" else not any("bf16" in n for n in names), share
     w_e = net_e.store.arena.detach().cpu().clone()
     net_c, tr_c = make()
     net_c.store.load_state_dict(sd)
@@ -126,6 +148,8 @@ def test_captured_gan_steps_equal_eager_bit_for_bit(dev):
     for o in (tr_c.dis_optimizer, tr_c.gen_optimizer):          # RMSProp slots back to their initial value (ones: TF's initial ms)
         o.ms.copy_(torch.ones_like(o.ms))
     lc = run(tr_c)
+    print("captured GAN steps (%s): losses eager %s captured %s; arenas differ in %d of %d floats" % (
+        dtype, le, lc, int((net_c.store.arena.detach().cpu() != w_e).sum()), w_e.numel()))
     assert tr_c._cap["dis"].replays == 2 and tr_c._cap["gen"].replays == 2
     assert lc == le, (lc, le)
     assert torch.equal(net_c.store.arena.detach().cpu(), w_e)

@@ -775,6 +775,52 @@ def test_captured_gan_steps_fall_back_to_eager_when_the_learning_rate_moved():
     assert t._captured("gen", 0.75, {"ct": (2, 256, 256, 3)}) is None and t._cap.get("warned")
 
 
+def test_filter_shadows_are_cast_inside_every_recording(monkeypatch):
+    """kernels.filter_shadows (ADVICE r6): a hipGraph recording must hold the cast of every bf16 filter shadow it reads, fresh or not —
+    once per filter and recording; a cast that was only recorded has not run, so the next eager reader casts again"""
+    K = pkg("kernels")
+    casts = []
+
+    class FakeLib(object):
+        def pnp_filter_bf16(self, *a):
+            casts.append("refresh")
+            return 0
+
+    capturing = [False]
+    monkeypatch.setattr(K._lib, "load", lambda: FakeLib())
+    monkeypatch.setattr(K, "_p", lambda t: t)
+    monkeypatch.setattr(K, "_ph", lambda t: t)
+    monkeypatch.setattr(K, "_stream", lambda: None)
+    monkeypatch.setattr(K, "filter_bf16", lambda w: (casts.append("new"), torch.zeros(1), torch.zeros(1))[1:])
+    monkeypatch.setattr(K, "_filter_cache", {})
+    monkeypatch.setattr(K, "_u_cache", {})
+    monkeypatch.setattr(K, "RECORDING", [None])
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: capturing[0])
+    w = torch.zeros(3, 3, 32, 64)
+    K.filter_shadows(w)
+    K.filter_shadows(w)
+    assert casts == ["new"]                               # eager: fresh shadows are reused
+    for _ in range(2):                                    # two recordings: each holds the cast, once
+        capturing[0], K.RECORDING[0] = True, object()
+        del casts[:]
+        K.filter_shadows(w)
+        K.filter_shadows(w)
+        assert casts == ["refresh"]
+        K.weights_changed([(w.data_ptr(), w.data_ptr() + 4 * w.numel())])     # an optimiser node in the middle of the recording
+        K.filter_shadows(w)
+        assert casts == ["refresh", "refresh"]
+    capturing[0], K.RECORDING[0] = False, None
+    del casts[:]
+    K.filter_shadows(w)                                   # the recorded cast has not run
+    K.filter_shadows(w)
+    assert casts == ["refresh"]
+    capturing[0] = True                                   # a recording that is not a CapturedStep's: every read is cast
+    del casts[:]
+    K.filter_shadows(w)
+    K.filter_shadows(w)
+    assert casts == ["refresh", "refresh"]
+
+
 def test_memory_report_counts_what_the_caches_hold():
     """kernels.memory_report (VERDICT r5 weak #10): every cache the host side keeps between steps is in the sum"""
     import torch
