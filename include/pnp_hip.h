@@ -116,6 +116,23 @@ int pnp_conv2d_fwd_stats_ws(const float* x, const float* w, float* y, const pnp_
                             const float* shift /*nullable*/, float* parts, size_t parts_bytes,
                             void* workspace, size_t workspace_bytes, void* stream);
 int32_t pnp_conv2d_wino_chosen(const pnp_conv_geom* g, int32_t kind);   /* 0: direct kernels; else the route's output tile edge (2 or 4) */
+/* Which kernel family serves a layer, given the workspace its query asks for (kind 0: forward with the plain epilogue; 1: data gradient;
+ * 2: filter gradient — g = the FORWARD geometry): the first candidate of the plan the entry points launch from (csrc/conv_igemm.hip:
+ * plan_fwd / plan_dgrad / plan_wgrad).  pnp_conv2d_wino_chosen stays the Winograd planner's tile, which also sizes the workspace of the
+ * narrow layers that PNP_ROUTE_X3D then runs.  -1: bad geometry. */
+#define PNP_ROUTE_IGEMM 0        /* implicit-GEMM MFMA tiles (forward; data gradient as a convolution of dy, zero-upsampled when strided) */
+#define PNP_ROUTE_N16 1          /* 16-filter 16x16x4-MFMA kernels (conv_small.hip) */
+#define PNP_ROUTE_NARROW 2       /* narrow-output vector-ALU kernel */
+#define PNP_ROUTE_WINO 3         /* Winograd F(2x2) / F(4x4) (conv_wino.hip) */
+#define PNP_ROUTE_X3D 4          /* direct split-bf16, stride 1 (conv_x3_direct.hip) */
+#define PNP_ROUTE_X3S 5          /* direct split-bf16, strided */
+#define PNP_ROUTE_PHASES 6       /* strided data gradient on the fp32 stride-phase kernels */
+#define PNP_ROUTE_WINO_WGRAD 7   /* filter gradient: Winograd */
+#define PNP_ROUTE_X3W 8          /* filter gradient: direct split-bf16 (conv_x3_wgrad.hip) */
+#define PNP_ROUTE_N16_WGRAD 9    /* filter gradient: 16x16x4-MFMA kernel */
+#define PNP_ROUTE_WGD 10         /* filter gradient: vector-ALU kernel */
+#define PNP_ROUTE_RING 11        /* filter gradient: MFMA ring kernel */
+int32_t pnp_conv2d_route(const pnp_conv_geom* g, int32_t kind);
 /* sets the route policy at run time (0 / 1 / 2 as PNP_WINOGRAD; < 0: read only) and returns the previous one */
 int32_t pnp_conv2d_wino_mode(int32_t mode);
 /* Round 5: the route has two output tiles.  F(4x4, 3x3) — 36 multiplications per 4x4 output tile instead of the direct sum's 144

@@ -22,6 +22,9 @@ PAD_SYMMETRIC = 1
 OPT_CHUNK = 1024
 DTYPE_F32, DTYPE_BF16, DTYPE_F64 = 0, 1, 2
 COMM_ID_BYTES = 128
+# PNP_ROUTE_* (pnp_conv2d_route)
+(ROUTE_IGEMM, ROUTE_N16, ROUTE_NARROW, ROUTE_WINO, ROUTE_X3D, ROUTE_X3S, ROUTE_PHASES,
+ ROUTE_WINO_WGRAD, ROUTE_X3W, ROUTE_N16_WGRAD, ROUTE_WGD, ROUTE_RING) = range(12)
 ABI_VERSION = 4
 
 
@@ -75,6 +78,7 @@ PROTOTYPES = {
     "pnp_conv2d_fwd_stats_ws_parts": (c_int32, [_G]),
     "pnp_conv2d_fwd_stats_ws": (c_int, [_F, _F, _F, _G, c_float, c_uint64, c_uint32, _F, _F, c_size_t, c_void_p, c_size_t, c_void_p]),
     "pnp_conv2d_wino_chosen": (c_int32, [_G, c_int32]),
+    "pnp_conv2d_route": (c_int32, [_G, c_int32]),
     "pnp_conv2d_wino_mode": (c_int32, [c_int32]),
     "pnp_conv2d_wino_wgrad_mode": (c_int32, [c_int32]),
     "pnp_conv2d_wino_tile": (c_int32, [c_int32]),

@@ -1,5 +1,6 @@
 // conv_common.h — what the convolution translation units share: the kernel argument block, tile / XCD mapping, accumulators and the
-// buffer-descriptor loads (conv_igemm.hip: fp32 MFMA + vector-ALU kernels and ALL host planning; conv_bf16.hip: bf16-operand MFMA kernels).
+// buffer-descriptor loads (conv_igemm.hip: fp32 MFMA + vector-ALU kernels, the plan of every pass — plan_fwd / plan_dgrad / plan_wgrad, the
+// one place that combines the predicates declared below — and the entry points; conv_bf16.hip: bf16-operand MFMA kernels).
 #pragma once
 #include "pnp_common.h"
 
@@ -377,35 +378,33 @@ int n16_wgrad_blocks(const pnp_conv_geom* g);
 int launch_n16_wgrad(const ConvArgs& a, float* part, hipStream_t st);
 // Winograd F(2x2, 3x3) route of the wide stride-1 3x3 convolutions, forward and data gradient (conv_wino.hip).  eligible: the geometry can
 // run it; chosen: eligible and the policy takes it (PNP_WINOGRAD = 0 never / 1 where the cost model says it pays / 2 wherever eligible).
-// launch_wino honours the whole epilogue of ConvArgs (dropout, residual add, statistics partials, fused inference BN); its statistics
+// launch_wino runs Winograd and nothing else, with the whole epilogue of ConvArgs (dropout, residual add, statistics partials, fused inference BN); its statistics
 // partial rows are the tile slabs of the output transform (wino_stats_parts), not the direct kernel's wave rows.
 // Round 5: the route has two output tiles, F(2x2, 3x3) and F(4x4, 3x3) (36 instead of 64 multiplications per 4x4 outputs; PNP_WINOGRAD_TILE /
 // pnp_conv2d_wino_tile: the largest the planner may pick).  wino_tile: 0 (direct kernels), 2 or 4 for the forward of this geometry.
 bool wino_eligible(const pnp_conv_geom* g);
-// conv_x3_direct.hip: direct split-bf16 3x3 convolutions of the narrow layers; launch_wino() hands over what x3d_chosen() takes
+// conv_x3_direct.hip: direct split-bf16 3x3 convolutions of the narrow layers x3d_chosen() takes (the plan's route X3D, ahead of Winograd;
+// no fused inference BN)
 bool x3d_chosen(const pnp_conv_geom* g);
-bool x3d_chosen(const ConvArgs& a);
 int x3d_stats_parts(const pnp_conv_geom* g);
 size_t x3d_filter_bytes(int C, int K);
 int launch_x3_direct(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st);
 // ... and its strided layers (stride 2..4, zero padding): the forward (kind 0) as a sum over the input's stride phases, the data gradient
-// (kind 1) as all output stride phases in one launch; g = the FORWARD geometry.  x3s_chosen: the one predicate of workspace, partials and launch
+// (kind 1) as all output stride phases in one launch; g = the FORWARD geometry.  x3s_chosen: can / should the family take the layer (route X3S)
 bool x3s_chosen(const pnp_conv_geom* g, int kind);
 size_t x3s_filter_bytes(const pnp_conv_geom* g);
 int launch_x3_strided(const ConvArgs& a, const pnp_conv_geom* g, int kind, void* ws, size_t ws_bytes, hipStream_t st);
-// ... and the filter gradient of its stride-1 layers with 64 filters (conv_x3_wgrad.hip, PNP_X3_WGRAD).  x3w_chosen: the one predicate of the
-// workspace query and the launch; the partial sums pass through x3w_workspace_bytes(g) of workspace.  x3d_route_mode: PNP_X3_DIRECT's mode
+// ... and the filter gradient of its stride-1 layers with 64 filters (conv_x3_wgrad.hip, PNP_X3_WGRAD).  x3w_chosen: can / should the family
+// take the layer (route X3W); the partial sums pass through x3w_workspace_bytes(g) of workspace.  x3d_route_mode: PNP_X3_DIRECT's mode
 int x3d_route_mode();
 bool x3w_chosen(const pnp_conv_geom* g);
 size_t x3w_workspace_bytes(const pnp_conv_geom* g);
 int launch_x3_wgrad(const float* x, const float* dy, float* dw, const pnp_conv_geom* g, int accumulate, void* ws, size_t ws_bytes, hipStream_t st);
-bool wino_chosen(const pnp_conv_geom* g);
 int wino_tile(const pnp_conv_geom* g);
 size_t wino_workspace_bytes(const pnp_conv_geom* g);
 int wino_stats_parts(const pnp_conv_geom* g);
 int launch_wino(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st);
 // the filter gradient on the same route (its own switch, PNP_WINOGRAD_WGRAD): a = make_args(x, dy, -, g) of the forward geometry
-bool wino_wgrad_chosen(const pnp_conv_geom* g);
 int wino_wgrad_tile(const pnp_conv_geom* g);
 size_t wino_wgrad_workspace_bytes(const pnp_conv_geom* g);
 int launch_wino_wgrad(const ConvArgs& a, float* dw, int accumulate, void* ws, size_t ws_bytes, hipStream_t st);

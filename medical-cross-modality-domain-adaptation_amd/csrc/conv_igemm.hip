@@ -22,7 +22,9 @@
 //   wgrad_direct(4)_kernel  filter gradient for K <= 16 on the vector ALUs (dy through the scalar cache) + splitk_reduce_many_kernel
 //   flip_transpose(_phase)_kernel, splitk_reduce(_scatter/_drop)_kernel, sympad_fwd/bwd_kernel, bn_fold_kernel, naive_conv_kernel
 // Host planners: choose_tile / choose_split (dispatch-round filling), plan_phases (strided data gradients), wgrad_plan_split, wgd_plan,
-// narrow_fwd_ok — their decisions are visible through the pnp_conv2d_*_workspace_bytes queries (tests/test_abi.py).
+// narrow_fwd_ok answer "can / should this family take the layer", like the route files' predicates (conv_common.h).  plan_fwd / plan_dgrad /
+// plan_wgrad alone COMBINE them: one cascade per pass, read by the workspace / partial-row / route queries (pnp_conv2d_*_workspace_bytes,
+// pnp_conv2d_fwd_stats*_parts, pnp_conv2d_wino_chosen, pnp_conv2d_route; tests/test_abi.py) and by the entry points, which switch on the route.
 //
 // LDS layouts (dwords):
 //   fwd  A tile  [BM][36]     row = output pixel, 32 k's contiguous (+4 pad). A fragments are read with
@@ -2053,20 +2055,6 @@ int launch_wgd(const WgdArgs& a, const WgdPlan& pl, hipStream_t st) {
     return PNP_OK;
 }
 
-size_t wgrad_ws(const pnp_conv_geom* g) {
-    if (wino_wgrad_chosen(g)) return wino_wgrad_workspace_bytes(g);         // Winograd route (conv_wino.hip)
-    if (x3w_chosen(g)) return x3w_workspace_bytes(g);                       // direct split-bf16 route (conv_x3_wgrad.hip)
-    const size_t nout = (size_t)g->R * g->S * g->C * g->K;
-    if (n16_wgrad_ok(g)) return (size_t)n16_wgrad_blocks(g) * nout * sizeof(float);
-    const long long P = (long long)g->N * g->OH * g->OW;
-    const int bn = ((g->K & 3) != 0 || g->K <= 32) ? 32 : (g->K > 64 ? 128 : 64);
-    const int nblk = pnp_cdiv((long long)g->R * g->S * g->C, 128) * pnp_cdiv(g->K, bn);
-    const int nsplit = wgrad_plan_split(nblk, pnp_cdiv(P, BK));
-    const size_t mfma_ws = nsplit <= 1 ? 0 : (size_t)nsplit * nout * sizeof(float);
-    const WgdPlan pl = wgd_plan(g);
-    return (pl.use && pl.ws_bytes > mfma_ws) ? pl.ws_bytes : mfma_ws;
-}
-
 // ---- strided data gradient, one stride-phase at a time ---------------------------------------------------------------------
 // dx[h] only receives filter taps r with r = (h + pad) mod stride (mod stride), so the pixels of one residue class ("phase") form an
 // ordinary stride-1 convolution of dy with the sub-filter {r = a, a+stride, ...}:
@@ -2176,21 +2164,27 @@ int launch_phase_group(const float* dy, const float* wt, float* outp, const pnp_
 
 }  // namespace
 
-// the forward on the direct split-bf16 kernels (conv_x3_direct.hip) — THE predicate of the workspace, the partial count and the launches:
-// 0 no; 1 the stride-1 kernel; 2 the strided one
-static int fwd_x3_route(const pnp_conv_geom* g) {
-    if (wino_chosen(g) || n16_geom_ok(g) || narrow_fwd_ok(g, nullptr)) return 0;
-    if (x3d_chosen(g)) return 1;
-    return x3s_chosen(g, 0) ? 2 : 0;
-}
-static size_t fwd_x3_bytes(const pnp_conv_geom* g, int route) {
-    return route == 1 ? x3d_filter_bytes(g->C, g->K) : (route == 2 ? x3s_filter_bytes(g) : 0);
-}
+// ---- one plan per pass ---------------------------------------------------------------------------------------------------------
+// plan_fwd / plan_dgrad / plan_wgrad are the ONLY code that combines the families' predicates (n16_geom_ok, narrow_fwd_ok, wino_tile,
+// x3d_chosen, x3s_chosen, plan_phases, x3w_chosen, n16_wgrad_ok, wgd_plan, choose_tile / choose_split, wgrad_plan_split): each states the
+// precedence of its pass once, top to bottom.  The workspace / partial-row / route queries read the plan, and the entry points take the
+// first candidate whose workspace the caller brought and switch on its route.
+struct ConvPlan {
+    struct Cand { int route; size_t need; } cand[5];   // PNP_ROUTE_*, in order of preference; need: workspace bytes the launch asks for
+    int ncand;
+    size_t ws_bytes;      // what the pass's *_workspace_bytes query reports
+    int stats_parts;      // partial rows of the statistics epilogue on cand[0]; 0 = none
+    int tile;             // the Winograd planner's tile (0 / 2 / 4): it sizes the workspace ALSO where X3D takes the launch
+    void add(int route, size_t need) { cand[ncand].route = route; cand[ncand].need = need; ++ncand; }
+    const Cand& pick(const void* ws, size_t ws_bytes) const {
+        int i = 0;
+        while (i + 1 < ncand && cand[i].need > 0 && !(ws && ws_bytes >= cand[i].need)) ++i;
+        return cand[i];
+    }
+};
 
-extern "C" {
-
-// forward: only layers that leave at least 3/4 of the workgroup slots empty — at half a dispatch round the extra pass over the partials
-// costs more than the idle CUs (128->128@32^2, 256 tiles: 0.049 ms unsplit, 0.060 split in two)
+// forward reduction split: only layers that leave at least 3/4 of the workgroup slots empty — at half a dispatch round the extra pass over
+// the partials costs more than the idle CUs (128->128@32^2, 256 tiles: 0.049 ms unsplit, 0.060 split in two)
 static int fwd_split(const pnp_conv_geom* g) {
     if (g->pad_mode != PNP_PAD_ZERO) return 1;
     const long long M = (long long)g->N * g->OH * g->OW;
@@ -2200,15 +2194,175 @@ static int fwd_split(const pnp_conv_geom* g) {
     return choose_split(M, g->K, g->R * g->S * g->C, tile);
 }
 
-size_t pnp_conv2d_fwd_workspace_bytes(const pnp_conv_geom* g) {
-    if (!g) return 0;
-    if (wino_chosen(g)) return wino_workspace_bytes(g);           // Winograd route: transformed filter + input + product (conv_wino.hip)
+// what the ENTRY POINT asks of the forward: it takes a workspace / leaves statistics partials / applies the fused inference BN
+enum { EP_WS = 1, EP_STATS = 2, EP_BN = 4 };
+
+static ConvPlan plan_fwd(const pnp_conv_geom* g, unsigned ep) {
+    const bool ws = ep & EP_WS, stats = ep & EP_STATS, bn = ep & EP_BN;
+    ConvPlan p{};
+    p.tile = wino_tile(g);
+    const long long M = (long long)g->N * g->OH * g->OW;
     const int ns = fwd_split(g);
-    const size_t split = ns > 1 ? (size_t)ns * g->N * g->OH * g->OW * g->K * sizeof(float) : 0;
-    // direct split-bf16 convolution of a narrow layer the Winograd planner leaves alone (conv_x3_direct.hip): its filter image
-    const size_t x3d = fwd_x3_bytes(g, fwd_x3_route(g));
-    return split > x3d ? split : x3d;
+    const size_t split = ns > 1 ? (size_t)ns * M * g->K * sizeof(float) : 0;
+    p.ws_bytes = split;
+    if (n16_geom_ok(g)) p.add(PNP_ROUTE_N16, 0);
+    else if (!bn && narrow_fwd_ok(g, nullptr)) p.add(PNP_ROUTE_NARROW, 0);      // (no fused BN in the vector-ALU kernel)
+    else {
+        // the direct split-bf16 kernels (conv_x3_direct.hip) have dropout, statistics and the residual add, not the fused BN
+        const bool x3d = x3d_chosen(g);
+        if (p.tile) {
+            // the Winograd planner's layer: transformed filter + input + product (conv_wino.hip) — ALSO where the narrow layers then run on
+            // the direct split-bf16 kernel, whose filter image is smaller
+            p.ws_bytes = wino_workspace_bytes(g);
+            if (ws) p.add(x3d && !bn ? PNP_ROUTE_X3D : PNP_ROUTE_WINO, p.ws_bytes);
+        } else {
+            const size_t x3 = x3d ? x3d_filter_bytes(g->C, g->K) : (x3s_chosen(g, 0) ? x3s_filter_bytes(g) : 0);      // the split filter image
+            if (x3 > split) p.ws_bytes = x3;
+            if (x3 && ws && !bn) p.add(x3d ? PNP_ROUTE_X3D : PNP_ROUTE_X3S, x3);
+            else if (split && ws && !stats && !bn) p.add(PNP_ROUTE_IGEMM, split);      // need > 0: the reduction-split launch
+        }
+        p.add(PNP_ROUTE_IGEMM, 0);     // un-split (same result up to fp32 rounding): what runs when the workspace is missing
+    }
+    if (stats) {
+        const int r = p.cand[0].route;
+        // implicit GEMM: pixel tiles x wave rows of the tile (WM), from an un-split reduction only (the epilogue owns complete rows there);
+        // Winograd: the tile slabs of its output transform; the direct split-bf16 kernels: one partial per 64 output pixels
+        const int tile = choose_tile(M, g->K);
+        if (r == PNP_ROUTE_IGEMM) p.stats_parts = ns > 1 ? 0 : pnp_cdiv(M, 128) * ((tile == 0 || tile == 1) ? 2 : 4);
+        else if (r == PNP_ROUTE_WINO) p.stats_parts = wino_stats_parts(g);
+        else if (r == PNP_ROUTE_X3D || r == PNP_ROUTE_X3S) p.stats_parts = x3d_stats_parts(g);
+    }
+    return p;
 }
+
+// The convolution of dy that a data gradient is (flipped, transposed filter; a strided layer's dy is zero-upsampled by the launch).
+// SYMMETRIC: it computes the mirror-padded image, which sympad_bwd then folds onto dx.
+static pnp_conv_geom dgrad_as_conv(const pnp_conv_geom* g) {
+    const bool sym = g->pad_mode == PNP_PAD_SYMMETRIC;
+    pnp_conv_geom d{};
+    d.N = g->N; d.H = g->OH; d.W = g->OW; d.C = g->K; d.K = g->C; d.R = g->R; d.S = g->S;
+    d.OH = sym ? g->H + 2 * g->pad_t : g->H;
+    d.OW = sym ? g->W + 2 * g->pad_l : g->W;
+    d.stride = 1; d.dil = g->dil;
+    d.pad_t = g->dil * (g->R - 1) - (sym ? 0 : g->pad_t);
+    d.pad_l = g->dil * (g->S - 1) - (sym ? 0 : g->pad_l);
+    d.pad_mode = PNP_PAD_ZERO;
+    d.dtype = g->dtype;
+    return d;
+}
+
+// One candidate: pnp_conv2d_dgrad* refuses a workspace smaller than ws_bytes.
+// Workspace of the fp32 kernels: [flipped / transposed filters R*S*K*C] [+ padded dx for SYMMETRIC] [+ reduction-split partials]
+static ConvPlan plan_dgrad(const pnp_conv_geom* g) {
+    ConvPlan p{};
+    const bool sym = g->pad_mode == PNP_PAD_SYMMETRIC;
+    const pnp_conv_geom d = dgrad_as_conv(g);
+    const bool plain = g->stride == 1 && !sym && d.pad_t >= 0 && d.pad_l >= 0;      // a stride-1 zero-padded convolution of dy
+    p.tile = plain ? wino_tile(&d) : 0;
+    if (p.tile) {        // the Winograd planner's layer, as in the forward (the filter transform / image flips and transposes on the way)
+        p.ws_bytes = wino_workspace_bytes(&d);
+        p.add(x3d_chosen(&d) ? PNP_ROUTE_X3D : PNP_ROUTE_WINO, p.ws_bytes);
+        return p;
+    }
+    size_t b = ((size_t)g->R * g->S * g->C * g->K * sizeof(float) + 255) & ~(size_t)255;
+    const size_t outb = (size_t)d.N * d.OH * d.OW * d.K * sizeof(float);
+    if (sym) b += (outb + 255) & ~(size_t)255;
+    int route;
+    size_t x3 = 0;       // split filter image of the direct split-bf16 kernels
+    DgradPhase ph[16];
+    const int nph = plan_phases(g, ph);
+    if (nph > 0) {       // strided, one stride-phase at a time: the largest phase's partials (GEMM M = the phase's pixels, N = C, reduction T*U*K)
+        size_t mx = 0;
+        for (int i = 0; i < nph; ++i) {
+            const long long Mp = (long long)g->N * ph[i].I * ph[i].J;
+            if (Mp == 0) continue;
+            const int ns = choose_split(Mp, g->C, ph[i].T * ph[i].U * g->K, choose_tile(Mp, g->C));
+            if (ns > 1 && (size_t)ns * Mp * g->C * sizeof(float) > mx) mx = (size_t)ns * Mp * g->C * sizeof(float);
+        }
+        b += mx;
+        route = x3s_chosen(g, 1) ? PNP_ROUTE_X3S : PNP_ROUTE_PHASES;       // X3S: every phase in one launch
+        if (route == PNP_ROUTE_X3S) x3 = x3s_filter_bytes(g);
+    } else {
+        const long long Md = (long long)(outb / sizeof(float)) / g->C;
+        const int ns = choose_split(Md, g->C, g->R * g->S * g->K, choose_tile(Md, g->C));
+        if (ns > 1) b += (size_t)ns * outb;
+        if (!sym && n16_geom_ok(&d)) route = PNP_ROUTE_N16;                            // 16 INPUT channels: a 16-output conv of dy
+        else if (g->stride == 1 && narrow_fwd_ok(&d, nullptr)) route = PNP_ROUTE_NARROW;    // few INPUT channels: a narrow-output conv of dy
+        else if (plain && x3d_chosen(&d)) route = PNP_ROUTE_X3D;
+        else route = PNP_ROUTE_IGEMM;                                                  // (stride > 1 without phases: dy zero-upsampled)
+        if (route == PNP_ROUTE_X3D) x3 = x3d_filter_bytes(d.C, d.K);
+    }
+    p.ws_bytes = b > x3 ? b : x3;
+    p.add(route, p.ws_bytes);
+    return p;
+}
+
+// Every family against its own byte count, the 16x16x4-MFMA kernel against the query's; the ring kernel takes as many splits as fit.
+static ConvPlan plan_wgrad(const pnp_conv_geom* g) {
+    ConvPlan p{};
+    p.tile = wino_wgrad_tile(g);
+    if (p.tile) p.add(PNP_ROUTE_WINO_WGRAD, wino_wgrad_workspace_bytes(g));             // conv_wino.hip
+    if (x3w_chosen(g)) p.add(PNP_ROUTE_X3W, x3w_workspace_bytes(g));                    // conv_x3_wgrad.hip
+    const size_t nout = (size_t)g->R * g->S * g->C * g->K;
+    const WgdPlan pl = wgd_plan(g);
+    if (p.ncand) p.ws_bytes = p.cand[0].need;
+    else if (n16_wgrad_ok(g)) p.ws_bytes = (size_t)n16_wgrad_blocks(g) * nout * sizeof(float);
+    else {               // the larger of the vector-ALU kernel's slabs and the ring kernel's split partials
+        const long long P = (long long)g->N * g->OH * g->OW;
+        const int bn = ((g->K & 3) != 0 || g->K <= 32) ? 32 : (g->K > 64 ? 128 : 64);
+        const int nblk = pnp_cdiv((long long)g->R * g->S * g->C, 128) * pnp_cdiv(g->K, bn);
+        const int nsplit = wgrad_plan_split(nblk, pnp_cdiv(P, BK));
+        const size_t mfma_ws = nsplit <= 1 ? 0 : (size_t)nsplit * nout * sizeof(float);
+        p.ws_bytes = (pl.use && pl.ws_bytes > mfma_ws) ? pl.ws_bytes : mfma_ws;
+    }
+    if (n16_wgrad_ok(g)) p.add(PNP_ROUTE_N16_WGRAD, p.ws_bytes);
+    if (pl.use) p.add(PNP_ROUTE_WGD, pl.ws_bytes);
+    p.add(PNP_ROUTE_RING, 0);
+    return p;
+}
+
+static void set_dropout(ConvArgs& a, float keep_prob, uint64_t seed, uint32_t stream_id) {
+    if (keep_prob >= 1.f) return;
+    a.do_drop = 1;
+    a.drop_keep = keep_prob;
+    a.drop_key = pnp_drop_key(seed, stream_id);
+    a.drop_thresh = pnp_drop_thresh(keep_prob);
+    a.sp = pnp_step_params_ptr(); a.drop_sid = stream_id;
+}
+
+// the forward of g on candidate c, a = make_args(x, w, y, g) + the entry point's epilogue
+static int launch_fwd_cand(const ConvPlan::Cand& c, ConvArgs& a, const pnp_conv_geom* g, void* ws, size_t ws_bytes, hipStream_t st) {
+    switch (c.route) {
+    case PNP_ROUTE_N16: return launch_n16_fwd(a, 0, st);
+    case PNP_ROUTE_NARROW: return launch_narrow(a.x, a.w, a.y, g, a, st);
+    case PNP_ROUTE_WINO: return launch_wino(a, 0, false, ws, ws_bytes, st);
+    case PNP_ROUTE_X3D: return launch_x3_direct(a, 0, false, ws, ws_bytes, st);
+    case PNP_ROUTE_X3S: return launch_x3_strided(a, g, 0, ws, ws_bytes, st);
+    default: return launch_fwd<0>(a, st, c.need ? (float*)ws : nullptr);
+    }
+}
+
+// kind 0: forward (plain epilogue, workspace supplied); 2: filter gradient; else: data gradient — g = the FORWARD geometry
+static ConvPlan plan_of(const pnp_conv_geom* g, int kind) { return kind == 0 ? plan_fwd(g, EP_WS) : (kind == 2 ? plan_wgrad(g) : plan_dgrad(g)); }
+
+extern "C" {
+
+// which kernel family serves the layer (PNP_ROUTE_*) with the workspace of the query supplied; kind 0: forward (plain epilogue), 1: data
+// gradient, 2: filter gradient — g = the FORWARD geometry
+int32_t pnp_conv2d_route(const pnp_conv_geom* g, int32_t kind) {
+    if (!g || check_geom(g, "pnp_conv2d_route") != PNP_OK) return -1;
+    return plan_of(g, kind).cand[0].route;
+}
+
+// 0: direct kernels; else the Winograd planner's output tile edge (kind 0: forward; 1: data gradient; 2: filter gradient — g = the FORWARD geometry)
+int32_t pnp_conv2d_wino_chosen(const pnp_conv_geom* g, int32_t kind) {
+    if (!g || check_geom(g, "pnp_conv2d_wino_chosen") != PNP_OK) return 0;
+    return plan_of(g, kind).tile;
+}
+
+size_t pnp_conv2d_fwd_workspace_bytes(const pnp_conv_geom* g) { return g ? plan_fwd(g, EP_WS).ws_bytes : 0; }
+size_t pnp_conv2d_dgrad_workspace_bytes(const pnp_conv_geom* g) { return g ? plan_dgrad(g).ws_bytes : 0; }
+size_t pnp_conv2d_wgrad_workspace_bytes(const pnp_conv_geom* g) { return g ? plan_wgrad(g).ws_bytes : 0; }
 
 int pnp_conv2d_fwd(const float* x, const float* w, float* y, const pnp_conv_geom* g, float keep_prob, uint64_t seed,
                    uint32_t stream_id, void* stream) {
@@ -2221,96 +2375,52 @@ int pnp_conv2d_fwd_ws(const float* x, const float* w, float* y, const pnp_conv_g
     PNP_REQUIRE(x && w && y, "pnp_conv2d_fwd: null pointer");
     PNP_REQUIRE(keep_prob > 0.f, "pnp_conv2d_fwd: keep_prob must be > 0");
     ConvArgs a = make_args(x, w, y, g);
-    if (keep_prob < 1.f) {
-        a.do_drop = 1;
-        a.drop_keep = keep_prob;
-        a.drop_key = pnp_drop_key(seed, stream_id);
-        a.drop_thresh = pnp_drop_thresh(keep_prob);
-        a.sp = pnp_step_params_ptr(); a.drop_sid = stream_id;
-    }
-    if (n16_geom_ok(g)) return launch_n16_fwd(a, 0, (hipStream_t)stream);
-    if (narrow_fwd_ok(g, nullptr)) return launch_narrow(x, w, y, g, a, (hipStream_t)stream);
-    if (wino_chosen(g)) {          // (without the workspace the direct kernel runs: same result up to fp32 rounding)
-        if (workspace && workspace_bytes >= wino_workspace_bytes(g)) return launch_wino(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream);
-        return launch_fwd<0>(a, (hipStream_t)stream, nullptr);
-    }
-    if (const int x3 = fwd_x3_route(g)) {
-        if (workspace && workspace_bytes >= fwd_x3_bytes(g, x3))
-            return x3 == 1 ? launch_x3_direct(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream)
-                           : launch_x3_strided(a, g, 0, workspace, workspace_bytes, (hipStream_t)stream);
-    }
-    float* split_ws = (workspace && workspace_bytes >= pnp_conv2d_fwd_workspace_bytes(g) && pnp_conv2d_fwd_workspace_bytes(g) > 0)
-                          ? (float*)workspace : nullptr;
-    return launch_fwd<0>(a, (hipStream_t)stream, split_ws);
+    set_dropout(a, keep_prob, seed, stream_id);
+    return launch_fwd_cand(plan_fwd(g, EP_WS).pick(workspace, workspace_bytes), a, g, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 // ---- forward convolution that also leaves the batch-norm statistics partials of its output (training-mode conv -> dropout -> BN) ----
-// Only on the MFMA kernels with an un-split reduction (the epilogue owns complete output rows there); 0 parts = not available for
-// this geometry (narrow-output vector-ALU kernels, reduction-split tiny layers): the caller runs pnp_bn_stats on the output instead.
+// 0 parts = not available for this geometry (narrow-output vector-ALU kernels, reduction-split tiny layers): the caller runs pnp_bn_stats
+// on the output instead.  With a workspace (pnp_conv2d_fwd_workspace_bytes) the Winograd and direct split-bf16 routes take their layers and
+// leave their own partial rows: pnp_conv2d_fwd_stats_ws_parts says how many.
 static int fwd_stats_impl(const float* x, const float* w, float* y, const pnp_conv_geom* g, float keep_prob, uint64_t seed,
                           uint32_t stream_id, const float* shift, float* parts, size_t parts_bytes, void* workspace, size_t workspace_bytes,
-                          void* stream, bool with_ws);
+                          void* stream, unsigned ep) {
+    if (int e = check_geom(g, "pnp_conv2d_fwd_stats")) return e;
+    PNP_REQUIRE(x && w && y && parts, "pnp_conv2d_fwd_stats: null pointer");
+    PNP_REQUIRE(keep_prob > 0.f, "pnp_conv2d_fwd_stats: keep_prob must be > 0");
+    const ConvPlan p = plan_fwd(g, ep);
+    const ConvPlan::Cand& c = p.cand[0];         // the partial rows are this candidate's: no fall-back
+    PNP_REQUIRE(c.need == 0 || (workspace && workspace_bytes >= c.need), "pnp_conv2d_fwd_stats_ws: workspace too small (pnp_conv2d_fwd_workspace_bytes)");
+    PNP_REQUIRE(p.stats_parts > 0, "pnp_conv2d_fwd_stats: no epilogue statistics for this geometry (pnp_conv2d_fwd_stats_parts == 0)");
+    if (parts_bytes < (size_t)p.stats_parts * 2 * g->K * sizeof(float)) {
+        pnp_set_error("pnp_conv2d_fwd_stats: parts buffer too small (%zu < %zu)", parts_bytes, (size_t)p.stats_parts * 2 * g->K * sizeof(float));
+        return PNP_EWORKSPACE;
+    }
+    ConvArgs a = make_args(x, w, y, g);
+    set_dropout(a, keep_prob, seed, stream_id);
+    a.stat_ws = parts;
+    a.stat_shift = shift;
+    return launch_fwd_cand(c, a, g, workspace, workspace_bytes, (hipStream_t)stream);
+}
 
 int32_t pnp_conv2d_fwd_stats_parts(const pnp_conv_geom* g) {
-    if (!g || check_geom(g, "pnp_conv2d_fwd_stats_parts") != PNP_OK) return 0;
-    if (n16_geom_ok(g) || narrow_fwd_ok(g, nullptr) || fwd_split(g) > 1) return 0;
-    const long long M = (long long)g->N * g->OH * g->OW;
-    const int tile = choose_tile(M, g->K);
-    return pnp_cdiv(M, 128) * ((tile == 0 || tile == 1) ? 2 : 4);        // pixel tiles x wave rows of the tile (WM)
+    return (g && check_geom(g, "pnp_conv2d_fwd_stats_parts") == PNP_OK) ? plan_fwd(g, EP_STATS).stats_parts : 0;
 }
 
 int pnp_conv2d_fwd_stats(const float* x, const float* w, float* y, const pnp_conv_geom* g, float keep_prob, uint64_t seed,
                          uint32_t stream_id, const float* shift, float* parts, size_t parts_bytes, void* stream) {
-    return fwd_stats_impl(x, w, y, g, keep_prob, seed, stream_id, shift, parts, parts_bytes, nullptr, 0, stream, false);
+    return fwd_stats_impl(x, w, y, g, keep_prob, seed, stream_id, shift, parts, parts_bytes, nullptr, 0, stream, EP_STATS);
 }
 
-// The same with a workspace (pnp_conv2d_fwd_workspace_bytes): layers the planner gives to the Winograd route (conv_wino.hip) leave one
-// partial row per tile slab of its output transform — pnp_conv2d_fwd_stats_ws_parts says how many; every other layer is
-// pnp_conv2d_fwd_stats / pnp_conv2d_fwd_stats_parts.
 int32_t pnp_conv2d_fwd_stats_ws_parts(const pnp_conv_geom* g) {
-    if (!g || check_geom(g, "pnp_conv2d_fwd_stats_ws_parts") != PNP_OK) return 0;
-    if (wino_chosen(g)) return wino_stats_parts(g);
-    if (fwd_x3_route(g)) return x3d_stats_parts(g);             // (one partial per 64 output pixels on both kernels)
-    return pnp_conv2d_fwd_stats_parts(g);
+    return (g && check_geom(g, "pnp_conv2d_fwd_stats_ws_parts") == PNP_OK) ? plan_fwd(g, EP_STATS | EP_WS).stats_parts : 0;
 }
 
 int pnp_conv2d_fwd_stats_ws(const float* x, const float* w, float* y, const pnp_conv_geom* g, float keep_prob, uint64_t seed,
                             uint32_t stream_id, const float* shift, float* parts, size_t parts_bytes, void* workspace,
                             size_t workspace_bytes, void* stream) {
-    return fwd_stats_impl(x, w, y, g, keep_prob, seed, stream_id, shift, parts, parts_bytes, workspace, workspace_bytes, stream, true);
-}
-
-static int fwd_stats_impl(const float* x, const float* w, float* y, const pnp_conv_geom* g, float keep_prob, uint64_t seed,
-                          uint32_t stream_id, const float* shift, float* parts, size_t parts_bytes, void* workspace, size_t workspace_bytes,
-                          void* stream, bool with_ws) {
-    if (int e = check_geom(g, "pnp_conv2d_fwd_stats")) return e;
-    PNP_REQUIRE(x && w && y && parts, "pnp_conv2d_fwd_stats: null pointer");
-    PNP_REQUIRE(keep_prob > 0.f, "pnp_conv2d_fwd_stats: keep_prob must be > 0");
-    const bool wino = with_ws && wino_chosen(g);
-    if (wino) PNP_REQUIRE(workspace && workspace_bytes >= wino_workspace_bytes(g), "pnp_conv2d_fwd_stats_ws: workspace too small (pnp_conv2d_fwd_workspace_bytes)");
-    const int x3 = (with_ws && !wino) ? fwd_x3_route(g) : 0;
-    const bool x3d = x3 != 0;
-    if (x3d) PNP_REQUIRE(workspace && workspace_bytes >= fwd_x3_bytes(g, x3), "pnp_conv2d_fwd_stats_ws: workspace too small (pnp_conv2d_fwd_workspace_bytes)");
-    const int nparts = wino ? wino_stats_parts(g) : (x3d ? x3d_stats_parts(g) : pnp_conv2d_fwd_stats_parts(g));
-    PNP_REQUIRE(nparts > 0, "pnp_conv2d_fwd_stats: no epilogue statistics for this geometry (pnp_conv2d_fwd_stats_parts == 0)");
-    if (parts_bytes < (size_t)nparts * 2 * g->K * sizeof(float)) {
-        pnp_set_error("pnp_conv2d_fwd_stats: parts buffer too small (%zu < %zu)", parts_bytes, (size_t)nparts * 2 * g->K * sizeof(float));
-        return PNP_EWORKSPACE;
-    }
-    ConvArgs a = make_args(x, w, y, g);
-    if (keep_prob < 1.f) {
-        a.do_drop = 1;
-        a.drop_keep = keep_prob;
-        a.drop_key = pnp_drop_key(seed, stream_id);
-        a.drop_thresh = pnp_drop_thresh(keep_prob);
-        a.sp = pnp_step_params_ptr(); a.drop_sid = stream_id;
-    }
-    a.stat_ws = parts;
-    a.stat_shift = shift;
-    if (wino) return launch_wino(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream);
-    if (x3d) return x3 == 1 ? launch_x3_direct(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream)
-                            : launch_x3_strided(a, g, 0, workspace, workspace_bytes, (hipStream_t)stream);
-    return launch_fwd<0>(a, (hipStream_t)stream);
+    return fwd_stats_impl(x, w, y, g, keep_prob, seed, stream_id, shift, parts, parts_bytes, workspace, workspace_bytes, stream, EP_STATS | EP_WS);
 }
 
 int pnp_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var, float* scale, float* shift, int32_t C,
@@ -2328,7 +2438,8 @@ int pnp_conv2d_fwd_bn(const float* x, const float* w, float* y, const pnp_conv_g
     return pnp_conv2d_fwd_bn_ws(x, w, y, g, keep_prob, seed, stream_id, scale, shift, shortcut, Cs, alpha, nullptr, 0, stream);
 }
 
-// with a workspace of pnp_conv2d_fwd_workspace_bytes(g) bytes the layers the planner gives to the Winograd route take it (conv_wino.hip)
+// with a workspace of pnp_conv2d_fwd_workspace_bytes(g) bytes the layers the planner gives to the Winograd route take it (conv_wino.hip);
+// the reduction is never split on this path
 int pnp_conv2d_fwd_bn_ws(const float* x, const float* w, float* y, const pnp_conv_geom* g, float keep_prob, uint64_t seed,
                          uint32_t stream_id, const float* scale, const float* shift, const float* shortcut, int32_t Cs, float alpha,
                          void* workspace, size_t workspace_bytes, void* stream) {
@@ -2337,18 +2448,9 @@ int pnp_conv2d_fwd_bn_ws(const float* x, const float* w, float* y, const pnp_con
     PNP_REQUIRE(keep_prob > 0.f, "pnp_conv2d_fwd_bn: keep_prob must be > 0");
     if (shortcut) PNP_REQUIRE(Cs > 0 && Cs <= g->K && ((g->K - Cs) % 2) == 0, "pnp_conv2d_fwd_bn: bad shortcut channels");
     ConvArgs a = make_args(x, w, y, g);
-    if (keep_prob < 1.f) {
-        a.do_drop = 1;
-        a.drop_keep = keep_prob;
-        a.drop_key = pnp_drop_key(seed, stream_id);
-        a.drop_thresh = pnp_drop_thresh(keep_prob);
-        a.sp = pnp_step_params_ptr(); a.drop_sid = stream_id;
-    }
+    set_dropout(a, keep_prob, seed, stream_id);
     a.ep_scale = scale; a.ep_shift = shift; a.ep_res = shortcut; a.ep_cs = shortcut ? Cs : g->K; a.ep_alpha = alpha;
-    if (n16_geom_ok(g)) return launch_n16_fwd(a, 0, (hipStream_t)stream);
-    if (wino_chosen(g) && workspace && workspace_bytes >= wino_workspace_bytes(g))
-        return launch_wino(a, 0, false, workspace, workspace_bytes, (hipStream_t)stream);
-    return launch_fwd<0>(a, (hipStream_t)stream);      // the reduction is never split on this path
+    return launch_fwd_cand(plan_fwd(g, EP_WS | EP_BN).pick(workspace, workspace_bytes), a, g, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int pnp_conv2d_fwd_naive(const float* x, const float* w, float* y, const pnp_conv_geom* g, void* stream) {
@@ -2361,90 +2463,79 @@ int pnp_conv2d_fwd_naive(const float* x, const float* w, float* y, const pnp_con
     return PNP_OK;
 }
 
-// dgrad workspace: [flipped/transposed filters R*S*K*C] [+ padded dx for SYMMETRIC]
-// the data gradient of a stride-1 zero-padded convolution AS a convolution of dy (flipped, transposed filter)
-static pnp_conv_geom dgrad_as_conv(const pnp_conv_geom* g) {
-    pnp_conv_geom d{};
-    d.N = g->N; d.H = g->OH; d.W = g->OW; d.C = g->K; d.K = g->C; d.R = g->R; d.S = g->S;
-    d.OH = g->H; d.OW = g->W;
-    d.stride = 1; d.dil = g->dil;
-    d.pad_t = g->dil * (g->R - 1) - g->pad_t;
-    d.pad_l = g->dil * (g->S - 1) - g->pad_l;
-    d.pad_mode = PNP_PAD_ZERO;
-    d.dtype = g->dtype;
-    return d;
-}
-static bool dgrad_wino(const pnp_conv_geom* g, pnp_conv_geom* d) {
-    if (g->stride != 1 || g->pad_mode != PNP_PAD_ZERO) return false;
-    *d = dgrad_as_conv(g);
-    return d->pad_t >= 0 && d->pad_l >= 0 && wino_chosen(d);
-}
-
-// 1: the planner gives this layer to the Winograd route (kind 0: forward; 1: data gradient; 2: filter gradient — g = the FORWARD geometry); 0: direct kernels
-int32_t pnp_conv2d_wino_chosen(const pnp_conv_geom* g, int32_t kind) {
-    if (!g || check_geom(g, "pnp_conv2d_wino_chosen") != PNP_OK) return 0;
-    pnp_conv_geom d;
-    if (kind == 2) return wino_wgrad_tile(g);
-    return kind == 0 ? wino_tile(g) : (dgrad_wino(g, &d) ? wino_tile(&d) : 0);
-}
-
-// the data gradient as a direct split-bf16 convolution of dy (conv_x3_direct.hip) where the Winograd planner leaves the layer alone
-static bool dgrad_x3d(const pnp_conv_geom* g, pnp_conv_geom* d) {
-    if (g->stride != 1 || g->pad_mode != PNP_PAD_ZERO) return false;
-    *d = dgrad_as_conv(g);
-    return d->pad_t >= 0 && d->pad_l >= 0 && !wino_chosen(d) && !n16_geom_ok(d) && !narrow_fwd_ok(d, nullptr) && x3d_chosen(d);
-}
-
-static size_t dgrad_ws_base(const pnp_conv_geom* g);
-
-size_t pnp_conv2d_dgrad_workspace_bytes(const pnp_conv_geom* g) {
-    if (!g) return 0;
-    const size_t b = dgrad_ws_base(g);
-    pnp_conv_geom d;
-    if (dgrad_x3d(g, &d)) {
-        const size_t f = x3d_filter_bytes(d.C, d.K);
-        return b > f ? b : f;
-    }
-    if (x3s_chosen(g, 1)) {                              // strided: the split filter image of every stride phase
-        const size_t f = x3s_filter_bytes(g);
-        return b > f ? b : f;
-    }
-    return b;
-}
-
-static size_t dgrad_ws_base(const pnp_conv_geom* g) {
-    {
-        pnp_conv_geom d;
-        if (dgrad_wino(g, &d)) return wino_workspace_bytes(&d);
-    }
-    size_t b = (size_t)g->R * g->S * g->C * g->K * sizeof(float);
-    b = (b + 255) & ~(size_t)255;
-    size_t outb = (size_t)g->N * g->H * g->W * g->C * sizeof(float);
-    if (g->pad_mode == PNP_PAD_SYMMETRIC) {
-        outb = (size_t)g->N * (g->H + 2 * g->pad_t) * (g->W + 2 * g->pad_l) * g->C * sizeof(float);
-        b += (outb + 255) & ~(size_t)255;
-    }
-    // reduction-split partials of the data-gradient GEMM (M = output pixels of the dgrad, N = C, reduction R*S*K)
-    DgradPhase ph[16];
-    const int nph = plan_phases(g, ph);
-    if (nph > 0) {                                       // one stride-phase at a time: the largest phase's partials
-        size_t mx = 0;
-        for (int i = 0; i < nph; ++i) {
-            const long long Mp = (long long)g->N * ph[i].I * ph[i].J;
-            if (Mp == 0) continue;
-            const int ns = choose_split(Mp, g->C, ph[i].T * ph[i].U * g->K, choose_tile(Mp, g->C));
-            if (ns > 1 && (size_t)ns * Mp * g->C * sizeof(float) > mx) mx = (size_t)ns * Mp * g->C * sizeof(float);
-        }
-        return b + mx;
-    }
-    const long long Md = (long long)(outb / sizeof(float)) / g->C;
-    const int ns = choose_split(Md, g->C, g->R * g->S * g->K, choose_tile(Md, g->C));
-    if (ns > 1) b += (size_t)ns * outb;
-    return b;
-}
-
+// residual != null: dx = data gradient + residual.  Fused into the epilogue on the stride-1 MFMA paths (the residual blocks); every
+// other geometry computes the gradient and adds the residual with one more pass (pnp_axpby).
 static int dgrad_impl(const float* dy, const float* w, float* dx, const pnp_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream,
-                      const float* residual);
+                      const float* residual) {
+    if (int e = check_geom(g, "pnp_conv2d_dgrad")) return e;
+    PNP_REQUIRE(dy && w && dx && workspace, "pnp_conv2d_dgrad: null pointer");
+    const ConvPlan p = plan_dgrad(g);
+    PNP_REQUIRE(workspace_bytes >= p.ws_bytes, "pnp_conv2d_dgrad: workspace too small");
+    const bool sym = g->pad_mode == PNP_PAD_SYMMETRIC;
+    if (sym) PNP_REQUIRE(g->pad_t == g->pad_l, "pnp_conv2d_dgrad: SYMMETRIC needs pad_t == pad_l");
+    hipStream_t st = (hipStream_t)stream;
+    const int route = p.cand[0].route;
+    const pnp_conv_geom d = dgrad_as_conv(g);
+    if (route == PNP_ROUTE_X3S) {            // every phase on the direct split-bf16 kernel, one launch (its filter image flips per phase)
+        ConvArgs a = make_args(dy, w, dx, g);
+        if (int e = launch_x3_strided(a, g, 1, workspace, workspace_bytes, st)) return e;
+        return residual ? pnp_axpby(residual, dx, (size_t)g->N * g->H * g->W * g->C, 1.f, 1.f, stream) : PNP_OK;
+    }
+    if (route == PNP_ROUTE_WINO || route == PNP_ROUTE_X3D) {      // the filter transform / image flips and transposes on the way (no flip launch)
+        ConvArgs a = make_args(dy, w, dx, &d);
+        a.res_add = residual;
+        return route == PNP_ROUTE_WINO ? launch_wino(a, 1, true, workspace, workspace_bytes, st)
+                                       : launch_x3_direct(a, 1, true, workspace, workspace_bytes, st);
+    }
+    // the fp32 kernels: [flipped filters][padded dx for SYMMETRIC][reduction-split partials, where the caller brought room for them]
+    float* wt = (float*)workspace;
+    const size_t woff = ((size_t)g->R * g->S * g->C * g->K * sizeof(float) + 255) & ~(size_t)255;
+    float* out = sym ? (float*)((char*)workspace + woff) : dx;
+    const size_t poff = woff + (sym ? ((size_t)d.N * d.OH * d.OW * d.K * sizeof(float) + 255) & ~(size_t)255 : 0);
+    float* split_ws = (workspace_bytes > poff) ? (float*)((char*)workspace + poff) : nullptr;
+    const dim3 tg((unsigned)pnp_cdiv(g->K, 32), (unsigned)pnp_cdiv(g->C, 32), (unsigned)(g->R * g->S));
+    if (route == PNP_ROUTE_PHASES) {
+        DgradPhase ph[16];
+        const int nph = plan_phases(g, ph);
+        hipLaunchKernelGGL(flip_transpose_phase_kernel, tg, dim3(256), 0, st, w, wt, g->R, g->S, g->C, g->K, g->stride);
+        PNP_CHECK_LAUNCH("flip_transpose_phase_kernel");
+        if (phases_in_one_launch(g, ph, nph)) {
+            if (int e = launch_phase_group(dy, wt, out, g, ph, nph, d.OH, d.OW, st)) return e;
+        } else {
+            for (int i = 0; i < nph; ++i) {
+                const DgradPhase& q = ph[i];
+                if (q.I == 0 || q.J == 0) continue;
+                const pnp_conv_geom dp = phase_geom(g, q);
+                ConvArgs a = make_args(dy, wt + q.wt_off, out, &dp);
+                a.o_s = g->stride; a.o_H = d.OH; a.o_W = d.OW; a.o_h0 = q.h0; a.o_w0 = q.w0;
+                if (int e = launch_fwd<1>(a, st, split_ws)) return e;
+            }
+        }
+    } else {
+        hipLaunchKernelGGL(flip_transpose_kernel, tg, dim3(256), 0, st, w, wt, g->R, g->S, g->C, g->K);
+        PNP_CHECK_LAUNCH("flip_transpose_kernel");
+        PNP_REQUIRE(d.pad_t >= 0 && d.pad_l >= 0, "pnp_conv2d_dgrad: forward padding exceeds the filter extent");
+        ConvArgs a = make_args(dy, wt, out, &d);
+        a.ups = g->stride;                                     // dy zero-upsampled by `stride`
+        if (route == PNP_ROUTE_N16) {
+            a.res_add = residual;
+            return launch_n16_fwd(a, 1, st);
+        }
+        if (route == PNP_ROUTE_NARROW) {
+            if (int e = launch_narrow(dy, wt, out, &d, a, st)) return e;
+        } else {
+            if (residual && !sym && g->stride == 1) {          // rows of the GEMM == pixels of dx, plain row-major output: fused
+                a.res_add = residual;
+                residual = nullptr;
+            }
+            if (int e = (g->stride > 1 ? launch_fwd<2>(a, st, split_ws) : launch_fwd<1>(a, st, split_ws))) return e;
+        }
+    }
+    if (sym) {
+        if (int e = pnp_sympad_bwd(out, dx, g->N, g->H, g->W, g->C, g->pad_t, stream)) return e;
+    }
+    return residual ? pnp_axpby(residual, dx, (size_t)g->N * g->H * g->W * g->C, 1.f, 1.f, stream) : PNP_OK;
+}
 
 int pnp_conv2d_dgrad(const float* dy, const float* w, float* dx, const pnp_conv_geom* g, void* workspace,
                      size_t workspace_bytes, void* stream) {
@@ -2457,124 +2548,6 @@ int pnp_conv2d_dgrad_add(const float* dy, const float* w, const float* residual,
     return dgrad_impl(dy, w, dx, g, workspace, workspace_bytes, stream, residual);
 }
 
-// residual != null: dx = data gradient + residual.  Fused into the epilogue on the stride-1 MFMA paths (the residual blocks); every
-// other geometry computes the gradient and adds the residual with one more pass (pnp_axpby).
-static int dgrad_impl(const float* dy, const float* w, float* dx, const pnp_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream,
-                      const float* residual) {
-    if (int e = check_geom(g, "pnp_conv2d_dgrad")) return e;
-    PNP_REQUIRE(dy && w && dx && workspace, "pnp_conv2d_dgrad: null pointer");
-    PNP_REQUIRE(workspace_bytes >= pnp_conv2d_dgrad_workspace_bytes(g), "pnp_conv2d_dgrad: workspace too small");
-    if (g->pad_mode == PNP_PAD_SYMMETRIC) PNP_REQUIRE(g->pad_t == g->pad_l, "pnp_conv2d_dgrad: SYMMETRIC needs pad_t == pad_l");
-    hipStream_t st = (hipStream_t)stream;
-    float* wt = (float*)workspace;
-    size_t woff = ((size_t)g->R * g->S * g->C * g->K * sizeof(float) + 255) & ~(size_t)255;
-    const size_t dx_elems = (size_t)g->N * g->H * g->W * g->C;
-    auto add_residual = [&](float* out, const float* res) -> int {
-        return res ? pnp_axpby(res, out, dx_elems, 1.f, 1.f, stream) : PNP_OK;
-    };
-    DgradPhase ph[16];
-    const int nph = plan_phases(g, ph);
-    if (nph > 0) {
-        const bool symp = g->pad_mode == PNP_PAD_SYMMETRIC;
-        const int Ho = symp ? g->H + 2 * g->pad_t : g->H, Wo = symp ? g->W + 2 * g->pad_l : g->W;
-        float* outp = symp ? (float*)((char*)workspace + woff) : dx;
-        size_t poff = woff;
-        if (symp) poff += ((size_t)g->N * Ho * Wo * g->C * sizeof(float) + 255) & ~(size_t)255;
-        float* split_ws = (workspace_bytes > poff) ? (float*)((char*)workspace + poff) : nullptr;
-        if (x3s_chosen(g, 1)) {              // every phase on the direct split-bf16 kernel, one launch (its filter image flips per phase)
-            ConvArgs a = make_args(dy, w, dx, g);
-            if (int e = launch_x3_strided(a, g, 1, workspace, workspace_bytes, st)) return e;
-            return add_residual(dx, residual);
-        }
-        dim3 tgp((unsigned)pnp_cdiv(g->K, 32), (unsigned)pnp_cdiv(g->C, 32), (unsigned)(g->R * g->S));
-        hipLaunchKernelGGL(flip_transpose_phase_kernel, tgp, dim3(256), 0, st, w, wt, g->R, g->S, g->C, g->K, g->stride);
-        PNP_CHECK_LAUNCH("flip_transpose_phase_kernel");
-        if (phases_in_one_launch(g, ph, nph)) {
-            if (int e = launch_phase_group(dy, wt, outp, g, ph, nph, Ho, Wo, st)) return e;
-        } else {
-            for (int i = 0; i < nph; ++i) {
-                const DgradPhase& p = ph[i];
-                if (p.I == 0 || p.J == 0) continue;
-                const pnp_conv_geom d = phase_geom(g, p);
-                ConvArgs a = make_args(dy, wt + p.wt_off, outp, &d);
-                a.o_s = g->stride; a.o_H = Ho; a.o_W = Wo; a.o_h0 = p.h0; a.o_w0 = p.w0;
-                if (int e = launch_fwd<1>(a, st, split_ws)) return e;
-            }
-        }
-        if (symp) {
-            const size_t total = (size_t)g->N * g->H * g->W * g->C;
-            hipLaunchKernelGGL(sympad_bwd_kernel, dim3((unsigned)pnp_cdiv((long long)total, 256)), dim3(256), 0, st,
-                               (const float*)outp, dx, g->N, g->H, g->W, g->C, g->pad_t);
-            PNP_CHECK_LAUNCH("sympad_bwd_kernel");
-        }
-        return add_residual(dx, residual);
-    }
-    {
-        pnp_conv_geom dw_;
-        if (dgrad_wino(g, &dw_)) {           // Winograd route: the filter transform flips and transposes on the way (no flip launch)
-            ConvArgs a = make_args(dy, w, dx, &dw_);
-            a.res_add = residual;
-            return launch_wino(a, 1, true, workspace, workspace_bytes, st);
-        }
-    }
-    {
-        pnp_conv_geom dx_;
-        if (dgrad_x3d(g, &dx_)) {            // direct split-bf16 convolution of dy: its filter image flips and transposes (no flip launch)
-            ConvArgs a = make_args(dy, w, dx, &dx_);
-            a.res_add = residual;
-            return launch_x3_direct(a, 1, true, workspace, workspace_bytes, st);
-        }
-    }
-    dim3 tg((unsigned)pnp_cdiv(g->K, 32), (unsigned)pnp_cdiv(g->C, 32), (unsigned)(g->R * g->S));
-    hipLaunchKernelGGL(flip_transpose_kernel, tg, dim3(256), 0, st, w, wt, g->R, g->S, g->C, g->K);
-    PNP_CHECK_LAUNCH("flip_transpose_kernel");
-
-    // dgrad as a stride-1 convolution over dy (zero-upsampled by `stride`), output = (padded) input image
-    const bool sym = g->pad_mode == PNP_PAD_SYMMETRIC;
-    pnp_conv_geom d{};
-    d.N = g->N; d.H = g->OH; d.W = g->OW; d.C = g->K; d.K = g->C; d.R = g->R; d.S = g->S;
-    d.OH = sym ? g->H + 2 * g->pad_t : g->H;
-    d.OW = sym ? g->W + 2 * g->pad_l : g->W;
-    d.stride = 1; d.dil = g->dil;
-    d.pad_t = g->dil * (g->R - 1) - (sym ? 0 : g->pad_t);
-    d.pad_l = g->dil * (g->S - 1) - (sym ? 0 : g->pad_l);
-    d.pad_mode = PNP_PAD_ZERO;
-    d.dtype = g->dtype;
-    PNP_REQUIRE(d.pad_t >= 0 && d.pad_l >= 0, "pnp_conv2d_dgrad: forward padding exceeds the filter extent");
-    float* out = sym ? (float*)((char*)workspace + woff) : dx;
-    ConvArgs a = make_args(dy, wt, out, &d);
-    a.ups = g->stride;
-    if (!sym && n16_geom_ok(&d)) {                           // 16 INPUT channels: the data gradient is a 16-output conv of dy
-        a.res_add = residual;
-        return launch_n16_fwd(a, 1, st);
-    }
-    if (g->stride == 1 && narrow_fwd_ok(&d, nullptr)) {       // few INPUT channels: the data gradient is a narrow-output conv of dy
-        if (int e = launch_narrow(dy, wt, out, &d, a, st)) return e;
-        if (sym) {
-            const size_t total = (size_t)g->N * g->H * g->W * g->C;
-            hipLaunchKernelGGL(sympad_bwd_kernel, dim3((unsigned)pnp_cdiv((long long)total, 256)), dim3(256), 0, st,
-                               (const float*)out, dx, g->N, g->H, g->W, g->C, g->pad_t);
-            PNP_CHECK_LAUNCH("sympad_bwd_kernel");
-        }
-        return add_residual(dx, residual);
-    }
-    size_t poff = woff;
-    if (sym) poff += ((size_t)d.N * d.OH * d.OW * d.K * sizeof(float) + 255) & ~(size_t)255;
-    float* split_ws = (workspace_bytes > poff) ? (float*)((char*)workspace + poff) : nullptr;
-    const bool fuse_res = residual && !sym && g->stride == 1;          // rows of the GEMM == pixels of dx, plain row-major output
-    if (fuse_res) a.res_add = residual;
-    if (int e = (g->stride > 1 ? launch_fwd<2>(a, st, split_ws) : launch_fwd<1>(a, st, split_ws))) return e;
-    if (sym) {
-        const size_t total = (size_t)g->N * g->H * g->W * g->C;
-        hipLaunchKernelGGL(sympad_bwd_kernel, dim3((unsigned)pnp_cdiv((long long)total, 256)), dim3(256), 0, st,
-                           (const float*)out, dx, g->N, g->H, g->W, g->C, g->pad_t);
-        PNP_CHECK_LAUNCH("sympad_bwd_kernel");
-    }
-    return fuse_res ? PNP_OK : add_residual(dx, residual);
-}
-
-size_t pnp_conv2d_wgrad_workspace_bytes(const pnp_conv_geom* g) { return g ? wgrad_ws(g) : 0; }
-
 static int wgrad_impl(const float* x, const float* dy, float* dw, const pnp_conv_geom* g, void* workspace, size_t workspace_bytes, void* stream,
                       int accumulate) {
     if (int e = check_geom(g, "pnp_conv2d_wgrad")) return e;
@@ -2585,20 +2558,17 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, const pnp_conv
     hipStream_t st = (hipStream_t)stream;
     float* ws = (float*)workspace;
     if (!ws) workspace_bytes = 0;
-    if (wino_wgrad_chosen(g) && workspace_bytes >= wino_wgrad_workspace_bytes(g))
-        return launch_wino_wgrad(a, dw, accumulate, workspace, workspace_bytes, st);
-    if (x3w_chosen(g) && workspace_bytes >= x3w_workspace_bytes(g))
-        return launch_x3_wgrad(x, dy, dw, g, accumulate, workspace, workspace_bytes, st);
-    if (n16_wgrad_ok(g) && workspace_bytes >= wgrad_ws(g)) {
+    const size_t nout = (size_t)a.Kred * a.K;
+    int nparts = 0;          // per-workgroup partials in ws, summed by splitk_reduce_many_kernel
+    switch (plan_wgrad(g).pick(workspace, workspace_bytes).route) {
+    case PNP_ROUTE_WINO_WGRAD: return launch_wino_wgrad(a, dw, accumulate, workspace, workspace_bytes, st);
+    case PNP_ROUTE_X3W: return launch_x3_wgrad(x, dy, dw, g, accumulate, workspace, workspace_bytes, st);
+    case PNP_ROUTE_N16_WGRAD:
         if (int e = launch_n16_wgrad(a, ws, st)) return e;
-        const size_t nout = (size_t)a.Kred * a.K;
-        hipLaunchKernelGGL(splitk_reduce_many_kernel, dim3((unsigned)pnp_cdiv((long long)nout, 64)), dim3(1024), 0, st,
-                           (const float*)ws, dw, (int)nout, n16_wgrad_blocks(g), accumulate);
-        PNP_CHECK_LAUNCH("splitk_reduce_many_kernel");
-        return PNP_OK;
-    }
-    const WgdPlan pl = wgd_plan(g);
-    if (pl.use && workspace_bytes >= pl.ws_bytes) {
+        nparts = n16_wgrad_blocks(g);
+        break;
+    case PNP_ROUTE_WGD: {
+        const WgdPlan pl = wgd_plan(g);
         WgdArgs d{};
         d.x = x; d.dy = dy; d.part = ws;
         d.N = g->N; d.H = g->H; d.W = g->W; d.C = g->C; d.K = g->K; d.R = g->R; d.S = g->S; d.OH = g->OH; d.OW = g->OW;
@@ -2611,16 +2581,19 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, const pnp_conv
         else if (g->K <= 8) e = launch_wgd<8, false>(d, pl, st);
         else e = launch_wgd<16, false>(d, pl, st);
         if (e) return e;
-        const size_t nout = (size_t)a.Kred * a.K;
-        hipLaunchKernelGGL(splitk_reduce_many_kernel, dim3((unsigned)pnp_cdiv((long long)nout, 64)), dim3(1024), 0, st,
-                           (const float*)ws, dw, (int)nout, pl.nblk, accumulate);
-        PNP_CHECK_LAUNCH("splitk_reduce_many_kernel");
-        return PNP_OK;
+        nparts = pl.nblk;
+        break;
     }
-    if ((a.K & 3) != 0) return launch_wgrad_tile<128, 32, 4, 1, false>(a, dw, ws, workspace_bytes, st);
-    if (a.K > 64) return launch_wgrad_tile<128, 128, 2, 2, true>(a, dw, ws, workspace_bytes, st);
-    if (a.K > 32) return launch_wgrad_tile<128, 64, 2, 2, true>(a, dw, ws, workspace_bytes, st);
-    return launch_wgrad_tile<128, 32, 4, 1, true>(a, dw, ws, workspace_bytes, st);
+    default:                 // the ring kernel, with as many reduction splits as the workspace holds
+        if ((a.K & 3) != 0) return launch_wgrad_tile<128, 32, 4, 1, false>(a, dw, ws, workspace_bytes, st);
+        if (a.K > 64) return launch_wgrad_tile<128, 128, 2, 2, true>(a, dw, ws, workspace_bytes, st);
+        if (a.K > 32) return launch_wgrad_tile<128, 64, 2, 2, true>(a, dw, ws, workspace_bytes, st);
+        return launch_wgrad_tile<128, 32, 4, 1, true>(a, dw, ws, workspace_bytes, st);
+    }
+    hipLaunchKernelGGL(splitk_reduce_many_kernel, dim3((unsigned)pnp_cdiv((long long)nout, 64)), dim3(1024), 0, st,
+                       (const float*)ws, dw, (int)nout, nparts, accumulate);
+    PNP_CHECK_LAUNCH("splitk_reduce_many_kernel");
+    return PNP_OK;
 }
 
 int pnp_conv2d_wgrad(const float* x, const float* dy, float* dw, const pnp_conv_geom* g, void* workspace,

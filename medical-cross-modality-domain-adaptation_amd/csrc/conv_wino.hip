@@ -1344,7 +1344,6 @@ bool wino_eligible(const pnp_conv_geom* g) {
 }
 
 int wino_tile(const pnp_conv_geom* g) { return plan_tile(g, false); }
-bool wino_chosen(const pnp_conv_geom* g) { return plan_tile(g, false) != 0; }
 
 // One plan per GEMM launch of forward / data gradient, shared by the workspace query, the launch and the output transform.
 // Persistent (grid = 512 = 2 workgroups per CU, 64 per XCD) when there are more tiles than slots and every transform point fits 31-bit
@@ -1391,7 +1390,6 @@ size_t wino_workspace_bytes(const pnp_conv_geom* g) {
 }
 
 int wino_stats_parts(const pnp_conv_geom* g) {
-    if (x3d_chosen(g)) return x3d_stats_parts(g);            // (conv_x3_direct.hip takes the layer from launch_wino)
     const int m = plan_tile(g, false);
     const WinoGeom w = make_wgeom(g, m ? m : 2);
     int tpb, nblk;
@@ -1492,17 +1490,14 @@ static int launch_wino_m(const ConvArgs& a, int kind, bool flip_transpose, void*
 
 // a: the convolution's arguments as make_args built them (kind 1: of the data gradient AS a convolution of dy: a.C = the forward's K,
 // a.K = its C) with every epilogue field honoured; flip_transpose: a.w is the FORWARD filter [3][3][a.K][a.C].  The tile is planned here
-// from the same fields the workspace / parts queries see (one decision per call)
+// from the same fields the workspace / parts queries see (one decision per call).  Winograd and nothing else: the narrow layers that run as
+// direct split-bf16 convolutions instead are another route of the plan (conv_igemm.hip: plan_fwd / plan_dgrad)
 int launch_wino(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st) {
-    // the narrow layers (32 / 64 input channels, <= 128 filters) run as DIRECT split-bf16 convolutions where that is on: no transforms,
-    // no 2.25x tensors (conv_x3_direct.hip; the workspace this route asked for is more than its filter image needs)
-    if (x3d_chosen(a)) return launch_x3_direct(a, kind, flip_transpose, ws, ws_bytes, st);
     const int m = plan_tile(a, false);
     PNP_REQUIRE(m == 2 || m == 4, "launch_wino: the planner does not route this layer (policy changed between the query and the launch?)");
     return m == 4 ? launch_wino_m<4>(a, kind, flip_transpose, ws, ws_bytes, st) : launch_wino_m<2>(a, kind, flip_transpose, ws, ws_bytes, st);
 }
 
-bool wino_wgrad_chosen(const pnp_conv_geom* g) { return plan_tile(g, true) != 0; }
 int wino_wgrad_tile(const pnp_conv_geom* g) { return plan_tile(g, true); }
 
 // the filter gradient's GEMMs on the split-bf16 kernel (PNP_WINOGRAD_X3 on, PNP_WINOGRAD_X3_WGRAD != 0).  Mode 1: where measured to pay at

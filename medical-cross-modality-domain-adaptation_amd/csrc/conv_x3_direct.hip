@@ -19,10 +19,10 @@
 // (same counter hash on the flat output index, a division like tf.nn.dropout), residual add (data gradients), batch-norm statistics
 // partials (one per consumer wave = 64 pixels), then stores of 128 contiguous bytes per pixel.  Accuracy: every product exact, one fp32
 // chain of 9 C terms — 8e-7 of max|ref| on 64 -> 64 (the direct fp32 kernel 2.9e-6, F(4x4) 1.2e-6 .. 8e-6).
-// Entry: launch_wino() hands the layers x3d_chosen() takes to launch_x3_direct() (they are layers the Winograd planner owns: workspace and
-// partial-count queries go through the same functions).  PNP_X3_DIRECT / pnp_conv2d_x3_direct(): 0 off, 1 where a launch fills the chip, 2 wherever the shapes allow.
+// Entry: plan_fwd / plan_dgrad (conv_igemm.hip) give the layers x3d_chosen() takes the route X3D — also layers the Winograd planner owns,
+// which keep that route's (larger) workspace; the fused inference BN is not in this epilogue.  PNP_X3_DIRECT / pnp_conv2d_x3_direct(): 0 off, 1 where a launch fills the chip, 2 wherever the shapes allow.
 // The strided layers (conv_x3_direct_kernel_strided below, PNP_X3_STRIDED): forward and stride-phase data gradient as sums of stride-1
-// sub-convolutions on the same LDS layout, MFMA order and epilogue; entered from pnp_conv2d_fwd* / dgrad_impl through x3s_chosen().
+// sub-convolutions on the same LDS layout, MFMA order and epilogue; the plan's route X3S, through x3s_chosen().
 // The FILTER gradient of the stride-1 layers with 64 filters is conv_x3_wgrad.hip (PNP_X3_WGRAD), under this file's mode (x3d_route_mode()).
 #include <atomic>
 #include <cstdlib>
@@ -911,17 +911,13 @@ bool x3d_chosen(const pnp_conv_geom* g) {
     return x3d_mode() > 0 && g->dtype == PNP_DTYPE_F32 && (g->pad_mode == PNP_PAD_ZERO || (g->pad_t == 0 && g->pad_l == 0)) && dims_ok(g->R, g->S, g->stride, g->dil, g->C, g->K, g->OH, g->OW, (long long)g->N * g->OH * g->OW);
 }
 
-bool x3d_chosen(const ConvArgs& a) {
-    return x3d_mode() > 0 && a.dtype == PNP_DTYPE_F32 && (a.pad_mode == PNP_PAD_ZERO || (a.pad_t == 0 && a.pad_l == 0)) && a.ups == 1 && a.o_s == 0 && a.y_h == nullptr && a.ep_scale == nullptr &&
-           dims_ok(a.R, a.S, a.stride, a.dil, a.C, a.K, a.OH, a.OW, a.M);
-}
-
 // one partial per consumer wave: 64 pixels (4 rows x 16) — M / 64 of them
 int x3d_stats_parts(const pnp_conv_geom* g) { return (int)(((long long)g->N * g->OH * g->OW) / 64); }
 
 size_t x3d_filter_bytes(int C, int K) { return (size_t)9 * C * K * 6; }
 
 int launch_x3_direct(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st) {
+    PNP_REQUIRE(a.ep_scale == nullptr && a.y_h == nullptr && a.o_s == 0 && a.ups == 1, "launch_x3_direct: unsupported epilogue");
     const size_t fbytes = x3d_filter_bytes(a.C, a.K);
     if (!ws || ws_bytes < fbytes) {
         pnp_set_error("launch_x3_direct: workspace too small (%zu < %zu)", ws_bytes, fbytes);

@@ -25,7 +25,7 @@
 //   * persistent workgroups (at most one per CU) over a STATIC contiguous share of the tiles; each writes its partial [9 C 64] once, and
 //     x3w_reduce_kernel sums the partials in a fixed order (two deterministic levels: 16 interleaved chains per value, then the 16 in order)
 //     and adds into dW for the accumulating entry point.  No atomics: two runs are bit-identical.
-// Entry: wgrad_impl (conv_igemm.hip) asks x3w_chosen() after the Winograd filter-gradient planner and before the fp32-pipe ring kernel;
+// Entry: plan_wgrad (conv_igemm.hip) asks x3w_chosen() after the Winograd filter-gradient planner and before the fp32-pipe ring kernel;
 // x3w_workspace_bytes() is what wgrad_ws() reports for the layers the predicate takes.  PNP_X3_WGRAD / pnp_conv2d_x3_wgrad(): 0 off, 1 on,
 // under PNP_X3_DIRECT's mode (0 there: off; 1: layers with >= 256 tiles; 2: wherever the shapes allow).
 #include <atomic>

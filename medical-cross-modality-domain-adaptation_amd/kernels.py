@@ -181,6 +181,12 @@ def wino_chosen(g, kind=0):
     return int(_lib.load().pnp_conv2d_wino_chosen(ctypes.byref(g), int(kind)))
 
 
+def conv_route(g, kind=0):
+    """the kernel family (_lib.ROUTE_*) that serves this layer's forward with the plain epilogue (kind 0) / data gradient (1) / filter gradient
+    (2) when the workspace of the query is supplied (g = the forward geometry): pnp_conv2d_route"""
+    return int(_lib.load().pnp_conv2d_route(ctypes.byref(g), int(kind)))
+
+
 # ---- transformed-filter cache of the Winograd route (pnp_conv2d_wino_filter_bind) ------------------------------------------------------
 # U = G g G^T changes only when the filter does.  Filters OWNED BY A VariableStore (variables.py marks their tensors `_pnp_var`) get one
 # buffer per pass, lent to the library; the library skips wino_filter_kernel while the entry is valid.  Validity: the library drops an

@@ -42,6 +42,39 @@ def test_workspace_queries_and_error_channel(built):
     assert rc == -1 and b"non-positive" in lib.pnp_last_error()
 
 
+def test_short_workspace_is_refused_before_any_launch(built):
+    """pnp_conv2d_fwd_stats_ws and pnp_conv2d_dgrad with a workspace ONE BYTE short of the query, on a layer of the Winograd route, of the
+    direct split-bf16 route (stride 1: alone, and under the Winograd planner, whose larger workspace it keeps) and of its strided kernels:
+    PNP_EINVAL "workspace too small", decided on the host before the first HIP call — the tensors are small host buffers, never read"""
+    import ctypes
+    L = built._lib
+    lib = L.load()
+    K = pkg("kernels")
+    geo = lambda N, H, W, C, Kf, k=3, stride=1: K.conv_geom((N, H, W, C), (k, k, C, Kf), stride, 1, "SAME")
+    buf = ctypes.create_string_buffer(256)
+    ptr = ctypes.c_void_p(ctypes.addressof(buf))
+    prev = (K.wino_mode(-1), K.x3_direct(-1), K.x3_strided(-1))
+    try:
+        #            wino_mode, x3_direct, geometry
+        for wm, xm, g in ((1, 0, geo(16, 32, 32, 512, 512)),                    # Winograd
+                          (0, 2, geo(3, 160, 176, 64, 64)),                     # direct split-bf16, stride 1: its filter image
+                          (2, 2, geo(3, 160, 176, 64, 64)),                     # ... as a layer of the Winograd planner: that route's workspace
+                          (1, 2, geo(6, 224, 256, 64, 64, stride=2))):          # direct split-bf16, strided
+            K.wino_mode(wm); K.x3_direct(xm); K.x3_strided(1)
+            need_f = int(lib.pnp_conv2d_fwd_workspace_bytes(ctypes.byref(g)))
+            need_d = int(lib.pnp_conv2d_dgrad_workspace_bytes(ctypes.byref(g)))
+            assert need_f > 256 and need_d > 256, (wm, xm, need_f, need_d)
+            assert int(lib.pnp_conv2d_fwd_stats_ws_parts(ctypes.byref(g))) > 0
+            rc = lib.pnp_conv2d_fwd_stats_ws(ptr, ptr, ptr, ctypes.byref(g), 1.0, 0, 0, None, ptr, 1 << 40, ptr, need_f - 1, None)
+            assert rc == -1 and b"pnp_conv2d_fwd_stats_ws: workspace too small" in lib.pnp_last_error(), (wm, xm, rc, lib.pnp_last_error())
+            rc = lib.pnp_conv2d_fwd_stats_ws(ptr, ptr, ptr, ctypes.byref(g), 1.0, 0, 0, None, ptr, 1 << 40, None, need_f, None)
+            assert rc == -1 and b"pnp_conv2d_fwd_stats_ws: workspace too small" in lib.pnp_last_error(), (wm, xm, rc, lib.pnp_last_error())
+            rc = lib.pnp_conv2d_dgrad(ptr, ptr, ptr, ctypes.byref(g), ptr, need_d - 1, None)
+            assert rc == -1 and b"pnp_conv2d_dgrad: workspace too small" in lib.pnp_last_error(), (wm, xm, rc, lib.pnp_last_error())
+    finally:
+        K.wino_mode(prev[0]); K.x3_direct(prev[1]); K.x3_strided(prev[2])
+
+
 def test_no_cpu_fallback(built):
     K = pkg("kernels")
     x = torch.zeros((1, 8, 8, 4))
@@ -184,6 +217,16 @@ def test_resident_bf16_planners_on_the_host(built):
     assert ws(geo(16, 256, 16, 16, 3)) == 0 and lib.pnp_conv2d_wgrad_bf16r_workspace_bytes(None) == 0
 
 
+def _tiles_and_routes(K, L, g):
+    """(pnp_conv2d_wino_chosen, pnp_conv2d_route) for kinds 0..2, with what ties them: a layer of the Winograd planner (tile != 0) launches
+    Winograd or — a narrow layer — the direct split-bf16 kernel in its workspace; nothing else launches Winograd"""
+    tiles, routes = tuple(K.wino_chosen(g, k) for k in (0, 1, 2)), tuple(K.conv_route(g, k) for k in (0, 1, 2))
+    for k in (0, 1):
+        assert (routes[k] == L.ROUTE_WINO) <= (tiles[k] != 0) and (tiles[k] != 0) <= (routes[k] in (L.ROUTE_WINO, L.ROUTE_X3D)), (k, tiles, routes)
+    assert (routes[2] == L.ROUTE_WINO_WGRAD) == (tiles[2] != 0), (tiles, routes)
+    return tiles, routes
+
+
 def test_winograd_route_planner_on_the_host(built):
     """which layers the Winograd F(2x2, 3x3) route takes (csrc/conv_wino.hip), its workspace (transformed filter + input + product) and
     its statistics partial rows are host functions of the C-ABI: pinned here without a GPU, for every policy mode"""
@@ -192,7 +235,8 @@ def test_winograd_route_planner_on_the_host(built):
     K, L = importlib.import_module(built.__name__ + ".kernels"), built._lib
     lib = L.load()
     geo = lambda N, H, C, Kf, k=3, stride=1, dil=1, pad="SAME", dt=L.DTYPE_F32: K.conv_geom((N, H, H, C), (k, k, C, Kf), stride, dil, pad, dtype=dt)
-    ch = lambda g: (bool(K.wino_chosen(g, 0)), bool(K.wino_chosen(g, 1)))
+    ch = lambda g: tuple(bool(t) for t in _tiles_and_routes(K, L, g)[0][:2])
+    rt = lambda g: _tiles_and_routes(K, L, g)[1]
     prev, prev_t = K.wino_mode(-1), K.wino_tile(2)          # F(2x2, 3x3) alone first; F(4x4, 3x3): the next test
     prev_x3 = K.wino_x3(0)                                  # (the fp32-pipe plan; the split-bf16 GEMM's: test_winograd_x3_plan_on_the_host)
     try:
@@ -203,6 +247,9 @@ def test_winograd_route_planner_on_the_host(built):
         assert direct_ws == 0 and direct_parts == int(lib.pnp_conv2d_fwd_stats_parts(ctypes.byref(g))) > 0
         K.wino_mode(1)
         assert ch(geo(16, 32, 512, 512)) == (True, True)                        # group_7..9
+        assert rt(geo(16, 32, 512, 512))[:2] == (L.ROUTE_WINO, L.ROUTE_WINO) and rt(geo(16, 34, 512, 2560, pad="VALID"))[:2] == (L.ROUTE_WINO, L.ROUTE_WINO)
+        assert rt(geo(16, 32, 128, 128))[:2] == (L.ROUTE_IGEMM, L.ROUTE_IGEMM)  # (what "not chosen" then launches)
+        assert rt(geo(16, 128, 128, 128, k=5, stride=2))[1] in (L.ROUTE_X3S, L.ROUTE_PHASES) and rt(geo(16, 64, 256, 256, stride=2))[1] == L.ROUTE_PHASES
         assert ch(geo(16, 32, 512, 512, dil=2)) == (True, True)                 # group_8 (atrous rate 2)
         assert ch(geo(16, 32, 256, 256)) == (True, True) and ch(geo(16, 32, 256, 512)) == (True, True)
         assert ch(geo(16, 34, 512, 2560, pad="VALID")) == (True, True)          # group_10 on its mirror-padded input; dgrad: padding 2
@@ -233,14 +280,15 @@ def test_winograd_route_planner_on_the_host(built):
         try:
             g = geo(16, 32, 512, 512)
             direct = int(lib.pnp_conv2d_wgrad_workspace_bytes(ctypes.byref(g)))
-            assert not K.wino_chosen(g, 2) and direct % (9 * 512 * 512 * 4) == 0
+            assert not K.wino_chosen(g, 2) and direct % (9 * 512 * 512 * 4) == 0 and rt(g)[2] == L.ROUTE_RING
             K.wino_wgrad_mode(1)
+            assert rt(g)[2] == L.ROUTE_WINO_WGRAD and rt(geo(16, 32, 128, 256))[2] == L.ROUTE_RING
             assert K.wino_chosen(g, 2) and K.wino_chosen(geo(16, 32, 256, 256), 2) and not K.wino_chosen(geo(16, 32, 128, 256), 2)      # break-even 256 -> 256
             assert not K.wino_chosen(geo(16, 32, 128, 128), 2) and not K.wino_chosen(geo(16, 64, 256, 256, stride=2), 2)
             T = 16 * 16 * 16                    # 256 tiles of 128 x 128 x 16 points: split in two to fill a dispatch round
             assert int(lib.pnp_conv2d_wgrad_workspace_bytes(ctypes.byref(g))) == 16 * 4 * (T * 512 + T * 512 + 2 * 512 * 512)
             K.wino_mode(0)
-            assert not K.wino_chosen(g, 2)              # PNP_WINOGRAD=0 is the master switch of the route
+            assert not K.wino_chosen(g, 2) and rt(g) == (L.ROUTE_IGEMM, L.ROUTE_IGEMM, L.ROUTE_RING)      # PNP_WINOGRAD=0 is the master switch of the route
             K.wino_mode(1)
             g10 = geo(16, 34, 512, 2560, pad="VALID")       # 1280 tiles: un-split
             assert int(lib.pnp_conv2d_wgrad_workspace_bytes(ctypes.byref(g10))) == 16 * 4 * (T * 512 + T * 2560 + 512 * 2560)
@@ -261,10 +309,20 @@ def test_winograd_f4_planner_on_the_host(built):
     K, L = importlib.import_module(built.__name__ + ".kernels"), built._lib
     lib = L.load()
     geo = lambda N, H, C, Kf, k=3, stride=1, dil=1, pad="SAME", dt=L.DTYPE_F32: K.conv_geom((N, H, H, C), (k, k, C, Kf), stride, dil, pad, dtype=dt)
-    ch = lambda g: (K.wino_chosen(g, 0), K.wino_chosen(g, 1), K.wino_chosen(g, 2))
+    ch = lambda g: _tiles_and_routes(K, L, g)[0]
+    rt = lambda g: _tiles_and_routes(K, L, g)[1]
     prev, prev_w, prev_t, prev_x3 = K.wino_mode(1), K.wino_wgrad_mode(1), K.wino_tile(4), K.wino_x3(0)
+    prev_d, prev_dw = K.x3_direct(1), K.x3_wgrad(1)         # (the library's defaults: the narrow layers' direct split-bf16 kernels on)
     try:
         assert K.wino_tile(-1) == 4
+        assert rt(geo(16, 32, 512, 512)) == (L.ROUTE_WINO, L.ROUTE_WINO, L.ROUTE_WINO_WGRAD)
+        assert rt(geo(16, 32, 128, 128)) == (L.ROUTE_IGEMM, L.ROUTE_IGEMM, L.ROUTE_WINO_WGRAD)
+        # cls1 64 -> 64 @256^2 is the Winograd planner's (tile 4: its workspace) and RUNS on the direct split-bf16 kernels; 32 -> 64 likewise
+        # without the planner; with that family off both launch what wino_chosen says
+        assert rt(geo(16, 256, 64, 64)) == (L.ROUTE_X3D, L.ROUTE_X3D, L.ROUTE_X3W) and rt(geo(16, 256, 32, 64)) == (L.ROUTE_X3D, L.ROUTE_X3D, L.ROUTE_X3W)
+        K.x3_direct(0)
+        assert rt(geo(16, 256, 64, 64)) == (L.ROUTE_WINO, L.ROUTE_WINO, L.ROUTE_RING) and rt(geo(16, 256, 32, 64))[:2] == (L.ROUTE_IGEMM, L.ROUTE_IGEMM)
+        K.x3_direct(1)
         assert ch(geo(16, 32, 512, 512)) == (4, 4, 4) and ch(geo(16, 32, 512, 512, dil=2)) == (4, 4, 4)
         assert ch(geo(16, 34, 512, 2560, pad="VALID")) == (4, 2, 4)             # group_10: its data gradient reduces over 2 560 channels -> F(2x2) (rounding)
         assert ch(geo(16, 32, 256, 256)) == (4, 4, 4)
@@ -299,11 +357,14 @@ def test_winograd_f4_planner_on_the_host(built):
         K.wino_mode(2)
         K.wino_wgrad_mode(2)
         assert ch(geo(1, 8, 64, 32)) == (4, 4, 4) and ch(geo(16, 256, 32, 16)) == (0, 0, 0)
+        assert rt(geo(1, 8, 64, 32)) == (L.ROUTE_WINO, L.ROUTE_WINO, L.ROUTE_WINO_WGRAD) and rt(geo(16, 256, 32, 16))[0] == L.ROUTE_N16
     finally:
         K.wino_mode(prev)
         K.wino_wgrad_mode(prev_w)
         K.wino_tile(prev_t)
         K.wino_x3(prev_x3)
+        K.x3_direct(prev_d)
+        K.x3_wgrad(prev_dw)
 
 
 def test_winograd_x3_plan_on_the_host(built):
@@ -327,7 +388,7 @@ def test_winograd_x3_plan_on_the_host(built):
         g512, g256, g128, g10 = geo(16, 32, 512, 512), geo(16, 32, 256, 512), geo(16, 128, 128, 128), geo(16, 34, 512, 2560, pad="VALID")
         assert ws(g512) == x3(g512, T) and ws(g256) == x3(g256, T) and ws(g10) == x3(g10, T)
         assert ws(g128) == f32(g128, 16 * 32 * 32)                               # 128-channel reduction: stays on the fp32 pipe under mode 1
-        assert K.wino_chosen(g10, 1) == 4                                        # data gradient: reduction over 2 560 channels, chunked
+        assert K.wino_chosen(g10, 1) == 4 and K.conv_route(g10, 1) == L.ROUTE_WINO   # data gradient: reduction over 2 560 channels, chunked
         Td = 16 * 9 * 9                                                          # its output is the 34 x 34 mirror-padded map: 9 x 9 tiles of 4 x 4
         assert int(lib.pnp_conv2d_dgrad_workspace_bytes(ctypes.byref(g10))) == al(36 * 6 * 2560 * 512) + al(36 * 6 * Td * 2560) + al(36 * 4 * Td * 512)
         assert int(lib.pnp_conv2d_wino_filter_bytes(512, 512)) == 36 * 6 * 512 * 512          # an entry of the transformed-filter cache serves either format

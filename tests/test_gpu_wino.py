@@ -147,6 +147,54 @@ def test_winograd_fwd_dgrad_vs_float64_and_direct(dev, wino, case):
     assert max(errs.values()) < BAR, errs
 
 
+def test_without_a_workspace_the_fp32_mfma_kernels_run(dev):
+    """pnp_conv2d_fwd_ws and pnp_conv2d_wgrad called WITHOUT a workspace on layers the planner gives to a route that needs one (Winograd;
+    the direct split-bf16 kernels, strided forward and filter gradient): the un-split implicit-GEMM / ring kernels run, nothing else, and
+    meet the float64 convolution at this file's bar"""
+    import ctypes
+    K, L = pkg("kernels"), pkg("_lib")
+    lib = L.load()
+    prev = (K.wino_mode(-1), K.wino_wgrad_mode(-1), K.x3_direct(-1), K.x3_strided(-1), K.x3_wgrad(-1))
+    #        (N, H, W, C, K, stride), wino_mode, wino_wgrad_mode, filter gradient?
+    table = [((4, 32, 32, 512, 512, 1), 2, 2, False),        # forward: Winograd
+             ((3, 32, 96, 64, 64, 2), 1, 0, False),          # forward: strided split-bf16
+             ((4, 32, 32, 512, 512, 1), 2, 2, True),         # filter gradient: Winograd
+             ((2, 32, 48, 64, 64, 1), 1, 0, True)]           # filter gradient: split-bf16
+    try:
+        K.x3_direct(2); K.x3_strided(1); K.x3_wgrad(1)
+        for (N, H, W, C, Kf, s), wm, wwm, wgrad in table:
+            K.wino_mode(wm); K.wino_wgrad_mode(wwm)
+            rng = np.random.default_rng(N + H + W + C + Kf + s)
+            x = rng.standard_normal((N, H, W, C)).astype(np.float32)
+            w = (rng.standard_normal((3, 3, C, Kf)) * np.sqrt(2.0 / (9 * C))).astype(np.float32)
+            g = K.conv_geom(x.shape, w.shape, s, 1, "SAME")
+            dy = rng.standard_normal((N, g.OH, g.OW, Kf)).astype(np.float32)
+            xd, wd, dyd = (torch.from_numpy(a).to(dev) for a in (x, w, dy))
+            wg = torch.from_numpy(w).double().requires_grad_(True)
+            yo = T.conv2d(torch.from_numpy(x).double(), wg, s, 1, "SAME")
+            yo.backward(torch.from_numpy(dy).double())
+            query = lib.pnp_conv2d_wgrad_workspace_bytes if wgrad else lib.pnp_conv2d_fwd_workspace_bytes
+            with_ws = (lambda: K.conv2d_wgrad(xd, dyd, g)) if wgrad else (lambda: K.conv2d_fwd(xd, wd, g))
+            cls = L.PROF_CONV_WGRAD if wgrad else L.PROF_CONV_FWD
+            _, routed = _ran(L, with_ws, cls)
+            assert int(query(ctypes.byref(g))) > 0 and any("wino" in n or "x3" in n for n in routed), routed     # the layer IS on such a route
+            out = torch.empty(w.shape if wgrad else tuple(yo.shape), dtype=torch.float32, device=dev)
+
+            def bare():
+                if wgrad:
+                    L.check(lib.pnp_conv2d_wgrad(K._p(xd), K._p(dyd), K._p(out), ctypes.byref(g), None, 0, K._stream()), "pnp_conv2d_wgrad")
+                else:
+                    L.check(lib.pnp_conv2d_fwd_ws(K._p(xd), K._p(wd), K._p(out), ctypes.byref(g), 1.0, 0, 0, None, 0, K._stream()), "pnp_conv2d_fwd_ws")
+            _, names = _ran(L, bare, cls)
+            ok = ("conv_wgrad_ring_kernel<", "conv_wgrad_kernel<") if wgrad else ("conv_taps_kernel<", "conv_taps3_kernel<", "conv_fwd_kernel<")
+            assert names and all(n.startswith(ok) for n in names), names
+            err = _rel(out, wg.grad if wgrad else yo.detach())
+            print("no workspace, %s of %s: ran %s, %.2e of max|ref|" % ("filter gradient" if wgrad else "forward", (N, H, W, C, Kf, s), names, err))
+            assert err < BAR, err
+    finally:
+        K.wino_mode(prev[0]); K.wino_wgrad_mode(prev[1]); K.x3_direct(prev[2]); K.x3_strided(prev[3]); K.x3_wgrad(prev[4])
+
+
 def test_winograd_epilogues_equal_the_direct_route(dev, wino):
     """dropout (the same mask stream: identical zero pattern), BN statistics partials -> mean / variance / moving averages, fused
     inference BN + channel-padded shortcut + leaky-ReLU: the Winograd route's output transform against conv_epilogue of the direct kernels"""

@@ -33,13 +33,7 @@ def _rel(a, b):
     return float((a - b).abs().max() / (b.abs().max() + 1e-300))
 
 
-def _ran(L, fn, cls):
-    L.prof_summary()
-    L.prof_enable(cls)
-    out = fn()
-    torch.cuda.synchronize()
-    L.prof_enable(0)
-    return out, sorted(r["name"] for r in L.prof_summary())
+from test_gpu_x3_domain import _ran          # (symbols that ran; with a geometry: and the route the library reports is their family)
 
 
 @pytest.fixture
@@ -68,17 +62,17 @@ def test_direct_split_bf16_fwd_dgrad_vs_float64(dev, route, case):
     assert K.wino_chosen(g, 0) == 4
 
     K.x3_direct(0)
-    y0, names0 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD)
+    y0, names0 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD, g)
     assert not any("x3_direct" in n or "x3d" in n for n in names0), names0
     dx0 = K.conv2d_dgrad(dyd, wd, g)
     K.x3_direct(2)          # (2: wherever the shapes allow — mode 1 leaves launches that cannot fill the chip to the old route)
-    y1, names1 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD)
+    y1, names1 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD, g)
     taken_f = g.OH % 16 == 0 and g.OW % 16 == 0
     if taken_f:
         assert names1 == sorted(["x3d_filter_kernel<false>", "conv_x3_direct_kernel<%d, %d, 0>" % (C // 32, 32 if Kf == 32 else 64)]), names1
     else:
         assert not any("x3_direct" in n for n in names1), names1
-    dx1, names2 = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD)
+    dx1, names2 = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD, g)
     # (the data gradient is a convolution of dy: Kf input channels, C filters, H x W outputs — taken when THOSE fit)
     taken_d = Kf in (32, 64) and C in (32, 64, 128) and H % 16 == 0 and W % 16 == 0
     if taken_d:

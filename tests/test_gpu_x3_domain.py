@@ -110,13 +110,30 @@ def _rel(a, b):
     return float((a - b).abs().max() / (b.abs().max() + 1e-300))
 
 
-def _ran(L, fn, cls):
+def route_of(L, names):
+    """the kernel family (L.ROUTE_*) the recorded symbols of one launch belong to; None: a family this file does not name"""
+    for mark, r in (("conv_x3_direct_kernel_strided<", L.ROUTE_X3S), ("conv_x3_direct_kernel<", L.ROUTE_X3D), ("conv_x3_wgrad_kernel<", L.ROUTE_X3W),
+                    ("wino_wgrad_out_kernel<", L.ROUTE_WINO_WGRAD), ("wino_out_kernel<", L.ROUTE_WINO), ("conv_wgrad_ring_kernel<", L.ROUTE_RING),
+                    ("conv_wgrad_kernel<", L.ROUTE_RING)):
+        if any(n.startswith(mark) for n in names):
+            return r
+    return None
+
+
+def _ran(L, fn, cls, g=None):
+    """-> (result, symbols that ran); with g: the route the library reports for that pass of g is the family of those symbols"""
     L.prof_summary()
     L.prof_enable(cls)
     out = fn()
     torch.cuda.synchronize()
     L.prof_enable(0)
-    return out, sorted(r["name"] for r in L.prof_summary())
+    names = sorted(r["name"] for r in L.prof_summary())
+    if g is not None:
+        said = pkg("kernels").conv_route(g, {L.PROF_CONV_FWD: 0, L.PROF_CONV_DGRAD: 1, L.PROF_CONV_WGRAD: 2}[cls])
+        fam = route_of(L, names)
+        named = (L.ROUTE_X3S, L.ROUTE_X3D, L.ROUTE_X3W, L.ROUTE_WINO_WGRAD, L.ROUTE_WINO, L.ROUTE_RING)
+        assert said == fam if fam is not None else said not in named, (said, fam, names)
+    return out, names
 
 
 def _no_x3(names):
@@ -153,12 +170,12 @@ def _oracle(x, w, dy, stride, padding):
 def _strided_pair(K, L, xd, wd, dyd, g, case, want):
     """forward and data gradient with the strided route off (the fp32-pipe kernels of the same tree) and on; the symbols of both checked"""
     K.x3_strided(0)
-    y0, n0 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD)
-    dx0, n0d = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD)
+    y0, n0 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD, g)
+    dx0, n0d = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD, g)
     assert _no_x3(n0) and _no_x3(n0d), n0 + n0d
     K.x3_strided(1)
-    y1, n1 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD)
-    dx1, n1d = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD)
+    y1, n1 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD, g)
+    dx1, n1d = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD, g)
     taken = (x3s_expected(case, 0) > 0, x3s_expected(case, 1) > 0)
     assert taken == want, (case, taken, want)
     if taken[0]:
@@ -212,11 +229,11 @@ def test_stride1_domain_fwd_dgrad_wgrad_vs_float64(dev, route, case):
     errs, ran = {}, []
     want_f, want_d, want_w = (x3d_expected(case, k) for k in (0, 1, 2))
     assert want_f is not None, "every case of the table is a forward case"
-    y1, names = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD)
+    y1, names = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD, g)
     assert names == sorted(want_f), names
     ran += names
     errs["y"] = _rel(y1, yo)
-    dx1, names = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD)
+    dx1, names = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD, g)
     ran += names
     if want_d is not None:
         assert names == sorted(want_d), names
@@ -227,13 +244,13 @@ def test_stride1_domain_fwd_dgrad_wgrad_vs_float64(dev, route, case):
     bar_w = None
     if want_w is not None:
         K.x3_wgrad(0)                                     # the fp32-pipe route of the same tree: the yardstick of the bar
-        dw0, names0 = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g), L.PROF_CONV_WGRAD)
+        dw0, names0 = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g), L.PROF_CONV_WGRAD, g)
         assert _no_x3(names0), names0
         K.x3_wgrad(1)
-        dw1, names = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g), L.PROF_CONV_WGRAD)
+        dw1, names = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g), L.PROF_CONV_WGRAD, g)
         assert names == sorted(want_w), names
         ran += names
-        acc, names_a = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g, into=pred.clone()), L.PROF_CONV_WGRAD)
+        acc, names_a = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g, into=pred.clone()), L.PROF_CONV_WGRAD, g)
         assert names_a == sorted(want_w), names_a
         assert torch.equal(acc, pred + dw1), "accumulate differs from pre-fill + gradient"
         assert torch.equal(dw1, K.conv2d_wgrad(xd, dyd, g)), "two launches differ"
@@ -241,7 +258,7 @@ def test_stride1_domain_fwd_dgrad_wgrad_vs_float64(dev, route, case):
         errs["dw"], errs["dw fp32 route"] = _rel(dw1, dwo), _rel(dw0, dwo)
         bar_w = _bar(errs["dw fp32 route"])
     else:
-        _, names = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g), L.PROF_CONV_WGRAD)
+        _, names = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g), L.PROF_CONV_WGRAD, g)
         assert names and not any("x3w" in n or "x3_wgrad" in n for n in names), names
     print("x3 domain stride-1 %s: %s; ran %s" % (case, {k: "%.2e" % v for k, v in errs.items()}, ran))
     assert all(errs[k] < BAR for k in ("y", "dx", "dx+res") if k in errs), errs
@@ -289,12 +306,12 @@ def test_wide_operands_and_exact_zeros(dev, route, case):
         (y0, dx0), (y1, dx1), names = _strided_pair(K, L, xd, wd, dyd, g, case, (True, True))
     else:
         K.x3_direct(0)
-        y0, n0 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD)
-        dx0, n0d = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD)
+        y0, n0 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD, g)
+        dx0, n0d = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD, g)
         assert _no_x3(n0) and _no_x3(n0d), n0 + n0d
         K.x3_direct(2)
-        y1, n1 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD)
-        dx1, n1d = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD)
+        y1, n1 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD, g)
+        dx1, n1d = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD, g)
         assert n1 == sorted(x3d_expected(case, 0)) and n1d == sorted(x3d_expected(case, 1)), n1 + n1d
         names = n1 + n1d
     errs = {"y": _rel(y1, yo), "y fp32 route": _rel(y0, yo), "dx": _rel(dx1, dxo), "dx fp32 route": _rel(dx0, dxo)}

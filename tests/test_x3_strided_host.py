@@ -2,8 +2,9 @@
 the C-ABI show its choice wherever the split filter image (R S C K 6 bytes) is larger than what the fp32-pipe route asks for.  Relations,
 not absolute numbers: route taken -> on == max(off, image) (and on != off in the rows listed as moving); refused -> on == off.  The same
 Python restatement of the predicate (test_gpu_x3_domain.x3s_expected) decides which symbols tests/test_gpu_x3_domain.py expects on the GPU,
-so this file tells a reader of a GPU log, without a GPU, which of that table's cases the route owns.  (Where the fp32 route's own
-reduction-split workspace is larger than the image the query cannot show the choice: those cases are decided by the symbol names.)"""
+so this file tells a reader of a GPU log, without a GPU, which of that table's cases the route owns.  Where the fp32 route's own
+reduction-split workspace is larger than the image the byte counts cannot show the choice; pnp_conv2d_route says it outright, and every
+row is held to it as well: route == X3S exactly where the table says the route takes the layer."""
 import ctypes
 
 import pytest
@@ -59,13 +60,17 @@ def queries(built):
         K.x3_strided(strided)
         g = _geom(K, case, **kw)
         fn = lib.pnp_conv2d_dgrad_workspace_bytes if kind else lib.pnp_conv2d_fwd_workspace_bytes
+        ws.route = K.conv_route(g, kind)                                # (what the library says it launches, in the same setting)
         return int(fn(ctypes.byref(g)))
     yield K, L, ws
     K.x3_direct(prev[0]); K.x3_strided(prev[1]); K.wino_mode(prev[2])
 
 
 def _check(ws, case, kind, taken, moves=None):
-    off, on = ws(case, kind, 0), ws(case, kind, 1)
+    off = ws(case, kind, 0)
+    assert ws.route != pkg("_lib").ROUTE_X3S, (case, kind)
+    on = ws(case, kind, 1)
+    assert (ws.route == pkg("_lib").ROUTE_X3S) == taken, (case, kind, ws.route)
     if taken:
         assert on == max(off, _image(case)), (case, kind, off, on)
     else:
