@@ -265,7 +265,9 @@ __global__ void __launch_bounds__(NT) colreduce_kernel(ColArgs a) {
     }
 }
 
-// scalar fallback for C % 4 != 0 or C > 1024: one thread per channel per block-slab
+// scalar fallback for C % 4 != 0 or C > 1024: one thread per channel per block-slab.  The thread walks ALL rows of its slab (P below 64 rows, 64 or more otherwise) in
+// one chain, where a thread of colreduce_kernel walks rows_per_block / rpi of them: the chain is summed in double (a float32 chain of 63
+// rows missed the statistics' 1e-6 / 1e-5 bars at C = 1028: tests/test_gpu_elementwise_domain.py), the partial is rounded to float once
 template <int KIND>
 __global__ void colreduce_scalar_kernel(ColArgs a) {
     const int c = blockIdx.y * blockDim.x + threadIdx.x;
@@ -273,7 +275,7 @@ __global__ void colreduce_scalar_kernel(ColArgs a) {
     const long long r0 = (long long)blockIdx.x * a.rows_per_block;
     long long r1 = r0 + a.rows_per_block;
     if (r1 > a.P) r1 = a.P;
-    float s0 = 0.f, s1 = 0.f;
+    double s0 = 0.0, s1 = 0.0;
     float m, rs = 0.f;
     if constexpr (KIND == 0) m = a.x[c];
     else { m = a.mean[c]; rs = 1.0f / sqrtf(a.var[c] + a.eps); }
@@ -281,21 +283,21 @@ __global__ void colreduce_scalar_kernel(ColArgs a) {
         const size_t off = (size_t)r * a.C + c;
         float xv = a.x[off];
         if constexpr (KIND == 0) {
-            float d = xv - m;
-            s0 += d;
-            s1 = fmaf(d, d, s1);
+            const float d = xv - m;
+            s0 += (double)d;
+            s1 += (double)d * (double)d;
         } else {
             float g = a.dout[off];
             if (a.alpha >= 0.f) {
                 const float o = a.out ? a.out[off] : fmaf(xv - m, a.gamma[c] * rs, a.beta[c]);
                 g = o > 0.f ? g : g * a.alpha;
             }
-            s0 += g;
-            s1 = fmaf(g, (xv - m) * rs, s1);
+            s0 += (double)g;
+            s1 += (double)g * (double)((xv - m) * rs);
         }
     }
-    a.ws[((size_t)blockIdx.x * 2 + 0) * a.C + c] = s0;
-    a.ws[((size_t)blockIdx.x * 2 + 1) * a.C + c] = s1;
+    a.ws[((size_t)blockIdx.x * 2 + 0) * a.C + c] = (float)s0;
+    a.ws[((size_t)blockIdx.x * 2 + 1) * a.C + c] = (float)s1;
 }
 
 // Long partial lists (the convolution epilogue leaves one partial per 64 output rows: 16 384 of them for a 64-channel layer at 256^2,
@@ -590,9 +592,13 @@ struct BnBwdArgs {
     __bf16* dxh;     // bf16 copy of dx (operand of the bf16-resident data / filter gradient kernels); null: none
 };
 
-// (VEC: the thread-owns-a-channel-quad mapping of bn_apply_kernel; same expressions in the same order as the element-at-a-time form)
+// (VEC: the thread-owns-a-channel-quad mapping of bn_apply_kernel; same expressions in the same order as the element-at-a-time form.
+// Which products are fused into an FMA is written out and not left to the compiler: it fused g - dbeta * invP in the scalar form, where the
+// vector form holds the rounded product in a register, and the two forms differed in the last bit of a training-mode dx:
+// tests/test_gpu_elementwise_domain.py)
 template <bool VEC>
 __global__ void __launch_bounds__(NT) bn_bwd_apply_kernel(BnBwdArgs a) {
+#pragma clang fp contract(off)
     const int cpad = (a.C - a.Cs) / 2;
     const float invP = (float)(1.0 / (double)a.P_norm);
     const uint32_t dkey = a.do_drop ? pnp_eff_drop_key(a.drop_key, a.sp, a.drop_sid) : 0u;
@@ -646,7 +652,7 @@ __global__ void __launch_bounds__(NT) bn_bwd_apply_kernel(BnBwdArgs a) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float xh = (xv[e] - m[e]) * rs[e];
-                    r[e] = gsc[e] * (g[e] - dbp[e] - xh * dgp[e]);
+                    r[e] = gsc[e] * fmaf(-xh, dgp[e], g[e] - dbp[e]);
                 }
             } else {
 #pragma unroll
@@ -680,7 +686,7 @@ __global__ void __launch_bounds__(NT) bn_bwd_apply_kernel(BnBwdArgs a) {
             float r;
             if (a.training) {
                 float xh = (a.x[i] - a.mean[c]) * rs;
-                r = a.gamma[c] * rs * (g - a.dbeta[c] * invP - xh * (a.dgamma[c] * invP));
+                r = (a.gamma[c] * rs) * fmaf(-xh, a.dgamma[c] * invP, g - a.dbeta[c] * invP);
             } else {
                 r = a.gamma[c] * rs * g;
             }
