@@ -486,6 +486,48 @@ int pnp_axpby(const float* x, float* y, size_t n, float a, float b, void* stream
 /* out = x + y (out may alias neither): the gradient sum of a tensor that feeds two branches of the graph (TF autodiff's AddN) */
 int pnp_add(const float* x, const float* y, float* out, size_t n, void* stream);
 
+/* ---- training input from resident volumes (csrc/augment.hip; no counterpart in the reference, whose README only names
+ * the steps that produced its tfrecords: crop, cut the top 2 % of the intensity histogram, z-score, sample augmented 2-D slices) ----------
+ *
+ * pnp_volume_preprocess: one stream-ordered call, no host synchronisation.  v: n finite float32 voxels (NaN is unsupported: the caller's
+ * error); out (may be v itself): (min(v, clip) - mean) / std in float32, all zeros when std == 0.
+ *   clip  = the exact order statistic sorted(v)[k], k = (percentile * (n - 1) + 99) / 100 in integer arithmetic (percentile in [0, 100];
+ *           98 = "top 2 % cut off", numpy's method="higher" without a float index) — radix selection over the order-preserving uint32 key
+ *           of the float, 4 rounds of 8 bits, integer atomics only;
+ *   mean, std (population, ddof 0) of min(v, clip): float64 per-block partials summed in a fixed order, two passes (sum, then squared
+ *           deviations from the mean) — bit-identical from run to run;
+ *   stats[4] (device, float64): clip, mean, std, the normalised minimum (= the smallest value of `out`; the default fill of pnp_aug_slices).
+ * Refused on the host before any HIP call: n < 1, n >= 2^31, percentile outside [0, 100], null pointers, a short workspace. */
+size_t pnp_volume_preprocess_workspace_bytes(int64_t n);
+int pnp_volume_preprocess(const float* v, float* out, int64_t n, int32_t percentile, double* stats, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* one resident volume: image [X, Y, Z] float32 and label [X, Y, Z] uint8, both C order (z fastest: the array order of a NIfTI reader);
+ * `fill` is what an image corner outside [0, X) x [0, Y) contributes */
+typedef struct pnp_aug_volume {
+    const float* image;
+    const uint8_t* label;
+    int32_t X, Y, Z;
+    float fill;
+} pnp_aug_volume;
+/* one output slice: volume index, centre frame z in [1, Z - 2] and the affine map of output pixel (i, j) to source coordinates
+ *   sx = fmaf(m[0], i, fmaf(m[1], j, m[2])),  sy = fmaf(m[3], i, fmaf(m[4], j, m[5]))      (this order is part of the contract) */
+typedef struct pnp_aug_sample {
+    int32_t volume, frame;
+    float m[6];
+} pnp_aug_sample;
+/* x [B, H, W, 3]: channels = frames z-1, z, z+1, each bilinear between the four corners around (sx, sy), a corner outside the slice
+ *   contributing `fill` (scipy map_coordinates order=1, mode="grid-constant", cval=fill);
+ * label [B, H, W]: the label voxel at (floor(sx + 0.5), floor(sy + 0.5), z) as float32, 0 outside (order=0, grid-constant, cval=0);
+ * onehot [B, H, W, ncls] (nullable): the rows pnp_label_decomp gives for `label` (a label >= ncls: an all-zero row), same pass.
+ * vols_host / vols_dev: the same nvol descriptors in host memory (checked here, before any launch: X, Y in [1, 4096], Z >= 3, non-null
+ * pointers) and in device memory (read by the kernel).  A sample whose volume index or frame is out of range is not an error of the
+ * call: it is written as fill / 0 (0 / 0 when the volume index itself is bad) and counted once in *errors (device uint32, added to, never
+ * reset here).  x, label and onehot must be 16-byte aligned. */
+int pnp_aug_slices(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_dev, int32_t nvol, const pnp_aug_sample* samples_dev,
+                   int32_t B, int32_t H, int32_t W, float* x, float* label, float* onehot /*nullable*/, int32_t ncls,
+                   uint32_t* errors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -43,6 +43,16 @@ class ProfRow(ctypes.Structure):
                 ("bytes", ctypes.c_double)]
 
 
+class AugVolume(ctypes.Structure):
+    """mirror of `pnp_aug_volume` (include/pnp_hip.h)"""
+    _fields_ = [("image", c_void_p), ("label", c_void_p), ("X", c_int32), ("Y", c_int32), ("Z", c_int32), ("fill", c_float)]
+
+
+class AugSample(ctypes.Structure):
+    """mirror of `pnp_aug_sample` (include/pnp_hip.h)"""
+    _fields_ = [("volume", c_int32), ("frame", c_int32), ("m", c_float * 6)]
+
+
 PROF_CONV_FWD, PROF_CONV_DGRAD, PROF_CONV_WGRAD, PROF_CONV_DIRECT = 1, 2, 4, 8
 
 
@@ -165,6 +175,9 @@ PROTOTYPES = {
     "pnp_comm_init": (c_int, [c_int32, c_int32, c_void_p, POINTER(c_void_p)]),
     "pnp_comm_allreduce": (c_int, [c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
     "pnp_comm_destroy": (c_int, [c_void_p]),
+    "pnp_volume_preprocess_workspace_bytes": (c_size_t, [c_int64]),
+    "pnp_volume_preprocess": (c_int, [_F, _F, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnp_aug_slices": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, _F, _F, _F, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,0 +1,402 @@
+// Training input from resident volumes: per-volume preprocessing (clip at an exact order statistic, z-score) and the
+// augmented slice gather (affine-warped 3-frame slices, bilinear image / nearest label / one-hot, one pass).
+//
+//   preprocess   init          zero the 4 histograms, the selection state {prefix, k}
+//                hist x 4      per block: LDS histogram of the round's 8-bit digit over the keys that share the prefix found so far, then
+//                              integer atomics of the non-empty bins into the round's global histogram
+//                pick  x 4     one wave walks the 256 bins: the digit whose bin holds rank k; prefix |= digit << shift, k -= bins below
+//                sum           per-block float64 partial sums of min(v, clip) and partial minima of v (fixed grid, fixed tree)
+//                dev           every block re-adds the partial sums in the same fixed order -> mean; partial sums of squared deviations
+//                normalize     every block re-adds both partial lists -> mean, std; out = (min(v, clip) - mean) / std; block 0 writes stats
+//   gather       one launch: a lane owns 4 consecutive output pixels = three float4 of image, one float4 of label, ncls float4 of one-hot
+//
+// Every sum is a fixed-order tree over a grid that depends on n alone, every atomic is an integer atomic: results are bit-identical
+// from run to run.
+#include <algorithm>
+#include <math.h>
+
+#include "pnp_common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 1024;        // grid of the reductions: the partial lists have at most this many entries
+constexpr int kMaxExtentXY = 4096;
+constexpr int kMaxCls = 32;
+
+struct SelState {
+    uint32_t prefix;    // the key bits fixed by the rounds done so far
+    uint32_t k;         // rank of the wanted element among the keys that share the prefix (n < 2^31)
+};
+
+// order-preserving key of a finite float: negative values flip all bits, the others set the sign bit (-0.0 sorts just below +0.0: the
+// two are equal by value, which is all the clip needs)
+__device__ __forceinline__ uint32_t key_of(float f) {
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float float_of(uint32_t key) {
+    return __uint_as_float((key & 0x80000000u) ? (key & 0x7fffffffu) : ~key);
+}
+
+__global__ void __launch_bounds__(kThreads) pre_init_kernel(unsigned int* __restrict__ hist, SelState* __restrict__ st, uint32_t k) {
+    for (int i = threadIdx.x; i < 4 * 256; i += kThreads) hist[i] = 0u;
+    if (threadIdx.x == 0) {
+        st->prefix = 0u;
+        st->k = k;
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) pre_hist_kernel(const float* __restrict__ v, long long n, int shift, uint32_t mask,
+                                                            const SelState* __restrict__ st, unsigned int* __restrict__ hist) {
+    __shared__ unsigned int h[256];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t prefix = st->prefix;
+    const long long gs = (long long)gridDim.x * kThreads;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += gs) {
+        const uint32_t key = key_of(v[i]);
+        if ((key & mask) == prefix) atomicAdd(&h[(key >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const unsigned int c = h[threadIdx.x];
+    if (c) atomicAdd(&hist[threadIdx.x], c);
+}
+
+__global__ void __launch_bounds__(64) pre_pick_kernel(const unsigned int* __restrict__ hist, int shift, SelState* __restrict__ st) {
+    if (threadIdx.x != 0) return;
+    uint32_t k = st->k;
+    int b = 0;
+    for (; b < 255; ++b) {
+        const unsigned int c = hist[b];
+        if (k < c) break;
+        k -= c;
+    }
+    st->prefix |= (uint32_t)b << shift;
+    st->k = k;
+}
+
+// fixed-order sum of a partial list by one block: thread t adds entries t, t + 256, ... then a tree over the 256 threads
+__device__ __forceinline__ double block_sum_of_list(const double* __restrict__ p, int np, double* sh) {
+    double a = 0.0;
+    for (int i = threadIdx.x; i < np; i += kThreads) a += p[i];
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+__device__ __forceinline__ double block_tree(double a, double* sh) {
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+__global__ void __launch_bounds__(kThreads) pre_sum_kernel(const float* __restrict__ v, long long n, const SelState* __restrict__ st,
+                                                           double* __restrict__ psum, float* __restrict__ pmin) {
+    __shared__ double sh[kThreads];
+    __shared__ float shm[kThreads];
+    const float clip = float_of(st->prefix);
+    const long long gs = (long long)gridDim.x * kThreads;
+    double a = 0.0;
+    float m = INFINITY;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += gs) {
+        const float x = v[i];
+        a += (double)fminf(x, clip);
+        m = fminf(m, x);
+    }
+    shm[threadIdx.x] = m;
+    const double s = block_tree(a, sh);
+    for (int h = kThreads / 2; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) shm[threadIdx.x] = fminf(shm[threadIdx.x], shm[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        psum[blockIdx.x] = s;
+        pmin[blockIdx.x] = shm[0];
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) pre_dev_kernel(const float* __restrict__ v, long long n, const SelState* __restrict__ st,
+                                                           const double* __restrict__ psum, double* __restrict__ pdev) {
+    __shared__ double sh[kThreads];
+    const float clip = float_of(st->prefix);
+    const double mean = block_sum_of_list(psum, gridDim.x, sh) / (double)n;
+    const long long gs = (long long)gridDim.x * kThreads;
+    double a = 0.0;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += gs) {
+        const double d = (double)fminf(v[i], clip) - mean;
+        a = fma(d, d, a);
+    }
+    const double s = block_tree(a, sh);
+    if (threadIdx.x == 0) pdev[blockIdx.x] = s;
+}
+
+__device__ __forceinline__ float normalized(float x, float clip, double mean, double inv_std) {
+    return (float)(((double)fminf(x, clip) - mean) * inv_std);
+}
+
+__global__ void __launch_bounds__(kThreads) pre_normalize_kernel(const float* v, float* out, long long n, const SelState* __restrict__ st,
+                                                                 const double* __restrict__ psum, const double* __restrict__ pdev,
+                                                                 const float* __restrict__ pmin, double* __restrict__ stats) {
+    __shared__ double sh[kThreads];
+    __shared__ float shm[kThreads];
+    const float clip = float_of(st->prefix);
+    const double mean = block_sum_of_list(psum, gridDim.x, sh) / (double)n;
+    const double std_ = sqrt(block_sum_of_list(pdev, gridDim.x, sh) / (double)n);
+    const double inv_std = std_ > 0.0 ? 1.0 / std_ : 0.0;          // std == 0: every output is 0
+    if (blockIdx.x == 0) {
+        float m = INFINITY;
+        for (int i = threadIdx.x; i < (int)gridDim.x; i += kThreads) m = fminf(m, pmin[i]);
+        shm[threadIdx.x] = m;
+        __syncthreads();
+        for (int h = kThreads / 2; h > 0; h >>= 1) {
+            if ((int)threadIdx.x < h) shm[threadIdx.x] = fminf(shm[threadIdx.x], shm[threadIdx.x + h]);
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            stats[0] = (double)clip;
+            stats[1] = mean;
+            stats[2] = std_;
+            stats[3] = (double)normalized(shm[0], clip, mean, inv_std);
+        }
+    }
+    const long long gs = (long long)gridDim.x * kThreads;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += gs) out[i] = normalized(v[i], clip, mean, inv_std);
+}
+
+// ---- the gather ---------------------------------------------------------------------------------------------------------------------
+struct Px {
+    float c[3];
+    float lab;
+};
+
+__device__ __forceinline__ Px sample_pixel(const pnp_aug_volume& vol, bool ok, int z, const float* m, int i, int j) {
+    Px r;
+    const float fill = vol.fill;
+    r.c[0] = r.c[1] = r.c[2] = fill;
+    r.lab = 0.f;
+    if (!ok) return r;
+    const float sx = fmaf(m[0], (float)i, fmaf(m[1], (float)j, m[2]));
+    const float sy = fmaf(m[3], (float)i, fmaf(m[4], (float)j, m[5]));
+    const int X = vol.X, Y = vol.Y, Z = vol.Z;
+    // outside (-1, X) x (-1, Y) all four corners are outside the slice (a NaN coordinate fails the comparisons too)
+    if (!(sx > -1.f && sx < (float)X && sy > -1.f && sy < (float)Y)) return r;
+    const float fx0 = floorf(sx), fy0 = floorf(sy);
+    const int x0 = (int)fx0, y0 = (int)fy0;             // in [-1, X - 1] x [-1, Y - 1]
+    const float tx = sx - fx0, ty = sy - fy0;           // exact (Sterbenz / small magnitudes)
+    const float ux = 1.f - tx, uy = 1.f - ty;
+    const bool xin0 = x0 >= 0, xin1 = x0 + 1 < X, yin0 = y0 >= 0, yin1 = y0 + 1 < Y;
+    const float* img = vol.image;
+    const long long rowY = (long long)Y * Z;
+    const long long o00 = (long long)x0 * rowY + (long long)y0 * Z + (z - 1);
+    float v00[3], v01[3], v10[3], v11[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        v00[c] = (xin0 && yin0) ? img[o00 + c] : fill;
+        v01[c] = (xin0 && yin1) ? img[o00 + Z + c] : fill;
+        v10[c] = (xin1 && yin0) ? img[o00 + rowY + c] : fill;
+        v11[c] = (xin1 && yin1) ? img[o00 + rowY + Z + c] : fill;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float a = fmaf(v01[c], ty, v00[c] * uy);          // along y at x0
+        const float b = fmaf(v11[c], ty, v10[c] * uy);          // along y at x0 + 1
+        r.c[c] = fmaf(b, tx, a * ux);
+    }
+    const float lxf = floorf(sx + 0.5f), lyf = floorf(sy + 0.5f);
+    if (lxf >= 0.f && lxf < (float)X && lyf >= 0.f && lyf < (float)Y)
+        r.lab = (float)vol.label[(long long)(int)lxf * rowY + (long long)(int)lyf * Z + z];
+    return r;
+}
+
+__global__ void __launch_bounds__(kThreads) aug_slices_kernel(const pnp_aug_volume* __restrict__ vols, int nvol,
+                                                              const pnp_aug_sample* __restrict__ samples, int H, int W, long long P,
+                                                              float* __restrict__ x, float* __restrict__ label,
+                                                              float* __restrict__ onehot, int ncls, unsigned int* __restrict__ errors) {
+    const long long g = (long long)blockIdx.x * kThreads + threadIdx.x;      // group of 4 consecutive pixels of the flat [B*H*W] index
+    const long long p0 = g * 4;
+    if (p0 >= P) return;
+    const long long HW = (long long)H * W;
+    int b = (int)(p0 / HW);
+    const long long q = p0 - (long long)b * HW;
+    int i = (int)(q / W), j = (int)(q - (long long)i * W);
+    const int cnt = (int)((P - p0 < 4) ? (P - p0) : 4);
+    Px px[4];
+    int cur = -1;
+    pnp_aug_volume vol;
+    pnp_aug_sample s;
+    bool ok = false;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        if (t < cnt) {
+            if (b != cur) {
+                cur = b;
+                s = samples[b];
+                const bool vok = s.volume >= 0 && s.volume < nvol;
+                if (vok) {
+                    vol = vols[s.volume];
+                } else {
+                    vol.image = nullptr; vol.label = nullptr; vol.X = vol.Y = vol.Z = 0; vol.fill = 0.f;
+                }
+                ok = vok && s.frame >= 1 && s.frame <= vol.Z - 2;
+                if (!ok && i == 0 && j == 0) atomicAdd(errors, 1u);       // once per refused sample: by the lane that owns its first pixel
+            }
+            px[t] = sample_pixel(vol, ok, s.frame, s.m, i, j);
+            if (++j == W) {
+                j = 0;
+                if (++i == H) {
+                    i = 0;
+                    ++b;
+                }
+            }
+        } else {
+            px[t].c[0] = px[t].c[1] = px[t].c[2] = px[t].lab = 0.f;
+        }
+    }
+    if (cnt == 4) {
+        f32x4* xo = (f32x4*)(x + p0 * 3);
+        xo[0] = f32x4{px[0].c[0], px[0].c[1], px[0].c[2], px[1].c[0]};
+        xo[1] = f32x4{px[1].c[1], px[1].c[2], px[2].c[0], px[2].c[1]};
+        xo[2] = f32x4{px[2].c[2], px[3].c[0], px[3].c[1], px[3].c[2]};
+        *(f32x4*)(label + p0) = f32x4{px[0].lab, px[1].lab, px[2].lab, px[3].lab};
+        if (onehot) {
+            f32x4* oo = (f32x4*)(onehot + p0 * ncls);
+            int t = 0, c = 0;                                // element e = 4 * w + u of the group's 4 * ncls floats: pixel t, class c
+            for (int w = 0; w < ncls; ++w) {
+                f32x4 o;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const float lab = t == 0 ? px[0].lab : t == 1 ? px[1].lab : t == 2 ? px[2].lab : px[3].lab;
+                    o[u] = lab == (float)c ? 1.f : 0.f;
+                    if (++c == ncls) {
+                        c = 0;
+                        ++t;
+                    }
+                }
+                oo[w] = o;
+            }
+        }
+    } else {
+        for (int t = 0; t < cnt; ++t) {
+            const float lab = t == 0 ? px[0].lab : t == 1 ? px[1].lab : px[2].lab;
+            const float c0 = t == 0 ? px[0].c[0] : t == 1 ? px[1].c[0] : px[2].c[0];
+            const float c1 = t == 0 ? px[0].c[1] : t == 1 ? px[1].c[1] : px[2].c[1];
+            const float c2 = t == 0 ? px[0].c[2] : t == 1 ? px[1].c[2] : px[2].c[2];
+            x[(p0 + t) * 3 + 0] = c0;
+            x[(p0 + t) * 3 + 1] = c1;
+            x[(p0 + t) * 3 + 2] = c2;
+            label[p0 + t] = lab;
+            if (onehot)
+                for (int c = 0; c < ncls; ++c) onehot[(p0 + t) * ncls + c] = lab == (float)c ? 1.f : 0.f;
+        }
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------------
+struct PreLayout {
+    size_t hist, state, psum, pdev, pmin, total;
+};
+
+PreLayout pre_layout() {
+    PreLayout L;
+    size_t o = 0;
+    L.hist = o;  o += 4 * 256 * sizeof(unsigned int);
+    L.state = o; o += 256;
+    L.psum = o;  o += kMaxBlocks * sizeof(double);
+    L.pdev = o;  o += kMaxBlocks * sizeof(double);
+    L.pmin = o;  o += kMaxBlocks * sizeof(float);
+    L.total = o;
+    return L;
+}
+
+bool pre_n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 31); }
+
+}  // namespace
+
+extern "C" {
+
+size_t pnp_volume_preprocess_workspace_bytes(int64_t n) {
+    if (!pre_n_ok(n)) return 0;
+    return pre_layout().total;
+}
+
+int pnp_volume_preprocess(const float* v, float* out, int64_t n, int32_t percentile, double* stats, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    PNP_REQUIRE(n >= 1, "pnp_volume_preprocess: n = %lld, at least one voxel is needed", (long long)n);
+    PNP_REQUIRE(pre_n_ok(n), "pnp_volume_preprocess: n = %lld is not below 2^31", (long long)n);
+    PNP_REQUIRE(percentile >= 0 && percentile <= 100, "pnp_volume_preprocess: percentile %d outside [0, 100]", (int)percentile);
+    PNP_REQUIRE(v && out && stats && workspace, "pnp_volume_preprocess: null pointer");
+    const PreLayout L = pre_layout();
+    PNP_REQUIRE(workspace_bytes >= L.total, "pnp_volume_preprocess: workspace too small: %zu bytes < %zu (pnp_volume_preprocess_workspace_bytes)",
+                workspace_bytes, L.total);
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    unsigned int* hist = (unsigned int*)(ws + L.hist);
+    SelState* state = (SelState*)(ws + L.state);
+    double* psum = (double*)(ws + L.psum);
+    double* pdev = (double*)(ws + L.pdev);
+    float* pmin = (float*)(ws + L.pmin);
+    const uint32_t k = (uint32_t)(((long long)percentile * (n - 1) + 99) / 100);        // <= n - 1 for every percentile in [0, 100]
+    const unsigned nb = (unsigned)std::min<long long>((n + kThreads - 1) / kThreads, kMaxBlocks);
+
+    hipLaunchKernelGGL(pre_init_kernel, dim3(1), dim3(kThreads), 0, st, hist, state, k);
+    PNP_CHECK_LAUNCH("pre_init_kernel");
+    uint32_t mask = 0u;
+    for (int r = 0; r < 4; ++r) {
+        const int shift = 24 - 8 * r;
+        hipLaunchKernelGGL(pre_hist_kernel, dim3(nb), dim3(kThreads), 0, st, v, (long long)n, shift, mask, state, hist + r * 256);
+        PNP_CHECK_LAUNCH("pre_hist_kernel");
+        hipLaunchKernelGGL(pre_pick_kernel, dim3(1), dim3(64), 0, st, hist + r * 256, shift, state);
+        PNP_CHECK_LAUNCH("pre_pick_kernel");
+        mask |= 255u << shift;
+    }
+    hipLaunchKernelGGL(pre_sum_kernel, dim3(nb), dim3(kThreads), 0, st, v, (long long)n, state, psum, pmin);
+    PNP_CHECK_LAUNCH("pre_sum_kernel");
+    hipLaunchKernelGGL(pre_dev_kernel, dim3(nb), dim3(kThreads), 0, st, v, (long long)n, state, psum, pdev);
+    PNP_CHECK_LAUNCH("pre_dev_kernel");
+    hipLaunchKernelGGL(pre_normalize_kernel, dim3(nb), dim3(kThreads), 0, st, v, out, (long long)n, state, psum, pdev, pmin, stats);
+    PNP_CHECK_LAUNCH("pre_normalize_kernel");
+    return PNP_OK;
+}
+
+int pnp_aug_slices(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_dev, int32_t nvol, const pnp_aug_sample* samples_dev,
+                   int32_t B, int32_t H, int32_t W, float* x, float* label, float* onehot, int32_t ncls, uint32_t* errors,
+                   void* stream) {
+    PNP_REQUIRE(B >= 1, "pnp_aug_slices: B = %d, at least one sample is needed", (int)B);
+    PNP_REQUIRE(H >= 1 && W >= 1, "pnp_aug_slices: output size %d x %d must be at least 1 x 1", (int)H, (int)W);
+    PNP_REQUIRE(vols_host && vols_dev && samples_dev, "pnp_aug_slices: null table");
+    PNP_REQUIRE(nvol >= 1, "pnp_aug_slices: nvol = %d, at least one volume is needed", (int)nvol);
+    PNP_REQUIRE(x && label && errors, "pnp_aug_slices: null output pointer");
+    PNP_REQUIRE(!onehot || (ncls >= 1 && ncls <= kMaxCls), "pnp_aug_slices: ncls %d outside [1, %d]", (int)ncls, kMaxCls);
+    PNP_REQUIRE(((uintptr_t)x | (uintptr_t)label | (uintptr_t)onehot) % 16 == 0, "pnp_aug_slices: outputs must be 16-byte aligned");
+    const long long P = (long long)B * H * W;
+    PNP_REQUIRE(P < ((long long)1 << 31), "pnp_aug_slices: B * H * W = %lld is not below 2^31", P);
+    for (int i = 0; i < nvol; ++i) {
+        const pnp_aug_volume& v = vols_host[i];
+        PNP_REQUIRE(v.image && v.label, "pnp_aug_slices: volume %d: null pointer", i);
+        PNP_REQUIRE(v.X >= 1 && v.Y >= 1 && v.X <= kMaxExtentXY && v.Y <= kMaxExtentXY,
+                    "pnp_aug_slices: volume %d: extents %d x %d outside [1, %d]", i, (int)v.X, (int)v.Y, kMaxExtentXY);
+        PNP_REQUIRE(v.Z >= 3, "pnp_aug_slices: volume %d: Z = %d, at least 3 frames are needed", i, (int)v.Z);
+        PNP_REQUIRE((long long)v.X * v.Y * v.Z < ((long long)1 << 40), "pnp_aug_slices: volume %d is too large", i);
+    }
+    const long long groups = (P + 3) / 4;
+    const unsigned nb = (unsigned)((groups + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(aug_slices_kernel, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, vols_dev, (int)nvol, samples_dev, (int)H, (int)W,
+                       P, x, label, onehot, (int)(onehot ? ncls : 0), errors);
+    PNP_CHECK_LAUNCH("aug_slices_kernel");
+    return PNP_OK;
+}
+
+}  // extern "C"

@@ -8,6 +8,10 @@ lib.py:75-92) and feeds both arrays through feed_dict — a synchronous pageable
 
 and the training loop's `next()` only makes the compute stream wait on that event, so at >400 slices/s the step never
 sees the input path.  On a CPU device (host-logic tests) the same code runs without streams or pinning.
+
+A source that builds its batches on the device (`next_device_batch(batch_size, num_cls) -> (x, one-hot, fids)`, e.g.
+volume_source.AugmentedSliceSource: slices gathered from HBM-resident volumes) is driven on the same copy stream and handed over with the
+same event and `record_stream` discipline; nothing is staged on the host for it.
 """
 import queue
 import threading
@@ -23,6 +27,7 @@ class DeviceFeeder(object):
 
     `source` is anything with `next_batch(batch_size) -> (np.ndarray [B,H,W,4], fids)` (tfrecord.SliceQueue, synthetic sources):
     image channels 0:3, integer-valued label map in channel 3 — the pair_feed layout of source_segmenter.py:344-355.
+    On a GPU, a source that also has `next_device_batch(batch_size, num_cls)` is asked for device batches instead.
     """
 
     def __init__(self, source, batch_size, num_cls, device, depth=2):
@@ -59,7 +64,15 @@ class DeviceFeeder(object):
             if self.cuda:
                 torch.cuda.set_device(self.device)
             i = 0
+            on_device = self.cuda and hasattr(self.source, "next_device_batch")
             while not self._stop:
+                if on_device:
+                    with torch.cuda.stream(self._stream):
+                        xd, yd, fids = self.source.next_device_batch(self.batch_size, self.num_cls)
+                        done = torch.cuda.Event()
+                        done.record(self._stream)
+                    self._put((xd, yd, fids, done))
+                    continue
                 batch, fids = self.source.next_batch(self.batch_size)
                 xs, ls, ev = self._stage(i, np.asarray(batch))
                 i += 1
@@ -76,15 +89,17 @@ class DeviceFeeder(object):
                     xd = xs.clone()
                     yd = torch.from_numpy(_label_decomp(self.num_cls, ls.numpy()))
                     done = None
-                item = (xd, yd, fids, done)
-                while not self._stop:
-                    try:
-                        self._q.put(item, timeout=0.05)
-                        break
-                    except queue.Full:
-                        continue
+                self._put((xd, yd, fids, done))
         except BaseException as e:      # surface input failures in the training loop instead of hanging it
             self._error = e
+
+    def _put(self, item):
+        while not self._stop:
+            try:
+                self._q.put(item, timeout=0.05)
+                break
+            except queue.Full:
+                continue
 
     # -- consumer ---------------------------------------------------------------------------------------------
     def next(self):

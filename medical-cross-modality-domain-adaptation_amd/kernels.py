@@ -981,3 +981,35 @@ def filled(shape, value, device):
     t = torch.empty(shape, dtype=torch.float32, device=device)
     check(_lib.load().pnp_fill(_p(t), t.numel(), float(value), _stream()), "pnp_fill")
     return t
+
+
+# ---- training input from resident volumes (csrc/augment.hip, volume_source.py) -------------------------------------------------------
+def volume_preprocess(v, percentile=98, out=None):
+    """pnp_volume_preprocess of a float32 CUDA tensor (any shape, finite values): clip at the exact order statistic
+    k = (percentile * (n - 1) + 99) // 100, z-score with the population std -> (normalised tensor, float64 [4] device tensor: clip, mean,
+    std, normalised minimum).  out=v normalises in place.  Stream-ordered, no host synchronisation."""
+    pv = _p(v)
+    out = torch.empty_like(v) if out is None else out
+    stats = torch.empty(4, dtype=torch.float64, device=v.device)
+    lib = _lib.load()
+    n = v.numel()
+    need = lib.pnp_volume_preprocess_workspace_bytes(n)
+    ws = workspace(need, v.device, slot="augment")
+    check(lib.pnp_volume_preprocess(pv, _p(out), n, int(percentile), ctypes.c_void_p(stats.data_ptr()), ctypes.c_void_p(ws.data_ptr()),
+                                    ws.numel(), _stream()), "pnp_volume_preprocess")
+    return out, stats
+
+
+def aug_slices(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls=0, want_onehot=True):
+    """pnp_aug_slices: vols_host (ctypes array of _lib.AugVolume) / vols_dev (its device copy, uint8 tensor), samples_dev (device copy of B
+    _lib.AugSample records, uint8 tensor), errors (int32 [1] device counter) -> (x [B,H,W,3], label [B,H,W], one-hot [B,H,W,ncls] or None)"""
+    dev = vols_dev.device
+    if not (vols_dev.is_cuda and samples_dev.is_cuda and errors.is_cuda):
+        raise _lib.PnpError("aug_slices: pnp kernels need CUDA/HIP tensors (got a CPU tensor) — there is no CPU fallback")
+    x = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    label = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    onehot = torch.empty((B, H, W, int(ncls)), dtype=torch.float32, device=dev) if want_onehot else None
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(_lib.load().pnp_aug_slices(ctypes.cast(vols_host, ctypes.c_void_p), vp(vols_dev), int(nvol), vp(samples_dev), int(B), int(H), int(W),
+                                     _p(x), _p(label), _p(onehot), int(ncls), vp(errors), _stream()), "pnp_aug_slices")
+    return x, label, onehot

@@ -3,7 +3,8 @@
   --phase train-gan : joint training (20 dis : 1 gen, lambda_mask_loss = rate, dis_sub_iter += 1 every 300 steps)
   --phase fine-tune : continue from a breakpoint (the reference's `training_config` NameError at train_gan.py:121 is fixed)
 Extra flags: --synthetic N, --batch-size, --iters, --epochs, --output, --baseline (source-segmenter .npz for the pre-train hand-off),
---gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference).
+--mr-nii-train / --mr-nii-val / --ct-nii-train / --ct-nii-val LIST (all four: train from NIfTI volumes kept on the device,
+volume_source.py; --augment JSON / --no-augment), --gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference).
 """
 import argparse
 import datetime
@@ -51,6 +52,9 @@ def configure(phase):
     return ck, nc, tc
 
 
+NII_FLAGS = ("mr_nii_train", "mr_nii_val", "ct_nii_train", "ct_nii_val")
+
+
 def parse_args(phase, argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--phase", default=phase)
@@ -67,7 +71,17 @@ def parse_args(phase, argv=None):
                     "(default); bf16 = BASELINE configs[4]: bf16 MFMA operands, fp32 accumulation / master weights / BN")
     ap.add_argument("--gp-weight", type=float, default=0.0, help="WGAN-GP gradient penalty weight of the critics (f = miu_dis * D; 10 = "
                     "the WGAN-GP paper's value); > 0 replaces the +-0.03 weight clip.  fp32, without --sync-stats; default 0")
+    for flag in NII_FLAGS:
+        ap.add_argument("--" + flag.replace("_", "-"), default=None, metavar="LIST", help="NIfTI list file (one `image.nii[.gz] "
+                        "label.nii[.gz]` pair per line, volume_source.py); the four --*-nii-* flags go together")
+    from .volume_source import add_augment_flags
+    add_augment_flags(ap)
     args = ap.parse_args(argv)
+    given = [getattr(args, f) is not None for f in NII_FLAGS]
+    if any(given) and not all(given):
+        ap.error("--mr-nii-train, --mr-nii-val, --ct-nii-train and --ct-nii-val go together")
+    if all(given) and args.synthetic:
+        ap.error("the --*-nii-* lists and --synthetic exclude each other")
     if not args.gp_weight >= 0.0:
         ap.error("--gp-weight must be >= 0, got %r" % args.gp_weight)
     if args.gp_weight > 0 and args.dtype != "f32":
@@ -100,7 +114,14 @@ def main(phase, argv=None):
         local = 0
     device = "cuda:%d" % local if (world > 1 and args.device == "cuda") else args.device
     os.makedirs(output_path, exist_ok=True)
-    if args.synthetic:
+    if args.mr_nii_train:
+        from .volume_source import augment_from_args, sources_from_lists
+        shard = (rank, world) if world > 1 else None
+        mr_train, mr_val = sources_from_lists(args.mr_nii_train, args.mr_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
+                                              seed=0, shard=shard)
+        ct_train, ct_val = sources_from_lists(args.ct_nii_train, args.ct_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
+                                              seed=2, shard=shard)
+    elif args.synthetic:
         from .synthetic import write_dataset
         sets = (("syn_mr_train", args.synthetic, 0, "mr"), ("syn_ct_train", args.synthetic, 1, "ct"),
                 ("syn_mr_val", batch_size, 100, "mr"), ("syn_ct_val", batch_size, 101, "ct"))

@@ -1,6 +1,7 @@
 """Entry point mirroring the reference's train_segmenter.py (same hard-coded config dicts, train_segmenter.py:22-80): trains the
 source segmenter.  Extra flags (defaults keep the reference behaviour): --synthetic N writes N synthetic tfrecords and trains on
-them, --batch-size, --iters, --epochs, --output.  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
+them, --batch-size, --iters, --epochs, --output; --nii-train LIST --nii-val LIST train from NIfTI volumes kept on the device
+(volume_source.py: one `image.nii[.gz] label.nii[.gz]` pair per line; --augment JSON / --no-augment).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
 one process per GPU over RCCL, --batch-size slices PER RANK, file lists sharded by rank, rank 0 writes the checkpoint.
   python -m "medical-cross-modality-domain-adaptation_amd.train_segmenter" --synthetic 8 --batch-size 4 --iters 2 --epochs 1
 """
@@ -28,7 +29,16 @@ def main(argv=None):
     ap.add_argument("--restore", action="store_true")
     ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32", help="arithmetic of the convolution operands: f32 = the reference's "
                     "(default); bf16 = BASELINE configs[4]: bf16 MFMA operands, fp32 accumulation / master weights / BN")
+    ap.add_argument("--nii-train", default=None, metavar="LIST", help="train from NIfTI volumes resident on the device: a list file with one "
+                    "`image.nii[.gz] label.nii[.gz]` pair per line (volume_source.py); needs --nii-val")
+    ap.add_argument("--nii-val", default=None, metavar="LIST", help="validation volumes (never augmented)")
+    from .volume_source import add_augment_flags, augment_from_args
+    add_augment_flags(ap)
     args = ap.parse_args(argv)
+    if (args.nii_train is None) != (args.nii_val is None):
+        ap.error("--nii-train and --nii-val go together")
+    if args.nii_train and args.synthetic:
+        ap.error("--nii-train and --synthetic exclude each other")
     from .functional import set_conv_dtype
     set_conv_dtype(args.dtype)
 
@@ -49,7 +59,11 @@ def main(argv=None):
     device = "cuda:%d" % local if (world > 1 and args.device == "cuda") else args.device
     os.makedirs(output_path, exist_ok=True)
 
-    if args.synthetic:
+    if args.nii_train:
+        from .volume_source import sources_from_lists
+        train_list, val_list = sources_from_lists(args.nii_train, args.nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
+                                                  shard=(rank, world) if world > 1 else None)
+    elif args.synthetic:
         from .synthetic import write_dataset
         # next to (not inside) output_path: Trainer.train(restore=False) clears output_path like the reference (source_segmenter.py:416-418)
         data_root = output_path.rstrip("/") + "_data"

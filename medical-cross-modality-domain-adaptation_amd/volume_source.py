@@ -1,0 +1,351 @@
+"""Training input straight from NIfTI volumes: the four steps the reference's README names for its data set — crop, cut
+the top 2 % of each volume's intensity histogram, z-score each volume, sample 2-D slices with data augmentation — of which it ships no
+code.  The volumes stay resident in HBM; preprocessing and the augmented slice gather are kernels of libpnp_hip.so (csrc/augment.hip),
+the host only draws the parameters.
+
+  VolumeSet             loads image / label pairs (nifti.load), flips and reorders them like volume_eval.test_eval, optionally crops to
+                        the label bounding box, uploads, normalises on the device (pnp_volume_preprocess) and keeps the per-volume stats
+  AugmentedSliceSource  draws (volume, frame, affine map) per sample from a seeded numpy Generator and gathers the batch on the device
+                        (pnp_aug_slices): next_device_batch() for feeder.DeviceFeeder, next_batch() for every consumer of the trainers'
+                        [B, H, W, 4] numpy protocol
+
+A list file holds one `image.nii[.gz] label.nii[.gz]` pair per line (paths relative to the list file's folder unless absolute).
+
+  python -m "medical-cross-modality-domain-adaptation_amd.volume_source" --export N OUTDIR --list LIST [--augment JSON | --no-augment]
+writes N slices in the reference's tfrecord layout (tfrecord.write_slice) plus OUTDIR/slice_list, so that the TensorFlow reference can be
+fed from the same volumes.
+
+Output pixel (i, j) of an [H, W] slice reads the source slice [X, Y] at (sx, sy) = M (i, j, 1); `compose_matrix` folds centring, the
+resize from (X, Y) to (H, W), rotation, scale, translation and flip into the six float32 entries of M.  The kernel knows nothing of angles.
+"""
+import argparse
+import ctypes
+import json
+import logging
+import math
+import os
+
+import numpy as np
+
+from . import _lib
+from .parallel import rank_seed
+
+# rotation in degrees (+-), scale (+-, log-uniform in [1 / (1 + s), 1 + s]), translation in source voxels (+-), flip probability (mirror of
+# the second slice axis).  Mild by design: the hearts of MMWHS keep their orientation, so the default does not flip.
+DEFAULT_AUGMENT = {"rotate": 15.0, "scale": 0.1, "translate": 10.0, "flip": 0.0}
+_AUGMENT_KEYS = tuple(sorted(DEFAULT_AUGMENT))
+
+
+def read_pairs(list_file):
+    """list file -> [(image path, label path)]; blank lines and lines starting with # are skipped"""
+    if not os.path.isfile(list_file):
+        raise IOError("volume list %s does not exist" % list_file)
+    base = os.path.dirname(os.path.abspath(list_file))
+    pairs = []
+    with open(list_file) as f:
+        for no, line in enumerate(f, 1):
+            line = line.strip()
+            if not line or line.startswith("#"):
+                continue
+            parts = line.split()
+            if len(parts) != 2:
+                raise ValueError("%s:%d: expected `image.nii[.gz] label.nii[.gz]`, got %d fields" % (list_file, no, len(parts)))
+            for p in parts:
+                if not p.endswith((".nii", ".nii.gz")):
+                    raise ValueError("%s:%d: %s is not a .nii / .nii.gz file name" % (list_file, no, p))
+            pair = tuple(p if os.path.isabs(p) else os.path.join(base, p) for p in parts)
+            for p in pair:
+                if not os.path.isfile(p):
+                    raise IOError("%s:%d: %s does not exist" % (list_file, no, p))
+            pairs.append(pair)
+    if not pairs:
+        raise ValueError("%s: no volume pair listed" % list_file)
+    return pairs
+
+
+def check_augment(augment):
+    """None (identity) or a dict with a subset of DEFAULT_AUGMENT's keys -> a full dict / None"""
+    if augment is None:
+        return None
+    unknown = sorted(set(augment) - set(_AUGMENT_KEYS))
+    if unknown:
+        raise ValueError("augment: unknown keys %s (known: %s)" % (unknown, list(_AUGMENT_KEYS)))
+    a = {k: float(augment.get(k, 0.0)) for k in _AUGMENT_KEYS}
+    if a["rotate"] < 0 or a["scale"] < 0 or a["translate"] < 0 or not 0.0 <= a["flip"] <= 1.0:
+        raise ValueError("augment: rotate, scale, translate must be >= 0 and flip in [0, 1], got %r" % (a,))
+    return a
+
+
+def _cos_sin(deg):
+    """exact at the multiples of 90 degrees: those rotations are integer permutations of the pixel grid"""
+    q = deg / 90.0
+    if q == math.floor(q):
+        return ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(q) % 4]
+    r = math.radians(deg)
+    return math.cos(r), math.sin(r)
+
+
+def compose_matrix(src_xy, out_hw, rotate=0.0, scale=1.0, translate=(0.0, 0.0), flip=False):
+    """the six float32 entries (m00, m01, m02, m10, m11, m12) of
+         s = c_src + t + (1 / scale) R(rotate) F D (p - c_out),   c = (extent - 1) / 2,  D = diag(X / H, Y / W),  F = diag(1, -1) if flip
+    composed in float64.  scale > 1 magnifies (the output sees a smaller part of the source).  The identity with (X, Y) = (H, W) is
+    exactly (1, 0, 0, 0, 1, 0); rotations by multiples of 90 degrees and the flip of a square slice are exact integer permutations."""
+    X, Y = float(src_xy[0]), float(src_xy[1])
+    H, W = float(out_hw[0]), float(out_hw[1])
+    c, s = _cos_sin(float(rotate))
+    inv = 1.0 / float(scale)
+    dx, dy = X / H, Y / W
+    f = -1.0 if flip else 1.0
+    a00, a01 = inv * c * dx, inv * -s * f * dy
+    a10, a11 = inv * s * dx, inv * c * f * dy
+    ci, cj = (H - 1.0) / 2.0, (W - 1.0) / 2.0
+    m02 = (X - 1.0) / 2.0 + float(translate[0]) - (a00 * ci + a01 * cj)
+    m12 = (Y - 1.0) / 2.0 + float(translate[1]) - (a10 * ci + a11 * cj)
+    return np.array([a00, a01, m02, a10, a11, m12], dtype=np.float32)
+
+
+def sample_params(rng, dims, batch_size, out_hw, augment):
+    """B draws from `rng` (numpy Generator) -> (records [B] of _lib.AugSample layout, raw draws as a dict of arrays).
+    dims: [(X, Y, Z)] per volume.  Every sample draws volume and frame; with augment, rotation, log-scale, two translations and the flip
+    coin follow in that order, whatever their ranges — the stream of a seed does not depend on which ranges are zero."""
+    B = int(batch_size)
+    rec = np.zeros(B, dtype=SAMPLE_DTYPE)
+    raw = {k: np.zeros(B) for k in ("rotate", "scale", "tx", "ty")}
+    raw["flip"] = np.zeros(B, dtype=bool)
+    raw["scale"][:] = 1.0
+    for b in range(B):
+        v = int(rng.integers(0, len(dims)))
+        X, Y, Z = dims[v]
+        z = int(rng.integers(1, Z - 1))           # [1, Z - 2]
+        if augment is not None:
+            raw["rotate"][b] = rng.uniform(-augment["rotate"], augment["rotate"])
+            ls = math.log1p(augment["scale"])
+            raw["scale"][b] = math.exp(rng.uniform(-ls, ls))
+            raw["tx"][b] = rng.uniform(-augment["translate"], augment["translate"])
+            raw["ty"][b] = rng.uniform(-augment["translate"], augment["translate"])
+            raw["flip"][b] = rng.random() < augment["flip"]
+        rec["volume"][b], rec["frame"][b] = v, z
+        rec["m"][b] = compose_matrix((X, Y), out_hw, raw["rotate"][b], raw["scale"][b], (raw["tx"][b], raw["ty"][b]), bool(raw["flip"][b]))
+    return rec, raw
+
+
+VOLUME_DTYPE = np.dtype([("image", "<u8"), ("label", "<u8"), ("X", "<i4"), ("Y", "<i4"), ("Z", "<i4"), ("fill", "<f4")])
+SAMPLE_DTYPE = np.dtype([("volume", "<i4"), ("frame", "<i4"), ("m", "<f4", (6,))])
+assert VOLUME_DTYPE.itemsize == ctypes.sizeof(_lib.AugVolume) and SAMPLE_DTYPE.itemsize == ctypes.sizeof(_lib.AugSample)
+
+
+def label_bounding_box(label, margin):
+    """(slices per axis) of the non-zero labels grown by `margin` voxels and clamped to the volume; the whole volume when it has no label"""
+    nz = np.nonzero(label)
+    if len(nz[0]) == 0:
+        return tuple(slice(0, n) for n in label.shape)
+    return tuple(slice(max(int(a.min()) - margin, 0), min(int(a.max()) + 1 + margin, n)) for a, n in zip(nz, label.shape))
+
+
+def prepare_pair(image, label, flip_correction=True, axis=2, crop=None):
+    """host numpy, once per volume: the double flip of volume_eval.test_eval, `axis` moved last, the optional crop to the label bounding
+    box plus `crop` voxels -> (float32 image [X, Y, Z], uint8 label [X, Y, Z]), both C-contiguous"""
+    image, label = np.asarray(image), np.asarray(label)
+    if image.ndim != 3 or image.shape != label.shape:
+        raise ValueError("image %s / label %s: a 3-D pair of equal shape expected" % (image.shape, label.shape))
+    if flip_correction:
+        image = np.flip(np.flip(image, axis=0), axis=1)
+        label = np.flip(np.flip(label, axis=0), axis=1)
+    image, label = np.moveaxis(image, axis, -1), np.moveaxis(label, axis, -1)
+    if label.dtype.kind == "f" and not np.all(label == np.floor(label)):
+        raise ValueError("labels must be integer-valued")
+    if label.size and (label.min() < 0 or label.max() > 255):
+        raise ValueError("labels outside [0, 255] (%s .. %s)" % (label.min(), label.max()))
+    if crop is not None:
+        box = label_bounding_box(label, int(crop))
+        image, label = image[box], label[box]
+    if not np.all(np.isfinite(image)):
+        raise ValueError("the image holds non-finite voxels")
+    return np.ascontiguousarray(image, dtype=np.float32), np.ascontiguousarray(label, dtype=np.uint8)
+
+
+class VolumeSet(object):
+    """Normalised volumes resident on `device`.  pairs: [(image path, label path)] (read_pairs).  Per volume, in this order: the double
+    flip volume_eval.test_eval applies (flip_correction), `axis` moved last (the slicing axis), crop=None or a margin in voxels around
+    the label bounding box, upload, pnp_volume_preprocess (clip at the `percentile` order statistic, z-score).
+    .images / .labels: device tensors [X, Y, Z] float32 / uint8;  .stats: [{clip, mean, std, fill}];  .names: image basenames."""
+
+    def __init__(self, pairs, device, flip_correction=True, axis=2, crop=None, percentile=98):
+        from . import nifti
+        arrays, names = [], []
+        for image_fid, label_fid in pairs:
+            arrays.append(prepare_pair(nifti.load(image_fid).get_data(), nifti.load(label_fid).get_data(), flip_correction, axis, crop))
+            names.append(os.path.basename(str(image_fid)))
+        self._build(arrays, names, device, percentile)
+
+    @classmethod
+    def from_arrays(cls, images, labels, names, device, percentile=98):
+        """volumes already in slicing order [X, Y, Z] (no flip, no crop): float32-convertible images, integer labels in [0, 255]"""
+        self = cls.__new__(cls)
+        arrays = [prepare_pair(i, l, flip_correction=False, axis=2, crop=None) for i, l in zip(images, labels)]
+        self._build(arrays, [str(n) for n in names], device, percentile)
+        return self
+
+    def _build(self, arrays, names, device, percentile):
+        import torch
+        from . import kernels as K
+        if not arrays:
+            raise ValueError("VolumeSet: no volume")
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.PnpError("VolumeSet: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (self.device,))
+        self.names, self.percentile = list(names), int(percentile)
+        self.images, self.labels, stats = [], [], []
+        for (img, lab), name in zip(arrays, names):
+            X, Y, Z = img.shape
+            if Z < 3 or X > 4096 or Y > 4096:
+                raise ValueError("%s: volume %s needs at least 3 frames and slice extents <= 4096" % (name, img.shape))
+            v = torch.from_numpy(img).to(self.device)
+            _, st = K.volume_preprocess(v, self.percentile, out=v)
+            self.images.append(v)
+            self.labels.append(torch.from_numpy(lab).to(self.device))
+            stats.append(st)
+        self.dims = [tuple(int(d) for d in v.shape) for v in self.images]
+        host = torch.stack(stats).cpu().numpy()          # one read for the whole set: the fill values enter the descriptor table
+        self.stats = [{"clip": float(r[0]), "mean": float(r[1]), "std": float(r[2]), "fill": float(r[3])} for r in host]
+        self.set_fill(None)
+
+    def set_fill(self, fill):
+        """fill value of image corners outside the slice: None = each volume's normalised minimum (its background), or one number"""
+        import torch
+        tab = np.zeros(len(self.images), dtype=VOLUME_DTYPE)
+        for n, (v, l) in enumerate(zip(self.images, self.labels)):
+            tab[n] = (v.data_ptr(), l.data_ptr()) + self.dims[n] + (self.stats[n]["fill"] if fill is None else float(fill),)
+        self._table_host_np = tab
+        self.table_host = (_lib.AugVolume * len(tab)).from_buffer(tab)          # shares tab's memory
+        self.table_dev = torch.from_numpy(tab.view(np.uint8).copy()).to(self.device)
+
+    def __len__(self):
+        return len(self.images)
+
+
+class AugmentedSliceSource(object):
+    """Endless stream of augmented slices of a VolumeSet.
+      augment   None = identity: a centre-aligned resize, the raw normalised frames bit for bit when (X, Y) = out_size;
+                a dict with any of DEFAULT_AUGMENT's keys otherwise (the default: DEFAULT_AUGMENT)
+      seed      the parameter stream is numpy.random.default_rng(seed + rank_seed(rank)): reproducible, and ranks differ
+      shard     (rank, world) under data parallelism, as the trainers pass it; every rank holds all volumes and draws its own samples
+    next_device_batch() -> (x [B,H,W,3], one-hot [B,H,W,num_cls], fids) on the device, on the current stream (what feeder.DeviceFeeder drives);
+    next_batch(B) -> ([B,H,W,4] numpy: image channels 0:3, label map in channel 3, fids): the trainers' source protocol.
+    A fid is "<image basename>#<frame>"."""
+
+    def __init__(self, volumes, batch_size, out_size=(256, 256), augment=DEFAULT_AUGMENT, seed=0, shard=None, num_cls=5):
+        import torch
+        self.volumes, self.batch_size = volumes, int(batch_size)
+        self.out_size = (int(out_size[0]), int(out_size[1]))
+        self.augment = check_augment(augment)
+        self.num_cls = int(num_cls)
+        self.rank = shard[0] if shard else 0
+        self.rng = np.random.default_rng(int(seed) + rank_seed(self.rank))
+        self._errors = torch.zeros(1, dtype=torch.int32, device=volumes.device)
+        self.last_params = None
+
+    def _gather(self, batch_size, num_cls, want_onehot):
+        B = int(batch_size or self.batch_size)
+        rec, raw = sample_params(self.rng, self.volumes.dims, B, self.out_size, self.augment)
+        return self.gather_records(rec, num_cls, want_onehot) + (rec,)
+
+    def gather_records(self, rec, num_cls=None, want_onehot=True):
+        """the batch of given sample records (SAMPLE_DTYPE) -> (x, label, one-hot or None) on the device"""
+        import torch
+        from . import kernels as K
+        vs = self.volumes
+        rec = np.ascontiguousarray(rec, dtype=SAMPLE_DTYPE)
+        self.last_params = rec
+        staged = torch.from_numpy(rec.view(np.uint8).copy()).pin_memory()
+        sd = staged.to(vs.device, non_blocking=True)
+        return K.aug_slices(vs.table_host, vs.table_dev, len(vs), sd, len(rec), self.out_size[0], self.out_size[1], self._errors,
+                            ncls=int(num_cls or self.num_cls), want_onehot=want_onehot)
+
+    def _fids(self, rec):
+        return ["%s#%d" % (self.volumes.names[int(v)], int(z)) for v, z in zip(rec["volume"], rec["frame"])]
+
+    def next_device_batch(self, batch_size=None, num_cls=None):
+        x, _, onehot, rec = self._gather(batch_size, num_cls, True)
+        return x, onehot, self._fids(rec)
+
+    def next_batch(self, batch_size=None):
+        import torch
+        x, label, _, rec = self._gather(batch_size, None, False)
+        return torch.cat([x, label.unsqueeze(-1)], dim=-1).cpu().numpy(), self._fids(rec)
+
+    def errors(self):
+        """samples the kernel refused so far (volume index or frame out of range): reads the device counter, i.e. synchronises"""
+        return int(self._errors.item())
+
+    def close(self):
+        n = self.errors()
+        if n:
+            raise _lib.PnpError("AugmentedSliceSource: the gather refused %d samples (volume index or frame out of range); they were "
+                                "delivered as fill / label 0" % n)
+
+
+def sources_from_lists(train_list, val_list, device, batch_size, num_cls, augment=DEFAULT_AUGMENT, seed=0, shard=None):
+    """the two sources of a trainer from two list files: the training one augmented, the validation one with augment=None"""
+    train = AugmentedSliceSource(VolumeSet(read_pairs(train_list), device), batch_size, augment=augment, seed=seed, shard=shard,
+                                 num_cls=num_cls)
+    val = AugmentedSliceSource(VolumeSet(read_pairs(val_list), device), batch_size, augment=None, seed=seed + 1, shard=shard, num_cls=num_cls)
+    return train, val
+
+
+def add_augment_flags(ap):
+    g = ap.add_mutually_exclusive_group()
+    g.add_argument("--augment", default=None, metavar="JSON", help="augmentation ranges of the NIfTI training sources, e.g. "
+                   "'{\"rotate\": 15, \"scale\": 0.1, \"translate\": 10, \"flip\": 0}' (the default)")
+    g.add_argument("--no-augment", action="store_true", help="NIfTI training sources without augmentation (centre-aligned resize only)")
+
+
+def augment_from_args(args):
+    if args.no_augment:
+        return None
+    if args.augment is None:
+        return dict(DEFAULT_AUGMENT)
+    try:
+        a = json.loads(args.augment)
+    except ValueError as e:
+        raise ValueError("--augment: not JSON: %s" % e)
+    if not isinstance(a, dict):
+        raise ValueError("--augment: a JSON object expected")
+    return check_augment(a)
+
+
+def export(n, outdir, list_file, device="cuda", augment=DEFAULT_AUGMENT, seed=0, batch_size=16, out_size=(256, 256)):
+    """N augmented slices as one-record tfrecords in the reference's layout plus OUTDIR/slice_list.  data_vol is the [H, W, 3] image;
+    label_vol repeats the centre frame's label map in its three channels (the reference's decoder reads channel 1 only)."""
+    from .tfrecord import write_slice
+    src = AugmentedSliceSource(VolumeSet(read_pairs(list_file), device), batch_size, out_size=out_size, augment=augment, seed=seed)
+    os.makedirs(outdir, exist_ok=True)
+    files = []
+    while len(files) < n:
+        batch, fids = src.next_batch(min(batch_size, n - len(files)))
+        for sl, fid in zip(batch, fids):
+            path = os.path.join(outdir, "slice_%05d.tfrecords" % len(files))
+            write_slice(path, sl[:, :, 0:3], np.repeat(sl[:, :, 3:4], 3, axis=2))
+            files.append(path)
+            logging.info("%s <- %s" % (path, fid))
+    src.close()
+    with open(os.path.join(outdir, "slice_list"), "w") as f:
+        f.write("\n".join(files) + "\n")
+    return files
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="export augmented slices of NIfTI volumes as tfrecords")
+    ap.add_argument("--export", nargs=2, metavar=("N", "OUTDIR"), required=True)
+    ap.add_argument("--list", required=True, help="list file: one `image.nii[.gz] label.nii[.gz]` pair per line")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--device", default="cuda")
+    add_augment_flags(ap)
+    args = ap.parse_args(argv)
+    files = export(int(args.export[0]), args.export[1], args.list, device=args.device, augment=augment_from_args(args), seed=args.seed)
+    print("wrote %d slices and %s" % (len(files), os.path.join(args.export[1], "slice_list")))
+    return files
+
+
+if __name__ == "__main__":
+    main()
