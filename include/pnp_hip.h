@@ -528,6 +528,24 @@ int pnp_aug_slices(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_d
                    int32_t B, int32_t H, int32_t W, float* x, float* label, float* onehot /*nullable*/, int32_t ncls,
                    uint32_t* errors, void* stream);
 
+/* ---- volume inference, the way back (csrc/paste.hip): labels of a batch of logits written onto the scan's own grid --------
+ *
+ * logits [B, H, W, ncls] float32 (device, finite: anything else is the caller's error), 1 <= ncls <= 8; slice b < nb <= B is frame z0 + b.
+ * For every x < X, y < Y, b < nb one label byte is written at vol[origin + x * sx + y * sy + (z0 + b) * sz] (element strides of any sign:
+ * one launch writes the array order of the NIfTI file, the double flip, the axis move and a crop offset folded into origin and strides);
+ * nothing else of `vol` is touched.  The label of voxel column (x, y):
+ *   pi = fmaf(inv[0], x, fmaf(inv[1], y, inv[2])),  pj = fmaf(inv[3], x, fmaf(inv[4], y, inv[5]))     (this order is part of the contract;
+ *        inv: six HOST floats, the map from a source voxel to output-plane coordinates)
+ *   each clamped into [0, H - 1] / [0, W - 1] (NaN -> 0, before any integer conversion);
+ *   every class's logit bilinear between the four corners (scipy map_coordinates order=1, mode="nearest"; a fractional part of 0 returns
+ *   the corner's value bit for bit); the label is the lowest index among the strictly largest interpolated logits.
+ * Refused on the host before any HIP call: null pointers; B, H, W, X, Y < 1; H, W, X, Y > 4096; ncls outside [1, 8]; nb outside [1, B];
+ * z0 < 0; vol_elems < 1; an addressed element outside [0, vol_elems) (from the extreme corners of the box); strides under which two
+ * voxels of the box collide (sorted by magnitude, each must be at least the one before it times that axis' extent). */
+int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, const float* inv,
+                     int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -178,6 +178,8 @@ PROTOTYPES = {
     "pnp_volume_preprocess_workspace_bytes": (c_size_t, [c_int64]),
     "pnp_volume_preprocess": (c_int, [_F, _F, c_int64, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnp_aug_slices": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, _F, _F, _F, c_int32, c_void_p, c_void_p]),
+    "pnp_paste_labels": (c_int, [_F, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_int32, c_int32, c_void_p, c_int64,
+                                 c_int64, c_int64, c_int64, c_int64, c_void_p]),
 }
 
 _lib = None

@@ -1013,3 +1013,20 @@ def aug_slices(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls=0, 
     check(_lib.load().pnp_aug_slices(ctypes.cast(vols_host, ctypes.c_void_p), vp(vols_dev), int(nvol), vp(samples_dev), int(B), int(H), int(W),
                                      _p(x), _p(label), _p(onehot), int(ncls), vp(errors), _stream()), "pnp_aug_slices")
     return x, label, onehot
+
+
+# ---- volume inference (csrc/paste.hip, volume_predict.py) -------------------------------------------------------------------------------
+def paste_labels(logits, nb, z0, inv, src_xy, vol, origin, strides):
+    """pnp_paste_labels: logits [B, H, W, ncls] -> one label byte per (x < X, y < Y, b < nb) at vol.view(-1)[origin + x sx + y sy + (z0 + b) sz].
+    inv: the six float32 entries of the map from a source voxel to output-plane coordinates (host); vol: a contiguous uint8 CUDA tensor (the
+    whole allocation the offsets are checked against); strides = (sx, sy, sz) in elements, any sign.  Stream-ordered, returns vol."""
+    if logits.dim() != 4:
+        raise _lib.PnpError("paste_labels: logits must be [B, H, W, ncls], got %s" % (tuple(logits.shape),))
+    if not vol.is_cuda or vol.dtype != torch.uint8 or not vol.is_contiguous():
+        raise _lib.PnpError("paste_labels: vol must be a contiguous uint8 CUDA tensor (got %s %s) — there is no CPU fallback" % (vol.device, vol.dtype))
+    B, H, W, ncls = (int(d) for d in logits.shape)
+    m = (ctypes.c_float * 6)(*[float(v) for v in inv])
+    check(_lib.load().pnp_paste_labels(_p(logits), B, H, W, ncls, int(nb), int(z0), m, int(src_xy[0]), int(src_xy[1]),
+                                       ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
+                                       int(strides[2]), _stream()), "pnp_paste_labels")
+    return vol

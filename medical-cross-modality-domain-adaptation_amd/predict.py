@@ -1,0 +1,154 @@
+"""Segment NIfTI volumes with a trained checkpoint: image.nii.gz in, pred_image.nii.gz on the same grid out (volume_predict.py).
+
+    python -m "medical-cross-modality-domain-adaptation_amd.predict" --model CKPT.npz --net segmenter|adapted
+           (--images A.nii.gz ... | --list LIST) --out DIR [--labels ...] [--edge replicate|skip]
+           [--crop x0:x1,y0:y1,z0:z1 | --crop-margin N] [--axis 2] [--no-flip-correction] [--batch-size 16]
+           [--score [--spacing unit|header] [--json F]]
+
+--list holds one `image.nii[.gz]` or `image.nii[.gz] label.nii[.gz]` per line (all lines alike; paths relative to the list's folder unless
+absolute).  The net is built as train_segmenter / train_gan build theirs, with their default configuration: `segmenter` is the source
+segmenter, `adapted` the CT path of the adversarial model.  Labels are used for the crop margin, for the dense_pred_* / gth_dense_pred_*
+pair and for --score, which runs evaluate.evaluate on that pair; they never reach the network.
+"""
+import argparse
+import json
+import os
+import sys
+
+NETS = ("segmenter", "adapted")
+# train_segmenter.py's cost_kwargs (the values do not enter inference; the constructor wants them)
+SEGMENTER_COST = {"cross_flag": True, "miu_cross": 1.0, "dice_flag": True, "miu_dice": 1.0, "regularizer": 1e-4}
+
+
+def parse_crop(text):
+    """'x0:x1,y0:y1,z0:z1' -> ((x0, x1), (y0, y1), (z0, z1))"""
+    parts = text.split(",")
+    if len(parts) != 3:
+        raise ValueError("--crop: three ranges x0:x1,y0:y1,z0:z1 expected, got %r" % text)
+    box = []
+    for p in parts:
+        ab = p.split(":")
+        if len(ab) != 2 or not all(s.strip().lstrip("+").isdigit() for s in ab):
+            raise ValueError("--crop: %r is not a range a:b of non-negative integers" % p)
+        a, b = int(ab[0]), int(ab[1])
+        if not a < b:
+            raise ValueError("--crop: the range %r is empty" % p)
+        box.append((a, b))
+    return tuple(box)
+
+
+def read_list(list_file):
+    """-> (images, labels or None)"""
+    if not os.path.isfile(list_file):
+        raise IOError("list %s does not exist" % list_file)
+    base = os.path.dirname(os.path.abspath(list_file))
+    rows = []
+    with open(list_file) as f:
+        for no, line in enumerate(f, 1):
+            parts = line.split()
+            if not parts or parts[0].startswith("#"):
+                continue
+            if len(parts) > 2:
+                raise ValueError("%s:%d: expected `image` or `image label`, got %d fields" % (list_file, no, len(parts)))
+            for p in parts:
+                if not p.endswith((".nii", ".nii.gz")):
+                    raise ValueError("%s:%d: %s is not a .nii / .nii.gz file name" % (list_file, no, p))
+            rows.append([p if os.path.isabs(p) else os.path.join(base, p) for p in parts])
+    if not rows:
+        raise ValueError("%s: no volume listed" % list_file)
+    if len({len(r) for r in rows}) != 1:
+        raise ValueError("%s: every line must have a label or none" % list_file)
+    return [r[0] for r in rows], ([r[1] for r in rows] if len(rows[0]) == 2 else None)
+
+
+def parse_args(argv=None):
+    """-> (args, images, labels or None, segment_volume options); every argument error ends in SystemExit, before any GPU work"""
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--model", required=True, help="checkpoint (.npz of this package)")
+    ap.add_argument("--net", required=True, choices=NETS)
+    ap.add_argument("--images", nargs="+", default=None)
+    ap.add_argument("--list", default=None, help="list file: `image` or `image label` per line")
+    ap.add_argument("--labels", nargs="+", default=None, help="ground truth, in the order of --images")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--edge", choices=("replicate", "skip"), default="replicate")
+    ap.add_argument("--crop", default=None, metavar="x0:x1,y0:y1,z0:z1", help="box in slicing order; outside it the prediction is 0")
+    ap.add_argument("--crop-margin", type=int, default=None, metavar="N", help="crop to the label's bounding box plus N voxels")
+    ap.add_argument("--axis", type=int, default=2, choices=(0, 1, 2), help="the slicing axis of the file")
+    ap.add_argument("--no-flip-correction", action="store_true")
+    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--score", action="store_true", help="score the predictions against the labels (evaluate.evaluate)")
+    ap.add_argument("--spacing", choices=("unit", "header"), default="unit")
+    ap.add_argument("--json", default=None, help="write the score here")
+    ap.add_argument("--device", default="cuda")
+    a = ap.parse_args(argv)
+    if (a.images is None) == (a.list is None):
+        ap.error("give either --images or --list")
+    try:
+        if a.list is not None:
+            if a.labels:
+                ap.error("--labels goes with --images; a list carries its own labels")
+            images, labels = read_list(a.list)
+        else:
+            images, labels = list(a.images), (list(a.labels) if a.labels else None)
+        box = parse_crop(a.crop) if a.crop is not None else None
+    except (IOError, ValueError) as e:
+        ap.error(str(e))
+    if labels is not None and len(labels) != len(images):
+        ap.error("--labels: %d labels for %d images" % (len(labels), len(images)))
+    if a.crop is not None and a.crop_margin is not None:
+        ap.error("--crop and --crop-margin exclude each other")
+    if a.crop_margin is not None and (labels is None or a.crop_margin < 0):
+        ap.error("--crop-margin needs labels and a margin >= 0")
+    if a.score and labels is None:
+        ap.error("--score needs labels")
+    if (a.json or a.spacing != "unit") and not a.score:
+        ap.error("--json and --spacing go with --score")
+    if a.batch_size < 1:
+        ap.error("--batch-size must be at least 1")
+    for p in [a.model] + images + (labels or []):
+        if not os.path.isfile(p):
+            ap.error("%s does not exist" % p)
+    options = {"edge": a.edge, "axis": a.axis, "flip_correction": not a.no_flip_correction, "batch_size": a.batch_size,
+               "crop": box if box is not None else a.crop_margin}
+    return a, images, labels, options
+
+
+def build_trainer(kind, model, batch_size, device="cuda", num_cls=5):
+    """the net as its training entry point builds it (default configuration), restored from `model`, inside its Trainer"""
+    if kind == "segmenter":
+        from . import source_segmenter as drn
+        net = drn.Full_DRN(channels=3, batch_size=batch_size, n_class=num_cls, cost_kwargs=dict(SEGMENTER_COST), device=device, world_size=1)
+        net.restore(None, model)
+        return drn.Trainer(net, train_list=[], val_list=[], num_cls=num_cls, batch_size=batch_size)
+    from . import adversarial as drn
+    from .train_gan import configure
+    ck, nc, _ = configure("train-gan")
+    net = drn.Full_DRN(channels=3, batch_size=batch_size, n_class=num_cls, cost_kwargs=ck, network_config=nc, device=device, world_size=1)
+    net.restore(None, model)
+    return drn.Trainer(net, [], [], [], [], num_cls=num_cls, batch_size=batch_size)
+
+
+def main(argv=None):
+    """-> {"paths": [pred_* files], "score": evaluate.evaluate's result or None}"""
+    a, images, labels, options = parse_args(argv)
+    trainer = build_trainer(a.net, a.model, a.batch_size, a.device)
+    paths = trainer.predict_volumes(images, a.out, label_list=labels, **options)
+    for p in paths:
+        print("wrote %s" % p)
+    score = None
+    if a.score:
+        from . import evaluate as ev
+        dense = [os.path.join(a.out, "dense_pred_" + os.path.basename(i).split(".")[0] + ".nii.gz") for i in images]
+        score = ev.evaluate([(d, os.path.join(a.out, "gth_" + os.path.basename(d))) for d in dense], trainer.num_cls, a.spacing, trainer.net.device)
+        for organ, r in score["organs"].items():
+            print("%-9s dice %.4f +- %.4f   assd %.4f +- %.4f   hd95 %.4f +- %.4f   (%d undefined)" % (
+                organ, r["dice_mean"], r["dice_std"], r["assd_mean"], r["assd_std"], r["hd95_mean"], r["hd95_std"], r["undefined"]))
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(score, f, indent=1)
+    return {"paths": paths, "score": score}
+
+
+if __name__ == "__main__":
+    main()
+    sys.exit(0)

@@ -1,0 +1,163 @@
+"""Inference of whole NIfTI volumes onto their own grid: image.nii.gz in, label volume of the same shape and axis order
+out.  Unlike Trainer.test_eval (volume_eval.py, kept quirk for quirk from the reference) it takes any in-plane size, needs no ground
+truth, predicts every frame and keeps the volume on the device from upload to the finished label volume.
+
+  segment_volume(logits_fn, image, ...)   one volume: orientation and crop like volume_source.prepare_pair, pnp_volume_preprocess, then per
+                                          batch of ascending frames the gather (pnp_aug_slices with the un-augmented compose_matrix map),
+                                          logits_fn, and pnp_paste_labels with the inverse map straight into the file's array order
+  invert_matrix(m)                        the inverse of a compose_matrix map: source voxel (x, y) -> output-plane coordinates
+  segmenter_logits / adapted_logits       the logits_fn of source_segmenter.Full_DRN and of the CT path of adversarial.Full_DRN
+  predict_volumes(...)                    files in, pred_<basename> files out (what both trainers' predict_volumes call)
+
+The label of a voxel is the argmax of the bilinearly interpolated LOGITS (not probabilities): no exp, and for an identity map exactly
+argmax(logits).
+"""
+import os
+
+import numpy as np
+
+from . import _lib
+from .volume_source import SAMPLE_DTYPE, AugmentedSliceSource, VolumeSet, compose_matrix, label_bounding_box, prepare_pair
+
+EDGES = ("replicate", "skip")
+
+
+def invert_matrix(m, dtype=np.float32):
+    """six float32 entries (m00, m01, m02, m10, m11, m12) of s = A p + t  ->  the six entries of p = A^-1 s - A^-1 t, inverted in float64
+    and rounded once to `dtype` (float32: what the kernel gets; float64: unrounded).  The identity, quarter turns and the flip of a square
+    slice come back as exact 0 / +-1 entries."""
+    a00, a01, t0, a10, a11, t1 = (float(v) for v in np.asarray(m, dtype=np.float32).astype(np.float64))
+    det = a00 * a11 - a01 * a10
+    if det == 0.0 or not np.isfinite(det):
+        raise ValueError("invert_matrix: the map %r is singular" % (list(m),))
+    b00, b01, b10, b11 = a11 / det, -a01 / det, -a10 / det, a00 / det
+    out = np.array([b00, b01, -(b00 * t0 + b01 * t1), b10, b11, -(b10 * t0 + b11 * t1)], dtype=np.float64) + 0.0      # (-0.0 -> 0.0)
+    return out.astype(dtype)
+
+
+def file_layout(shape, flip_correction=True, axis=2, box=None):
+    """where voxel (x, y, z) of the slicing order (double flip, `axis` moved last, optional box ((x0, x1), (y0, y1), (z0, z1))) lies in
+    the C-order array of the file's `shape`: (origin, (sx, sy, sz), (X, Y, Z)) in elements.  Taken from the strides numpy itself gives the
+    view that prepare_pair builds, so the two cannot disagree."""
+    probe = np.empty(tuple(int(n) for n in shape), dtype=np.uint8)          # never touched: only its address arithmetic is used
+    v = probe
+    if flip_correction:
+        v = np.flip(np.flip(v, axis=0), axis=1)
+    v = np.moveaxis(v, axis, -1)
+    if box is not None:
+        v = v[tuple(slice(int(a), int(b)) for a, b in box)]
+    origin = v.__array_interface__["data"][0] - probe.__array_interface__["data"][0]
+    return int(origin), tuple(int(s) for s in v.strides), tuple(int(n) for n in v.shape)
+
+
+def _box_of(crop, label, dims):
+    if crop is None:
+        return tuple((0, n) for n in dims)
+    if isinstance(crop, (int, np.integer)):
+        if label is None:
+            raise ValueError("crop=%d is a margin around the label's bounding box: a label is needed" % crop)
+        if crop < 0:
+            raise ValueError("crop margin %d is negative" % crop)
+        return tuple((s.start, s.stop) for s in label_bounding_box(label, int(crop)))
+    box = tuple((int(a), int(b)) for a, b in crop)
+    if len(box) != 3 or any(not 0 <= a < b <= n for (a, b), n in zip(box, dims)):
+        raise ValueError("crop box %r does not lie inside the volume %r (slicing order, half-open)" % (crop, tuple(dims)))
+    return box
+
+
+def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
+                   out_size=(256, 256), num_cls=5, device="cuda"):
+    """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
+      logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits)
+      label      optional ground truth of the same shape: only its bounding box is used (crop = a margin in voxels)
+      crop       None, a margin around the label's bounding box, or a box ((x0, x1), (y0, y1), (z0, z1)) in slicing order; outside it: 0
+      edge       "replicate": the normalised volume is padded with a copy of its first and last frame, every frame is predicted;
+                 "skip": frames 1 .. Z - 2 only (the reference's frame set), the two edge frames stay 0
+    Frames run in ascending order, batch_size at a time; the last, short batch repeats its last frame and pastes nb < B slices.  Nothing
+    synchronises between batches; the gather's error counter is read once at the end."""
+    import torch
+    from . import kernels as K
+    if edge not in EDGES:
+        raise ValueError("edge must be one of %s, got %r" % (EDGES, edge))
+    B, H, W = int(batch_size), int(out_size[0]), int(out_size[1])
+    if B < 1:
+        raise ValueError("batch_size must be at least 1")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.PnpError("segment_volume: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (device,))
+    image = np.asarray(image)
+    img, lab = prepare_pair(image, np.zeros(image.shape, np.uint8) if label is None else label, flip_correction, axis, None)
+    box = _box_of(crop, None if label is None else lab, img.shape)
+    origin, strides, (X, Y, Z) = file_layout(image.shape, flip_correction, axis, box)
+    if edge == "skip" and Z < 3:
+        raise ValueError("edge='skip' needs at least 3 frames, the box has %d" % Z)
+    out = torch.zeros(tuple(image.shape), dtype=torch.uint8, device=device)
+
+    v = torch.from_numpy(np.ascontiguousarray(img[tuple(slice(a, b) for a, b in box)])).to(device)
+    _, stats = K.volume_preprocess(v, int(percentile), out=v)
+    fill = float(stats[3].item())                       # the one read before the loop: the fill enters the gather's descriptor table
+    if edge == "replicate":
+        v = torch.cat([v[:, :, :1], v, v[:, :, -1:]], dim=2).contiguous()          # statistics: of the unpadded volume, above
+        first, count, shift = 1, Z, -1                  # centre frames 1 .. Z of the padded volume are output frames 0 .. Z - 1
+    else:
+        first, count, shift = 1, Z - 2, 0
+    vs = VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=device)], ["volume"], [fill], percentile)
+    src = AugmentedSliceSource(vs, B, out_size=(H, W), augment=None, num_cls=num_cls)
+    m = compose_matrix((X, Y), (H, W))
+    inv = invert_matrix(m)
+    rec = np.zeros(B, dtype=SAMPLE_DTYPE)
+    rec["m"][:] = m
+    for k in range(0, count, B):
+        nb = min(B, count - k)
+        rec["frame"] = np.minimum(first + k + np.arange(B), first + k + nb - 1)
+        x, _, _ = src.gather_records(rec, num_cls, want_onehot=False)
+        logits = logits_fn(x)
+        if tuple(logits.shape) != (B, H, W, int(num_cls)):
+            raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
+        K.paste_labels(logits.detach().contiguous(), nb, first + k + shift, inv, (X, Y), out, origin, strides)
+    src.close()
+    return out
+
+
+def segmenter_logits(net):
+    """logits_fn of source_segmenter.Full_DRN: every BN in inference mode, no dropout"""
+    import torch
+
+    def fn(x):
+        with torch.no_grad():
+            return net.forward(x, 1.0, main_bn=False, adapt_bn=False)
+    return fn
+
+
+def adapted_logits(net):
+    """logits_fn of the CT path of adversarial.Full_DRN (adapt_* front + shared second half), critics pruned"""
+    import torch
+
+    def fn(x):
+        with torch.no_grad():
+            return net._graph(None, x, 1.0, mr_front_bn=False, joint_bn=False, ct_front_bn=False, critics=False)["ct_logits"]
+    return fn
+
+
+def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5, device="cuda", **options):
+    """every image of nii_list -> <output_path>/pred_<basename>: uint8 NIfTI on the input's grid with the input's affine.  With
+    label_list (same order) also the dense_pred_<name>.nii.gz / gth_dense_pred_<name>.nii.gz pair that `evaluate --pred-dir` reads (the
+    ground truth with labels >= num_cls set to 0).  options: segment_volume's.  Returns the pred_* paths."""
+    from . import nifti
+    nii_list = list(nii_list)
+    if label_list is not None and len(label_list) != len(nii_list):
+        raise ValueError("%d labels for %d images" % (len(label_list), len(nii_list)))
+    os.makedirs(output_path, exist_ok=True)
+    paths = []
+    for n, fid in enumerate(nii_list):
+        img = nifti.load(fid)
+        gt = None if label_list is None else np.asarray(nifti.load(label_list[n]).get_data())
+        pred = segment_volume(logits_fn, img.get_data(), label=gt, num_cls=num_cls, device=device, **options).cpu().numpy()
+        base = os.path.basename(str(fid))
+        paths.append(nifti.save(nifti.Nifti1Image(pred, img.affine), os.path.join(output_path, "pred_" + base)))
+        if gt is not None:
+            dense = "dense_pred_" + base.split(".")[0] + ".nii.gz"
+            nifti.save(nifti.Nifti1Image(pred, img.affine), os.path.join(output_path, dense))
+            g = np.where(gt > num_cls - 1, 0, gt).astype(np.uint8)
+            nifti.save(nifti.Nifti1Image(g, img.affine), os.path.join(output_path, "gth_" + dense))
+    return paths

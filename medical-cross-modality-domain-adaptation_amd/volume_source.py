@@ -5,6 +5,7 @@ the host only draws the parameters.
 
   VolumeSet             loads image / label pairs (nifti.load), flips and reorders them like volume_eval.test_eval, optionally crops to
                         the label bounding box, uploads, normalises on the device (pnp_volume_preprocess) and keeps the per-volume stats
+                        (from_device: volumes that are on the device and normalised already — volume_predict.py's way in)
   AugmentedSliceSource  draws (volume, frame, affine map) per sample from a seeded numpy Generator and gathers the batch on the device
                         (pnp_aug_slices): next_device_batch() for feeder.DeviceFeeder, next_batch() for every consumer of the trainers'
                         [B, H, W, 4] numpy protocol
@@ -184,6 +185,29 @@ class VolumeSet(object):
         self = cls.__new__(cls)
         arrays = [prepare_pair(i, l, flip_correction=False, axis=2, crop=None) for i, l in zip(images, labels)]
         self._build(arrays, [str(n) for n in names], device, percentile)
+        return self
+
+    @classmethod
+    def from_device(cls, images, labels, names, fills, percentile=98):
+        """volumes that are on the device and normalised already (volume_predict.py pads a normalised volume with copies of its edge
+        frames): contiguous float32 / uint8 tensors [X, Y, Z] in slicing order, one fill value per volume.  Nothing is copied or computed."""
+        import torch
+        self = cls.__new__(cls)
+        if not images or not (len(images) == len(labels) == len(names) == len(fills)):
+            raise ValueError("VolumeSet.from_device: images, labels, names and fills must be equally long and not empty")
+        self.device = images[0].device
+        for v, l, name in zip(images, labels, names):
+            if not (v.is_cuda and l.is_cuda):
+                raise _lib.PnpError("VolumeSet: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (v.device,))
+            if v.dtype != torch.float32 or l.dtype != torch.uint8 or v.shape != l.shape or v.dim() != 3 or not (v.is_contiguous() and l.is_contiguous()):
+                raise ValueError("%s: a contiguous float32 image and uint8 label of one 3-D shape expected" % name)
+            if v.shape[2] < 3 or v.shape[0] > 4096 or v.shape[1] > 4096:
+                raise ValueError("%s: volume %s needs at least 3 frames and slice extents <= 4096" % (name, tuple(v.shape)))
+        self.names, self.percentile = [str(n) for n in names], int(percentile)
+        self.images, self.labels = list(images), list(labels)
+        self.dims = [tuple(int(d) for d in v.shape) for v in self.images]
+        self.stats = [{"clip": None, "mean": None, "std": None, "fill": float(f)} for f in fills]
+        self.set_fill(None)
         return self
 
     def _build(self, arrays, names, device, percentile):

@@ -1,0 +1,146 @@
+"""Cost of volume inference (volume_predict.py, csrc/paste.hip) on one GPU: one seeded 256 x 256 x 200 volume and one
+180 x 210 x 160 volume, B = 16, num_cls = 5, the source segmenter's forward (random initialisation) as logits_fn.  Records
+  1. the wall time per volume of segment_volume (array in host memory to finished label volume on the device, synchronised once at the
+     end) against volume_eval.eval_volume, the host-driven loop of Trainer.test_eval, on the same 256 x 256 x 200 array; and the two
+     through files (Trainer.test_eval / Trainer.predict_volumes), with the time of reading and writing the .nii.gz files alone,
+  2. per batch by HIP events around back-to-back launches of one fixed batch: the gather, the forward, the paste — the per-kernel figures
+     of record come from a separate `rocprofv3 --kernel-trace --stats -- python tools/bench_predict.py --profile-step` run,
+  3. the paste kernel's bytes per second (reads B H W ncls fp32, writes B X Y bytes) against the 6.3 TB/s achievable HBM figure, for a
+     z-fastest destination (the array order of a NIfTI reader) and a z-slowest one (the file stores the slicing axis first).
+Prints one JSON object and writes it to --out (default profiles/predict_timing.json)."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+PKG = "medical-cross-modality-domain-adaptation_amd"
+vp = importlib.import_module(PKG + ".volume_predict")
+vs = importlib.import_module(PKG + ".volume_source")
+ss = importlib.import_module(PKG + ".source_segmenter")
+nifti = importlib.import_module(PKG + ".nifti")
+K = importlib.import_module(PKG + ".kernels")
+
+HBM_ACHIEVABLE = 6.3e12
+COST = {"cross_flag": True, "miu_cross": 1.0, "dice_flag": True, "miu_dice": 1.0, "regularizer": 1e-4}
+
+
+def scan(shape, seed):
+    rng = np.random.default_rng(seed)
+    v = rng.standard_normal(shape, dtype=np.float32) * 200 + 300
+    v[::7, ::5, ::3] += 3000
+    return v.astype(np.int16)
+
+
+def events(fn, reps, warm=3):
+    for _ in range(warm):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def wall(fn, reps=3):
+    out = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3)
+    return {"median_ms": float(np.median(out)), "runs_ms": out}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch-size", type=int, default=16)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "predict_timing.json"))
+    ap.add_argument("--profile-step", action="store_true", help="one 16-frame warm-up volume, then both volumes once: for a rocprofv3 --kernel-trace run")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B, ncls = a.batch_size, 5
+    net = ss.Full_DRN(channels=3, n_class=ncls, batch_size=B, device=dev, seed=0, cost_kwargs=dict(COST))
+    fn = vp.segmenter_logits(net)
+    big, small = scan((256, 256, 200), 0), scan((180, 210, 160), 1)
+    kw = dict(batch_size=B, num_cls=ncls, device=dev)
+    vp.segment_volume(fn, scan((256, 256, 16), 2), **kw)          # warm-up: 1 batch
+    torch.cuda.synchronize()
+    if a.profile_step:
+        vp.segment_volume(fn, big, **kw)                          # 13 batches
+        vp.segment_volume(fn, small, **kw)                        # 10 batches
+        torch.cuda.synchronize()
+        print(json.dumps({"profile_step": True, "batches": 1 + 13 + 10}))
+        return
+    res = {"device": torch.cuda.get_device_name(0), "batch_size": B, "num_cls": ncls, "out_size": [256, 256]}
+    # 1. wall time per volume
+    res["segment_volume_256x256x200"] = wall(lambda: vp.segment_volume(fn, big, **kw))
+    res["segment_volume_180x210x160"] = wall(lambda: vp.segment_volume(fn, small, **kw))
+    res["segment_volume_256x256x200_to_host"] = wall(lambda: vp.segment_volume(fn, big, **kw).cpu())
+    with tempfile.TemporaryDirectory() as tmp:
+        img, lab = os.path.join(tmp, "scan.nii.gz"), os.path.join(tmp, "scan_label.nii.gz")
+        nifti.save(nifti.Nifti1Image(big), img)
+        nifti.save(nifti.Nifti1Image((np.random.default_rng(3).random((16, 16, 200)) * 5).astype(np.uint8).repeat(16, 0).repeat(16, 1)), lab)
+        tr = ss.Trainer(net, train_list=[], val_list=[], num_cls=ncls, batch_size=B, test_nii_list=[img], test_label_list=[lab])
+        logging_off()
+        ve = importlib.import_module(PKG + ".volume_eval")
+        raw, raw_y = np.asarray(nifti.load(img).get_data()), np.asarray(nifti.load(lab).get_data())
+        loop = lambda: ve.eval_volume(tr._predict_batch, raw, raw_y, B, ncls, shuffle=False)
+        loop()
+        res["eval_volume_256x256x200_in_memory"] = wall(loop)
+        res["eval_volume_over_segment_volume"] = res["eval_volume_256x256x200_in_memory"]["median_ms"] / res["segment_volume_256x256x200"]["median_ms"]
+        res["nifti_load_gz_ms"] = wall(lambda: nifti.load(img))["median_ms"]
+        pred = vp.segment_volume(fn, big, **kw).cpu().numpy()
+        res["nifti_save_gz_ms"] = wall(lambda: nifti.save(nifti.Nifti1Image(pred), os.path.join(tmp, "w.nii.gz")))["median_ms"]
+        tr.test_eval(output_path=os.path.join(tmp, "te"))         # warm-up
+        res["test_eval_256x256x200_files"] = wall(lambda: tr.test_eval(output_path=os.path.join(tmp, "te")))
+        res["predict_volumes_256x256x200_files"] = wall(lambda: tr.predict_volumes([img], os.path.join(tmp, "pv")))
+    res["test_eval_over_predict_volumes_files"] = res["test_eval_256x256x200_files"]["median_ms"] / res["predict_volumes_256x256x200_files"]["median_ms"]
+    res["note_wall"] = ("test_eval predicts 192 of the 200 frames (not the first, the last, nor those past the last whole batch), scores every batch "
+                        "and reads the image and the label file without writing; predict_volumes predicts all 200, reads one .nii.gz and writes one")
+    # 2. one fixed batch, stage by stage
+    v = torch.from_numpy(big.astype(np.float32)).to(dev)
+    _, st = K.volume_preprocess(v, 98, out=v)
+    vset = vs.VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=dev)], ["v"], [float(st[3].item())])
+    src = vs.AugmentedSliceSource(vset, B, augment=None, num_cls=ncls)
+    rec = np.zeros(B, dtype=vs.SAMPLE_DTYPE)
+    rec["frame"], rec["m"][:] = 50 + np.arange(B), vs.compose_matrix((256, 256), (256, 256))
+    x = src.gather_records(rec, ncls, want_onehot=False)[0]
+    logits = fn(x).contiguous()
+    res["gather_ms_incl_upload_and_allocation"] = events(lambda: src.gather_records(rec, ncls, want_onehot=False), 50)
+    res["forward_ms"] = events(lambda: fn(x), 20)
+    # 3. the paste alone, both stride patterns (identity map and the 180 x 210 resize)
+    for name, (X, Y, Z) in (("256x256", (256, 256, 200)), ("180x210", (180, 210, 160))):
+        inv = vp.invert_matrix(vs.compose_matrix((X, Y), (256, 256)))
+        for pattern, shape, axis in (("z_fastest", (X, Y, Z), 2), ("z_slowest", (Z, X, Y), 0)):
+            origin, strides, _ = vp.file_layout(shape, True, axis, None)
+            out = torch.zeros(shape, dtype=torch.uint8, device=dev)
+            ms = events(lambda: K.paste_labels(logits, B, 50, inv, (X, Y), out, origin, strides), 50)
+            nbytes = B * 256 * 256 * ncls * 4 + B * X * Y
+            res["paste_%s_%s" % (name, pattern)] = {"ms_back_to_back": ms, "strides": list(strides), "bytes_read_plus_written": nbytes,
+                                                    "tb_per_s": nbytes / (ms * 1e-3) / 1e12, "fraction_of_achievable_hbm": nbytes / (ms * 1e-3) / HBM_ACHIEVABLE}
+    res["gather_plus_paste_over_forward"] = (res["gather_ms_incl_upload_and_allocation"] + res["paste_256x256_z_fastest"]["ms_back_to_back"]) / res["forward_ms"]
+    src.close()
+    print(json.dumps(res))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def logging_off():
+    import logging
+    logging.disable(logging.INFO)
+
+
+if __name__ == "__main__":
+    main()
