@@ -546,6 +546,24 @@ int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32
                      int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
                      void* stream);
 
+/* ---- ensemble inference (csrc/paste.hip): M members' logits -> label, mean probabilities, normalised entropy ------------------
+ *
+ * logits: HOST array of M device pointers (1 <= M <= 8; a pointer may repeat), each [B, H, W, ncls] float32, finite; inv: HOST array of
+ * 6 * M floats, member m's map from a source voxel to its output plane.  The box, vol, origin and strides are pnp_paste_labels'.  Per voxel
+ * (x, y, frame b), with e = origin + x * sx + y * sy + (z0 + b) * sz:
+ *   for m ascending: r_m[c] exactly as pnp_paste_labels interpolates with inv_m (a map that leaves the plane contributes the clamped edge
+ *     value); mx = max_c r_m[c]; e_c = expf(r_m[c] - mx); s = sum of e_c over ascending c; p_c = e_c / s;
+ *   acc_c = (p_c of members 0 .. 3 summed ascending) + (those of members 4 .. 7 summed ascending; absent for M <= 4);
+ *   P_c = acc_c * (1.0f / M) (exact for M = 1, 2, 4, 8; M equal members give P = p bit for bit for those M);
+ *   vol[e] = the lowest c with the strictly largest acc_c;
+ *   prob[c * vol_elems + e] = P_c (nullable; class-major planes of vol_elems floats);
+ *   entropy[e] = -sum_c fmaf-accumulated P_c * logf(P_c) / logf(ncls), a term with P_c == 0 contributing 0; 0 for ncls == 1 (nullable).
+ * Nothing else of vol, prob or entropy is touched.  Refused on the host before any HIP call: all that pnp_paste_labels refuses; M outside
+ * [1, 8]; a null member pointer; a null inv; ncls * vol_elems overflowing int64. */
+int pnp_paste_ensemble(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
+                       int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                       float* prob /*nullable*/, float* entropy /*nullable*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

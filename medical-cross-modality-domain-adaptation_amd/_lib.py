@@ -180,6 +180,8 @@ PROTOTYPES = {
     "pnp_aug_slices": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, _F, _F, _F, c_int32, c_void_p, c_void_p]),
     "pnp_paste_labels": (c_int, [_F, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_int32, c_int32, c_void_p, c_int64,
                                  c_int64, c_int64, c_int64, c_int64, c_void_p]),
+    "pnp_paste_ensemble": (c_int, [c_int32, POINTER(c_void_p), POINTER(c_float), c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                   c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, _F, _F, c_void_p]),
 }
 
 _lib = None

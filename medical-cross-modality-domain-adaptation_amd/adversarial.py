@@ -771,14 +771,16 @@ class Trainer(object):
             self.surface_eval_list = ve.finish_surface_log(slog, output_path, verbose)
         return self.sample_metric_stddev(sample_eval_list)
 
-    def predict_volumes(self, nii_list, output_path, label_list=None, **options):
+    def predict_volumes(self, nii_list, output_path, label_list=None, ensemble=None, **options):
         """volume_predict.predict_volumes with this trainer's net (no counterpart in the reference): every image ->
         <output_path>/pred_<basename>, a uint8 label volume on the image's own grid with its affine; with label_list also the
         dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  options: volume_predict.segment_volume's (edge, crop, axis,
-        flip_correction, batch_size [default: the net's], percentile, out_size).  Returns the pred_* paths.  test_eval is untouched."""
+        flip_correction, batch_size [default: the net's], percentile, out_size; tta, prob, entropy: DESIGN.md §15, which also write prob_* /
+        entropy_* files).  ensemble: further nets of this class, averaged with this trainer's.  Returns the pred_* paths.  test_eval is untouched."""
         from . import volume_predict as vp
         options.setdefault("batch_size", self.net.batch_size)
-        return vp.predict_volumes(vp.adapted_logits(self.net), nii_list, output_path, label_list=label_list, num_cls=self.num_cls,
+        fn = vp.adapted_logits(self.net) if not ensemble else [vp.adapted_logits(n) for n in [self.net] + list(ensemble)]
+        return vp.predict_volumes(fn, nii_list, output_path, label_list=label_list, num_cls=self.num_cls,
                                   device=self.net.device, **options)
 
     def test_model(self, this_model, output_path):

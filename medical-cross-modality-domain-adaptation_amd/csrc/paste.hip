@@ -13,6 +13,14 @@
 //   otherwise (the file stores the slicing axis first)          one byte per frame and lane; with |sy| == 1 a wave's 64 lanes write 64
 //                         adjacent bytes with one store instruction.
 // Every output element has exactly one writer (the host refuses strides under which two voxels collide): no atomics.
+//
+//   paste_ensemble_kernel   the same lane layout and the same three store paths for M <= 8 members: per voxel every member's
+//                         logits are interpolated through that member's own inverse map (the very expressions of label_at), passed
+//                         through softmax and summed in a fixed order; the label is the first strict maximum of the sum, and on request
+//                         the mean probabilities (class-major fp32 planes) and the normalised entropy go to the same element index.
+//                         A member's corner data is recomputed per frame from its six kernel-argument floats: 8 members x 8 values kept
+//                         per lane would be 64 VGPRs or an indexed private array (scratch); the ~30 VALU operations per member and frame
+//                         stand against 4 * ncls dependent-address loads, ncls expf and ncls divisions.
 #include <algorithm>
 #include <math.h>
 
@@ -99,24 +107,156 @@ __global__ void __launch_bounds__(kThreads) paste_labels_kernel(const PasteArgs 
     }
 }
 
+constexpr int kMaxMembers = 8;
+constexpr int kGroup = 4;      // members are summed in runs of 4: see ensemble_at
+
+struct EnsembleArgs {
+    const float* logits[kMaxMembers];      // [B, H, W, ncls] each
+    unsigned char* vol;
+    float* prob;               // nullable: ncls planes of vol_elems floats
+    float* entropy;            // nullable: vol_elems floats
+    long long vol_elems;
+    long long origin;
+    long long sx, sy, sz;
+    long long plane;
+    float inv[6 * kMaxMembers];
+    float inv_m;               // 1.0f / M
+    int M, H, W, ncls, nb, z0, X, Y;
+};
+
+// acc[c] = sum over the members of softmax_c(interpolated logits), frame offset `off` (floats); returns the first strict maximum of acc.
+// Order of the sum: members 0 .. 3 ascending into one accumulator, members 4 .. 7 ascending into a second one, then first + second.  For
+// M <= 4 that is the plain ascending sum; the split makes M = 8 copies of one member sum to exactly 8 p (p + p + p + p is exact in
+// binary floating point, a run of 8 is not: 5 p and 7 p round), which the exactness of P = acc * (1 / M) for M = 8 needs.
+template <int NCLS>
+__device__ __forceinline__ int ensemble_at(const EnsembleArgs& A, float fx, float fy, long long off, float (&acc)[NCLS]) {
+    float hi[NCLS];
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) acc[c] = hi[c] = 0.f;
+    for (int m = 0; m < A.M; ++m) {
+        const float* iv = A.inv + 6 * m;
+        float pi = fmaf(iv[0], fx, fmaf(iv[1], fy, iv[2]));
+        float pj = fmaf(iv[3], fx, fmaf(iv[4], fy, iv[5]));
+        pi = fminf(fmaxf(pi, 0.f), (float)(A.H - 1));         // as paste_labels_kernel: NaN -> 0, clamped before any integer conversion
+        pj = fminf(fmaxf(pj, 0.f), (float)(A.W - 1));
+        const float fi = floorf(pi), fj = floorf(pj);
+        const int i0 = (int)fi, j0 = (int)fj;
+        const int i1 = min(i0 + 1, A.H - 1), j1 = min(j0 + 1, A.W - 1);
+        const float ti = pi - fi, tj = pj - fj;
+        const float ui = 1.f - ti, uj = 1.f - tj;
+        const float* __restrict__ p = A.logits[m] + off;
+        const float* __restrict__ p00 = p + (i0 * A.W + j0) * NCLS;
+        const float* __restrict__ p01 = p + (i0 * A.W + j1) * NCLS;
+        const float* __restrict__ p10 = p + (i1 * A.W + j0) * NCLS;
+        const float* __restrict__ p11 = p + (i1 * A.W + j1) * NCLS;
+        float r[NCLS];
+        float mx = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) {
+            const float a = fmaf(p01[c], tj, p00[c] * uj);        // the three steps of label_at
+            const float b = fmaf(p11[c], tj, p10[c] * uj);
+            r[c] = fmaf(b, ti, a * ui);
+            mx = c == 0 ? r[c] : fmaxf(mx, r[c]);
+        }
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) {
+            r[c] = expf(r[c] - mx);
+            s += r[c];
+        }
+        if (m < kGroup) {
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) acc[c] += r[c] / s;
+        } else {
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) hi[c] += r[c] / s;
+        }
+    }
+    int am = 0;
+    float best = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) {
+        if (A.M > kGroup) acc[c] += hi[c];
+        if (c == 0 || acc[c] > best) {
+            best = acc[c];
+            am = c;
+        }
+    }
+    return am;
+}
+
+// the mean probabilities and the normalised entropy of one voxel at element index e (plain dword stores, one writer per element)
+template <int NCLS>
+__device__ __forceinline__ void store_soft(const EnsembleArgs& A, long long e, const float (&acc)[NCLS], float inv_logn) {
+    if (A.prob) {
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) A.prob[(long long)c * A.vol_elems + e] = acc[c] * A.inv_m;
+    }
+    if (A.entropy) {
+        float h = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) {
+            const float P = acc[c] * A.inv_m;
+            if (P > 0.f) h = fmaf(P, logf(P), h);
+        }
+        A.entropy[e] = NCLS == 1 ? 0.f : -h * inv_logn;
+    }
+}
+
+template <int NCLS>
+__global__ void __launch_bounds__(kThreads) paste_ensemble_kernel(const EnsembleArgs A) {
+    const int g = blockIdx.x * kThreads + threadIdx.x;        // flat column index, y fastest, as in paste_labels_kernel
+    if (g >= A.X * A.Y) return;
+    const int x = g / A.Y, y = g - x * A.Y;
+    const float fx = (float)x, fy = (float)y;
+    const int nb = A.nb;
+    const bool soft = A.prob || A.entropy;
+    const float inv_logn = NCLS > 1 ? 1.f / logf((float)NCLS) : 0.f;
+    const long long col = A.origin + (long long)x * A.sx + (long long)y * A.sy + (long long)A.z0 * A.sz;      // frame z0 of this column
+    float acc[NCLS];
+    // t counts elements from the lowest address when z is fastest: frame t (sz = 1) or nb - 1 - t (sz = -1); otherwise t is the frame.
+    // The three store paths of paste_labels_kernel in one loop: labels collect in `w` at their byte lane; a word that fills all four
+    // lanes goes out as one aligned dword, the head (before the first 4-byte boundary) and the tail as single bytes.
+    const bool zfast = A.sz == 1 || A.sz == -1, up = A.sz != -1;
+    const long long e0 = up ? col : col - (nb - 1);
+    unsigned int w = 0u;
+    int first = 0;
+    for (int t = 0; t < nb; ++t) {
+        const int b = up ? t : nb - 1 - t;
+        const long long e = zfast ? e0 + t : col + (long long)b * A.sz;
+        const unsigned int lab = (unsigned int)ensemble_at<NCLS>(A, fx, fy, (long long)b * A.plane, acc);
+        if (soft) store_soft<NCLS>(A, e, acc, inv_logn);
+        if (!zfast) {
+            A.vol[e] = (unsigned char)lab;
+            continue;
+        }
+        const unsigned int lane = (unsigned int)((uintptr_t)(A.vol + e) & 3u);
+        w |= lab << (8u * lane);
+        if (lane == 3u || t == nb - 1) {
+            if (t - first == 3) {
+                *(unsigned int*)(A.vol + e - 3) = w;                  // lane == 3 and four labels: an aligned dword
+            } else {
+                for (int q = first; q <= t; ++q) A.vol[e0 + q] = (unsigned char)(w >> (8u * (unsigned int)((uintptr_t)(A.vol + e0 + q) & 3u)));
+            }
+            w = 0u;
+            first = t + 1;
+        }
+    }
+}
+
 long long abs_ll(long long v) { return v < 0 ? -v : v; }
 
-}  // namespace
-
-extern "C" {
-
-int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, const float* inv,
-                     int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
-                     void* stream) {
-    PNP_REQUIRE(logits && inv && vol, "pnp_paste_labels: null pointer");
-    PNP_REQUIRE(B >= 1 && H >= 1 && W >= 1, "pnp_paste_labels: logits [%d, %d, %d] must be at least [1, 1, 1]", (int)B, (int)H, (int)W);
-    PNP_REQUIRE(X >= 1 && Y >= 1, "pnp_paste_labels: source extents %d x %d must be at least 1 x 1", (int)X, (int)Y);
-    PNP_REQUIRE(H <= kMaxExtent && W <= kMaxExtent, "pnp_paste_labels: output plane %d x %d above %d", (int)H, (int)W, kMaxExtent);
-    PNP_REQUIRE(X <= kMaxExtent && Y <= kMaxExtent, "pnp_paste_labels: source extents %d x %d above %d", (int)X, (int)Y, kMaxExtent);
-    PNP_REQUIRE(ncls >= 1 && ncls <= MAXC, "pnp_paste_labels: ncls %d outside [1, %d]", (int)ncls, MAXC);
-    PNP_REQUIRE(nb >= 1 && nb <= B, "pnp_paste_labels: nb = %d outside [1, B = %d]", (int)nb, (int)B);
-    PNP_REQUIRE(z0 >= 0, "pnp_paste_labels: z0 = %d is negative", (int)z0);
-    PNP_REQUIRE(vol_elems >= 1, "pnp_paste_labels: vol_elems = %lld, at least one element is needed", (long long)vol_elems);
+// the argument checks both entry points share (everything but the null pointers), with the caller's name in the text
+int check_paste(const char* who, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, int32_t X, int32_t Y, int64_t vol_elems,
+                int64_t origin, int64_t sx, int64_t sy, int64_t sz) {
+    PNP_REQUIRE(B >= 1 && H >= 1 && W >= 1, "%s: logits [%d, %d, %d] must be at least [1, 1, 1]", who, (int)B, (int)H, (int)W);
+    PNP_REQUIRE(X >= 1 && Y >= 1, "%s: source extents %d x %d must be at least 1 x 1", who, (int)X, (int)Y);
+    PNP_REQUIRE(H <= kMaxExtent && W <= kMaxExtent, "%s: output plane %d x %d above %d", who, (int)H, (int)W, kMaxExtent);
+    PNP_REQUIRE(X <= kMaxExtent && Y <= kMaxExtent, "%s: source extents %d x %d above %d", who, (int)X, (int)Y, kMaxExtent);
+    PNP_REQUIRE(ncls >= 1 && ncls <= MAXC, "%s: ncls %d outside [1, %d]", who, (int)ncls, MAXC);
+    PNP_REQUIRE(nb >= 1 && nb <= B, "%s: nb = %d outside [1, B = %d]", who, (int)nb, (int)B);
+    PNP_REQUIRE(z0 >= 0, "%s: z0 = %d is negative", who, (int)z0);
+    PNP_REQUIRE(vol_elems >= 1, "%s: vol_elems = %lld, at least one element is needed", who, (long long)vol_elems);
     // the extreme corners of the box, in 128-bit integers: a stride is any int64
     const __int128 ext[3] = {X - 1, Y - 1, nb - 1};
     const __int128 str[3] = {sx, sy, sz};
@@ -125,7 +265,7 @@ int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32
         const __int128 span = ext[d] * str[d];
         if (span < 0) lo += span; else hi += span;
     }
-    PNP_REQUIRE(lo >= 0 && hi < (__int128)vol_elems, "pnp_paste_labels: the box addresses elements outside [0, %lld) (origin %lld, strides %lld %lld %lld)",
+    PNP_REQUIRE(lo >= 0 && hi < (__int128)vol_elems, "%s: the box addresses elements outside [0, %lld) (origin %lld, strides %lld %lld %lld)", who,
                 (long long)vol_elems, (long long)origin, (long long)sx, (long long)sy, (long long)sz);
     // one writer per element: over the axes of extent > 1, sorted by |stride|, each stride covers the whole run of the one before it
     long long as[3];
@@ -146,10 +286,22 @@ int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32
             }
     __int128 need = 1;
     for (int d = 0; d < n; ++d) {
-        PNP_REQUIRE((__int128)as[d] >= need, "pnp_paste_labels: strides %lld %lld %lld let two voxels of a %d x %d x %d box collide",
+        PNP_REQUIRE((__int128)as[d] >= need, "%s: strides %lld %lld %lld let two voxels of a %d x %d x %d box collide", who,
                     (long long)sx, (long long)sy, (long long)sz, (int)X, (int)Y, (int)nb);
         need = (__int128)as[d] * ae[d];
     }
+    return PNP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, const float* inv,
+                     int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                     void* stream) {
+    PNP_REQUIRE(logits && inv && vol, "pnp_paste_labels: null pointer");
+    if (const int rc = check_paste("pnp_paste_labels", B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
     PasteArgs A;
     A.logits = logits;
     A.vol = vol;
@@ -161,6 +313,41 @@ int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32
     const unsigned blocks = (unsigned)(((long long)X * Y + kThreads - 1) / kThreads);
     hipLaunchKernelGGL(paste_labels_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A);
     PNP_CHECK_LAUNCH("paste_labels_kernel");
+    return PNP_OK;
+}
+
+int pnp_paste_ensemble(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
+                       int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                       float* prob, float* entropy, void* stream) {
+    PNP_REQUIRE(M >= 1 && M <= kMaxMembers, "pnp_paste_ensemble: M = %d members outside [1, %d]", (int)M, kMaxMembers);
+    PNP_REQUIRE(logits && vol, "pnp_paste_ensemble: null pointer");
+    PNP_REQUIRE(inv, "pnp_paste_ensemble: null inv (6 floats per member)");
+    for (int m = 0; m < M; ++m) PNP_REQUIRE(logits[m], "pnp_paste_ensemble: member %d of %d is a null pointer", m, (int)M);
+    if (const int rc = check_paste("pnp_paste_ensemble", B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
+    PNP_REQUIRE((__int128)ncls * vol_elems <= (__int128)INT64_MAX, "pnp_paste_ensemble: ncls * vol_elems = %d * %lld overflows int64", (int)ncls,
+                (long long)vol_elems);
+    EnsembleArgs A;
+    for (int m = 0; m < kMaxMembers; ++m) {
+        A.logits[m] = logits[m < M ? m : 0];
+        for (int i = 0; i < 6; ++i) A.inv[6 * m + i] = inv[6 * (m < M ? m : 0) + i];
+    }
+    A.vol = vol;
+    A.prob = prob;
+    A.entropy = entropy;
+    A.vol_elems = vol_elems;
+    A.origin = origin;
+    A.sx = sx; A.sy = sy; A.sz = sz;
+    A.plane = (long long)H * W * ncls;
+    A.inv_m = 1.0f / (float)M;
+    A.M = M; A.H = H; A.W = W; A.ncls = ncls; A.nb = nb; A.z0 = z0; A.X = X; A.Y = Y;
+    const unsigned blocks = (unsigned)(((long long)X * Y + kThreads - 1) / kThreads);
+    switch (ncls) {
+#define PNP_ENSEMBLE_CASE(n) case n: hipLaunchKernelGGL(paste_ensemble_kernel<n>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
+        PNP_ENSEMBLE_CASE(1) PNP_ENSEMBLE_CASE(2) PNP_ENSEMBLE_CASE(3) PNP_ENSEMBLE_CASE(4)
+        PNP_ENSEMBLE_CASE(5) PNP_ENSEMBLE_CASE(6) PNP_ENSEMBLE_CASE(7) PNP_ENSEMBLE_CASE(8)
+#undef PNP_ENSEMBLE_CASE
+    }
+    PNP_CHECK_LAUNCH("paste_ensemble_kernel");
     return PNP_OK;
 }
 

@@ -1030,3 +1030,36 @@ def paste_labels(logits, nb, z0, inv, src_xy, vol, origin, strides):
                                        ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
                                        int(strides[2]), _stream()), "pnp_paste_labels")
     return vol
+
+
+def paste_ensemble(logits, nb, z0, invs, src_xy, vol, origin, strides, prob=None, entropy=None):
+    """pnp_paste_ensemble: M = len(logits) members, each [B, H, W, ncls] float32 (a tensor may repeat), invs: one six-entry map per member
+    (host) -> per (x < X, y < Y, b < nb) at e = origin + x sx + y sy + (z0 + b) sz: vol.view(-1)[e] = the first strict maximum of the
+    members' summed softmax of the interpolated logits, prob.view(ncls, -1)[c, e] = the mean probability (prob: contiguous float32,
+    ncls * vol.numel() elements, or None), entropy.view(-1)[e] = the entropy normalised by log(ncls) (contiguous float32 of vol.numel()
+    elements, or None).  Stream-ordered, returns (vol, prob, entropy)."""
+    logits = list(logits)
+    if not logits or len(invs) != len(logits):
+        raise _lib.PnpError("paste_ensemble: %d members with %d maps" % (len(logits), len(invs)))
+    shape = tuple(logits[0].shape)
+    for t in logits:
+        if t.dim() != 4 or tuple(t.shape) != shape:
+            raise _lib.PnpError("paste_ensemble: every member must be [B, H, W, ncls] of one shape, got %s and %s" % (shape, tuple(t.shape)))
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.PnpError("paste_ensemble: logits must be contiguous float32 CUDA tensors (got %s %s) — there is no CPU fallback" % (t.device, t.dtype))
+    if not vol.is_cuda or vol.dtype != torch.uint8 or not vol.is_contiguous():
+        raise _lib.PnpError("paste_ensemble: vol must be a contiguous uint8 CUDA tensor (got %s %s) — there is no CPU fallback" % (vol.device, vol.dtype))
+    B, H, W, ncls = (int(d) for d in shape)
+    for name, t, n in (("prob", prob, ncls * vol.numel()), ("entropy", entropy, vol.numel())):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise _lib.PnpError("paste_ensemble: %s must be a contiguous float32 CUDA tensor of %d elements (got %s %s, %d) — there is no CPU fallback"
+                                % (name, n, t.device, t.dtype, t.numel()))
+    M = len(logits)
+    ptrs = (ctypes.c_void_p * M)(*[t.data_ptr() for t in logits])
+    m = (ctypes.c_float * (6 * M))(*[float(v) for inv in invs for v in inv])
+    if len(m) != 6 * M:
+        raise _lib.PnpError("paste_ensemble: every map has six entries")
+    check(_lib.load().pnp_paste_ensemble(M, ptrs, m, B, H, W, ncls, int(nb), int(z0), int(src_xy[0]), int(src_xy[1]),
+                                         ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
+                                         int(strides[2]), _p(prob), _p(entropy), _stream()), "pnp_paste_ensemble")
+    return vol, prob, entropy

@@ -4,11 +4,16 @@
            (--images A.nii.gz ... | --list LIST) --out DIR [--labels ...] [--edge replicate|skip]
            [--crop x0:x1,y0:y1,z0:z1 | --crop-margin N] [--axis 2] [--no-flip-correction] [--batch-size 16]
            [--score [--spacing unit|header] [--json F]]
+           [--tta default|JSON] [--prob] [--entropy] [--ensemble CKPT [CKPT ...]]
 
 --list holds one `image.nii[.gz]` or `image.nii[.gz] label.nii[.gz]` per line (all lines alike; paths relative to the list's folder unless
 absolute).  The net is built as train_segmenter / train_gan build theirs, with their default configuration: `segmenter` is the source
 segmenter, `adapted` the CT path of the adversarial model.  Labels are used for the crop margin, for the dense_pred_* / gth_dense_pred_*
 pair and for --score, which runs evaluate.evaluate on that pair; they never reach the network.
+
+Ensemble inference: --tta averages several views of every slice (`default`, or a JSON list of objects with the keys
+rotate, scale, translate, flip), --ensemble adds further checkpoints of the same --net (each built and restored as --model is); members =
+checkpoints x views, at most 8.  --prob / --entropy also write prob_<basename> (float32, [*shape, classes]) and entropy_<basename> (float32).
 """
 import argparse
 import json
@@ -80,6 +85,11 @@ def parse_args(argv=None):
     ap.add_argument("--spacing", choices=("unit", "header"), default="unit")
     ap.add_argument("--json", default=None, help="write the score here")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--tta", default=None, metavar="default|JSON", help="views of every slice, averaged: `default` or a JSON list of "
+                    "objects with the keys rotate, scale, translate, flip")
+    ap.add_argument("--prob", action="store_true", help="also write prob_<basename>: float32 class probabilities, [*shape, classes]")
+    ap.add_argument("--entropy", action="store_true", help="also write entropy_<basename>: float32 entropy normalised by log(classes)")
+    ap.add_argument("--ensemble", nargs="+", default=None, metavar="CKPT", help="further checkpoints of the same --net, averaged with --model")
     a = ap.parse_args(argv)
     if (a.images is None) == (a.list is None):
         ap.error("give either --images or --list")
@@ -105,11 +115,28 @@ def parse_args(argv=None):
         ap.error("--json and --spacing go with --score")
     if a.batch_size < 1:
         ap.error("--batch-size must be at least 1")
-    for p in [a.model] + images + (labels or []):
+    for p in [a.model] + images + (labels or []) + (a.ensemble or []):
         if not os.path.isfile(p):
             ap.error("%s does not exist" % p)
     options = {"edge": a.edge, "axis": a.axis, "flip_correction": not a.no_flip_correction, "batch_size": a.batch_size,
                "crop": box if box is not None else a.crop_margin}
+    # the ensemble options enter only when given: without them segment_volume takes its default path
+    if a.tta is not None:
+        from .volume_predict import tta_entries
+        try:
+            tta = "default" if a.tta == "default" else json.loads(a.tta)
+            options["tta"] = tta_entries(tta)
+        except ValueError as e:
+            ap.error("--tta: %s" % e)
+    from .volume_predict import MAX_MEMBERS
+    members = (1 + len(a.ensemble or [])) * len(options.get("tta", [None]))
+    if members > MAX_MEMBERS:
+        ap.error("--ensemble / --tta: %d checkpoints x %d views = %d members, at most %d" % (1 + len(a.ensemble or []), len(options.get("tta", [None])),
+                                                                                           members, MAX_MEMBERS))
+    if a.prob:
+        options["prob"] = True
+    if a.entropy:
+        options["entropy"] = True
     return a, images, labels, options
 
 
@@ -132,6 +159,8 @@ def main(argv=None):
     """-> {"paths": [pred_* files], "score": evaluate.evaluate's result or None}"""
     a, images, labels, options = parse_args(argv)
     trainer = build_trainer(a.net, a.model, a.batch_size, a.device)
+    if a.ensemble:
+        options["ensemble"] = [build_trainer(a.net, ck, a.batch_size, a.device).net for ck in a.ensemble]
     paths = trainer.predict_volumes(images, a.out, label_list=labels, **options)
     for p in paths:
         print("wrote %s" % p)

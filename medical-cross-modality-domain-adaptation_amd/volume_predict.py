@@ -11,7 +11,13 @@ truth, predicts every frame and keeps the volume on the device from upload to th
 
 The label of a voxel is the argmax of the bilinearly interpolated LOGITS (not probabilities): no exp, and for an identity map exactly
 argmax(logits).
+
+Ensemble inference (opt-in): with a list of callables (checkpoints), tta= (views of the same slice) or prob= / entropy=,
+segment_volume gathers once per distinct map, runs one forward per member and makes ONE pnp_paste_ensemble launch per batch, which
+interpolates every member's logits through that member's own inverse map, averages the softmax and writes the label, the mean
+probabilities and the normalised entropy in the file's array order.  With the defaults nothing of this is reached.
 """
+import collections
 import os
 
 import numpy as np
@@ -20,6 +26,10 @@ from . import _lib
 from .volume_source import SAMPLE_DTYPE, AugmentedSliceSource, VolumeSet, compose_matrix, label_bounding_box, prepare_pair
 
 EDGES = ("replicate", "skip")
+MAX_MEMBERS = 8                          # pnp_paste_ensemble's
+TTA_KEYS = ("rotate", "scale", "translate", "flip")      # compose_matrix's keywords
+DEFAULT_TTA = ({}, {"rotate": 7.5}, {"rotate": -7.5}, {"scale": 0.95}, {"scale": 1.05})
+Ensemble = collections.namedtuple("Ensemble", ("label", "prob", "entropy"))
 
 
 def invert_matrix(m, dtype=np.float32):
@@ -65,10 +75,71 @@ def _box_of(crop, label, dims):
     return box
 
 
+def tta_entries(tta):
+    """None -> [{}]; "default" -> DEFAULT_TTA; a list of dicts of compose_matrix's keywords -> a list of validated copies.  Raises ValueError
+    for an empty list, an entry that is no dict, unknown keys and values compose_matrix cannot take (checked here, on the host)."""
+    if tta is None:
+        return [{}]
+    if isinstance(tta, str):
+        if tta != "default":
+            raise ValueError("tta: the only named set is 'default', got %r" % tta)
+        return [dict(e) for e in DEFAULT_TTA]
+    if isinstance(tta, dict) or not isinstance(tta, (list, tuple)):
+        raise ValueError("tta must be None, 'default' or a list of dicts, got %r" % (tta,))
+    if len(tta) == 0:
+        raise ValueError("tta: an empty list has no member")
+    out = []
+    for n, e in enumerate(tta):
+        if not isinstance(e, dict):
+            raise ValueError("tta[%d]: a dict of %s expected, got %r" % (n, TTA_KEYS, e))
+        unknown = sorted(set(e) - set(TTA_KEYS))
+        if unknown:
+            raise ValueError("tta[%d]: unknown keys %s (known: %s)" % (n, unknown, list(TTA_KEYS)))
+        e = dict(e)
+        try:
+            for k in ("rotate", "scale"):
+                if k in e:
+                    e[k] = float(e[k])
+                    if not np.isfinite(e[k]):
+                        raise ValueError("%s is not finite" % k)
+            if "scale" in e and not e["scale"] > 0.0:
+                raise ValueError("scale must be positive")
+            if "translate" in e:
+                t = tuple(float(v) for v in e["translate"])
+                if len(t) != 2 or not all(np.isfinite(t)):
+                    raise ValueError("translate must be two finite numbers")
+                e["translate"] = t
+            if "flip" in e:
+                if not isinstance(e["flip"], (bool, np.bool_)):
+                    raise ValueError("flip must be a bool")
+                e["flip"] = bool(e["flip"])
+        except (TypeError, ValueError) as err:
+            raise ValueError("tta[%d] = %r: %s" % (n, tta[n], err))
+        out.append(e)
+    return out
+
+
+def ensemble_members(logits_fn, tta):
+    """-> (callables, entries): the members are callables x entries, callable-major; more than MAX_MEMBERS is a ValueError"""
+    fns = list(logits_fn) if isinstance(logits_fn, (list, tuple)) else [logits_fn]
+    if not fns:
+        raise ValueError("logits_fn: an empty list has no member")
+    entries = tta_entries(tta)
+    if len(fns) * len(entries) > MAX_MEMBERS:
+        raise ValueError("%d callables x %d tta entries = %d members, at most %d" % (len(fns), len(entries), len(fns) * len(entries), MAX_MEMBERS))
+    return fns, entries
+
+
 def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
-                   out_size=(256, 256), num_cls=5, device="cuda"):
+                   out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False):
     """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
-      logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits)
+      logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
+                 checkpoint ensemble
+      tta        None, "default" (DEFAULT_TTA) or a list of dicts of compose_matrix's keywords: the views of every slice
+      prob, entropy   also return the mean class probabilities [num_cls, *image.shape] / the entropy normalised by log(num_cls) (float32)
+    With a list of callables, tta, prob or entropy the result is Ensemble(label, prob, entropy) (a field not asked for is None; outside the
+    crop box all three are 0) and every batch ends in one pnp_paste_ensemble launch; with the defaults it is the label
+    tensor alone, through pnp_paste_labels.
       label      optional ground truth of the same shape: only its bounding box is used (crop = a margin in voxels)
       crop       None, a margin around the label's bounding box, or a box ((x0, x1), (y0, y1), (z0, z1)) in slicing order; outside it: 0
       edge       "replicate": the normalised volume is padded with a copy of its first and last frame, every frame is predicted;
@@ -82,6 +153,9 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     B, H, W = int(batch_size), int(out_size[0]), int(out_size[1])
     if B < 1:
         raise ValueError("batch_size must be at least 1")
+    ensemble = isinstance(logits_fn, (list, tuple)) or tta is not None or bool(prob) or bool(entropy)
+    if ensemble:
+        fns, entries = ensemble_members(logits_fn, tta)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.PnpError("segment_volume: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (device,))
@@ -103,6 +177,29 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         first, count, shift = 1, Z - 2, 0
     vs = VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=device)], ["volume"], [fill], percentile)
     src = AugmentedSliceSource(vs, B, out_size=(H, W), augment=None, num_cls=num_cls)
+    if ensemble:
+        maps = [compose_matrix((X, Y), (H, W), **e) for e in entries]
+        invs = [invert_matrix(m) for m in maps] * len(fns)                  # callable-major, like the members
+        out_p = torch.zeros((int(num_cls),) + tuple(image.shape), dtype=torch.float32, device=device) if prob else None
+        out_e = torch.zeros(tuple(image.shape), dtype=torch.float32, device=device) if entropy else None
+        rec = np.zeros(B, dtype=SAMPLE_DTYPE)
+        for k in range(0, count, B):
+            nb = min(B, count - k)
+            rec["frame"] = np.minimum(first + k + np.arange(B), first + k + nb - 1)
+            xs = []
+            for m in maps:                                                  # one gather per distinct map, shared by the callables
+                rec["m"][:] = m
+                xs.append(src.gather_records(rec, num_cls, want_onehot=False)[0])
+            members = []
+            for fn in fns:
+                for x in xs:
+                    logits = fn(x)
+                    if tuple(logits.shape) != (B, H, W, int(num_cls)):
+                        raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
+                    members.append(logits.detach().contiguous())
+            K.paste_ensemble(members, nb, first + k + shift, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e)
+        src.close()
+        return Ensemble(out, out_p, out_e)
     m = compose_matrix((X, Y), (H, W))
     inv = invert_matrix(m)
     rec = np.zeros(B, dtype=SAMPLE_DTYPE)
@@ -142,7 +239,8 @@ def adapted_logits(net):
 def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5, device="cuda", **options):
     """every image of nii_list -> <output_path>/pred_<basename>: uint8 NIfTI on the input's grid with the input's affine.  With
     label_list (same order) also the dense_pred_<name>.nii.gz / gth_dense_pred_<name>.nii.gz pair that `evaluate --pred-dir` reads (the
-    ground truth with labels >= num_cls set to 0).  options: segment_volume's.  Returns the pred_* paths."""
+    ground truth with labels >= num_cls set to 0).  options: segment_volume's; with prob= / entropy= also prob_<basename> (float32,
+    [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine.  Returns the pred_* paths."""
     from . import nifti
     nii_list = list(nii_list)
     if label_list is not None and len(label_list) != len(nii_list):
@@ -152,9 +250,16 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
     for n, fid in enumerate(nii_list):
         img = nifti.load(fid)
         gt = None if label_list is None else np.asarray(nifti.load(label_list[n]).get_data())
-        pred = segment_volume(logits_fn, img.get_data(), label=gt, num_cls=num_cls, device=device, **options).cpu().numpy()
+        res = segment_volume(logits_fn, img.get_data(), label=gt, num_cls=num_cls, device=device, **options)
         base = os.path.basename(str(fid))
+        soft = res if isinstance(res, Ensemble) else Ensemble(res, None, None)
+        pred = soft.label.cpu().numpy()
         paths.append(nifti.save(nifti.Nifti1Image(pred, img.affine), os.path.join(output_path, "pred_" + base)))
+        if soft.prob is not None:            # class-major planes on the device -> the class axis last in the file
+            p = np.ascontiguousarray(np.moveaxis(soft.prob.cpu().numpy(), 0, -1), dtype=np.float32)
+            nifti.save(nifti.Nifti1Image(p, img.affine), os.path.join(output_path, "prob_" + base))
+        if soft.entropy is not None:
+            nifti.save(nifti.Nifti1Image(soft.entropy.cpu().numpy().astype(np.float32, copy=False), img.affine), os.path.join(output_path, "entropy_" + base))
         if gt is not None:
             dense = "dense_pred_" + base.split(".")[0] + ".nii.gz"
             nifti.save(nifti.Nifti1Image(pred, img.affine), os.path.join(output_path, dense))
