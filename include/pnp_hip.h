@@ -564,6 +564,33 @@ int pnp_paste_ensemble(int32_t M, const float* const* logits, const float* inv, 
                        int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
                        float* prob /*nullable*/, float* entropy /*nullable*/, void* stream);
 
+/* ---- connected components of label volumes (csrc/components.hip): keep the largest 3-D component of every structure -------
+ *
+ * vol: uint8 labels [D0, D1, D2], C order (D2 fastest: what pnp_paste_labels writes and a NIfTI reader returns), each extent in [1, 4096],
+ * n = D0 * D1 * D2 < 2^31; 2 <= ncls <= 8; a label >= ncls counts as background (0).  A component is a maximal set of voxels of ONE non-zero
+ * label joined by steps of the 6 / 18 / 26 neighbourhood (connectivity 1 / 2 / 3: scipy's generate_binary_structure(3, connectivity)); all
+ * classes in one pass, voxels of different classes are never joined.
+ * pnp_label_components: roots [n] int32 = -1 for background, otherwise the smallest flat index among the voxels of the voxel's component.
+ *   Union-find, three launches whatever the data, no host read in between; bit-identical from run to run.
+ * pnp_filter_components: out [n] uint8 (may be vol itself) from vol and the roots of the SAME vol, ncls and connectivity.  A component of a
+ *   class c in [1, ncls) whose bit is set in class_mask survives when its size is >= min_size and, if keep > 0, it is among the `keep`
+ *   largest of its class, ties going to the lower root (the key (size << 32) | ~root, largest first); its voxels keep their label, those of
+ *   a removed component become 0.  Classes outside the mask pass through unchanged; labels >= ncls become 0.
+ *   stats [ncls, 4] int64 = components found, voxels before, voxels kept, size of the largest component; row 0 is all zero; classes outside
+ *   the mask report kept = before.  3 + max(keep, 1) launches.
+ * Workspace: pnp_components_workspace_bytes (0 for unsupported extents), one size for both calls.  Its first two uint32 are device error
+ * counters the caller reads after the call(s): [0], zeroed and written by pnp_label_components only, counts union-find loops that reached
+ * their cap of n steps (they cannot: a non-zero value means the result is not to be used); [1], zeroed and written by
+ * pnp_filter_components, counts waves that met a roots entry >= n (roots that are not pnp_label_components' output).
+ * Refused on the host before any HIP call: null pointers; an extent outside [1, 4096]; n >= 2^31; ncls outside [2, 8]; connectivity outside
+ * {1, 2, 3}; keep outside [0, 8]; min_size < 0; class_mask with bit 0 or a bit >= ncls; a short workspace. */
+size_t pnp_components_workspace_bytes(int64_t D0, int64_t D1, int64_t D2);
+int pnp_label_components(const uint8_t* vol, int64_t D0, int64_t D1, int64_t D2, int32_t ncls, int32_t connectivity, int32_t* roots,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int pnp_filter_components(const uint8_t* vol, const int32_t* roots, int64_t D0, int64_t D1, int64_t D2, int32_t ncls, uint32_t class_mask,
+                          int32_t keep, int64_t min_size, uint8_t* out, int64_t* stats, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1063,3 +1063,41 @@ def paste_ensemble(logits, nb, z0, invs, src_xy, vol, origin, strides, prob=None
                                          ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
                                          int(strides[2]), _p(prob), _p(entropy), _stream()), "pnp_paste_ensemble")
     return vol, prob, entropy
+
+
+# ---- connected components of label volumes (csrc/components.hip, components.py) ------------------------------------------------------------
+def _components_ws(vol):
+    D0, D1, D2 = (int(d) for d in vol.shape)
+    lib = _lib.load()
+    need = lib.pnp_components_workspace_bytes(D0, D1, D2)
+    if need == 0:
+        raise _lib.PnpError("components: unsupported volume %s (each extent in [1, 4096], fewer than 2^31 voxels)" % ((D0, D1, D2),))
+    return lib, (D0, D1, D2), workspace(need, vol.device, slot="components")
+
+
+def components_errors(ws):
+    """the two device error counters at the head of a components workspace (label, filter): one host read"""
+    e = ws[:8].view(torch.int32).cpu()
+    return int(e[0]), int(e[1])
+
+
+def label_components(vol, ncls, connectivity=1):
+    """pnp_label_components of a contiguous uint8 [D0, D1, D2] CUDA tensor -> (roots int32 [D0, D1, D2], the workspace: its head holds the
+    error counters, components_errors).  Stream-ordered."""
+    lib, (D0, D1, D2), ws = _components_ws(vol)
+    roots = torch.empty(tuple(vol.shape), dtype=torch.int32, device=vol.device)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(lib.pnp_label_components(vp(vol), D0, D1, D2, int(ncls), int(connectivity), vp(roots), vp(ws), ws.numel(), _stream()),
+          "pnp_label_components")
+    return roots, ws
+
+
+def filter_components(vol, roots, ncls, class_mask, keep, min_size, out):
+    """pnp_filter_components: vol / roots as label_components takes / returns them, out a uint8 tensor of vol's shape (vol itself filters
+    in place) -> (out, stats int64 [ncls, 4], the workspace).  Stream-ordered."""
+    lib, (D0, D1, D2), ws = _components_ws(vol)
+    stats = torch.empty((int(ncls), 4), dtype=torch.int64, device=vol.device)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(lib.pnp_filter_components(vp(vol), vp(roots), D0, D1, D2, int(ncls), int(class_mask), int(keep), int(min_size), vp(out), vp(stats),
+                                    vp(ws), ws.numel(), _stream()), "pnp_filter_components")
+    return out, stats, ws

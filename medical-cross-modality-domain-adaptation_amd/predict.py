@@ -5,6 +5,7 @@
            [--crop x0:x1,y0:y1,z0:z1 | --crop-margin N] [--axis 2] [--no-flip-correction] [--batch-size 16]
            [--score [--spacing unit|header] [--json F]]
            [--tta default|JSON] [--prob] [--entropy] [--ensemble CKPT [CKPT ...]]
+           [--keep-largest [K]] [--min-size N] [--connectivity 1|2|3]
 
 --list holds one `image.nii[.gz]` or `image.nii[.gz] label.nii[.gz]` per line (all lines alike; paths relative to the list's folder unless
 absolute).  The net is built as train_segmenter / train_gan build theirs, with their default configuration: `segmenter` is the source
@@ -14,6 +15,10 @@ pair and for --score, which runs evaluate.evaluate on that pair; they never reac
 Ensemble inference: --tta averages several views of every slice (`default`, or a JSON list of objects with the keys
 rotate, scale, translate, flip), --ensemble adds further checkpoints of the same --net (each built and restored as --model is); members =
 checkpoints x views, at most 8.  --prob / --entropy also write prob_<basename> (float32, [*shape, classes]) and entropy_<basename> (float32).
+
+Connected components: --keep-largest [K] keeps the K largest 3-D components of every class (a bare flag: 1), --min-size N
+drops components of fewer than N voxels, --connectivity picks 6, 18 or 26 neighbours; the label volumes written (and scored) are the
+filtered ones, and one line per volume reports per class the components found, the voxels before and after and the largest component.
 """
 import argparse
 import json
@@ -90,6 +95,8 @@ def parse_args(argv=None):
     ap.add_argument("--prob", action="store_true", help="also write prob_<basename>: float32 class probabilities, [*shape, classes]")
     ap.add_argument("--entropy", action="store_true", help="also write entropy_<basename>: float32 entropy normalised by log(classes)")
     ap.add_argument("--ensemble", nargs="+", default=None, metavar="CKPT", help="further checkpoints of the same --net, averaged with --model")
+    from . import components
+    components.add_cli_arguments(ap)
     a = ap.parse_args(argv)
     if (a.images is None) == (a.list is None):
         ap.error("give either --images or --list")
@@ -137,6 +144,9 @@ def parse_args(argv=None):
         options["prob"] = True
     if a.entropy:
         options["entropy"] = True
+    post = components.cli_option(ap, a)
+    if post is not None:
+        options["keep_largest"] = post
     return a, images, labels, options
 
 
@@ -156,14 +166,21 @@ def build_trainer(kind, model, batch_size, device="cuda", num_cls=5):
 
 
 def main(argv=None):
-    """-> {"paths": [pred_* files], "score": evaluate.evaluate's result or None}"""
+    """-> {"paths": [pred_* files], "score": evaluate.evaluate's result or None}; with the component filter also "component_stats": one
+    [num_cls][4] list per volume"""
     a, images, labels, options = parse_args(argv)
     trainer = build_trainer(a.net, a.model, a.batch_size, a.device)
     if a.ensemble:
         options["ensemble"] = [build_trainer(a.net, ck, a.batch_size, a.device).net for ck in a.ensemble]
+    stats = [] if "keep_largest" in options else None
+    if stats is not None:
+        options["component_stats"] = stats
     paths = trainer.predict_volumes(images, a.out, label_list=labels, **options)
-    for p in paths:
+    for n, p in enumerate(paths):
         print("wrote %s" % p)
+        if stats is not None:
+            from . import components
+            print("  components  %s" % components.stats_line(stats[n]))
     score = None
     if a.score:
         from . import evaluate as ev
@@ -175,7 +192,10 @@ def main(argv=None):
         if a.json:
             with open(a.json, "w") as f:
                 json.dump(score, f, indent=1)
-    return {"paths": paths, "score": score}
+    res = {"paths": paths, "score": score}
+    if stats is not None:
+        res["component_stats"] = [t.cpu().tolist() for t in stats]
+    return res
 
 
 if __name__ == "__main__":

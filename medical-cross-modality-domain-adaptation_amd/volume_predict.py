@@ -16,6 +16,9 @@ Ensemble inference (opt-in): with a list of callables (checkpoin
 segment_volume gathers once per distinct map, runs one forward per member and makes ONE pnp_paste_ensemble launch per batch, which
 interpolates every member's logits through that member's own inverse map, averages the softmax and writes the label, the mean
 probabilities and the normalised entropy in the file's array order.  With the defaults nothing of this is reached.
+
+Connected-component filtering (opt-in): keep_largest= runs components.keep_largest on the finished label volume, on the
+device, before it is returned.
 """
 import collections
 import os
@@ -131,7 +134,7 @@ def ensemble_members(logits_fn, tta):
 
 
 def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
-                   out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False):
+                   out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None):
     """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
       logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
                  checkpoint ensemble
@@ -142,6 +145,10 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     tensor alone, through pnp_paste_labels.
       label      optional ground truth of the same shape: only its bounding box is used (crop = a margin in voxels)
       crop       None, a margin around the label's bounding box, or a box ((x0, x1), (y0, y1), (z0, z1)) in slicing order; outside it: 0
+      keep_largest   None, an int K (keep the K largest 3-D components of every class) or a dict of components.keep_largest's keywords
+                 (keep, min_size, connectivity, classes): applied in place to the finished label volume on the device.  On
+                 the ensemble path only Ensemble.label is filtered: prob and entropy are returned as computed, also where the label became 0.
+      component_stats   optional list: the filter's int64 [num_cls, 4] stats tensor is appended to it
       edge       "replicate": the normalised volume is padded with a copy of its first and last frame, every frame is predicted;
                  "skip": frames 1 .. Z - 2 only (the reference's frame set), the two edge frames stay 0
     Frames run in ascending order, batch_size at a time; the last, short batch repeats its last frame and pastes nb < B slices.  Nothing
@@ -150,6 +157,8 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     from . import kernels as K
     if edge not in EDGES:
         raise ValueError("edge must be one of %s, got %r" % (EDGES, edge))
+    from . import components
+    post = components.parse_option(keep_largest, num_cls)
     B, H, W = int(batch_size), int(out_size[0]), int(out_size[1])
     if B < 1:
         raise ValueError("batch_size must be at least 1")
@@ -199,6 +208,7 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
                     members.append(logits.detach().contiguous())
             K.paste_ensemble(members, nb, first + k + shift, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e)
         src.close()
+        _filter_components(out, post, num_cls, component_stats)
         return Ensemble(out, out_p, out_e)
     m = compose_matrix((X, Y), (H, W))
     inv = invert_matrix(m)
@@ -213,7 +223,18 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
             raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
         K.paste_labels(logits.detach().contiguous(), nb, first + k + shift, inv, (X, Y), out, origin, strides)
     src.close()
+    _filter_components(out, post, num_cls, component_stats)
     return out
+
+
+def _filter_components(label, post, num_cls, component_stats):
+    """components.keep_largest on the finished label volume, in place; post: components.parse_option's keywords or None (nothing runs)"""
+    if post is None:
+        return
+    from . import components
+    _, stats = components.keep_largest(label, num_cls=num_cls, out=label, **post)
+    if component_stats is not None:
+        component_stats.append(stats)
 
 
 def segmenter_logits(net):
@@ -240,7 +261,8 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
     """every image of nii_list -> <output_path>/pred_<basename>: uint8 NIfTI on the input's grid with the input's affine.  With
     label_list (same order) also the dense_pred_<name>.nii.gz / gth_dense_pred_<name>.nii.gz pair that `evaluate --pred-dir` reads (the
     ground truth with labels >= num_cls set to 0).  options: segment_volume's; with prob= / entropy= also prob_<basename> (float32,
-    [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine.  Returns the pred_* paths."""
+    [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine; with keep_largest= every label volume written
+    is the filtered one (component_stats=[]: one stats tensor per volume is appended).  Returns the pred_* paths."""
     from . import nifti
     nii_list = list(nii_list)
     if label_list is not None and len(label_list) != len(nii_list):
