@@ -528,6 +528,30 @@ int pnp_aug_slices(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_d
                    int32_t B, int32_t H, int32_t W, float* x, float* label, float* onehot /*nullable*/, int32_t ncls,
                    uint32_t* errors, void* stream);
 
+/* ---- sampling on a millimetre grid (csrc/augment.hip): the outer channels at a fractional frame distance ---------------------
+ *
+ * one output slice of pnp_aug_slices_z: volume index, centre frame in [0, Z - 1], the frame step dz >= 0 (frames per channel: the wanted
+ * millimetres between channels over the volume's frame spacing) and pnp_aug_sample's map */
+typedef struct pnp_aug_sample_z {
+    int32_t volume, frame;
+    float dz;
+    float m[6];
+} pnp_aug_sample_z;
+/* pnp_aug_slices with these differences (everything else, the lane layout and the 16-byte alignment included, is pnp_aug_slices'):
+ *   volumes need Z >= 1 (checked on the host); `frame` may be any of 0 .. Z - 1;
+ *   channel 1 is frame `frame`; channels 0 / 2 read at zf = fminf(fmaxf((float)frame -+ dz, 0), Z - 1) (the clamp replicates the first and
+ *   the last frame): with z0 = floorf(zf), z1 = min(z0 + 1, Z - 1), t = zf - z0 an in-slice corner contributes
+ *   fmaf(t, v[z1] - v[z0], v[z0]) — the lerp along z comes FIRST — and an out-of-slice corner `fill`; then pnp_aug_slices' bilinear chain
+ *   (this order is part of the contract);
+ *   label and one-hot: at (floor(sx + 0.5), floor(sy + 0.5), frame), unchanged.
+ * With dz == 1 and frame in [1, Z - 2] image, label and one-hot equal pnp_aug_slices' bit for bit (t = 0 returns v[z0]); with dz == 1 at
+ * frame 0 or Z - 1 the missing neighbour is the edge frame itself.  A sample whose volume index or frame is out of range, or whose dz is
+ * NaN, infinite or negative, is written as fill / 0 and counted once in *errors; dz is compared before it enters any arithmetic and no
+ * unchecked float is converted to an integer. */
+int pnp_aug_slices_z(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_dev, int32_t nvol, const pnp_aug_sample_z* samples_dev,
+                     int32_t B, int32_t H, int32_t W, float* x, float* label, float* onehot /*nullable*/, int32_t ncls,
+                     uint32_t* errors, void* stream);
+
 /* ---- volume inference, the way back (csrc/paste.hip): labels of a batch of logits written onto the scan's own grid --------
  *
  * logits [B, H, W, ncls] float32 (device, finite: anything else is the caller's error), 1 <= ncls <= 8; slice b < nb <= B is frame z0 + b.
@@ -563,6 +587,20 @@ int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32
 int pnp_paste_ensemble(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
                        int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
                        float* prob /*nullable*/, float* entropy /*nullable*/, void* stream);
+
+/* ---- paste inside the field of view only (csrc/paste.hip) -----------------------------------------------------------------------
+ *
+ * The arguments, the checks and the arithmetic of pnp_paste_labels / pnp_paste_ensemble.  A voxel column (x, y) is COVERED iff for every
+ * member m (one for pnp_paste_labels_fov) the unclamped plane coordinates — the same two fmaf chains, before the clamp — satisfy
+ *   -0.5 <= pi <= H - 0.5  and  -0.5 <= pj <= W - 0.5        (a NaN coordinate is not covered).
+ * For a covered column the entry writes exactly the bytes / floats the entry without _fov writes, bit for bit; for an uncovered column
+ * nothing of vol, prob or entropy is touched.  Coverage does not depend on the frame: still one writer per element, no atomics. */
+int pnp_paste_labels_fov(const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, const float* inv,
+                         int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                         void* stream);
+int pnp_paste_ensemble_fov(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
+                           int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
+                           int64_t sz, float* prob /*nullable*/, float* entropy /*nullable*/, void* stream);
 
 /* ---- connected components of label volumes (csrc/components.hip): keep the largest 3-D component of every structure -------
  *

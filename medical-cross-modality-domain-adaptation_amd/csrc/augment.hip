@@ -14,6 +14,7 @@
 // from run to run.
 #include <algorithm>
 #include <math.h>
+#include <type_traits>
 
 #include "pnp_common.h"
 
@@ -182,7 +183,11 @@ struct Px {
     float lab;
 };
 
-__device__ __forceinline__ Px sample_pixel(const pnp_aug_volume& vol, bool ok, int z, const float* m, int i, int j) {
+// FRAC (pnp_aug_slices_z): channels 0 / 2 sit at the fractional frames zlo / zhi (clamped into [0, Z - 1] by the caller);
+// a corner's value there is the lerp between the two frames around it, taken BEFORE the bilinear chain (z is the fastest axis: the two
+// reads are adjacent).  Without FRAC the three channels are the frames z - 1, z, z + 1 and (zlo, zhi) are not read.
+template <bool FRAC>
+__device__ __forceinline__ Px sample_pixel(const pnp_aug_volume& vol, bool ok, int z, float zlo, float zhi, const float* m, int i, int j) {
     Px r;
     const float fill = vol.fill;
     r.c[0] = r.c[1] = r.c[2] = fill;
@@ -200,14 +205,38 @@ __device__ __forceinline__ Px sample_pixel(const pnp_aug_volume& vol, bool ok, i
     const bool xin0 = x0 >= 0, xin1 = x0 + 1 < X, yin0 = y0 >= 0, yin1 = y0 + 1 < Y;
     const float* img = vol.image;
     const long long rowY = (long long)Y * Z;
-    const long long o00 = (long long)x0 * rowY + (long long)y0 * Z + (z - 1);
     float v00[3], v01[3], v10[3], v11[3];
+    if constexpr (FRAC) {
+        const long long o00 = (long long)x0 * rowY + (long long)y0 * Z;      // frame 0 of corner (x0, y0)
+        const float flo = floorf(zlo), fhi = floorf(zhi);                   // zlo, zhi in [0, Z - 1]: the conversions are safe
+        const float tz[2] = {zlo - flo, zhi - fhi};                         // exact
+        const int za[2] = {(int)flo, (int)fhi};
+        const int zb[2] = {min(za[0] + 1, Z - 1), min(za[1] + 1, Z - 1)};
+        // one corner: in-slice ? lerp along z (outer channels) / the centre frame : fill
+        auto corner = [&](bool in, long long o, float* v) {
+            v[0] = v[1] = v[2] = fill;
+            if (in) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        v00[c] = (xin0 && yin0) ? img[o00 + c] : fill;
-        v01[c] = (xin0 && yin1) ? img[o00 + Z + c] : fill;
-        v10[c] = (xin1 && yin0) ? img[o00 + rowY + c] : fill;
-        v11[c] = (xin1 && yin1) ? img[o00 + rowY + Z + c] : fill;
+                for (int e = 0; e < 2; ++e) {
+                    const float a = img[o + za[e]], b = img[o + zb[e]];
+                    v[2 * e] = fmaf(tz[e], b - a, a);
+                }
+                v[1] = img[o + z];
+            }
+        };
+        corner(xin0 && yin0, o00, v00);
+        corner(xin0 && yin1, o00 + Z, v01);
+        corner(xin1 && yin0, o00 + rowY, v10);
+        corner(xin1 && yin1, o00 + rowY + Z, v11);
+    } else {
+        const long long o00 = (long long)x0 * rowY + (long long)y0 * Z + (z - 1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            v00[c] = (xin0 && yin0) ? img[o00 + c] : fill;
+            v01[c] = (xin0 && yin1) ? img[o00 + Z + c] : fill;
+            v10[c] = (xin1 && yin0) ? img[o00 + rowY + c] : fill;
+            v11[c] = (xin1 && yin1) ? img[o00 + rowY + Z + c] : fill;
+        }
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -221,9 +250,12 @@ __device__ __forceinline__ Px sample_pixel(const pnp_aug_volume& vol, bool ok, i
     return r;
 }
 
+// one kernel, two records: FRAC = false is pnp_aug_slices (pnp_aug_sample, frames z - 1, z, z + 1), FRAC = true pnp_aug_slices_z
+// (pnp_aug_sample_z: any centre frame, the outer channels at frame -+ dz, clamped)
+template <bool FRAC>
 __global__ void __launch_bounds__(kThreads) aug_slices_kernel(const pnp_aug_volume* __restrict__ vols, int nvol,
-                                                              const pnp_aug_sample* __restrict__ samples, int H, int W, long long P,
-                                                              float* __restrict__ x, float* __restrict__ label,
+                                                              const std::conditional_t<FRAC, pnp_aug_sample_z, pnp_aug_sample>* __restrict__ samples,
+                                                              int H, int W, long long P, float* __restrict__ x, float* __restrict__ label,
                                                               float* __restrict__ onehot, int ncls, unsigned int* __restrict__ errors) {
     const long long g = (long long)blockIdx.x * kThreads + threadIdx.x;      // group of 4 consecutive pixels of the flat [B*H*W] index
     const long long p0 = g * 4;
@@ -236,8 +268,9 @@ __global__ void __launch_bounds__(kThreads) aug_slices_kernel(const pnp_aug_volu
     Px px[4];
     int cur = -1;
     pnp_aug_volume vol;
-    pnp_aug_sample s;
+    std::conditional_t<FRAC, pnp_aug_sample_z, pnp_aug_sample> s;
     bool ok = false;
+    float zlo = 0.f, zhi = 0.f;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         if (t < cnt) {
@@ -250,10 +283,20 @@ __global__ void __launch_bounds__(kThreads) aug_slices_kernel(const pnp_aug_volu
                 } else {
                     vol.image = nullptr; vol.label = nullptr; vol.X = vol.Y = vol.Z = 0; vol.fill = 0.f;
                 }
-                ok = vok && s.frame >= 1 && s.frame <= vol.Z - 2;
+                if constexpr (FRAC) {
+                    // dz: finite and >= 0 (NaN fails both comparisons); the clamp replicates the edge frames
+                    ok = vok && s.frame >= 0 && s.frame <= vol.Z - 1 && s.dz >= 0.f && s.dz < INFINITY;
+                    if (ok) {
+                        const float top = (float)(vol.Z - 1);
+                        zlo = fminf(fmaxf((float)s.frame - s.dz, 0.f), top);
+                        zhi = fminf(fmaxf((float)s.frame + s.dz, 0.f), top);
+                    }
+                } else {
+                    ok = vok && s.frame >= 1 && s.frame <= vol.Z - 2;
+                }
                 if (!ok && i == 0 && j == 0) atomicAdd(errors, 1u);       // once per refused sample: by the lane that owns its first pixel
             }
-            px[t] = sample_pixel(vol, ok, s.frame, s.m, i, j);
+            px[t] = sample_pixel<FRAC>(vol, ok, s.frame, zlo, zhi, s.m, i, j);
             if (++j == W) {
                 j = 0;
                 if (++i == H) {
@@ -323,6 +366,37 @@ PreLayout pre_layout() {
 
 bool pre_n_ok(int64_t n) { return n >= 1 && n < ((int64_t)1 << 31); }
 
+// the checks and the launch both gather entry points share; `who` names the caller in the messages.  FRAC needs Z >= 1, the other Z >= 3.
+template <bool FRAC>
+int aug_slices_launch(const char* who, const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_dev, int32_t nvol,
+                      const std::conditional_t<FRAC, pnp_aug_sample_z, pnp_aug_sample>* samples_dev, int32_t B, int32_t H, int32_t W, float* x,
+                      float* label, float* onehot, int32_t ncls, uint32_t* errors, void* stream) {
+    constexpr int kMinZ = FRAC ? 1 : 3;
+    PNP_REQUIRE(B >= 1, "%s: B = %d, at least one sample is needed", who, (int)B);
+    PNP_REQUIRE(H >= 1 && W >= 1, "%s: output size %d x %d must be at least 1 x 1", who, (int)H, (int)W);
+    PNP_REQUIRE(vols_host && vols_dev && samples_dev, "%s: null table", who);
+    PNP_REQUIRE(nvol >= 1, "%s: nvol = %d, at least one volume is needed", who, (int)nvol);
+    PNP_REQUIRE(x && label && errors, "%s: null output pointer", who);
+    PNP_REQUIRE(!onehot || (ncls >= 1 && ncls <= kMaxCls), "%s: ncls %d outside [1, %d]", who, (int)ncls, kMaxCls);
+    PNP_REQUIRE(((uintptr_t)x | (uintptr_t)label | (uintptr_t)onehot) % 16 == 0, "%s: outputs must be 16-byte aligned", who);
+    const long long P = (long long)B * H * W;
+    PNP_REQUIRE(P < ((long long)1 << 31), "%s: B * H * W = %lld is not below 2^31", who, P);
+    for (int i = 0; i < nvol; ++i) {
+        const pnp_aug_volume& v = vols_host[i];
+        PNP_REQUIRE(v.image && v.label, "%s: volume %d: null pointer", who, i);
+        PNP_REQUIRE(v.X >= 1 && v.Y >= 1 && v.X <= kMaxExtentXY && v.Y <= kMaxExtentXY,
+                    "%s: volume %d: extents %d x %d outside [1, %d]", who, i, (int)v.X, (int)v.Y, kMaxExtentXY);
+        PNP_REQUIRE(v.Z >= kMinZ, "%s: volume %d: Z = %d, at least %d frames are needed", who, i, (int)v.Z, kMinZ);
+        PNP_REQUIRE((long long)v.X * v.Y * v.Z < ((long long)1 << 40), "%s: volume %d is too large", who, i);
+    }
+    const long long groups = (P + 3) / 4;
+    const unsigned nb = (unsigned)((groups + kThreads - 1) / kThreads);
+    hipLaunchKernelGGL(aug_slices_kernel<FRAC>, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, vols_dev, (int)nvol, samples_dev, (int)H, (int)W,
+                       P, x, label, onehot, (int)(onehot ? ncls : 0), errors);
+    PNP_CHECK_LAUNCH("aug_slices_kernel");
+    return PNP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -374,29 +448,13 @@ int pnp_volume_preprocess(const float* v, float* out, int64_t n, int32_t percent
 int pnp_aug_slices(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_dev, int32_t nvol, const pnp_aug_sample* samples_dev,
                    int32_t B, int32_t H, int32_t W, float* x, float* label, float* onehot, int32_t ncls, uint32_t* errors,
                    void* stream) {
-    PNP_REQUIRE(B >= 1, "pnp_aug_slices: B = %d, at least one sample is needed", (int)B);
-    PNP_REQUIRE(H >= 1 && W >= 1, "pnp_aug_slices: output size %d x %d must be at least 1 x 1", (int)H, (int)W);
-    PNP_REQUIRE(vols_host && vols_dev && samples_dev, "pnp_aug_slices: null table");
-    PNP_REQUIRE(nvol >= 1, "pnp_aug_slices: nvol = %d, at least one volume is needed", (int)nvol);
-    PNP_REQUIRE(x && label && errors, "pnp_aug_slices: null output pointer");
-    PNP_REQUIRE(!onehot || (ncls >= 1 && ncls <= kMaxCls), "pnp_aug_slices: ncls %d outside [1, %d]", (int)ncls, kMaxCls);
-    PNP_REQUIRE(((uintptr_t)x | (uintptr_t)label | (uintptr_t)onehot) % 16 == 0, "pnp_aug_slices: outputs must be 16-byte aligned");
-    const long long P = (long long)B * H * W;
-    PNP_REQUIRE(P < ((long long)1 << 31), "pnp_aug_slices: B * H * W = %lld is not below 2^31", P);
-    for (int i = 0; i < nvol; ++i) {
-        const pnp_aug_volume& v = vols_host[i];
-        PNP_REQUIRE(v.image && v.label, "pnp_aug_slices: volume %d: null pointer", i);
-        PNP_REQUIRE(v.X >= 1 && v.Y >= 1 && v.X <= kMaxExtentXY && v.Y <= kMaxExtentXY,
-                    "pnp_aug_slices: volume %d: extents %d x %d outside [1, %d]", i, (int)v.X, (int)v.Y, kMaxExtentXY);
-        PNP_REQUIRE(v.Z >= 3, "pnp_aug_slices: volume %d: Z = %d, at least 3 frames are needed", i, (int)v.Z);
-        PNP_REQUIRE((long long)v.X * v.Y * v.Z < ((long long)1 << 40), "pnp_aug_slices: volume %d is too large", i);
-    }
-    const long long groups = (P + 3) / 4;
-    const unsigned nb = (unsigned)((groups + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(aug_slices_kernel, dim3(nb), dim3(kThreads), 0, (hipStream_t)stream, vols_dev, (int)nvol, samples_dev, (int)H, (int)W,
-                       P, x, label, onehot, (int)(onehot ? ncls : 0), errors);
-    PNP_CHECK_LAUNCH("aug_slices_kernel");
-    return PNP_OK;
+    return aug_slices_launch<false>("pnp_aug_slices", vols_host, vols_dev, nvol, samples_dev, B, H, W, x, label, onehot, ncls, errors, stream);
+}
+
+int pnp_aug_slices_z(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_dev, int32_t nvol, const pnp_aug_sample_z* samples_dev,
+                     int32_t B, int32_t H, int32_t W, float* x, float* label, float* onehot, int32_t ncls, uint32_t* errors,
+                     void* stream) {
+    return aug_slices_launch<true>("pnp_aug_slices_z", vols_host, vols_dev, nvol, samples_dev, B, H, W, x, label, onehot, ncls, errors, stream);
 }
 
 }  // extern "C"

@@ -62,12 +62,23 @@ __device__ __forceinline__ int label_at(const float* __restrict__ p, const Corne
     return am;
 }
 
+// a column is inside the field of view iff its UNCLAMPED plane coordinates lie in [-0.5, H - 0.5] x [-0.5, W - 0.5] (NaN: outside)
+__device__ __forceinline__ bool in_fov(float pi, float pj, int H, int W) {
+    return pi >= -0.5f && pi <= (float)H - 0.5f && pj >= -0.5f && pj <= (float)W - 0.5f;
+}
+
+// FOV (pnp_paste_labels_fov): a column outside the field of view writes nothing; coverage does not depend on the frame, so
+// the lane returns before the store paths, which are unchanged
+template <bool FOV>
 __global__ void __launch_bounds__(kThreads) paste_labels_kernel(const PasteArgs A) {
     const int g = blockIdx.x * kThreads + threadIdx.x;        // flat column index, y fastest (X * Y <= 2^24)
     if (g >= A.X * A.Y) return;
     const int x = g / A.Y, y = g - x * A.Y;
     float pi = fmaf(A.inv[0], (float)x, fmaf(A.inv[1], (float)y, A.inv[2]));
     float pj = fmaf(A.inv[3], (float)x, fmaf(A.inv[4], (float)y, A.inv[5]));
+    if constexpr (FOV) {
+        if (!in_fov(pi, pj, A.H, A.W)) return;
+    }
     pi = fminf(fmaxf(pi, 0.f), (float)(A.H - 1));             // fmaxf(NaN, 0) = 0: clamped before any integer conversion
     pj = fminf(fmaxf(pj, 0.f), (float)(A.W - 1));
     const float fi = floorf(pi), fj = floorf(pj);
@@ -203,12 +214,22 @@ __device__ __forceinline__ void store_soft(const EnsembleArgs& A, long long e, c
     }
 }
 
-template <int NCLS>
+// FOV (pnp_paste_ensemble_fov): a column that ANY member's map takes outside its plane writes nothing (the same two fmaf chains as
+// ensemble_at, before the clamp)
+template <int NCLS, bool FOV>
 __global__ void __launch_bounds__(kThreads) paste_ensemble_kernel(const EnsembleArgs A) {
     const int g = blockIdx.x * kThreads + threadIdx.x;        // flat column index, y fastest, as in paste_labels_kernel
     if (g >= A.X * A.Y) return;
     const int x = g / A.Y, y = g - x * A.Y;
     const float fx = (float)x, fy = (float)y;
+    if constexpr (FOV) {
+        for (int m = 0; m < A.M; ++m) {
+            const float* iv = A.inv + 6 * m;
+            const float pi = fmaf(iv[0], fx, fmaf(iv[1], fy, iv[2]));
+            const float pj = fmaf(iv[3], fx, fmaf(iv[4], fy, iv[5]));
+            if (!in_fov(pi, pj, A.H, A.W)) return;
+        }
+    }
     const int nb = A.nb;
     const bool soft = A.prob || A.entropy;
     const float inv_logn = NCLS > 1 ? 1.f / logf((float)NCLS) : 0.f;
@@ -293,15 +314,13 @@ int check_paste(const char* who, int32_t B, int32_t H, int32_t W, int32_t ncls, 
     return PNP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, const float* inv,
-                     int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
-                     void* stream) {
-    PNP_REQUIRE(logits && inv && vol, "pnp_paste_labels: null pointer");
-    if (const int rc = check_paste("pnp_paste_labels", B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
+// the two label entry points: the same checks, arguments and launch, with and without the field-of-view rule
+template <bool FOV>
+int paste_labels_launch(const char* who, const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0,
+                        const float* inv, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
+                        int64_t sz, void* stream) {
+    PNP_REQUIRE(logits && inv && vol, "%s: null pointer", who);
+    if (const int rc = check_paste(who, B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
     PasteArgs A;
     A.logits = logits;
     A.vol = vol;
@@ -311,20 +330,21 @@ int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32
     for (int i = 0; i < 6; ++i) A.inv[i] = inv[i];
     A.H = H; A.W = W; A.ncls = ncls; A.nb = nb; A.z0 = z0; A.X = X; A.Y = Y;
     const unsigned blocks = (unsigned)(((long long)X * Y + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(paste_labels_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A);
+    hipLaunchKernelGGL(paste_labels_kernel<FOV>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A);
     PNP_CHECK_LAUNCH("paste_labels_kernel");
     return PNP_OK;
 }
 
-int pnp_paste_ensemble(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
-                       int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
-                       float* prob, float* entropy, void* stream) {
-    PNP_REQUIRE(M >= 1 && M <= kMaxMembers, "pnp_paste_ensemble: M = %d members outside [1, %d]", (int)M, kMaxMembers);
-    PNP_REQUIRE(logits && vol, "pnp_paste_ensemble: null pointer");
-    PNP_REQUIRE(inv, "pnp_paste_ensemble: null inv (6 floats per member)");
-    for (int m = 0; m < M; ++m) PNP_REQUIRE(logits[m], "pnp_paste_ensemble: member %d of %d is a null pointer", m, (int)M);
-    if (const int rc = check_paste("pnp_paste_ensemble", B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
-    PNP_REQUIRE((__int128)ncls * vol_elems <= (__int128)INT64_MAX, "pnp_paste_ensemble: ncls * vol_elems = %d * %lld overflows int64", (int)ncls,
+template <bool FOV>
+int paste_ensemble_launch(const char* who, int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls,
+                          int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
+                          int64_t sz, float* prob, float* entropy, void* stream) {
+    PNP_REQUIRE(M >= 1 && M <= kMaxMembers, "%s: M = %d members outside [1, %d]", who, (int)M, kMaxMembers);
+    PNP_REQUIRE(logits && vol, "%s: null pointer", who);
+    PNP_REQUIRE(inv, "%s: null inv (6 floats per member)", who);
+    for (int m = 0; m < M; ++m) PNP_REQUIRE(logits[m], "%s: member %d of %d is a null pointer", who, m, (int)M);
+    if (const int rc = check_paste(who, B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
+    PNP_REQUIRE((__int128)ncls * vol_elems <= (__int128)INT64_MAX, "%s: ncls * vol_elems = %d * %lld overflows int64", who, (int)ncls,
                 (long long)vol_elems);
     EnsembleArgs A;
     for (int m = 0; m < kMaxMembers; ++m) {
@@ -342,13 +362,43 @@ int pnp_paste_ensemble(int32_t M, const float* const* logits, const float* inv, 
     A.M = M; A.H = H; A.W = W; A.ncls = ncls; A.nb = nb; A.z0 = z0; A.X = X; A.Y = Y;
     const unsigned blocks = (unsigned)(((long long)X * Y + kThreads - 1) / kThreads);
     switch (ncls) {
-#define PNP_ENSEMBLE_CASE(n) case n: hipLaunchKernelGGL(paste_ensemble_kernel<n>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
+#define PNP_ENSEMBLE_CASE(n) case n: hipLaunchKernelGGL((paste_ensemble_kernel<n, FOV>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
         PNP_ENSEMBLE_CASE(1) PNP_ENSEMBLE_CASE(2) PNP_ENSEMBLE_CASE(3) PNP_ENSEMBLE_CASE(4)
         PNP_ENSEMBLE_CASE(5) PNP_ENSEMBLE_CASE(6) PNP_ENSEMBLE_CASE(7) PNP_ENSEMBLE_CASE(8)
 #undef PNP_ENSEMBLE_CASE
     }
     PNP_CHECK_LAUNCH("paste_ensemble_kernel");
     return PNP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, const float* inv,
+                     int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                     void* stream) {
+    return paste_labels_launch<false>("pnp_paste_labels", logits, B, H, W, ncls, nb, z0, inv, X, Y, vol, vol_elems, origin, sx, sy, sz, stream);
+}
+
+int pnp_paste_labels_fov(const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, const float* inv,
+                         int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                         void* stream) {
+    return paste_labels_launch<true>("pnp_paste_labels_fov", logits, B, H, W, ncls, nb, z0, inv, X, Y, vol, vol_elems, origin, sx, sy, sz, stream);
+}
+
+int pnp_paste_ensemble(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
+                       int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                       float* prob, float* entropy, void* stream) {
+    return paste_ensemble_launch<false>("pnp_paste_ensemble", M, logits, inv, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy, sz, prob,
+                                        entropy, stream);
+}
+
+int pnp_paste_ensemble_fov(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
+                           int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
+                           float* prob, float* entropy, void* stream) {
+    return paste_ensemble_launch<true>("pnp_paste_ensemble_fov", M, logits, inv, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy, sz,
+                                       prob, entropy, stream);
 }
 
 }  // extern "C"

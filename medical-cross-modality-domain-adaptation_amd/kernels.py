@@ -1000,24 +1000,34 @@ def volume_preprocess(v, percentile=98, out=None):
     return out, stats
 
 
-def aug_slices(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls=0, want_onehot=True):
+def aug_slices(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls=0, want_onehot=True, entry="pnp_aug_slices"):
     """pnp_aug_slices: vols_host (ctypes array of _lib.AugVolume) / vols_dev (its device copy, uint8 tensor), samples_dev (device copy of B
     _lib.AugSample records, uint8 tensor), errors (int32 [1] device counter) -> (x [B,H,W,3], label [B,H,W], one-hot [B,H,W,ncls] or None)"""
     dev = vols_dev.device
     if not (vols_dev.is_cuda and samples_dev.is_cuda and errors.is_cuda):
         raise _lib.PnpError("aug_slices: pnp kernels need CUDA/HIP tensors (got a CPU tensor) — there is no CPU fallback")
+    if samples_dev.numel() * samples_dev.element_size() != int(B) * ctypes.sizeof(_lib.AugSampleZ if entry == "pnp_aug_slices_z" else _lib.AugSample):
+        raise _lib.PnpError("%s: the sample table holds %d bytes, not B = %d records" % (entry, samples_dev.numel() * samples_dev.element_size(), B))
     x = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
     label = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     onehot = torch.empty((B, H, W, int(ncls)), dtype=torch.float32, device=dev) if want_onehot else None
     vp = lambda t: ctypes.c_void_p(t.data_ptr())
-    check(_lib.load().pnp_aug_slices(ctypes.cast(vols_host, ctypes.c_void_p), vp(vols_dev), int(nvol), vp(samples_dev), int(B), int(H), int(W),
-                                     _p(x), _p(label), _p(onehot), int(ncls), vp(errors), _stream()), "pnp_aug_slices")
+    check(getattr(_lib.load(), entry)(ctypes.cast(vols_host, ctypes.c_void_p), vp(vols_dev), int(nvol), vp(samples_dev), int(B), int(H), int(W),
+                                      _p(x), _p(label), _p(onehot), int(ncls), vp(errors), _stream()), entry)
     return x, label, onehot
 
 
+def aug_slices_z(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls=0, want_onehot=True):
+    """pnp_aug_slices_z: aug_slices with samples_dev holding B _lib.AugSampleZ records — any centre frame, the outer
+    channels at frame -+ dz (fractional, clamped at the ends), volumes of one frame or more"""
+    return aug_slices(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls, want_onehot, entry="pnp_aug_slices_z")
+
+
 # ---- volume inference (csrc/paste.hip, volume_predict.py) -------------------------------------------------------------------------------
-def paste_labels(logits, nb, z0, inv, src_xy, vol, origin, strides):
-    """pnp_paste_labels: logits [B, H, W, ncls] -> one label byte per (x < X, y < Y, b < nb) at vol.view(-1)[origin + x sx + y sy + (z0 + b) sz].
+def paste_labels(logits, nb, z0, inv, src_xy, vol, origin, strides, fov=False):
+    """fov=True: pnp_paste_labels_fov — a voxel column whose plane coordinates leave [-0.5, H - 0.5] x [-0.5, W - 0.5] is
+    not written; otherwise
+    pnp_paste_labels: logits [B, H, W, ncls] -> one label byte per (x < X, y < Y, b < nb) at vol.view(-1)[origin + x sx + y sy + (z0 + b) sz].
     inv: the six float32 entries of the map from a source voxel to output-plane coordinates (host); vol: a contiguous uint8 CUDA tensor (the
     whole allocation the offsets are checked against); strides = (sx, sy, sz) in elements, any sign.  Stream-ordered, returns vol."""
     if logits.dim() != 4:
@@ -1026,14 +1036,17 @@ def paste_labels(logits, nb, z0, inv, src_xy, vol, origin, strides):
         raise _lib.PnpError("paste_labels: vol must be a contiguous uint8 CUDA tensor (got %s %s) — there is no CPU fallback" % (vol.device, vol.dtype))
     B, H, W, ncls = (int(d) for d in logits.shape)
     m = (ctypes.c_float * 6)(*[float(v) for v in inv])
-    check(_lib.load().pnp_paste_labels(_p(logits), B, H, W, ncls, int(nb), int(z0), m, int(src_xy[0]), int(src_xy[1]),
-                                       ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
-                                       int(strides[2]), _stream()), "pnp_paste_labels")
+    entry = "pnp_paste_labels_fov" if fov else "pnp_paste_labels"
+    check(getattr(_lib.load(), entry)(_p(logits), B, H, W, ncls, int(nb), int(z0), m, int(src_xy[0]), int(src_xy[1]),
+                                      ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
+                                      int(strides[2]), _stream()), entry)
     return vol
 
 
-def paste_ensemble(logits, nb, z0, invs, src_xy, vol, origin, strides, prob=None, entropy=None):
-    """pnp_paste_ensemble: M = len(logits) members, each [B, H, W, ncls] float32 (a tensor may repeat), invs: one six-entry map per member
+def paste_ensemble(logits, nb, z0, invs, src_xy, vol, origin, strides, prob=None, entropy=None, fov=False):
+    """fov=True: pnp_paste_ensemble_fov — a voxel column that any member's map takes outside its plane is written in none
+    of vol, prob, entropy; otherwise
+    pnp_paste_ensemble: M = len(logits) members, each [B, H, W, ncls] float32 (a tensor may repeat), invs: one six-entry map per member
     (host) -> per (x < X, y < Y, b < nb) at e = origin + x sx + y sy + (z0 + b) sz: vol.view(-1)[e] = the first strict maximum of the
     members' summed softmax of the interpolated logits, prob.view(ncls, -1)[c, e] = the mean probability (prob: contiguous float32,
     ncls * vol.numel() elements, or None), entropy.view(-1)[e] = the entropy normalised by log(ncls) (contiguous float32 of vol.numel()
@@ -1059,9 +1072,10 @@ def paste_ensemble(logits, nb, z0, invs, src_xy, vol, origin, strides, prob=None
     m = (ctypes.c_float * (6 * M))(*[float(v) for inv in invs for v in inv])
     if len(m) != 6 * M:
         raise _lib.PnpError("paste_ensemble: every map has six entries")
-    check(_lib.load().pnp_paste_ensemble(M, ptrs, m, B, H, W, ncls, int(nb), int(z0), int(src_xy[0]), int(src_xy[1]),
-                                         ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
-                                         int(strides[2]), _p(prob), _p(entropy), _stream()), "pnp_paste_ensemble")
+    entry = "pnp_paste_ensemble_fov" if fov else "pnp_paste_ensemble"
+    check(getattr(_lib.load(), entry)(M, ptrs, m, B, H, W, ncls, int(nb), int(z0), int(src_xy[0]), int(src_xy[1]),
+                                      ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
+                                      int(strides[2]), _p(prob), _p(entropy), _stream()), entry)
     return vol, prob, entropy
 
 

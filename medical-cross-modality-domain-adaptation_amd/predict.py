@@ -6,6 +6,7 @@
            [--score [--spacing unit|header] [--json F]]
            [--tta default|JSON] [--prob] [--entropy] [--ensemble CKPT [CKPT ...]]
            [--keep-largest [K]] [--min-size N] [--connectivity 1|2|3]
+           [--sample-mm MM|PI,PJ,FRAME]
 
 --list holds one `image.nii[.gz]` or `image.nii[.gz] label.nii[.gz]` per line (all lines alike; paths relative to the list's folder unless
 absolute).  The net is built as train_segmenter / train_gan build theirs, with their default configuration: `segmenter` is the source
@@ -19,6 +20,10 @@ checkpoints x views, at most 8.  --prob / --entropy also write prob_<basename> (
 Connected components: --keep-largest [K] keeps the K largest 3-D components of every class (a bare flag: 1), --min-size N
 drops components of fewer than N voxels, --connectivity picks 6, 18 or 26 neighbours; the label volumes written (and scored) are the
 filtered ones, and one line per volume reports per class the components found, the voxels before and after and the largest component.
+
+Millimetre grid: --sample-mm shows the network every scan at one pixel size and one distance between its three frames,
+taken from the voxel size in each file's header (--spacing is something else: the units of --score).  The plane is centred on the
+(cropped) volume; voxels outside its field of view stay 0, and the share covered is reported per file.
 """
 import argparse
 import json
@@ -97,7 +102,10 @@ def parse_args(argv=None):
     ap.add_argument("--ensemble", nargs="+", default=None, metavar="CKPT", help="further checkpoints of the same --net, averaged with --model")
     from . import components
     components.add_cli_arguments(ap)
+    from .volume_source import add_sample_mm_flag, sample_mm_from_args
+    add_sample_mm_flag(ap)
     a = ap.parse_args(argv)
+    sample_mm = sample_mm_from_args(ap, a)
     if (a.images is None) == (a.list is None):
         ap.error("give either --images or --list")
     try:
@@ -140,6 +148,8 @@ def parse_args(argv=None):
     if members > MAX_MEMBERS:
         ap.error("--ensemble / --tta: %d checkpoints x %d views = %d members, at most %d" % (1 + len(a.ensemble or []), len(options.get("tta", [None])),
                                                                                            members, MAX_MEMBERS))
+    if sample_mm is not None:
+        options["sample_mm"] = sample_mm
     if a.prob:
         options["prob"] = True
     if a.entropy:

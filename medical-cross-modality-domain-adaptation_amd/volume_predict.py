@@ -19,14 +19,20 @@ probabilities and the normalised entropy in the file's array order.  With the de
 
 Connected-component filtering (opt-in): keep_largest= runs components.keep_largest on the finished label volume, on the
 device, before it is returned.
+
+Millimetre grid (opt-in): with sample_mm= the plane has a fixed pixel size and is centred on the (cropped) volume, the
+outer channels lie frame_mm from the centre frame (pnp_aug_slices_z; its clamp is the edge replication, so nothing is padded) and the
+paste writes only the voxel columns inside the plane's field of view (pnp_paste_labels_fov / pnp_paste_ensemble_fov); the rest stays 0.
 """
 import collections
+import logging
 import os
 
 import numpy as np
 
 from . import _lib
-from .volume_source import SAMPLE_DTYPE, AugmentedSliceSource, VolumeSet, compose_matrix, label_bounding_box, prepare_pair
+from .volume_source import (SAMPLE_DTYPE, SAMPLE_Z_DTYPE, AugmentedSliceSource, VolumeSet, check_sample_mm, check_spacing, compose_matrix,
+                            label_bounding_box, prepare_pair, slicing_order)
 
 EDGES = ("replicate", "skip")
 MAX_MEMBERS = 8                          # pnp_paste_ensemble's
@@ -46,6 +52,20 @@ def invert_matrix(m, dtype=np.float32):
     b00, b01, b10, b11 = a11 / det, -a01 / det, -a10 / det, a00 / det
     out = np.array([b00, b01, -(b00 * t0 + b01 * t1), b10, b11, -(b10 * t0 + b11 * t1)], dtype=np.float64) + 0.0      # (-0.0 -> 0.0)
     return out.astype(dtype)
+
+
+def coverage(inv, X, Y, H, W):
+    """the share of the X * Y voxel columns that lie inside the field of view of EVERY given map (inv: six entries, or a list of such):
+    pnp_paste_*_fov's rule — unclamped plane coordinates in [-0.5, H - 0.5] x [-0.5, W - 0.5] — evaluated in float64 on the host from
+    the float32 entries the kernel gets"""
+    maps = np.asarray(inv, dtype=np.float32).astype(np.float64).reshape(-1, 6)
+    x = np.arange(int(X), dtype=np.float64)[:, None]
+    y = np.arange(int(Y), dtype=np.float64)[None, :]
+    ok = np.ones((int(X), int(Y)), dtype=bool)
+    for m in maps:
+        pi, pj = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+        ok &= (pi >= -0.5) & (pi <= H - 0.5) & (pj >= -0.5) & (pj <= W - 0.5)
+    return float(ok.mean())
 
 
 def file_layout(shape, flip_correction=True, axis=2, box=None):
@@ -134,7 +154,8 @@ def ensemble_members(logits_fn, tta):
 
 
 def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
-                   out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None):
+                   out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None,
+                   spacing=None, sample_mm=None, fov_stats=None):
     """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
       logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
                  checkpoint ensemble
@@ -149,6 +170,11 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
                  (keep, min_size, connectivity, classes): applied in place to the finished label volume on the device.  On
                  the ensemble path only Ensemble.label is filtered: prob and entropy are returned as computed, also where the label became 0.
       component_stats   optional list: the filter's int64 [num_cls, 4] stats tensor is appended to it
+      sample_mm  None, or a number / (pi_mm, pj_mm, frame_mm): sample on that millimetre grid.  Needs `spacing`, the voxel
+                 size in mm per ARRAY axis of `image` (surface.spacing_of(affine)).  The plane is centred on the crop box; a voxel column
+                 outside its field of view (for any member) stays 0 in label, prob and entropy, like outside the crop box; tta
+                 entries' translate is in mm; the edge frames are replicated by the gather's clamp, nothing is padded
+      fov_stats  optional list: with sample_mm the share of the box's voxel columns inside the field of view is appended (coverage)
       edge       "replicate": the normalised volume is padded with a copy of its first and last frame, every frame is predicted;
                  "skip": frames 1 .. Z - 2 only (the reference's frame set), the two edge frames stay 0
     Frames run in ascending order, batch_size at a time; the last, short batch repeats its last frame and pastes nb < B slices.  Nothing
@@ -162,6 +188,14 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     B, H, W = int(batch_size), int(out_size[0]), int(out_size[1])
     if B < 1:
         raise ValueError("batch_size must be at least 1")
+    mm = check_sample_mm(sample_mm)
+    if mm is not None:
+        if spacing is None:
+            raise ValueError("sample_mm needs spacing: the voxel size in mm per array axis of the image (surface.spacing_of(affine))")
+        vox = slicing_order(spacing, axis, "spacing")          # as prepare_pair moves `axis` last
+        geom = {"spacing_xy": vox[:2], "pixel_mm": mm[:2]}
+    else:
+        geom = {}
     ensemble = isinstance(logits_fn, (list, tuple)) or tta is not None or bool(prob) or bool(entropy)
     if ensemble:
         fns, entries = ensemble_members(logits_fn, tta)
@@ -179,19 +213,27 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     v = torch.from_numpy(np.ascontiguousarray(img[tuple(slice(a, b) for a, b in box)])).to(device)
     _, stats = K.volume_preprocess(v, int(percentile), out=v)
     fill = float(stats[3].item())                       # the one read before the loop: the fill enters the gather's descriptor table
-    if edge == "replicate":
+    if mm is not None:
+        first, count, shift = (0, Z, 0) if edge == "replicate" else (1, Z - 2, 0)       # pnp_aug_slices_z clamps: its own replication
+    elif edge == "replicate":
         v = torch.cat([v[:, :, :1], v, v[:, :, -1:]], dim=2).contiguous()          # statistics: of the unpadded volume, above
         first, count, shift = 1, Z, -1                  # centre frames 1 .. Z of the padded volume are output frames 0 .. Z - 1
     else:
         first, count, shift = 1, Z - 2, 0
-    vs = VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=device)], ["volume"], [fill], percentile)
-    src = AugmentedSliceSource(vs, B, out_size=(H, W), augment=None, num_cls=num_cls)
+    vs = VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=device)], ["volume"], [fill], percentile,
+                               min_frames=3 if mm is None else 1)
+    src = AugmentedSliceSource(vs, B, out_size=(H, W), augment=None, num_cls=num_cls, sample_mm=mm)
+    rec = np.zeros(B, dtype=SAMPLE_DTYPE if mm is None else SAMPLE_Z_DTYPE)
+    if mm is not None:
+        rec["dz"] = np.float32(mm[2] / vox[2])
+    fov = mm is not None
     if ensemble:
-        maps = [compose_matrix((X, Y), (H, W), **e) for e in entries]
+        maps = [compose_matrix((X, Y), (H, W), **e, **geom) for e in entries]
         invs = [invert_matrix(m) for m in maps] * len(fns)                  # callable-major, like the members
+        if fov and fov_stats is not None:
+            fov_stats.append(coverage(invs, X, Y, H, W))
         out_p = torch.zeros((int(num_cls),) + tuple(image.shape), dtype=torch.float32, device=device) if prob else None
         out_e = torch.zeros(tuple(image.shape), dtype=torch.float32, device=device) if entropy else None
-        rec = np.zeros(B, dtype=SAMPLE_DTYPE)
         for k in range(0, count, B):
             nb = min(B, count - k)
             rec["frame"] = np.minimum(first + k + np.arange(B), first + k + nb - 1)
@@ -206,13 +248,14 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
                     if tuple(logits.shape) != (B, H, W, int(num_cls)):
                         raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
                     members.append(logits.detach().contiguous())
-            K.paste_ensemble(members, nb, first + k + shift, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e)
+            K.paste_ensemble(members, nb, first + k + shift, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e, fov=fov)
         src.close()
         _filter_components(out, post, num_cls, component_stats)
         return Ensemble(out, out_p, out_e)
-    m = compose_matrix((X, Y), (H, W))
+    m = compose_matrix((X, Y), (H, W), **geom)
     inv = invert_matrix(m)
-    rec = np.zeros(B, dtype=SAMPLE_DTYPE)
+    if fov and fov_stats is not None:
+        fov_stats.append(coverage(inv, X, Y, H, W))
     rec["m"][:] = m
     for k in range(0, count, B):
         nb = min(B, count - k)
@@ -221,7 +264,7 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         logits = logits_fn(x)
         if tuple(logits.shape) != (B, H, W, int(num_cls)):
             raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
-        K.paste_labels(logits.detach().contiguous(), nb, first + k + shift, inv, (X, Y), out, origin, strides)
+        K.paste_labels(logits.detach().contiguous(), nb, first + k + shift, inv, (X, Y), out, origin, strides, fov=fov)
     src.close()
     _filter_components(out, post, num_cls, component_stats)
     return out
@@ -262,7 +305,9 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
     label_list (same order) also the dense_pred_<name>.nii.gz / gth_dense_pred_<name>.nii.gz pair that `evaluate --pred-dir` reads (the
     ground truth with labels >= num_cls set to 0).  options: segment_volume's; with prob= / entropy= also prob_<basename> (float32,
     [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine; with keep_largest= every label volume written
-    is the filtered one (component_stats=[]: one stats tensor per volume is appended).  Returns the pred_* paths."""
+    is the filtered one (component_stats=[]: one stats tensor per volume is appended); with sample_mm= every image's voxel size is read
+    from its affine, the share of its voxel columns inside the field of view is logged, and a share below 1 is a warning (the voxels
+    outside stay 0: choose crop / out_size / sample_mm so that the structure lies inside).  Returns the pred_* paths."""
     from . import nifti
     nii_list = list(nii_list)
     if label_list is not None and len(label_list) != len(nii_list):
@@ -272,7 +317,16 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
     for n, fid in enumerate(nii_list):
         img = nifti.load(fid)
         gt = None if label_list is None else np.asarray(nifti.load(label_list[n]).get_data())
-        res = segment_volume(logits_fn, img.get_data(), label=gt, num_cls=num_cls, device=device, **options)
+        extra = {}
+        if options.get("sample_mm") is not None:
+            from .surface import spacing_of
+            extra = {"spacing": check_spacing(spacing_of(img.affine), str(fid)), "fov_stats": []}
+        res = segment_volume(logits_fn, img.get_data(), label=gt, num_cls=num_cls, device=device, **options, **extra)
+        for share in extra.get("fov_stats", ()):
+            log = logging.warning if share < 1.0 else logging.info
+            log("%s: %.1f %% of the voxel columns lie inside the field of view (pixels of %s mm)%s" % (
+                fid, 100.0 * share, " x ".join("%g" % v for v in check_sample_mm(options["sample_mm"])[:2]),
+                "; the rest stays 0" if share < 1.0 else ""))
         base = os.path.basename(str(fid))
         soft = res if isinstance(res, Ensemble) else Ensemble(res, None, None)
         pred = soft.label.cpu().numpy()

@@ -13,11 +13,17 @@ the host only draws the parameters.
 A list file holds one `image.nii[.gz] label.nii[.gz]` pair per line (paths relative to the list file's folder unless absolute).
 
   python -m "medical-cross-modality-domain-adaptation_amd.volume_source" --export N OUTDIR --list LIST [--augment JSON | --no-augment]
+         [--sample-mm MM|PI,PJ,FRAME]
 writes N slices in the reference's tfrecord layout (tfrecord.write_slice) plus OUTDIR/slice_list, so that the TensorFlow reference can be
 fed from the same volumes.
 
 Output pixel (i, j) of an [H, W] slice reads the source slice [X, Y] at (sx, sy) = M (i, j, 1); `compose_matrix` folds centring, the
 resize from (X, Y) to (H, W), rotation, scale, translation and flip into the six float32 entries of M.  The kernel knows nothing of angles.
+
+Sampling on a millimetre grid (opt-in): with sample_mm = a number or (pi_mm, pj_mm, frame_mm) an output pixel is pi_mm x pj_mm
+millimetres whatever the volume's voxel size (VolumeSet.spacings, from the NIfTI affine), the plane is centred on the volume and the outer
+two channels lie frame_mm away from the centre frame, interpolated between frames (pnp_aug_slices_z).  Bilinear sampling aliases once a
+pixel is more than about twice the voxel, as the plain resize does: there is no prefilter.
 """
 import argparse
 import ctypes
@@ -86,31 +92,90 @@ def _cos_sin(deg):
     return math.cos(r), math.sin(r)
 
 
-def compose_matrix(src_xy, out_hw, rotate=0.0, scale=1.0, translate=(0.0, 0.0), flip=False):
+def compose_matrix(src_xy, out_hw, rotate=0.0, scale=1.0, translate=(0.0, 0.0), flip=False, *, spacing_xy=None, pixel_mm=None):
     """the six float32 entries (m00, m01, m02, m10, m11, m12) of
          s = c_src + t + (1 / scale) R(rotate) F D (p - c_out),   c = (extent - 1) / 2,  D = diag(X / H, Y / W),  F = diag(1, -1) if flip
     composed in float64.  scale > 1 magnifies (the output sees a smaller part of the source).  The identity with (X, Y) = (H, W) is
-    exactly (1, 0, 0, 0, 1, 0); rotations by multiples of 90 degrees and the flip of a square slice are exact integer permutations."""
+    exactly (1, 0, 0, 0, 1, 0); rotations by multiples of 90 degrees and the flip of a square slice are exact integer permutations.
+    With spacing_xy = (sx, sy) and pixel_mm = (pi_mm, pj_mm) (both or neither), S = diag(sx, sy), P = diag(pi_mm, pj_mm):
+         s = c_src + S^-1 (t_mm + (1 / scale) R(rotate) F P (p - c_out))
+    rotation and scale act in millimetres (right for anisotropic in-plane spacing), `translate` is in millimetres, and the extent of the
+    source enters through its centre only.  With pi_mm / sx = X / H, pj_mm / sy = Y / W and sx = sy the entries are the ones above."""
+    if (spacing_xy is None) != (pixel_mm is None):
+        raise ValueError("compose_matrix: spacing_xy and pixel_mm go together")
     X, Y = float(src_xy[0]), float(src_xy[1])
     H, W = float(out_hw[0]), float(out_hw[1])
     c, s = _cos_sin(float(rotate))
     inv = 1.0 / float(scale)
-    dx, dy = X / H, Y / W
     f = -1.0 if flip else 1.0
-    a00, a01 = inv * c * dx, inv * -s * f * dy
-    a10, a11 = inv * s * dx, inv * c * f * dy
     ci, cj = (H - 1.0) / 2.0, (W - 1.0) / 2.0
-    m02 = (X - 1.0) / 2.0 + float(translate[0]) - (a00 * ci + a01 * cj)
-    m12 = (Y - 1.0) / 2.0 + float(translate[1]) - (a10 * ci + a11 * cj)
+    if spacing_xy is None:
+        dx, dy = X / H, Y / W
+        a00, a01 = inv * c * dx, inv * -s * f * dy
+        a10, a11 = inv * s * dx, inv * c * f * dy
+        tx, ty = float(translate[0]), float(translate[1])
+    else:
+        sx, sy = float(spacing_xy[0]), float(spacing_xy[1])
+        pi, pj = float(pixel_mm[0]), float(pixel_mm[1])
+        if not (0.0 < sx < math.inf and 0.0 < sy < math.inf and 0.0 < pi < math.inf and 0.0 < pj < math.inf):
+            raise ValueError("compose_matrix: spacing_xy %r and pixel_mm %r must be positive and finite" % (spacing_xy, pixel_mm))
+        a00, a01 = inv * c * (pi / sx), inv * -s * f * (pj / sx)
+        a10, a11 = inv * s * (pi / sy), inv * c * f * (pj / sy)
+        tx, ty = float(translate[0]) / sx, float(translate[1]) / sy
+    m02 = (X - 1.0) / 2.0 + tx - (a00 * ci + a01 * cj)
+    m12 = (Y - 1.0) / 2.0 + ty - (a10 * ci + a11 * cj)
     return np.array([a00, a01, m02, a10, a11, m12], dtype=np.float32)
 
 
-def sample_params(rng, dims, batch_size, out_hw, augment):
+def check_sample_mm(sample_mm):
+    """None, a positive number (isotropic) or (pi_mm, pj_mm, frame_mm) -> None / a triple of floats; anything else is a ValueError"""
+    if sample_mm is None:
+        return None
+    try:
+        t = (float(sample_mm),) * 3 if np.isscalar(sample_mm) else tuple(float(v) for v in sample_mm)
+    except (TypeError, ValueError):
+        raise ValueError("sample_mm must be a number or (pi_mm, pj_mm, frame_mm), got %r" % (sample_mm,))
+    if len(t) != 3 or not all(0.0 < v < math.inf for v in t):
+        raise ValueError("sample_mm must be a positive finite number or three of them (pi_mm, pj_mm, frame_mm), got %r" % (sample_mm,))
+    return t
+
+
+def slicing_spacing(affine, axis=2, name="volume"):
+    """(sx, sy, sz) in mm of the slicing order: surface.spacing_of's per-array-axis spacings (the affine's column norms) with `axis`
+    moved last, as prepare_pair moves it (flips and crops change no spacing).  A non-finite or <= 0 spacing is a ValueError naming `name`."""
+    from .surface import spacing_of
+    return slicing_order(spacing_of(affine), axis, name)
+
+
+def slicing_order(spacing, axis=2, name="volume"):
+    """per-array-axis spacings -> slicing order (`axis` last), checked"""
+    if axis not in (0, 1, 2):
+        raise ValueError("%s: axis %r is not one of 0, 1, 2" % (name, axis))
+    sp = list(check_spacing(spacing, name))
+    return tuple(sp[:axis] + sp[axis + 1:] + [sp[axis]])
+
+
+def check_spacing(spacing, name="volume"):
+    try:
+        sp = tuple(float(v) for v in spacing)
+    except (TypeError, ValueError):
+        raise ValueError("%s: a voxel spacing is three numbers in mm, got %r" % (name, spacing))
+    if len(sp) != 3 or not all(0.0 < v < math.inf for v in sp):
+        raise ValueError("%s: voxel spacing %r must be three positive finite numbers (mm)" % (name, spacing))
+    return sp
+
+
+def sample_params(rng, dims, batch_size, out_hw, augment, sample_mm=None, spacings=None):
     """B draws from `rng` (numpy Generator) -> (records [B] of _lib.AugSample layout, raw draws as a dict of arrays).
     dims: [(X, Y, Z)] per volume.  Every sample draws volume and frame; with augment, rotation, log-scale, two translations and the flip
-    coin follow in that order, whatever their ranges — the stream of a seed does not depend on which ranges are zero."""
+    coin follow in that order, whatever their ranges — the stream of a seed does not depend on which ranges are zero.
+    With sample_mm (and spacings: [(sx, sy, sz)] per volume) the same values are drawn in the same order; the records are of
+    _lib.AugSampleZ layout with dz = frame_mm / sz, the map is compose_matrix's millimetre form and the translations are millimetres."""
     B = int(batch_size)
-    rec = np.zeros(B, dtype=SAMPLE_DTYPE)
+    mm = check_sample_mm(sample_mm)
+    if mm is not None and (spacings is None or len(spacings) != len(dims)):
+        raise ValueError("sample_params: sample_mm needs one spacing per volume")
+    rec = np.zeros(B, dtype=SAMPLE_DTYPE if mm is None else SAMPLE_Z_DTYPE)
     raw = {k: np.zeros(B) for k in ("rotate", "scale", "tx", "ty")}
     raw["flip"] = np.zeros(B, dtype=bool)
     raw["scale"][:] = 1.0
@@ -126,13 +191,20 @@ def sample_params(rng, dims, batch_size, out_hw, augment):
             raw["ty"][b] = rng.uniform(-augment["translate"], augment["translate"])
             raw["flip"][b] = rng.random() < augment["flip"]
         rec["volume"][b], rec["frame"][b] = v, z
-        rec["m"][b] = compose_matrix((X, Y), out_hw, raw["rotate"][b], raw["scale"][b], (raw["tx"][b], raw["ty"][b]), bool(raw["flip"][b]))
+        geom = {}
+        if mm is not None:
+            sx, sy, sz = spacings[v]
+            geom = {"spacing_xy": (sx, sy), "pixel_mm": mm[:2]}
+            rec["dz"][b] = np.float32(mm[2] / sz)
+        rec["m"][b] = compose_matrix((X, Y), out_hw, raw["rotate"][b], raw["scale"][b], (raw["tx"][b], raw["ty"][b]), bool(raw["flip"][b]), **geom)
     return rec, raw
 
 
 VOLUME_DTYPE = np.dtype([("image", "<u8"), ("label", "<u8"), ("X", "<i4"), ("Y", "<i4"), ("Z", "<i4"), ("fill", "<f4")])
 SAMPLE_DTYPE = np.dtype([("volume", "<i4"), ("frame", "<i4"), ("m", "<f4", (6,))])
+SAMPLE_Z_DTYPE = np.dtype([("volume", "<i4"), ("frame", "<i4"), ("dz", "<f4"), ("m", "<f4", (6,))])
 assert VOLUME_DTYPE.itemsize == ctypes.sizeof(_lib.AugVolume) and SAMPLE_DTYPE.itemsize == ctypes.sizeof(_lib.AugSample)
+assert SAMPLE_Z_DTYPE.itemsize == ctypes.sizeof(_lib.AugSampleZ) == 36
 
 
 def label_bounding_box(label, margin):
@@ -169,28 +241,43 @@ class VolumeSet(object):
     """Normalised volumes resident on `device`.  pairs: [(image path, label path)] (read_pairs).  Per volume, in this order: the double
     flip volume_eval.test_eval applies (flip_correction), `axis` moved last (the slicing axis), crop=None or a margin in voxels around
     the label bounding box, upload, pnp_volume_preprocess (clip at the `percentile` order statistic, z-score).
-    .images / .labels: device tensors [X, Y, Z] float32 / uint8;  .stats: [{clip, mean, std, fill}];  .names: image basenames."""
+    .images / .labels: device tensors [X, Y, Z] float32 / uint8;  .stats: [{clip, mean, std, fill}];  .names: image basenames;
+    .spacings: [(sx, sy, sz)] in mm, slicing order (from the image's affine; from_arrays / from_device: spacings=, default 1 mm)."""
 
     def __init__(self, pairs, device, flip_correction=True, axis=2, crop=None, percentile=98):
         from . import nifti
-        arrays, names = [], []
+        arrays, names, spacings = [], [], []
         for image_fid, label_fid in pairs:
-            arrays.append(prepare_pair(nifti.load(image_fid).get_data(), nifti.load(label_fid).get_data(), flip_correction, axis, crop))
+            image = nifti.load(image_fid)
+            arrays.append(prepare_pair(image.get_data(), nifti.load(label_fid).get_data(), flip_correction, axis, crop))
             names.append(os.path.basename(str(image_fid)))
+            spacings.append(slicing_spacing(image.affine, axis, str(image_fid)))
         self._build(arrays, names, device, percentile)
+        self.spacings = spacings
 
     @classmethod
-    def from_arrays(cls, images, labels, names, device, percentile=98):
-        """volumes already in slicing order [X, Y, Z] (no flip, no crop): float32-convertible images, integer labels in [0, 255]"""
+    def from_arrays(cls, images, labels, names, device, percentile=98, spacings=None):
+        """volumes already in slicing order [X, Y, Z] (no flip, no crop): float32-convertible images, integer labels in [0, 255];
+        spacings: one (sx, sy, sz) in mm per volume (default: 1 mm)"""
         self = cls.__new__(cls)
         arrays = [prepare_pair(i, l, flip_correction=False, axis=2, crop=None) for i, l in zip(images, labels)]
         self._build(arrays, [str(n) for n in names], device, percentile)
+        self._set_spacings(spacings)
         return self
 
+    def _set_spacings(self, spacings):
+        if spacings is None:
+            self.spacings = [(1.0, 1.0, 1.0)] * len(self.names)
+            return
+        if len(spacings) != len(self.names):
+            raise ValueError("VolumeSet: %d spacings for %d volumes" % (len(spacings), len(self.names)))
+        self.spacings = [check_spacing(sp, name) for sp, name in zip(spacings, self.names)]
+
     @classmethod
-    def from_device(cls, images, labels, names, fills, percentile=98):
+    def from_device(cls, images, labels, names, fills, percentile=98, spacings=None, min_frames=3):
         """volumes that are on the device and normalised already (volume_predict.py pads a normalised volume with copies of its edge
-        frames): contiguous float32 / uint8 tensors [X, Y, Z] in slicing order, one fill value per volume.  Nothing is copied or computed."""
+        frames): contiguous float32 / uint8 tensors [X, Y, Z] in slicing order, one fill value per volume.  Nothing is copied or computed.
+        spacings: one (sx, sy, sz) in mm per volume (default: 1 mm); min_frames=1: a set only pnp_aug_slices_z will read."""
         import torch
         self = cls.__new__(cls)
         if not images or not (len(images) == len(labels) == len(names) == len(fills)):
@@ -201,9 +288,10 @@ class VolumeSet(object):
                 raise _lib.PnpError("VolumeSet: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (v.device,))
             if v.dtype != torch.float32 or l.dtype != torch.uint8 or v.shape != l.shape or v.dim() != 3 or not (v.is_contiguous() and l.is_contiguous()):
                 raise ValueError("%s: a contiguous float32 image and uint8 label of one 3-D shape expected" % name)
-            if v.shape[2] < 3 or v.shape[0] > 4096 or v.shape[1] > 4096:
-                raise ValueError("%s: volume %s needs at least 3 frames and slice extents <= 4096" % (name, tuple(v.shape)))
+            if v.shape[2] < int(min_frames) or v.shape[0] > 4096 or v.shape[1] > 4096:
+                raise ValueError("%s: volume %s needs at least %d frames and slice extents <= 4096" % (name, tuple(v.shape), int(min_frames)))
         self.names, self.percentile = [str(n) for n in names], int(percentile)
+        self._set_spacings(spacings)
         self.images, self.labels = list(images), list(labels)
         self.dims = [tuple(int(d) for d in v.shape) for v in self.images]
         self.stats = [{"clip": None, "mean": None, "std": None, "fill": float(f)} for f in fills]
@@ -256,14 +344,17 @@ class AugmentedSliceSource(object):
       shard     (rank, world) under data parallelism, as the trainers pass it; every rank holds all volumes and draws its own samples
     next_device_batch() -> (x [B,H,W,3], one-hot [B,H,W,num_cls], fids) on the device, on the current stream (what feeder.DeviceFeeder drives);
     next_batch(B) -> ([B,H,W,4] numpy: image channels 0:3, label map in channel 3, fids): the trainers' source protocol.
-    A fid is "<image basename>#<frame>"."""
+    A fid is "<image basename>#<frame>".
+      sample_mm None, or a number / (pi_mm, pj_mm, frame_mm): sample on that millimetre grid — the plane map carries the
+                pixel size, the outer channels lie frame_mm from the centre frame (pnp_aug_slices_z), augment's translate is in mm."""
 
-    def __init__(self, volumes, batch_size, out_size=(256, 256), augment=DEFAULT_AUGMENT, seed=0, shard=None, num_cls=5):
+    def __init__(self, volumes, batch_size, out_size=(256, 256), augment=DEFAULT_AUGMENT, seed=0, shard=None, num_cls=5, sample_mm=None):
         import torch
         self.volumes, self.batch_size = volumes, int(batch_size)
         self.out_size = (int(out_size[0]), int(out_size[1]))
         self.augment = check_augment(augment)
         self.num_cls = int(num_cls)
+        self.sample_mm = check_sample_mm(sample_mm)
         self.rank = shard[0] if shard else 0
         self.rng = np.random.default_rng(int(seed) + rank_seed(self.rank))
         self._errors = torch.zeros(1, dtype=torch.int32, device=volumes.device)
@@ -271,20 +362,22 @@ class AugmentedSliceSource(object):
 
     def _gather(self, batch_size, num_cls, want_onehot):
         B = int(batch_size or self.batch_size)
-        rec, raw = sample_params(self.rng, self.volumes.dims, B, self.out_size, self.augment)
+        rec, raw = sample_params(self.rng, self.volumes.dims, B, self.out_size, self.augment, self.sample_mm,
+                                 getattr(self.volumes, "spacings", None))
         return self.gather_records(rec, num_cls, want_onehot) + (rec,)
 
     def gather_records(self, rec, num_cls=None, want_onehot=True):
-        """the batch of given sample records (SAMPLE_DTYPE) -> (x, label, one-hot or None) on the device"""
+        """the batch of given sample records (SAMPLE_DTYPE; SAMPLE_Z_DTYPE with sample_mm) -> (x, label, one-hot or None) on the device"""
         import torch
         from . import kernels as K
         vs = self.volumes
-        rec = np.ascontiguousarray(rec, dtype=SAMPLE_DTYPE)
+        frac = self.sample_mm is not None
+        rec = np.ascontiguousarray(rec, dtype=SAMPLE_Z_DTYPE if frac else SAMPLE_DTYPE)
         self.last_params = rec
         staged = torch.from_numpy(rec.view(np.uint8).copy()).pin_memory()
         sd = staged.to(vs.device, non_blocking=True)
-        return K.aug_slices(vs.table_host, vs.table_dev, len(vs), sd, len(rec), self.out_size[0], self.out_size[1], self._errors,
-                            ncls=int(num_cls or self.num_cls), want_onehot=want_onehot)
+        return (K.aug_slices_z if frac else K.aug_slices)(vs.table_host, vs.table_dev, len(vs), sd, len(rec), self.out_size[0], self.out_size[1],
+                                                          self._errors, ncls=int(num_cls or self.num_cls), want_onehot=want_onehot)
 
     def _fids(self, rec):
         return ["%s#%d" % (self.volumes.names[int(v)], int(z)) for v, z in zip(rec["volume"], rec["frame"])]
@@ -299,7 +392,8 @@ class AugmentedSliceSource(object):
         return torch.cat([x, label.unsqueeze(-1)], dim=-1).cpu().numpy(), self._fids(rec)
 
     def errors(self):
-        """samples the kernel refused so far (volume index or frame out of range): reads the device counter, i.e. synchronises"""
+        """samples the kernel refused so far (volume index or frame out of range; with sample_mm also a frame step that is not a finite
+        number >= 0): reads the device counter, i.e. synchronises"""
         return int(self._errors.item())
 
     def close(self):
@@ -309,12 +403,44 @@ class AugmentedSliceSource(object):
                                 "delivered as fill / label 0" % n)
 
 
-def sources_from_lists(train_list, val_list, device, batch_size, num_cls, augment=DEFAULT_AUGMENT, seed=0, shard=None):
-    """the two sources of a trainer from two list files: the training one augmented, the validation one with augment=None"""
+def sources_from_lists(train_list, val_list, device, batch_size, num_cls, augment=DEFAULT_AUGMENT, seed=0, shard=None, sample_mm=None):
+    """the two sources of a trainer from two list files: the training one augmented, the validation one with augment=None; sample_mm
+    (AugmentedSliceSource's) holds for both"""
     train = AugmentedSliceSource(VolumeSet(read_pairs(train_list), device), batch_size, augment=augment, seed=seed, shard=shard,
-                                 num_cls=num_cls)
-    val = AugmentedSliceSource(VolumeSet(read_pairs(val_list), device), batch_size, augment=None, seed=seed + 1, shard=shard, num_cls=num_cls)
+                                 num_cls=num_cls, sample_mm=sample_mm)
+    val = AugmentedSliceSource(VolumeSet(read_pairs(val_list), device), batch_size, augment=None, seed=seed + 1, shard=shard, num_cls=num_cls,
+                               sample_mm=sample_mm)
     return train, val
+
+
+def parse_sample_mm(text):
+    """--sample-mm: 'MM' or 'PI,PJ,FRAME' -> check_sample_mm's triple (None stays None)"""
+    if text is None:
+        return None
+    parts = str(text).split(",")
+    try:
+        vals = [float(p) for p in parts]
+    except ValueError:
+        raise ValueError("--sample-mm: %r is not a number or three numbers PI,PJ,FRAME" % (text,))
+    if len(vals) not in (1, 3):
+        raise ValueError("--sample-mm: one number or three numbers PI,PJ,FRAME expected, got %r" % (text,))
+    try:
+        return check_sample_mm(vals[0] if len(vals) == 1 else vals)
+    except ValueError as e:
+        raise ValueError("--sample-mm: %s" % e)
+
+
+def add_sample_mm_flag(ap):
+    ap.add_argument("--sample-mm", default=None, metavar="MM|PI,PJ,FRAME", help="sample NIfTI volumes on a millimetre grid: the size of an "
+                    "output pixel and the distance between the three channels' frames, whatever the voxel size in the header (one number: "
+                    "isotropic); default: the whole slice squeezed onto the plane, neighbouring array frames")
+
+
+def sample_mm_from_args(ap, args):
+    try:
+        return parse_sample_mm(args.sample_mm)
+    except ValueError as e:
+        ap.error(str(e))
 
 
 def add_augment_flags(ap):
@@ -338,11 +464,12 @@ def augment_from_args(args):
     return check_augment(a)
 
 
-def export(n, outdir, list_file, device="cuda", augment=DEFAULT_AUGMENT, seed=0, batch_size=16, out_size=(256, 256)):
+def export(n, outdir, list_file, device="cuda", augment=DEFAULT_AUGMENT, seed=0, batch_size=16, out_size=(256, 256), sample_mm=None):
     """N augmented slices as one-record tfrecords in the reference's layout plus OUTDIR/slice_list.  data_vol is the [H, W, 3] image;
     label_vol repeats the centre frame's label map in its three channels (the reference's decoder reads channel 1 only)."""
     from .tfrecord import write_slice
-    src = AugmentedSliceSource(VolumeSet(read_pairs(list_file), device), batch_size, out_size=out_size, augment=augment, seed=seed)
+    src = AugmentedSliceSource(VolumeSet(read_pairs(list_file), device), batch_size, out_size=out_size, augment=augment, seed=seed,
+                               sample_mm=sample_mm)
     os.makedirs(outdir, exist_ok=True)
     files = []
     while len(files) < n:
@@ -365,8 +492,10 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda")
     add_augment_flags(ap)
+    add_sample_mm_flag(ap)
     args = ap.parse_args(argv)
-    files = export(int(args.export[0]), args.export[1], args.list, device=args.device, augment=augment_from_args(args), seed=args.seed)
+    files = export(int(args.export[0]), args.export[1], args.list, device=args.device, augment=augment_from_args(args), seed=args.seed,
+                   sample_mm=sample_mm_from_args(ap, args))
     print("wrote %d slices and %s" % (len(files), os.path.join(args.export[1], "slice_list")))
     return files
 

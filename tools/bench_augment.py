@@ -7,6 +7,8 @@
      write-bound: 12 B image + 4 B label + 4 ncls B one-hot per pixel) against the 6.3 TB/s achievable HBM figure — the per-kernel figure
      of record comes from a separate `rocprofv3 --kernel-trace --stats -- python tools/bench_augment.py --profile-step` run,
   4. for scale, a CPU figure: the same batch (affine map, bilinear image, nearest label) built with numpy on 16 host threads.
+With --sample-mm the source samples on a millimetre grid — the volumes get the voxel size of --voxel-mm, the gather is
+pnp_aug_slices_z with a fractional frame step — and the host figure is left out; the default --out is then profiles/spacing_timing.json.
 Prints one JSON object and writes it to --out (default profiles/augment_timing.json)."""
 import argparse
 import importlib
@@ -96,15 +98,22 @@ def main():
     ap.add_argument("--batch-size", type=int, default=16)
     ap.add_argument("--batches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "augment_timing.json"))
+    ap.add_argument("--out", default=None)
+    vs.add_sample_mm_flag(ap)
+    ap.add_argument("--voxel-mm", default="0.8,0.8,1.6", help="with --sample-mm: the voxel size of every volume, slicing order")
     ap.add_argument("--profile-step", action="store_true", help="2 volumes, 20 batches, no host figure: for a rocprofv3 --kernel-trace run")
     a = ap.parse_args()
+    sample_mm = vs.sample_mm_from_args(ap, a)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "augment_timing.json" if sample_mm is None else "spacing_timing.json")
     dev = torch.device("cuda:0")
     shape, H, W, B, ncls = (256, 256, 200), 256, 256, a.batch_size, 5
     nvol = 2 if a.profile_step else a.volumes
     images, labels = make_volumes(nvol, shape, dev)
     vset, pre_ms = volume_set(images, labels, dev)
-    src = vs.AugmentedSliceSource(vset, B, out_size=(H, W), seed=0, num_cls=ncls)
+    vset.spacings = [vs.check_spacing(a.voxel_mm.split(","), "--voxel-mm")] * nvol
+    src = vs.AugmentedSliceSource(vset, B, out_size=(H, W), seed=0, num_cls=ncls, sample_mm=sample_mm)
+    gather = K.aug_slices if sample_mm is None else K.aug_slices_z
     if a.profile_step:
         for _ in range(20):
             src.next_device_batch()
@@ -112,7 +121,8 @@ def main():
         print(json.dumps({"profile_step": True, "errors": src.errors()}))
         return
     res = {"device": torch.cuda.get_device_name(0), "volumes": nvol, "volume_shape": list(shape), "batch_size": B, "out_size": [H, W],
-           "num_cls": ncls, "augment": src.augment, "preprocess_ms_per_volume": {"median": float(np.median(pre_ms)), "min": min(pre_ms), "max": max(pre_ms)}}
+           "num_cls": ncls, "augment": src.augment, "sample_mm": sample_mm, "voxel_mm": vset.spacings[0] if sample_mm else None,
+           "gather_entry": "pnp_aug_slices" if sample_mm is None else "pnp_aug_slices_z", "preprocess_ms_per_volume": {"median": float(np.median(pre_ms)), "min": min(pre_ms), "max": max(pre_ms)}}
     # 2. the source, end to end, synchronised at the end of the timed region only (the trainers never synchronise on it either)
     for _ in range(a.warmup):
         src.next_device_batch()
@@ -139,11 +149,11 @@ def main():
     sd = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
     for want in (True, False):
         for _ in range(3):
-            K.aug_slices(vset.table_host, vset.table_dev, nvol, sd, B, H, W, src._errors, ncls=ncls, want_onehot=want)
+            gather(vset.table_host, vset.table_dev, nvol, sd, B, H, W, src._errors, ncls=ncls, want_onehot=want)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         for _ in range(reps):
-            K.aug_slices(vset.table_host, vset.table_dev, nvol, sd, B, H, W, src._errors, ncls=ncls, want_onehot=want)
+            gather(vset.table_host, vset.table_dev, nvol, sd, B, H, W, src._errors, ncls=ncls, want_onehot=want)
         e1.record()
         e1.synchronize()
         ms = e0.elapsed_time(e1) / reps
@@ -152,6 +162,12 @@ def main():
             "ms_back_to_back_incl_output_allocation": ms, "bytes_written": nbytes, "tb_per_s_written": nbytes / (ms * 1e-3) / 1e12,
             "fraction_of_achievable_hbm": nbytes / (ms * 1e-3) / HBM_ACHIEVABLE}
     res["errors"] = src.errors()
+    if sample_mm is not None:
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     # 4. CPU figure for scale
     vols = [v.cpu().numpy() for v in vset.images[:4]]
     labs = [l.cpu().numpy() for l in vset.labels[:4]]

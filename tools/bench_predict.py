@@ -7,6 +7,9 @@
      of record come from a separate `rocprofv3 --kernel-trace --stats -- python tools/bench_predict.py --profile-step` run,
   3. the paste kernel's bytes per second (reads B H W ncls fp32, writes B X Y bytes) against the 6.3 TB/s achievable HBM figure, for a
      z-fastest destination (the array order of a NIfTI reader) and a z-slowest one (the file stores the slicing axis first).
+With --sample-mm (voxels of 1 mm, so --sample-mm 1.0 covers the whole scan) segment_volume runs on the millimetre grid:
+pnp_aug_slices_z without the padded copy and the pnp_paste_*_fov entries; only the segment_volume wall times and the stages of one
+fixed batch are recorded then, to --out (default profiles/spacing_predict_timing.json).
 Prints one JSON object and writes it to --out (default profiles/predict_timing.json)."""
 import argparse
 import importlib
@@ -65,15 +68,21 @@ def wall(fn, reps=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch-size", type=int, default=16)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "predict_timing.json"))
+    ap.add_argument("--out", default=None)
+    vs.add_sample_mm_flag(ap)
     ap.add_argument("--profile-step", action="store_true", help="one 16-frame warm-up volume, then both volumes once: for a rocprofv3 --kernel-trace run")
     a = ap.parse_args()
+    sample_mm = vs.sample_mm_from_args(ap, a)
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "predict_timing.json" if sample_mm is None else "spacing_predict_timing.json")
     dev = torch.device("cuda:0")
     B, ncls = a.batch_size, 5
     net = ss.Full_DRN(channels=3, n_class=ncls, batch_size=B, device=dev, seed=0, cost_kwargs=dict(COST))
     fn = vp.segmenter_logits(net)
     big, small = scan((256, 256, 200), 0), scan((180, 210, 160), 1)
     kw = dict(batch_size=B, num_cls=ncls, device=dev)
+    if sample_mm is not None:
+        kw.update(sample_mm=sample_mm, spacing=(1.0, 1.0, 1.0))
     vp.segment_volume(fn, scan((256, 256, 16), 2), **kw)          # warm-up: 1 batch
     torch.cuda.synchronize()
     if a.profile_step:
@@ -87,6 +96,32 @@ def main():
     res["segment_volume_256x256x200"] = wall(lambda: vp.segment_volume(fn, big, **kw))
     res["segment_volume_180x210x160"] = wall(lambda: vp.segment_volume(fn, small, **kw))
     res["segment_volume_256x256x200_to_host"] = wall(lambda: vp.segment_volume(fn, big, **kw).cpu())
+    if sample_mm is not None:
+        res["sample_mm"] = sample_mm
+        cov = []
+        vp.segment_volume(fn, small, fov_stats=cov, **kw)
+        res["coverage_180x210x160"] = cov[0]
+        v = torch.from_numpy(big.astype(np.float32)).to(dev)
+        _, st = K.volume_preprocess(v, 98, out=v)
+        vset = vs.VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=dev)], ["v"], [float(st[3].item())])
+        src = vs.AugmentedSliceSource(vset, B, augment=None, num_cls=ncls, sample_mm=sample_mm)
+        rec = np.zeros(B, dtype=vs.SAMPLE_Z_DTYPE)
+        geom = dict(spacing_xy=(1.0, 1.0), pixel_mm=sample_mm[:2])
+        rec["frame"], rec["dz"], rec["m"][:] = 50 + np.arange(B), sample_mm[2], vs.compose_matrix((256, 256), (256, 256), **geom)
+        logits = fn(src.gather_records(rec, ncls, want_onehot=False)[0]).contiguous()
+        res["gather_ms_incl_upload_and_allocation"] = events(lambda: src.gather_records(rec, ncls, want_onehot=False), 50)
+        inv = vp.invert_matrix(vs.compose_matrix((256, 256), (256, 256), **geom))
+        origin, strides, _ = vp.file_layout((256, 256, 200), True, 2, None)
+        out = torch.zeros((256, 256, 200), dtype=torch.uint8, device=dev)
+        for name, fov in (("paste_labels", False), ("paste_labels_fov", True)):
+            res[name + "_256x256_z_fastest_ms_back_to_back"] = events(lambda: K.paste_labels(logits, B, 50, inv, (256, 256), out, origin, strides, fov=fov), 50)
+        res["coverage_256x256"] = vp.coverage(inv, 256, 256, 256, 256)
+        src.close()
+        print(json.dumps(res))
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     with tempfile.TemporaryDirectory() as tmp:
         img, lab = os.path.join(tmp, "scan.nii.gz"), os.path.join(tmp, "scan_label.nii.gz")
         nifti.save(nifti.Nifti1Image(big), img)
