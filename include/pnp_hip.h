@@ -552,6 +552,44 @@ int pnp_aug_slices_z(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols
                      int32_t B, int32_t H, int32_t W, float* x, float* label, float* onehot /*nullable*/, int32_t ncls,
                      uint32_t* errors, void* stream);
 
+/* ---- elastic deformation and intensity augmentation in the gather (csrc/augment.hip) ------------------------------------------
+ *
+ * one output slice of pnp_aug_slices_warp: pnp_aug_sample_z's fields, then the intensity map out = gain * v + bias + noise * n of the image
+ * channels, the seed of the sample's noise stream and whether the sample is displaced by its control table (warp != 0) */
+typedef struct pnp_aug_sample_w {
+    int32_t volume, frame;
+    float dz;
+    float m[6];
+    float gain, bias, noise;
+    uint32_t seed;
+    int32_t warp;
+} pnp_aug_sample_w;
+/* pnp_aug_slices_z (frames, clamp, refusals, lane layout, alignment: all its own) with two additions.
+ * ctrl_dev [B][G + 3][G + 3][2] float32 (device, 8-byte aligned): per sample the control points (dx, dy) of a uniform cubic B-spline over
+ *   the output plane, in SOURCE-VOXEL units; 1 <= G <= 16 cells per axis, or G == 0 with ctrl_dev == NULL (then a sample with warp != 0 is
+ *   refused: fill / 0, counted once in *errors, as a bad frame is).
+ * Coordinates of output pixel (i, j): (sx, sy) by pnp_aug_sample's fmaf chain; if warp != 0, in float32 and in this order (the order is
+ *   part of the contract; no operation is contracted other than the fmaf written here):
+ *     rh = (float)G / (float)H;  gi = ((float)i + 0.5f) * rh;  ci = max(min((int)floorf(gi), G - 1), 0);  t = gi - (float)ci;
+ *     rw, gj, cj, s likewise from j and W;
+ *     weights of t (and of s):  u = 1 - t,  k = 1.f / 6.f,
+ *       B0 = ((u * u) * u) * k,  B1 = fmaf(t * t, fmaf(3, t, -6), 4) * k,  B2 = fmaf(t, fmaf(t, fmaf(-3, t, 3), 3), 1) * k,  B3 = ((t * t) * t) * k;
+ *     per column c = 0 .. 3, with P_a = ctrl[ci + a][cj + c] (each component):  R_c = fmaf(B3(t), P_3, fmaf(B2(t), P_2, fmaf(B1(t), P_1, B0(t) * P_0)));
+ *     d = fmaf(B3(s), R_3, fmaf(B2(s), R_2, fmaf(B1(s), R_1, B0(s) * R_0)));   sx = sx + d.x;  sy = sy + d.y.
+ *   Image (bilinear with fill) and label (nearest) are both read at the displaced coordinates.  A NaN, infinite or huge displacement ends
+ *   in pnp_aug_slices' comparison "outside -> fill / label 0", which comes before any conversion to an integer.
+ * Intensity of every image value v of an accepted sample (fill pixels included; the label is untouched):
+ *     v = (gain == 1 && bias == 0) ? v : fmaf(gain, v, bias);      if (noise != 0)  v = fmaf(noise, n, v)
+ *     e  = 3 * (i * W + j) + channel;   h1 = fmix32((2 e) * 0xCC9E2D51 ^ seed),  h2 = fmix32((2 e + 1) * 0xCC9E2D51 ^ seed)   (uint32, pnp_dropout's hash)
+ *     u1 = ((h1 >> 8) + 1) * 2^-24,  u2 = (h2 >> 8) * 2^-24;   n = sqrtf(-2.f * logf(u1)) * cosf(6.2831855f * u2)
+ *   With noise == 0 no random number is computed.  Refused samples are written as plain fill / 0.
+ * With warp == 0, gain == 1, bias == 0, noise == 0 the outputs equal pnp_aug_slices_z's bit for bit (and pnp_aug_slices' when dz == 1).
+ * Refused on the host before any HIP call: everything pnp_aug_slices_z refuses; G outside [0, 16]; ctrl_dev null with G >= 1 or non-null
+ * with G == 0; ctrl_dev not 8-byte aligned; 6 * H * W >= 2^32. */
+int pnp_aug_slices_warp(const pnp_aug_volume* vols_host, const pnp_aug_volume* vols_dev, int32_t nvol, const pnp_aug_sample_w* samples_dev,
+                        const float* ctrl_dev /*nullable*/, int32_t G, int32_t B, int32_t H, int32_t W, float* x, float* label,
+                        float* onehot /*nullable*/, int32_t ncls, uint32_t* errors, void* stream);
+
 /* ---- volume inference, the way back (csrc/paste.hip): labels of a batch of logits written onto the scan's own grid --------
  *
  * logits [B, H, W, ncls] float32 (device, finite: anything else is the caller's error), 1 <= ncls <= 8; slice b < nb <= B is frame z0 + b.

@@ -58,6 +58,12 @@ class AugSampleZ(ctypes.Structure):
     _fields_ = [("volume", c_int32), ("frame", c_int32), ("dz", c_float), ("m", c_float * 6)]
 
 
+class AugSampleW(ctypes.Structure):
+    """mirror of `pnp_aug_sample_w` (include/pnp_hip.h)"""
+    _fields_ = [("volume", c_int32), ("frame", c_int32), ("dz", c_float), ("m", c_float * 6), ("gain", c_float), ("bias", c_float),
+                ("noise", c_float), ("seed", c_uint32), ("warp", c_int32)]
+
+
 PROF_CONV_FWD, PROF_CONV_DGRAD, PROF_CONV_WGRAD, PROF_CONV_DIRECT = 1, 2, 4, 8
 
 
@@ -188,6 +194,8 @@ PROTOTYPES = {
     "pnp_paste_ensemble": (c_int, [c_int32, POINTER(c_void_p), POINTER(c_float), c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                    c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, _F, _F, c_void_p]),
     "pnp_aug_slices_z": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32, c_int32, _F, _F, _F, c_int32, c_void_p, c_void_p]),
+    "pnp_aug_slices_warp": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, _F, _F, _F, c_int32,
+                                    c_void_p, c_void_p]),
     "pnp_paste_labels_fov": (c_int, [_F, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, POINTER(c_float), c_int32, c_int32, c_void_p,
                                      c_int64, c_int64, c_int64, c_int64, c_int64, c_void_p]),
     "pnp_paste_ensemble_fov": (c_int, [c_int32, POINTER(c_void_p), POINTER(c_float), c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,

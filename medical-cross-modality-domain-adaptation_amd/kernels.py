@@ -1023,6 +1023,31 @@ def aug_slices_z(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls=0
     return aug_slices(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls, want_onehot, entry="pnp_aug_slices_z")
 
 
+def aug_slices_warp(vols_host, vols_dev, nvol, samples_dev, ctrl_dev, G, B, H, W, errors, ncls=0, want_onehot=True):
+    """pnp_aug_slices_warp: aug_slices_z with samples_dev holding B _lib.AugSampleW records (gain, bias, noise, seed, warp
+    after AugSampleZ's fields) and ctrl_dev the control points [B, G + 3, G + 3, 2] float32 of the samples' B-spline displacements in
+    source voxels (None with G == 0: no sample may ask for a warp)"""
+    dev = vols_dev.device
+    if not (vols_dev.is_cuda and samples_dev.is_cuda and errors.is_cuda and (ctrl_dev is None or ctrl_dev.is_cuda)):
+        raise _lib.PnpError("aug_slices_warp: pnp kernels need CUDA/HIP tensors (got a CPU tensor) — there is no CPU fallback")
+    if samples_dev.numel() * samples_dev.element_size() != int(B) * ctypes.sizeof(_lib.AugSampleW):
+        raise _lib.PnpError("pnp_aug_slices_warp: the sample table holds %d bytes, not B = %d records"
+                            % (samples_dev.numel() * samples_dev.element_size(), B))
+    if ctrl_dev is not None:
+        want = int(B) * (int(G) + 3) ** 2 * 2
+        if ctrl_dev.dtype != torch.float32 or not ctrl_dev.is_contiguous() or ctrl_dev.numel() != want:
+            raise _lib.PnpError("pnp_aug_slices_warp: the control table must be contiguous float32 [B, G + 3, G + 3, 2] = %d values for B = %d, "
+                                "G = %d, got %s %s" % (want, B, G, ctrl_dev.dtype, tuple(ctrl_dev.shape)))
+    x = torch.empty((B, H, W, 3), dtype=torch.float32, device=dev)
+    label = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    onehot = torch.empty((B, H, W, int(ncls)), dtype=torch.float32, device=dev) if want_onehot else None
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(_lib.load().pnp_aug_slices_warp(ctypes.cast(vols_host, ctypes.c_void_p), vp(vols_dev), int(nvol), vp(samples_dev),
+                                          None if ctrl_dev is None else vp(ctrl_dev), int(G), int(B), int(H), int(W), _p(x), _p(label),
+                                          _p(onehot), int(ncls), vp(errors), _stream()), "pnp_aug_slices_warp")
+    return x, label, onehot
+
+
 # ---- volume inference (csrc/paste.hip, volume_predict.py) -------------------------------------------------------------------------------
 def paste_labels(logits, nb, z0, inv, src_xy, vol, origin, strides, fov=False):
     """fov=True: pnp_paste_labels_fov — a voxel column whose plane coordinates leave [-0.5, H - 0.5] x [-0.5, W - 0.5] is

@@ -24,6 +24,11 @@ Sampling on a millimetre grid (opt-in): with sample_mm = a numbe
 millimetres whatever the volume's voxel size (VolumeSet.spacings, from the NIfTI affine), the plane is centred on the volume and the outer
 two channels lie frame_mm away from the centre frame, interpolated between frames (pnp_aug_slices_z).  Bilinear sampling aliases once a
 pixel is more than about twice the voxel, as the plain resize does: there is no prefilter.
+
+Elastic deformation and intensity augmentation (opt-in through five more `augment` keys): a coarse lattice of random
+control-point displacements per sample (a uniform cubic B-spline over the output plane, U-Net's warp) and gain / bias / Gaussian noise on
+the image channels, both inside the same gather launch (pnp_aug_slices_warp).  The host draws the control points in output pixels and maps
+them into source voxels with the linear part of the sample's own M.
 """
 import argparse
 import ctypes
@@ -41,6 +46,12 @@ from .parallel import rank_seed
 # the second slice axis).  Mild by design: the hearts of MMWHS keep their orientation, so the default does not flip.
 DEFAULT_AUGMENT = {"rotate": 15.0, "scale": 0.1, "translate": 10.0, "flip": 0.0}
 _AUGMENT_KEYS = tuple(sorted(DEFAULT_AUGMENT))
+# the opt-in keys of DESIGN.md §18 (none of them is in DEFAULT_AUGMENT): elastic = sigma of a control point's displacement in OUTPUT pixels,
+# elastic_grid = cells per axis of the control lattice (1 .. 16; 4 when elastic > 0 and none is given), contrast = gain log-uniform in
+# [1 / (1 + c), 1 + c], brightness = +- additive in z-score units, noise = the per-sample sigma is uniform in [0, noise]
+_WARP_KEYS = ("brightness", "contrast", "elastic", "elastic_grid", "noise")
+DEFAULT_ELASTIC_GRID = 4
+MAX_ELASTIC_GRID = 16
 
 
 def read_pairs(list_file):
@@ -71,16 +82,50 @@ def read_pairs(list_file):
 
 
 def check_augment(augment):
-    """None (identity) or a dict with a subset of DEFAULT_AUGMENT's keys -> a full dict / None"""
+    """None (identity) or a dict with a subset of DEFAULT_AUGMENT's keys and of the elastic / intensity keys (_WARP_KEYS) -> None / a dict
+    with all four classic keys plus those of the new keys that were given"""
     if augment is None:
         return None
-    unknown = sorted(set(augment) - set(_AUGMENT_KEYS))
+    unknown = sorted(set(augment) - set(_AUGMENT_KEYS) - set(_WARP_KEYS))
     if unknown:
-        raise ValueError("augment: unknown keys %s (known: %s)" % (unknown, list(_AUGMENT_KEYS)))
+        raise ValueError("augment: unknown keys %s (known: %s)" % (unknown, list(_AUGMENT_KEYS + _WARP_KEYS)))
     a = {k: float(augment.get(k, 0.0)) for k in _AUGMENT_KEYS}
     if a["rotate"] < 0 or a["scale"] < 0 or a["translate"] < 0 or not 0.0 <= a["flip"] <= 1.0:
         raise ValueError("augment: rotate, scale, translate must be >= 0 and flip in [0, 1], got %r" % (a,))
+    for k in _WARP_KEYS:
+        if k not in augment:
+            continue
+        v = augment[k]
+        if k == "elastic_grid":
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or v != int(v) or not 1 <= int(v) <= MAX_ELASTIC_GRID:
+                raise ValueError("augment: elastic_grid must be an integer in [1, %d], got %r" % (MAX_ELASTIC_GRID, v))
+            a[k] = int(v)
+        else:
+            a[k] = float(v)
+            if not 0.0 <= a[k] < math.inf:
+                raise ValueError("augment: %s must be a finite number >= 0, got %r" % (k, v))
     return a
+
+
+def uses_warp_entry(augment):
+    """whether a checked augment dict needs pnp_aug_slices_warp: one of elastic, contrast, brightness, noise is non-zero"""
+    return augment is not None and any(augment.get(k, 0.0) > 0 for k in ("elastic", "contrast", "brightness", "noise"))
+
+
+def elastic_grid_of(augment):
+    """cells per axis of the control lattice: 0 without elastic deformation, else elastic_grid (default 4)"""
+    if augment is None or augment.get("elastic", 0.0) <= 0:
+        return 0
+    return int(augment.get("elastic_grid", DEFAULT_ELASTIC_GRID))
+
+
+def check_elastic_fold(augment, out_hw):
+    """elastic <= 0.5 min(H, W) / G: neighbouring control points are min(H, W) / G pixels apart; displaced against each other by
+    2 sigma each they would meet, and the plane would fold"""
+    G = elastic_grid_of(augment)
+    if G and augment["elastic"] > 0.5 * min(out_hw) / G:
+        raise ValueError("augment: elastic = %g output pixels folds the %d x %d plane on a lattice of %d cells (at most 0.5 min(H, W) / G = %g)"
+                         % (augment["elastic"], out_hw[0], out_hw[1], G, 0.5 * min(out_hw) / G))
 
 
 def _cos_sin(deg):
@@ -165,17 +210,26 @@ def check_spacing(spacing, name="volume"):
     return sp
 
 
-def sample_params(rng, dims, batch_size, out_hw, augment, sample_mm=None, spacings=None):
+def sample_params(rng, dims, batch_size, out_hw, augment, sample_mm=None, spacings=None, *, rng2=None):
     """B draws from `rng` (numpy Generator) -> (records [B] of _lib.AugSample layout, raw draws as a dict of arrays).
     dims: [(X, Y, Z)] per volume.  Every sample draws volume and frame; with augment, rotation, log-scale, two translations and the flip
     coin follow in that order, whatever their ranges — the stream of a seed does not depend on which ranges are zero.
     With sample_mm (and spacings: [(sx, sy, sz)] per volume) the same values are drawn in the same order; the records are of
-    _lib.AugSampleZ layout with dz = frame_mm / sz, the map is compose_matrix's millimetre form and the translations are millimetres."""
+    _lib.AugSampleZ layout with dz = frame_mm / sz, the map is compose_matrix's millimetre form and the translations are millimetres.
+    With a non-zero elastic / contrast / brightness / noise the records are of _lib.AugSampleW layout (dz = 1 without
+    sample_mm) and `rng2`, a second Generator, gives per sample, in this order: the control points (only when elastic > 0:
+    (G + 3)^2 x 2 normals of sigma `elastic` output pixels, clipped at +-3 sigma), the log-gain, the bias, the noise sigma and the 32-bit
+    noise seed.  `rng` is read exactly as without those keys.  raw gains ctrl ([B, G + 3, G + 3, 2] float32 in SOURCE voxels — the draws
+    mapped through the linear part of the sample's float32 map in float64 — or None), ctrl_px (the draws, output pixels), gain, bias,
+    noise, seed."""
     B = int(batch_size)
     mm = check_sample_mm(sample_mm)
     if mm is not None and (spacings is None or len(spacings) != len(dims)):
         raise ValueError("sample_params: sample_mm needs one spacing per volume")
-    rec = np.zeros(B, dtype=SAMPLE_DTYPE if mm is None else SAMPLE_Z_DTYPE)
+    warp = uses_warp_entry(augment)
+    if warp and rng2 is None:
+        raise ValueError("sample_params: elastic / contrast / brightness / noise draw from a second generator: pass rng2")
+    rec = np.zeros(B, dtype=SAMPLE_W_DTYPE if warp else SAMPLE_DTYPE if mm is None else SAMPLE_Z_DTYPE)
     raw = {k: np.zeros(B) for k in ("rotate", "scale", "tx", "ty")}
     raw["flip"] = np.zeros(B, dtype=bool)
     raw["scale"][:] = 1.0
@@ -196,8 +250,42 @@ def sample_params(rng, dims, batch_size, out_hw, augment, sample_mm=None, spacin
             sx, sy, sz = spacings[v]
             geom = {"spacing_xy": (sx, sy), "pixel_mm": mm[:2]}
             rec["dz"][b] = np.float32(mm[2] / sz)
+        elif warp:
+            rec["dz"][b] = 1.0
         rec["m"][b] = compose_matrix((X, Y), out_hw, raw["rotate"][b], raw["scale"][b], (raw["tx"][b], raw["ty"][b]), bool(raw["flip"][b]), **geom)
+    if warp:
+        _sample_warp(rng2, rec, raw, out_hw, augment)
     return rec, raw
+
+
+def _sample_warp(rng2, rec, raw, out_hw, augment):
+    """the draws of DESIGN.md §18 from the second generator, into the records' gain / bias / noise / seed / warp and raw"""
+    B = len(rec)
+    check_elastic_fold(augment, out_hw)
+    G = elastic_grid_of(augment)
+    sigma = float(augment.get("elastic", 0.0))
+    lc = math.log1p(augment.get("contrast", 0.0))
+    br, nz = float(augment.get("brightness", 0.0)), float(augment.get("noise", 0.0))
+    raw["ctrl_px"] = np.zeros((B, G + 3, G + 3, 2)) if G else None
+    raw["gain"], raw["bias"], raw["noise"] = np.zeros(B), np.zeros(B), np.zeros(B)
+    raw["seed"] = np.zeros(B, dtype=np.uint32)
+    for b in range(B):
+        if G:
+            raw["ctrl_px"][b] = np.clip(rng2.standard_normal((G + 3, G + 3, 2)) * sigma, -3.0 * sigma, 3.0 * sigma)
+        raw["gain"][b] = math.exp(rng2.uniform(-lc, lc))
+        raw["bias"][b] = rng2.uniform(-br, br)
+        raw["noise"][b] = rng2.uniform(0.0, nz)
+        raw["seed"][b] = rng2.integers(0, 1 << 32, dtype=np.uint64)
+    rec["gain"], rec["bias"], rec["noise"], rec["seed"], rec["warp"] = raw["gain"], raw["bias"], raw["noise"], raw["seed"], 1 if G else 0
+    raw["ctrl"] = control_to_source(raw["ctrl_px"], rec["m"]) if G else None
+
+
+def control_to_source(ctrl_px, ms):
+    """control-point displacements (di, dj) in output pixels [B, n, n, 2] -> (dx, dy) in source voxels, float32: the linear part
+    (m00, m01; m10, m11) of each sample's float32 map, applied in float64"""
+    m = np.asarray(ms, dtype=np.float32).astype(np.float64).reshape(-1, 6)
+    lin = m[:, [0, 1, 3, 4]].reshape(-1, 1, 1, 2, 2)
+    return np.einsum("bnmxy,bnmy->bnmx", np.broadcast_to(lin, ctrl_px.shape[:3] + (2, 2)), np.asarray(ctrl_px, dtype=np.float64)).astype(np.float32)
 
 
 VOLUME_DTYPE = np.dtype([("image", "<u8"), ("label", "<u8"), ("X", "<i4"), ("Y", "<i4"), ("Z", "<i4"), ("fill", "<f4")])
@@ -205,6 +293,10 @@ SAMPLE_DTYPE = np.dtype([("volume", "<i4"), ("frame", "<i4"), ("m", "<f4", (6,))
 SAMPLE_Z_DTYPE = np.dtype([("volume", "<i4"), ("frame", "<i4"), ("dz", "<f4"), ("m", "<f4", (6,))])
 assert VOLUME_DTYPE.itemsize == ctypes.sizeof(_lib.AugVolume) and SAMPLE_DTYPE.itemsize == ctypes.sizeof(_lib.AugSample)
 assert SAMPLE_Z_DTYPE.itemsize == ctypes.sizeof(_lib.AugSampleZ) == 36
+SAMPLE_W_DTYPE = np.dtype([("volume", "<i4"), ("frame", "<i4"), ("dz", "<f4"), ("m", "<f4", (6,)), ("gain", "<f4"), ("bias", "<f4"), ("noise", "<f4"),
+                           ("seed", "<u4"), ("warp", "<i4")])
+assert SAMPLE_W_DTYPE.itemsize == ctypes.sizeof(_lib.AugSampleW) == 56
+assert all(SAMPLE_W_DTYPE.fields[n][1] == getattr(_lib.AugSampleW, n).offset for n in SAMPLE_W_DTYPE.names)
 
 
 def label_bounding_box(label, margin):
@@ -346,7 +438,10 @@ class AugmentedSliceSource(object):
     next_batch(B) -> ([B,H,W,4] numpy: image channels 0:3, label map in channel 3, fids): the trainers' source protocol.
     A fid is "<image basename>#<frame>".
       sample_mm None, or a number / (pi_mm, pj_mm, frame_mm): sample on that millimetre grid — the plane map carries the
-                pixel size, the outer channels lie frame_mm from the centre frame (pnp_aug_slices_z), augment's translate is in mm."""
+                pixel size, the outer channels lie frame_mm from the centre frame (pnp_aug_slices_z), augment's translate is in mm.
+    With a non-zero elastic, contrast, brightness or noise in `augment` the batches come from pnp_aug_slices_warp: the
+    records are SAMPLE_W_DTYPE, the new parameters are drawn from a second generator, default_rng([seed + rank_seed(rank), 1]) — the
+    classic fields of a seed's records do not depend on the new keys — and last_ctrl holds the batch's control table (or None)."""
 
     def __init__(self, volumes, batch_size, out_size=(256, 256), augment=DEFAULT_AUGMENT, seed=0, shard=None, num_cls=5, sample_mm=None):
         import torch
@@ -357,27 +452,61 @@ class AugmentedSliceSource(object):
         self.sample_mm = check_sample_mm(sample_mm)
         self.rank = shard[0] if shard else 0
         self.rng = np.random.default_rng(int(seed) + rank_seed(self.rank))
+        self.warp = uses_warp_entry(self.augment)
+        self.rng2 = np.random.default_rng([int(seed) + rank_seed(self.rank), 1]) if self.warp else None
+        check_elastic_fold(self.augment, self.out_size)
         self._errors = torch.zeros(1, dtype=torch.int32, device=volumes.device)
-        self.last_params = None
+        self.last_params = self.last_ctrl = None
 
     def _gather(self, batch_size, num_cls, want_onehot):
         B = int(batch_size or self.batch_size)
         rec, raw = sample_params(self.rng, self.volumes.dims, B, self.out_size, self.augment, self.sample_mm,
-                                 getattr(self.volumes, "spacings", None))
-        return self.gather_records(rec, num_cls, want_onehot) + (rec,)
+                                 getattr(self.volumes, "spacings", None), rng2=self.rng2)
+        return self.gather_records(rec, num_cls, want_onehot, ctrl=raw.get("ctrl")) + (rec,)
 
-    def gather_records(self, rec, num_cls=None, want_onehot=True):
-        """the batch of given sample records (SAMPLE_DTYPE; SAMPLE_Z_DTYPE with sample_mm) -> (x, label, one-hot or None) on the device"""
+    def gather_records(self, rec, num_cls=None, want_onehot=True, ctrl=None):
+        """the batch of given sample records (SAMPLE_DTYPE; SAMPLE_Z_DTYPE with sample_mm; SAMPLE_W_DTYPE with the elastic / intensity keys,
+        then with ctrl = the control table [B, G + 3, G + 3, 2] float32 in source voxels, or None) -> (x, label, one-hot or None) on the device"""
         import torch
         from . import kernels as K
         vs = self.volumes
+        H, W = self.out_size
+        ncls = int(num_cls or self.num_cls)
+        if self.warp:
+            return self._gather_warp(rec, ctrl, ncls, want_onehot)
+        if ctrl is not None:
+            raise ValueError("gather_records: a control table needs a source with elastic / intensity augmentation")
         frac = self.sample_mm is not None
         rec = np.ascontiguousarray(rec, dtype=SAMPLE_Z_DTYPE if frac else SAMPLE_DTYPE)
         self.last_params = rec
         staged = torch.from_numpy(rec.view(np.uint8).copy()).pin_memory()
         sd = staged.to(vs.device, non_blocking=True)
-        return (K.aug_slices_z if frac else K.aug_slices)(vs.table_host, vs.table_dev, len(vs), sd, len(rec), self.out_size[0], self.out_size[1],
-                                                          self._errors, ncls=int(num_cls or self.num_cls), want_onehot=want_onehot)
+        return (K.aug_slices_z if frac else K.aug_slices)(vs.table_host, vs.table_dev, len(vs), sd, len(rec), H, W,
+                                                          self._errors, ncls=ncls, want_onehot=want_onehot)
+
+    def _gather_warp(self, rec, ctrl, ncls, want_onehot):
+        """records and control table travel in ONE pinned staging buffer and one copy; the table starts 56 B bytes into it (8-byte aligned)"""
+        import torch
+        from . import kernels as K
+        vs = self.volumes
+        rec = np.ascontiguousarray(rec, dtype=SAMPLE_W_DTYPE)
+        B, G = len(rec), 0
+        nrec = rec.nbytes
+        if ctrl is not None:
+            ctrl = np.ascontiguousarray(ctrl, dtype=np.float32)
+            G = ctrl.shape[1] - 3 if ctrl.ndim == 4 else -1
+            if G < 1 or ctrl.shape != (B, G + 3, G + 3, 2):
+                raise ValueError("gather_records: the control table must be [B, G + 3, G + 3, 2] with G >= 1, got %s for B = %d" % (ctrl.shape, B))
+        self.last_params, self.last_ctrl = rec, ctrl
+        staged = torch.empty(nrec + (ctrl.nbytes if G else 0), dtype=torch.uint8).pin_memory()
+        host = staged.numpy()
+        host[:nrec] = rec.view(np.uint8)
+        if G:
+            host[nrec:] = ctrl.reshape(-1).view(np.uint8)
+        both = staged.to(vs.device, non_blocking=True)
+        cd = both[nrec:].view(torch.float32) if G else None
+        return K.aug_slices_warp(vs.table_host, vs.table_dev, len(vs), both[:nrec], cd, G, B, self.out_size[0], self.out_size[1], self._errors,
+                                 ncls=ncls, want_onehot=want_onehot)
 
     def _fids(self, rec):
         return ["%s#%d" % (self.volumes.names[int(v)], int(z)) for v, z in zip(rec["volume"], rec["frame"])]
@@ -393,7 +522,7 @@ class AugmentedSliceSource(object):
 
     def errors(self):
         """samples the kernel refused so far (volume index or frame out of range; with sample_mm also a frame step that is not a finite
-        number >= 0): reads the device counter, i.e. synchronises"""
+        number >= 0; a warp asked for without a control table): reads the device counter, i.e. synchronises"""
         return int(self._errors.item())
 
     def close(self):
@@ -446,7 +575,9 @@ def sample_mm_from_args(ap, args):
 def add_augment_flags(ap):
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--augment", default=None, metavar="JSON", help="augmentation ranges of the NIfTI training sources, e.g. "
-                   "'{\"rotate\": 15, \"scale\": 0.1, \"translate\": 10, \"flip\": 0}' (the default)")
+                   "'{\"rotate\": 15, \"scale\": 0.1, \"translate\": 10, \"flip\": 0}' (the default); opt-in keys: \"elastic\" (sigma of the "
+                   "control points of a B-spline warp, output pixels), \"elastic_grid\" (cells per axis, 1..16, default 4), \"contrast\" "
+                   "(gain in [1/(1+c), 1+c]), \"brightness\" (+- additive, z-score units), \"noise\" (Gaussian, sigma up to this)")
     g.add_argument("--no-augment", action="store_true", help="NIfTI training sources without augmentation (centre-aligned resize only)")
 
 

@@ -9,6 +9,8 @@
   4. for scale, a CPU figure: the same batch (affine map, bilinear image, nearest label) built with numpy on 16 host threads.
 With --sample-mm the source samples on a millimetre grid — the volumes get the voxel size of --voxel-mm, the gather is
 pnp_aug_slices_z with a fractional frame step — and the host figure is left out; the default --out is then profiles/spacing_timing.json.
+With --augment JSON the source uses those ranges; with one of the elastic / intensity keys the gather is pnp_aug_slices_warp, the
+host figure is left out and the default --out is profiles/warp_timing.json.
 Prints one JSON object and writes it to --out (default profiles/augment_timing.json)."""
 import argparse
 import importlib
@@ -100,29 +102,44 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=None)
     vs.add_sample_mm_flag(ap)
+    ap.add_argument("--augment", default=None, metavar="JSON", help="augmentation ranges of the source (volume_source's --augment); default: DEFAULT_AUGMENT")
     ap.add_argument("--voxel-mm", default="0.8,0.8,1.6", help="with --sample-mm: the voxel size of every volume, slicing order")
     ap.add_argument("--profile-step", action="store_true", help="2 volumes, 20 batches, no host figure: for a rocprofv3 --kernel-trace run")
     a = ap.parse_args()
     sample_mm = vs.sample_mm_from_args(ap, a)
+    a.no_augment = False            # (augment_from_args reads the pair of flags volume_source.add_augment_flags defines)
+    try:
+        augment = vs.augment_from_args(a)
+    except ValueError as e:
+        ap.error(str(e))
+    warp = vs.uses_warp_entry(augment)
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "augment_timing.json" if sample_mm is None else "spacing_timing.json")
+        a.out = os.path.join(ROOT, "profiles", "warp_timing.json" if warp else "augment_timing.json" if sample_mm is None else "spacing_timing.json")
     dev = torch.device("cuda:0")
     shape, H, W, B, ncls = (256, 256, 200), 256, 256, a.batch_size, 5
     nvol = 2 if a.profile_step else a.volumes
     images, labels = make_volumes(nvol, shape, dev)
     vset, pre_ms = volume_set(images, labels, dev)
     vset.spacings = [vs.check_spacing(a.voxel_mm.split(","), "--voxel-mm")] * nvol
-    src = vs.AugmentedSliceSource(vset, B, out_size=(H, W), seed=0, num_cls=ncls, sample_mm=sample_mm)
-    gather = K.aug_slices if sample_mm is None else K.aug_slices_z
+    src = vs.AugmentedSliceSource(vset, B, out_size=(H, W), augment=augment, seed=0, num_cls=ncls, sample_mm=sample_mm)
+    entry = "pnp_aug_slices_warp" if warp else "pnp_aug_slices" if sample_mm is None else "pnp_aug_slices_z"
     if a.profile_step:
         for _ in range(20):
             src.next_device_batch()
+        if warp:
+            # the same records without warp and intensity through pnp_aug_slices_z, 20 launches: the two kernels side by side in one trace
+            rz = np.zeros(B, dtype=vs.SAMPLE_Z_DTYPE)
+            for f in rz.dtype.names:
+                rz[f] = src.last_params[f]
+            sz = torch.from_numpy(rz.view(np.uint8).copy()).to(dev)
+            for _ in range(20):
+                K.aug_slices_z(vset.table_host, vset.table_dev, nvol, sz, B, H, W, src._errors, ncls=ncls)
         torch.cuda.synchronize()
         print(json.dumps({"profile_step": True, "errors": src.errors()}))
         return
     res = {"device": torch.cuda.get_device_name(0), "volumes": nvol, "volume_shape": list(shape), "batch_size": B, "out_size": [H, W],
            "num_cls": ncls, "augment": src.augment, "sample_mm": sample_mm, "voxel_mm": vset.spacings[0] if sample_mm else None,
-           "gather_entry": "pnp_aug_slices" if sample_mm is None else "pnp_aug_slices_z", "preprocess_ms_per_volume": {"median": float(np.median(pre_ms)), "min": min(pre_ms), "max": max(pre_ms)}}
+           "gather_entry": entry, "preprocess_ms_per_volume": {"median": float(np.median(pre_ms)), "min": min(pre_ms), "max": max(pre_ms)}}
     # 2. the source, end to end, synchronised at the end of the timed region only (the trainers never synchronise on it either)
     for _ in range(a.warmup):
         src.next_device_batch()
@@ -147,6 +164,12 @@ def main():
     rec = src.last_params.copy()
     reps = 50
     sd = torch.from_numpy(rec.view(np.uint8).copy()).to(dev)
+    if warp:
+        cd = None if src.last_ctrl is None else torch.from_numpy(src.last_ctrl).to(dev)
+        G = 0 if cd is None else cd.shape[1] - 3
+        gather = lambda th, td, n, s, *rest, **kw: K.aug_slices_warp(th, td, n, s, cd, G, *rest, **kw)
+    else:
+        gather = K.aug_slices if sample_mm is None else K.aug_slices_z
     for want in (True, False):
         for _ in range(3):
             gather(vset.table_host, vset.table_dev, nvol, sd, B, H, W, src._errors, ncls=ncls, want_onehot=want)
@@ -162,7 +185,7 @@ def main():
             "ms_back_to_back_incl_output_allocation": ms, "bytes_written": nbytes, "tb_per_s_written": nbytes / (ms * 1e-3) / 1e12,
             "fraction_of_achievable_hbm": nbytes / (ms * 1e-3) / HBM_ACHIEVABLE}
     res["errors"] = src.errors()
-    if sample_mm is not None:
+    if sample_mm is not None or warp:
         print(json.dumps(res))
         if a.out:
             with open(a.out, "w") as f:
