@@ -667,6 +667,26 @@ int pnp_filter_components(const uint8_t* vol, const int32_t* roots, int64_t D0, 
                           int32_t keep, int64_t min_size, uint8_t* out, int64_t* stats, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- anti-alias prefilter of a resident volume (csrc/smooth.hip) ---------------------------------------------------------------
+ *
+ * pnp_volume_smooth: dst = the separable filter of src, both float32 [X, Y, Z] in C order (z fastest), borders replicated (the index of
+ * every tap clamped into [0, n - 1] per axis: scipy.ndimage's mode="nearest").  wx / wy / wz: HOST pointers to 2 r + 1 float32 weights
+ * (tap k multiplies the voxel at index + k - r), null exactly when that r == 0; they are read during the call and travel to the kernels by
+ * value, so the caller may free them at once.  One stream-ordered call, no host synchronisation.
+ *   An axis with r == 0 is not filtered at all (no multiplication by 1: its values pass through bit for bit).  All radii 0: nothing is
+ *   launched when dst == src, a device-to-device copy otherwise.
+ *   dst == src (in place) and disjoint buffers are both served; the passes themselves run between src, dst and the workspace.
+ *   Every output of a pass is fmaf(w[2r], v[2r], ... fmaf(w[1], v[1], fmaf(w[0], v[0], 0))) in float32; the passes run in the order X, Y, Z.
+ *   No atomics: bit-identical from run to run, and in place equals out of place bit for bit.
+ * Workspace: pnp_volume_smooth_workspace_bytes (0 for unsupported arguments, and when no intermediate volume is needed): at most one volume,
+ *   rounded up to 256 bytes, unless all three axes are filtered and Z > 2048 (two).
+ * Refused on the host before any HIP call: null src / dst; an extent below 1; X or Y above 4096; X * Y * Z >= 2^31; a radius outside
+ * [0, 32]; null weights with r > 0; a weight that is not finite; src and dst overlapping partially; a short workspace. */
+size_t pnp_volume_smooth_workspace_bytes(int32_t X, int32_t Y, int32_t Z, int32_t rx, int32_t ry, int32_t rz);
+int pnp_volume_smooth(const float* src, float* dst, int32_t X, int32_t Y, int32_t Z, const float* wx /*host, nullable*/, int32_t rx,
+                      const float* wy /*host, nullable*/, int32_t ry, const float* wz /*host, nullable*/, int32_t rz, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -777,7 +777,7 @@ class Trainer(object):
         dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  options: volume_predict.segment_volume's (edge, crop, axis,
         flip_correction, batch_size [default: the net's], percentile, out_size; tta, prob, entropy: DESIGN.md §15, which also write prob_* /
         entropy_* files; keep_largest, component_stats: the connected-component filter of DESIGN.md §16;
-        sample_mm: the millimetre grid of DESIGN.md §17, with each file's voxel size read from its affine).  ensemble: further nets of this class, averaged with this trainer's.  Returns the pred_* paths.  test_eval is untouched."""
+        sample_mm: the millimetre grid of DESIGN.md §17, with each file's voxel size read from its affine; prefilter: the anti-alias prefilter of DESIGN.md §19).  ensemble: further nets of this class, averaged with this trainer's.  Returns the pred_* paths.  test_eval is untouched."""
         from . import volume_predict as vp
         options.setdefault("batch_size", self.net.batch_size)
         fn = vp.adapted_logits(self.net) if not ensemble else [vp.adapted_logits(n) for n in [self.net] + list(ensemble)]

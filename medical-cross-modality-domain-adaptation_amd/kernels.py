@@ -1000,6 +1000,48 @@ def volume_preprocess(v, percentile=98, out=None):
     return out, stats
 
 
+def volume_smooth(v, weights, out=None):
+    """pnp_volume_smooth of a contiguous float32 CUDA volume [X, Y, Z]: weights = (wx, wy, wz), each None (the axis is not
+    filtered) or 2 r + 1 float32-convertible taps, r <= 32 (volume_source.gaussian_weights); borders replicated.  out=None: a new tensor;
+    out=v: in place.  Stream-ordered, no host synchronisation; the workspace (at most one volume, slot "smooth") stays cached until
+    drop_workspace("smooth")."""
+    import numpy as np
+    if v.dim() != 3:
+        raise _lib.PnpError("volume_smooth: a volume [X, Y, Z] expected, got %s" % (tuple(v.shape),))
+    pv = _p(v)
+    out = torch.empty_like(v) if out is None else out
+    if tuple(out.shape) != tuple(v.shape):
+        raise _lib.PnpError("volume_smooth: out is %s, the volume %s" % (tuple(out.shape), tuple(v.shape)))
+    if len(weights) != 3:
+        raise _lib.PnpError("volume_smooth: three weight vectors (or None) expected, got %d" % len(weights))
+    taps, ptrs, radii = [], [], []
+    for a, w in enumerate(weights):
+        if w is None:
+            ptrs.append(None)
+            radii.append(0)
+            continue
+        w = np.ascontiguousarray(w, dtype=np.float32)
+        if w.ndim != 1 or w.size % 2 != 1:
+            raise _lib.PnpError("volume_smooth: axis %d: 2 r + 1 weights expected, got shape %s" % (a, w.shape))
+        taps.append(w)                      # alive until the call returns
+        ptrs.append(w.ctypes.data_as(ctypes.c_void_p))
+        radii.append(w.size // 2)
+    X, Y, Z = (int(d) for d in v.shape)
+    lib = _lib.load()
+    need = lib.pnp_volume_smooth_workspace_bytes(X, Y, Z, *radii)
+    ws = workspace(need, v.device, slot="smooth") if need else None
+    check(lib.pnp_volume_smooth(pv, _p(out), X, Y, Z, ptrs[0], radii[0], ptrs[1], radii[1], ptrs[2], radii[2],
+                                None if ws is None else ctypes.c_void_p(ws.data_ptr()), 0 if ws is None else ws.numel(), _stream()),
+          "pnp_volume_smooth")
+    return out
+
+
+def drop_workspace(slot):
+    """forget the cached scratch buffers of `slot` (every device and stream): the allocator gets them back in stream order"""
+    for key in [k for k in _ws_cache if k[1] == slot]:
+        del _ws_cache[key]
+
+
 def aug_slices(vols_host, vols_dev, nvol, samples_dev, B, H, W, errors, ncls=0, want_onehot=True, entry="pnp_aug_slices"):
     """pnp_aug_slices: vols_host (ctypes array of _lib.AugVolume) / vols_dev (its device copy, uint8 tensor), samples_dev (device copy of B
     _lib.AugSample records, uint8 tensor), errors (int32 [1] device counter) -> (x [B,H,W,3], label [B,H,W], one-hot [B,H,W,ncls] or None)"""

@@ -6,7 +6,7 @@
            [--score [--spacing unit|header] [--json F]]
            [--tta default|JSON] [--prob] [--entropy] [--ensemble CKPT [CKPT ...]]
            [--keep-largest [K]] [--min-size N] [--connectivity 1|2|3]
-           [--sample-mm MM|PI,PJ,FRAME]
+           [--sample-mm MM|PI,PJ,FRAME] [--prefilter auto|off|SX,SY,SZ]
 
 --list holds one `image.nii[.gz]` or `image.nii[.gz] label.nii[.gz]` per line (all lines alike; paths relative to the list's folder unless
 absolute).  The net is built as train_segmenter / train_gan build theirs, with their default configuration: `segmenter` is the source
@@ -24,6 +24,9 @@ filtered ones, and one line per volume reports per class the components found, t
 Millimetre grid: --sample-mm shows the network every scan at one pixel size and one distance between its three frames,
 taken from the voxel size in each file's header (--spacing is something else: the units of --score).  The plane is centred on the
 (cropped) volume; voxels outside its field of view stay 0, and the share covered is reported per file.
+
+Anti-alias prefilter: --prefilter low-passes every normalised scan on the device before it is sampled (auto: sigma from
+the voxels per output pixel; SX,SY,SZ: sigmas in voxels).  Use the setting the checkpoint was trained with.
 """
 import argparse
 import json
@@ -102,10 +105,12 @@ def parse_args(argv=None):
     ap.add_argument("--ensemble", nargs="+", default=None, metavar="CKPT", help="further checkpoints of the same --net, averaged with --model")
     from . import components
     components.add_cli_arguments(ap)
-    from .volume_source import add_sample_mm_flag, sample_mm_from_args
+    from .volume_source import add_prefilter_flag, add_sample_mm_flag, prefilter_from_args, sample_mm_from_args
     add_sample_mm_flag(ap)
+    add_prefilter_flag(ap)
     a = ap.parse_args(argv)
     sample_mm = sample_mm_from_args(ap, a)
+    prefilter = prefilter_from_args(ap, a)
     if (a.images is None) == (a.list is None):
         ap.error("give either --images or --list")
     try:
@@ -150,6 +155,8 @@ def parse_args(argv=None):
                                                                                            members, MAX_MEMBERS))
     if sample_mm is not None:
         options["sample_mm"] = sample_mm
+    if prefilter is not None:
+        options["prefilter"] = prefilter
     if a.prob:
         options["prob"] = True
     if a.entropy:

@@ -74,11 +74,13 @@ def parse_args(phase, argv=None):
     for flag in NII_FLAGS:
         ap.add_argument("--" + flag.replace("_", "-"), default=None, metavar="LIST", help="NIfTI list file (one `image.nii[.gz] "
                         "label.nii[.gz]` pair per line, volume_source.py); the four --*-nii-* flags go together")
-    from .volume_source import add_augment_flags, add_sample_mm_flag, sample_mm_from_args
+    from .volume_source import add_augment_flags, add_prefilter_flag, add_sample_mm_flag, prefilter_from_args, sample_mm_from_args
     add_augment_flags(ap)
     add_sample_mm_flag(ap)
+    add_prefilter_flag(ap)
     args = ap.parse_args(argv)
     args.sample_mm = sample_mm_from_args(ap, args)          # one grid for both modalities: that is the point
+    args.prefilter = prefilter_from_args(ap, args)          # one setting for both: the per-volume sigmas differ through the spacings
     given = [getattr(args, f) is not None for f in NII_FLAGS]
     if any(given) and not all(given):
         ap.error("--mr-nii-train, --mr-nii-val, --ct-nii-train and --ct-nii-val go together")
@@ -86,6 +88,8 @@ def parse_args(phase, argv=None):
         ap.error("the --*-nii-* lists and --synthetic exclude each other")
     if args.sample_mm is not None and not all(given):
         ap.error("--sample-mm goes with the --*-nii-* lists")
+    if args.prefilter is not None and not all(given):
+        ap.error("--prefilter goes with the --*-nii-* lists")
     if not args.gp_weight >= 0.0:
         ap.error("--gp-weight must be >= 0, got %r" % args.gp_weight)
     if args.gp_weight > 0 and args.dtype != "f32":
@@ -122,9 +126,9 @@ def main(phase, argv=None):
         from .volume_source import augment_from_args, sources_from_lists
         shard = (rank, world) if world > 1 else None
         mr_train, mr_val = sources_from_lists(args.mr_nii_train, args.mr_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
-                                              seed=0, shard=shard, sample_mm=args.sample_mm)
+                                              seed=0, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter)
         ct_train, ct_val = sources_from_lists(args.ct_nii_train, args.ct_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
-                                              seed=2, shard=shard, sample_mm=args.sample_mm)
+                                              seed=2, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter)
     elif args.synthetic:
         from .synthetic import write_dataset
         sets = (("syn_mr_train", args.synthetic, 0, "mr"), ("syn_ct_train", args.synthetic, 1, "ct"),

@@ -23,6 +23,9 @@ device, before it is returned.
 Millimetre grid (opt-in): with sample_mm= the plane has a fixed pixel size and is centred on the (cropped) volume, the
 outer channels lie frame_mm from the centre frame (pnp_aug_slices_z; its clamp is the edge replication, so nothing is padded) and the
 paste writes only the voxel columns inside the plane's field of view (pnp_paste_labels_fov / pnp_paste_ensemble_fov); the rest stays 0.
+
+Anti-alias prefilter (opt-in): with prefilter= the normalised box is low-passed on the device (pnp_volume_smooth) before
+anything samples it, with volume_source.prefilter_sigmas' rule — the setting the network was trained with.
 """
 import collections
 import logging
@@ -31,8 +34,8 @@ import os
 import numpy as np
 
 from . import _lib
-from .volume_source import (SAMPLE_DTYPE, SAMPLE_Z_DTYPE, AugmentedSliceSource, VolumeSet, check_sample_mm, check_spacing, compose_matrix,
-                            label_bounding_box, prepare_pair, slicing_order)
+from .volume_source import (SAMPLE_DTYPE, SAMPLE_Z_DTYPE, AugmentedSliceSource, VolumeSet, check_prefilter, check_sample_mm, check_spacing,
+                            compose_matrix, gaussian_weights, label_bounding_box, prefilter_sigmas, prepare_pair, slicing_order)
 
 EDGES = ("replicate", "skip")
 MAX_MEMBERS = 8                          # pnp_paste_ensemble's
@@ -155,7 +158,7 @@ def ensemble_members(logits_fn, tta):
 
 def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
                    out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None,
-                   spacing=None, sample_mm=None, fov_stats=None):
+                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None):
     """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
       logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
                  checkpoint ensemble
@@ -175,6 +178,11 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
                  outside its field of view (for any member) stays 0 in label, prob and entropy, like outside the crop box; tta
                  entries' translate is in mm; the edge frames are replicated by the gather's clamp, nothing is padded
       fov_stats  optional list: with sample_mm the share of the box's voxel columns inside the field of view is appended (coverage)
+      prefilter  None / "off", "auto" or sigmas in voxels (a number or (sx, sy, sz), slicing order): the anti-alias prefilter of DESIGN.md
+                 §19.  The normalised box is smoothed in place (pnp_volume_smooth) after pnp_volume_preprocess and before the edge frames
+                 are padded (the padding copies smoothed frames), with volume_source.prefilter_sigmas' sigmas from the box extents,
+                 out_size, spacing and sample_mm; tta scales are ignored.  "auto" with spacing but without sample_mm is the plain resize's
+                 rule.  The fill stays the unsmoothed minimum.  Use the setting the network was trained with.
       edge       "replicate": the normalised volume is padded with a copy of its first and last frame, every frame is predicted;
                  "skip": frames 1 .. Z - 2 only (the reference's frame set), the two edge frames stay 0
     Frames run in ascending order, batch_size at a time; the last, short batch repeats its last frame and pastes nb < B slices.  Nothing
@@ -189,6 +197,7 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     if B < 1:
         raise ValueError("batch_size must be at least 1")
     mm = check_sample_mm(sample_mm)
+    pre = check_prefilter(prefilter)
     if mm is not None:
         if spacing is None:
             raise ValueError("sample_mm needs spacing: the voxel size in mm per array axis of the image (surface.spacing_of(affine))")
@@ -213,6 +222,11 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     v = torch.from_numpy(np.ascontiguousarray(img[tuple(slice(a, b) for a, b in box)])).to(device)
     _, stats = K.volume_preprocess(v, int(percentile), out=v)
     fill = float(stats[3].item())                       # the one read before the loop: the fill enters the gather's descriptor table
+    if pre is not None:
+        taps = [gaussian_weights(s) for s in prefilter_sigmas(pre, (X, Y, Z), (H, W), vox if mm is not None else None, mm)]
+        if any(t is not None for t in taps):
+            K.volume_smooth(v, taps, out=v)
+            K.drop_workspace("smooth")
     if mm is not None:
         first, count, shift = (0, Z, 0) if edge == "replicate" else (1, Z - 2, 0)       # pnp_aug_slices_z clamps: its own replication
     elif edge == "replicate":
@@ -305,7 +319,8 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
     label_list (same order) also the dense_pred_<name>.nii.gz / gth_dense_pred_<name>.nii.gz pair that `evaluate --pred-dir` reads (the
     ground truth with labels >= num_cls set to 0).  options: segment_volume's; with prob= / entropy= also prob_<basename> (float32,
     [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine; with keep_largest= every label volume written
-    is the filtered one (component_stats=[]: one stats tensor per volume is appended); with sample_mm= every image's voxel size is read
+    is the filtered one (component_stats=[]: one stats tensor per volume is appended); prefilter= is segment_volume's (the
+    setting the network was trained with); with sample_mm= every image's voxel size is read
     from its affine, the share of its voxel columns inside the field of view is logged, and a share below 1 is a warning (the voxels
     outside stay 0: choose crop / out_size / sample_mm so that the structure lies inside).  Returns the pred_* paths."""
     from . import nifti
