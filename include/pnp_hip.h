@@ -640,6 +640,21 @@ int pnp_paste_ensemble_fov(int32_t M, const float* const* logits, const float* i
                            int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
                            int64_t sz, float* prob /*nullable*/, float* entropy /*nullable*/, void* stream);
 
+/* ---- tiled inference: overlapping planes blended over their union (csrc/paste.hip) ----------------------------------------------
+ *
+ * The arguments and checks of pnp_paste_ensemble_fov with 1 <= M <= 64 members and one more float, `ramp` >= 1 (plane pixels).  A member
+ * COVERS the voxel column (x, y) iff its unclamped plane coordinates (pi, pj) — the two fmaf chains — satisfy pnp_paste_labels_fov's rule.
+ * A column that no member covers is written in none of vol, prob, entropy.  For a covered column and frame b, over the covering members in
+ * ascending m:
+ *   w_m = g(pi; H) * g(pj; W),  g(p; n) = fminf(1, fmaxf(d, 0.5f) * (1.0f / ramp)),  d = fminf(p + 0.5f, (n - 0.5f) - p)
+ *   p_c as pnp_paste_ensemble computes member m's softmax;  acc_c += w_m * p_c (the product rounded, then the sum);  wsum += w_m;
+ *   vol[e] = the lowest c with the strictly largest acc_c;  prob[c * vol_elems + e] = P_c = acc_c / wsum;  entropy[e] from P as
+ *   pnp_paste_ensemble's.  A member given twice (same pointer, same map) leaves all three outputs as with that member given once, bit for bit.
+ * Refused on the host before any HIP call: all that pnp_paste_ensemble refuses (M outside [1, 64]); ramp not finite or < 1. */
+int pnp_paste_tiles(int32_t M, const float* const* logits, const float* inv, float ramp, int32_t B, int32_t H, int32_t W, int32_t ncls,
+                    int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
+                    int64_t sz, float* prob /*nullable*/, float* entropy /*nullable*/, void* stream);
+
 /* ---- connected components of label volumes (csrc/components.hip): keep the largest 3-D component of every structure -------
  *
  * vol: uint8 labels [D0, D1, D2], C order (D2 fastest: what pnp_paste_labels writes and a NIfTI reader returns), each extent in [1, 4096],

@@ -21,6 +21,14 @@
 //                         A member's corner data is recomputed per frame from its six kernel-argument floats: 8 members x 8 values kept
 //                         per lane would be 64 VGPRs or an indexed private array (scratch); the ~30 VALU operations per member and frame
 //                         stand against 4 * ncls dependent-address loads, ncls expf and ncls divisions.
+//
+//   paste_tiles_kernel       the same lane layout, store paths and one-writer rule for M <= 64 members that each cover a PART of
+//                         the box: a column is written iff at least one member covers it (a union), and the covering members' softmax is
+//                         blended with a separable window that trusts a plane's centre more than its border.  Per column, once: every
+//                         member's two coordinate chains, kept as one covering bit per member (two VGPRs), and the wave's union of those
+//                         bits (two SGPRs).  Per frame: the wave walks the set bits of the union, so the member's pointer and map are scalar
+//                         loads from the kernel-argument block, and a lane whose own bit is clear skips the member; the covering member's
+//                         corner data and weight are recomputed from its six floats as above.  No accumulator volume, no atomics.
 #include <algorithm>
 #include <math.h>
 
@@ -135,6 +143,46 @@ struct EnsembleArgs {
     int M, H, W, ncls, nb, z0, X, Y;
 };
 
+// the unclamped plane coordinates of voxel column (fx, fy) under the six-entry map iv: the two fmaf chains of the contract
+__device__ __forceinline__ void plane_coords(const float* iv, float fx, float fy, float& pi, float& pj) {
+    pi = fmaf(iv[0], fx, fmaf(iv[1], fy, iv[2]));
+    pj = fmaf(iv[3], fx, fmaf(iv[4], fy, iv[5]));
+}
+
+// one member at one voxel: the logits of plane p ([H, W, NCLS]) interpolated at the unclamped coordinates (pi, pj), r[c] = expf(r_c - max r),
+// returns their sum over ascending c (the softmax is r[c] / s).  Shared by paste_ensemble_kernel and paste_tiles_kernel.  Keep it free of
+// contractible a * b + c pairs (every multiply-add here is an explicit fmaf): tiles_at's contract(off) does not reach inlined callees, and
+// its exact-doubling property needs the same bits from every call.
+template <int NCLS>
+__device__ __forceinline__ float softmax_at(const float* __restrict__ p, float pi, float pj, int H, int W, float (&r)[NCLS]) {
+    pi = fminf(fmaxf(pi, 0.f), (float)(H - 1));               // as paste_labels_kernel: NaN -> 0, clamped before any integer conversion
+    pj = fminf(fmaxf(pj, 0.f), (float)(W - 1));
+    const float fi = floorf(pi), fj = floorf(pj);
+    const int i0 = (int)fi, j0 = (int)fj;
+    const int i1 = min(i0 + 1, H - 1), j1 = min(j0 + 1, W - 1);
+    const float ti = pi - fi, tj = pj - fj;
+    const float ui = 1.f - ti, uj = 1.f - tj;
+    const float* __restrict__ p00 = p + (i0 * W + j0) * NCLS;
+    const float* __restrict__ p01 = p + (i0 * W + j1) * NCLS;
+    const float* __restrict__ p10 = p + (i1 * W + j0) * NCLS;
+    const float* __restrict__ p11 = p + (i1 * W + j1) * NCLS;
+    float mx = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) {
+        const float a = fmaf(p01[c], tj, p00[c] * uj);        // the three steps of label_at
+        const float b = fmaf(p11[c], tj, p10[c] * uj);
+        r[c] = fmaf(b, ti, a * ui);
+        mx = c == 0 ? r[c] : fmaxf(mx, r[c]);
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) {
+        r[c] = expf(r[c] - mx);
+        s += r[c];
+    }
+    return s;
+}
+
 // acc[c] = sum over the members of softmax_c(interpolated logits), frame offset `off` (floats); returns the first strict maximum of acc.
 // Order of the sum: members 0 .. 3 ascending into one accumulator, members 4 .. 7 ascending into a second one, then first + second.  For
 // M <= 4 that is the plain ascending sum; the split makes M = 8 copies of one member sum to exactly 8 p (p + p + p + p is exact in
@@ -145,36 +193,10 @@ __device__ __forceinline__ int ensemble_at(const EnsembleArgs& A, float fx, floa
 #pragma unroll
     for (int c = 0; c < NCLS; ++c) acc[c] = hi[c] = 0.f;
     for (int m = 0; m < A.M; ++m) {
-        const float* iv = A.inv + 6 * m;
-        float pi = fmaf(iv[0], fx, fmaf(iv[1], fy, iv[2]));
-        float pj = fmaf(iv[3], fx, fmaf(iv[4], fy, iv[5]));
-        pi = fminf(fmaxf(pi, 0.f), (float)(A.H - 1));         // as paste_labels_kernel: NaN -> 0, clamped before any integer conversion
-        pj = fminf(fmaxf(pj, 0.f), (float)(A.W - 1));
-        const float fi = floorf(pi), fj = floorf(pj);
-        const int i0 = (int)fi, j0 = (int)fj;
-        const int i1 = min(i0 + 1, A.H - 1), j1 = min(j0 + 1, A.W - 1);
-        const float ti = pi - fi, tj = pj - fj;
-        const float ui = 1.f - ti, uj = 1.f - tj;
-        const float* __restrict__ p = A.logits[m] + off;
-        const float* __restrict__ p00 = p + (i0 * A.W + j0) * NCLS;
-        const float* __restrict__ p01 = p + (i0 * A.W + j1) * NCLS;
-        const float* __restrict__ p10 = p + (i1 * A.W + j0) * NCLS;
-        const float* __restrict__ p11 = p + (i1 * A.W + j1) * NCLS;
+        float pi, pj;
+        plane_coords(A.inv + 6 * m, fx, fy, pi, pj);
         float r[NCLS];
-        float mx = 0.f;
-#pragma unroll
-        for (int c = 0; c < NCLS; ++c) {
-            const float a = fmaf(p01[c], tj, p00[c] * uj);        // the three steps of label_at
-            const float b = fmaf(p11[c], tj, p10[c] * uj);
-            r[c] = fmaf(b, ti, a * ui);
-            mx = c == 0 ? r[c] : fmaxf(mx, r[c]);
-        }
-        float s = 0.f;
-#pragma unroll
-        for (int c = 0; c < NCLS; ++c) {
-            r[c] = expf(r[c] - mx);
-            s += r[c];
-        }
+        const float s = softmax_at<NCLS>(A.logits[m] + off, pi, pj, A.H, A.W, r);
         if (m < kGroup) {
 #pragma unroll
             for (int c = 0; c < NCLS; ++c) acc[c] += r[c] / s;
@@ -196,21 +218,36 @@ __device__ __forceinline__ int ensemble_at(const EnsembleArgs& A, float fx, floa
     return am;
 }
 
-// the mean probabilities and the normalised entropy of one voxel at element index e (plain dword stores, one writer per element)
+// the probabilities P and their normalised entropy of one voxel at element index e (plain dword stores, one writer per element)
 template <int NCLS>
-__device__ __forceinline__ void store_soft(const EnsembleArgs& A, long long e, const float (&acc)[NCLS], float inv_logn) {
-    if (A.prob) {
+__device__ __forceinline__ void store_soft(float* prob, float* entropy, long long vol_elems, long long e, const float (&P)[NCLS], float inv_logn) {
+    if (prob) {
 #pragma unroll
-        for (int c = 0; c < NCLS; ++c) A.prob[(long long)c * A.vol_elems + e] = acc[c] * A.inv_m;
+        for (int c = 0; c < NCLS; ++c) prob[(long long)c * vol_elems + e] = P[c];
     }
-    if (A.entropy) {
+    if (entropy) {
         float h = 0.f;
 #pragma unroll
-        for (int c = 0; c < NCLS; ++c) {
-            const float P = acc[c] * A.inv_m;
-            if (P > 0.f) h = fmaf(P, logf(P), h);
+        for (int c = 0; c < NCLS; ++c)
+            if (P[c] > 0.f) h = fmaf(P[c], logf(P[c]), h);
+        entropy[e] = NCLS == 1 ? 0.f : -h * inv_logn;
+    }
+}
+
+// the z-fastest store path of the soft kernels, one label per call in address order (t counts elements from e0, the lowest address): labels
+// collect in `w` at their byte lane; a word that fills all four lanes goes out as one aligned dword, the head (before the first 4-byte
+// boundary) and the tail as single bytes
+__device__ __forceinline__ void pack_label(unsigned char* vol, long long e0, long long e, int t, int nb, unsigned int lab, unsigned int& w, int& first) {
+    const unsigned int lane = (unsigned int)((uintptr_t)(vol + e) & 3u);
+    w |= lab << (8u * lane);
+    if (lane == 3u || t == nb - 1) {
+        if (t - first == 3) {
+            *(unsigned int*)(vol + e - 3) = w;                        // lane == 3 and four labels: an aligned dword
+        } else {
+            for (int q = first; q <= t; ++q) vol[e0 + q] = (unsigned char)(w >> (8u * (unsigned int)((uintptr_t)(vol + e0 + q) & 3u)));
         }
-        A.entropy[e] = NCLS == 1 ? 0.f : -h * inv_logn;
+        w = 0u;
+        first = t + 1;
     }
 }
 
@@ -224,9 +261,8 @@ __global__ void __launch_bounds__(kThreads) paste_ensemble_kernel(const Ensemble
     const float fx = (float)x, fy = (float)y;
     if constexpr (FOV) {
         for (int m = 0; m < A.M; ++m) {
-            const float* iv = A.inv + 6 * m;
-            const float pi = fmaf(iv[0], fx, fmaf(iv[1], fy, iv[2]));
-            const float pj = fmaf(iv[3], fx, fmaf(iv[4], fy, iv[5]));
+            float pi, pj;
+            plane_coords(A.inv + 6 * m, fx, fy, pi, pj);
             if (!in_fov(pi, pj, A.H, A.W)) return;
         }
     }
@@ -246,22 +282,119 @@ __global__ void __launch_bounds__(kThreads) paste_ensemble_kernel(const Ensemble
         const int b = up ? t : nb - 1 - t;
         const long long e = zfast ? e0 + t : col + (long long)b * A.sz;
         const unsigned int lab = (unsigned int)ensemble_at<NCLS>(A, fx, fy, (long long)b * A.plane, acc);
-        if (soft) store_soft<NCLS>(A, e, acc, inv_logn);
+        if (soft) {
+            float P[NCLS];
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) P[c] = acc[c] * A.inv_m;
+            store_soft<NCLS>(A.prob, A.entropy, A.vol_elems, e, P, inv_logn);
+        }
         if (!zfast) {
             A.vol[e] = (unsigned char)lab;
             continue;
         }
-        const unsigned int lane = (unsigned int)((uintptr_t)(A.vol + e) & 3u);
-        w |= lab << (8u * lane);
-        if (lane == 3u || t == nb - 1) {
-            if (t - first == 3) {
-                *(unsigned int*)(A.vol + e - 3) = w;                  // lane == 3 and four labels: an aligned dword
-            } else {
-                for (int q = first; q <= t; ++q) A.vol[e0 + q] = (unsigned char)(w >> (8u * (unsigned int)((uintptr_t)(A.vol + e0 + q) & 3u)));
-            }
-            w = 0u;
-            first = t + 1;
+        pack_label(A.vol, e0, e, t, nb, lab, w, first);
+    }
+}
+
+// ---- tiled inference (pnp_paste_tiles) ---------------------------------------------------------------------------------------
+constexpr int kMaxTiles = 64;
+
+struct TilesArgs {
+    const float* logits[kMaxTiles];        // [B, H, W, ncls] each
+    float inv[6 * kMaxTiles];
+    unsigned char* vol;
+    float* prob;               // nullable: ncls planes of vol_elems floats
+    float* entropy;            // nullable: vol_elems floats
+    long long vol_elems;
+    long long origin;
+    long long sx, sy, sz;
+    long long plane;
+    float inv_ramp;            // 1.0f / ramp
+    int M, H, W, ncls, nb, z0, X, Y;
+};
+static_assert(sizeof(TilesArgs) < 4096, "the member table travels by value in the kernel-argument block");
+
+// g(p; n) = min(1, max(d, 0.5) / ramp), d = min(p + 0.5, (n - 0.5) - p): the distance to the nearer border of the field of view in plane
+// pixels, at least half a pixel, over the ramp.  Inside the field of view 0.5 / ramp <= g <= 1.  (No a * b + c pair here either: see softmax_at.)
+__device__ __forceinline__ float window(float p, int n, float inv_ramp) {
+    const float d = fminf(p + 0.5f, ((float)n - 0.5f) - p);
+    return fminf(1.f, fmaxf(d, 0.5f) * inv_ramp);
+}
+
+// acc[c] = sum of w_m softmax_c(member m) and wsum = sum of w_m over the members whose bit is set in `mine`, ascending m, each product
+// rounded before its sum: contraction is switched off for this function's own arithmetic (the compiler otherwise fuses w q + acc for
+// some classes and not for others), so equal members give equal acc_c and a member given twice doubles acc and wsum exactly.  `wave` is
+// the union of the wave's masks: m, the member's pointer and its map are wave-uniform.  Returns the first strict maximum of acc.
+template <int NCLS>
+__device__ __forceinline__ int tiles_at(const TilesArgs& A, unsigned long long wave, unsigned long long mine, float fx, float fy, long long off,
+                                        float (&acc)[NCLS], float& wsum) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c) acc[c] = 0.f;
+    wsum = 0.f;
+    for (unsigned long long rest = wave; rest; rest &= rest - 1ull) {
+        const int m = __builtin_ctzll(rest);
+        if (!((mine >> m) & 1ull)) continue;
+        float pi, pj;
+        plane_coords(A.inv + 6 * m, fx, fy, pi, pj);
+        const float wm = window(pi, A.H, A.inv_ramp) * window(pj, A.W, A.inv_ramp);
+        float r[NCLS];
+        const float s = softmax_at<NCLS>(A.logits[m] + off, pi, pj, A.H, A.W, r);
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) acc[c] += wm * (r[c] / s);
+        wsum += wm;
+    }
+    int am = 0;
+    float best = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c)
+        if (c == 0 || acc[c] > best) {
+            best = acc[c];
+            am = c;
         }
+    return am;
+}
+
+template <int NCLS>
+__global__ void __launch_bounds__(kThreads) paste_tiles_kernel(const TilesArgs A) {
+    const int g = blockIdx.x * kThreads + threadIdx.x;        // flat column index, y fastest, as in paste_labels_kernel
+    if (g >= A.X * A.Y) return;
+    const int x = g / A.Y, y = g - x * A.Y;
+    const float fx = (float)x, fy = (float)y;
+    // coverage depends on the column only: one bit per member, once
+    unsigned long long mine = 0ull, wave = 0ull;
+    for (int m = 0; m < A.M; ++m) {
+        float pi, pj;
+        plane_coords(A.inv + 6 * m, fx, fy, pi, pj);
+        const bool in = in_fov(pi, pj, A.H, A.W);
+        if (in) mine |= 1ull << m;
+        if (__builtin_amdgcn_ballot_w64(in)) wave |= 1ull << m;
+    }
+    if (!mine) return;                                        // covered by no member: nothing of vol, prob, entropy is written
+    const int nb = A.nb;
+    const bool soft = A.prob || A.entropy;
+    const float inv_logn = NCLS > 1 ? 1.f / logf((float)NCLS) : 0.f;
+    const long long col = A.origin + (long long)x * A.sx + (long long)y * A.sy + (long long)A.z0 * A.sz;      // frame z0 of this column
+    float acc[NCLS], wsum;
+    const bool zfast = A.sz == 1 || A.sz == -1, up = A.sz != -1;      // t, e0, w, first: as in paste_ensemble_kernel
+    const long long e0 = up ? col : col - (nb - 1);
+    unsigned int w = 0u;
+    int first = 0;
+    for (int t = 0; t < nb; ++t) {
+        const int b = up ? t : nb - 1 - t;
+        const long long e = zfast ? e0 + t : col + (long long)b * A.sz;
+        const unsigned int lab = (unsigned int)tiles_at<NCLS>(A, wave, mine, fx, fy, (long long)b * A.plane, acc, wsum);
+        if (soft) {
+            float P[NCLS];
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) P[c] = acc[c] / wsum;
+            store_soft<NCLS>(A.prob, A.entropy, A.vol_elems, e, P, inv_logn);
+        }
+        if (!zfast) {
+            A.vol[e] = (unsigned char)lab;
+            continue;
+        }
+        pack_label(A.vol, e0, e, t, nb, lab, w, first);
     }
 }
 
@@ -371,6 +504,42 @@ int paste_ensemble_launch(const char* who, int32_t M, const float* const* logits
     return PNP_OK;
 }
 
+int paste_tiles_launch(const char* who, int32_t M, const float* const* logits, const float* inv, float ramp, int32_t B, int32_t H, int32_t W,
+                       int32_t ncls, int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx,
+                       int64_t sy, int64_t sz, float* prob, float* entropy, void* stream) {
+    PNP_REQUIRE(M >= 1 && M <= kMaxTiles, "%s: M = %d members outside [1, %d]", who, (int)M, kMaxTiles);
+    PNP_REQUIRE(logits && vol, "%s: null pointer", who);
+    PNP_REQUIRE(inv, "%s: null inv (6 floats per member)", who);
+    for (int m = 0; m < M; ++m) PNP_REQUIRE(logits[m], "%s: member %d of %d is a null pointer", who, m, (int)M);
+    PNP_REQUIRE(std::isfinite(ramp) && ramp >= 1.f, "%s: ramp = %g must be finite and at least 1 (plane pixels)", who, (double)ramp);
+    if (const int rc = check_paste(who, B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
+    PNP_REQUIRE((__int128)ncls * vol_elems <= (__int128)INT64_MAX, "%s: ncls * vol_elems = %d * %lld overflows int64", who, (int)ncls,
+                (long long)vol_elems);
+    TilesArgs A;
+    for (int m = 0; m < kMaxTiles; ++m) {
+        A.logits[m] = logits[m < M ? m : 0];
+        for (int i = 0; i < 6; ++i) A.inv[6 * m + i] = inv[6 * (m < M ? m : 0) + i];
+    }
+    A.vol = vol;
+    A.prob = prob;
+    A.entropy = entropy;
+    A.vol_elems = vol_elems;
+    A.origin = origin;
+    A.sx = sx; A.sy = sy; A.sz = sz;
+    A.plane = (long long)H * W * ncls;
+    A.inv_ramp = 1.0f / ramp;
+    A.M = M; A.H = H; A.W = W; A.ncls = ncls; A.nb = nb; A.z0 = z0; A.X = X; A.Y = Y;
+    const unsigned blocks = (unsigned)(((long long)X * Y + kThreads - 1) / kThreads);
+    switch (ncls) {
+#define PNP_TILES_CASE(n) case n: hipLaunchKernelGGL((paste_tiles_kernel<n>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
+        PNP_TILES_CASE(1) PNP_TILES_CASE(2) PNP_TILES_CASE(3) PNP_TILES_CASE(4)
+        PNP_TILES_CASE(5) PNP_TILES_CASE(6) PNP_TILES_CASE(7) PNP_TILES_CASE(8)
+#undef PNP_TILES_CASE
+    }
+    PNP_CHECK_LAUNCH("paste_tiles_kernel");
+    return PNP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -399,6 +568,13 @@ int pnp_paste_ensemble_fov(int32_t M, const float* const* logits, const float* i
                            float* prob, float* entropy, void* stream) {
     return paste_ensemble_launch<true>("pnp_paste_ensemble_fov", M, logits, inv, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy, sz,
                                        prob, entropy, stream);
+}
+
+int pnp_paste_tiles(int32_t M, const float* const* logits, const float* inv, float ramp, int32_t B, int32_t H, int32_t W, int32_t ncls,
+                    int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
+                    int64_t sz, float* prob, float* entropy, void* stream) {
+    return paste_tiles_launch("pnp_paste_tiles", M, logits, inv, ramp, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy, sz, prob,
+                              entropy, stream);
 }
 
 }  // extern "C"

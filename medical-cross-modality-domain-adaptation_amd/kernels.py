@@ -1146,6 +1146,38 @@ def paste_ensemble(logits, nb, z0, invs, src_xy, vol, origin, strides, prob=None
     return vol, prob, entropy
 
 
+def paste_tiles(logits, nb, z0, invs, ramp, src_xy, vol, origin, strides, prob=None, entropy=None):
+    """pnp_paste_tiles: paste_ensemble's arguments for M = len(logits) <= 64 members that each cover a part of the box, and
+    `ramp` >= 1, the width of the blending window's rise in plane pixels.  A voxel column is written iff at least one member's map keeps
+    it inside its plane; over the covering members vol gets the first strict maximum of the window-weighted softmax sum, prob the weighted
+    mean probabilities, entropy their normalised entropy.  Stream-ordered, returns (vol, prob, entropy)."""
+    logits = list(logits)
+    if len(invs) != len(logits):
+        raise _lib.PnpError("paste_tiles: %d members with %d maps" % (len(logits), len(invs)))
+    if any(len(inv) != 6 for inv in invs):
+        raise _lib.PnpError("paste_tiles: every map has six entries")
+    shape = tuple(logits[0].shape) if logits else (1, 1, 1, 1)          # M = 0 (and M > 64) is the library's refusal, before anything is read
+    for t in logits:
+        if t.dim() != 4 or tuple(t.shape) != shape:
+            raise _lib.PnpError("paste_tiles: every member must be [B, H, W, ncls] of one shape, got %s and %s" % (shape, tuple(t.shape)))
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.PnpError("paste_tiles: logits must be contiguous float32 CUDA tensors (got %s %s) — there is no CPU fallback" % (t.device, t.dtype))
+    if not vol.is_cuda or vol.dtype != torch.uint8 or not vol.is_contiguous():
+        raise _lib.PnpError("paste_tiles: vol must be a contiguous uint8 CUDA tensor (got %s %s) — there is no CPU fallback" % (vol.device, vol.dtype))
+    B, H, W, ncls = (int(d) for d in shape)
+    for name, t, n in (("prob", prob, ncls * vol.numel()), ("entropy", entropy, vol.numel())) if logits else ():
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise _lib.PnpError("paste_tiles: %s must be a contiguous float32 CUDA tensor of %d elements (got %s %s, %d) — there is no CPU fallback"
+                                % (name, n, t.device, t.dtype, t.numel()))
+    M = len(logits)
+    ptrs = (ctypes.c_void_p * M)(*[t.data_ptr() for t in logits])
+    m = (ctypes.c_float * (6 * M))(*[float(v) for inv in invs for v in inv])
+    check(_lib.load().pnp_paste_tiles(M, ptrs, m, float(ramp), B, H, W, ncls, int(nb), int(z0), int(src_xy[0]), int(src_xy[1]),
+                                      ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
+                                      int(strides[2]), _p(prob), _p(entropy), _stream()), "pnp_paste_tiles")
+    return vol, prob, entropy
+
+
 # ---- connected components of label volumes (csrc/components.hip, components.py) ------------------------------------------------------------
 def _components_ws(vol):
     D0, D1, D2 = (int(d) for d in vol.shape)

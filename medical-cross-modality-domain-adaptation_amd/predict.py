@@ -7,6 +7,7 @@
            [--tta default|JSON] [--prob] [--entropy] [--ensemble CKPT [CKPT ...]]
            [--keep-largest [K]] [--min-size N] [--connectivity 1|2|3]
            [--sample-mm MM|PI,PJ,FRAME] [--prefilter auto|off|SX,SY,SZ]
+           [--tiles auto|NIxNJ [--tile-overlap F]]
 
 --list holds one `image.nii[.gz]` or `image.nii[.gz] label.nii[.gz]` per line (all lines alike; paths relative to the list's folder unless
 absolute).  The net is built as train_segmenter / train_gan build theirs, with their default configuration: `segmenter` is the source
@@ -27,6 +28,11 @@ taken from the voxel size in each file's header (--spacing is something else: th
 
 Anti-alias prefilter: --prefilter low-passes every normalised scan on the device before it is sampled (auto: sigma from
 the voxels per output pixel; SX,SY,SZ: sigmas in voxels).  Use the setting the checkpoint was trained with.
+
+Tiles: with --sample-mm the plane covers out_size x pixel size millimetres only; --tiles covers the whole (cropped) scan
+with overlapping planes of the same grid (auto: as many as the scan needs; NIxNJ: that many per in-plane axis) and blends them where
+they overlap, --tile-overlap F in [0, 0.5] being the least share of a plane that its neighbour repeats.  Members = checkpoints x tiles x
+views, at most 64; the share reported per file is then the union of the planes.
 """
 import argparse
 import json
@@ -53,6 +59,16 @@ def parse_crop(text):
             raise ValueError("--crop: the range %r is empty" % p)
         box.append((a, b))
     return tuple(box)
+
+
+def parse_tiles(text):
+    """'auto' -> "auto"; 'NIxNJ' -> (NI, NJ), both >= 1"""
+    if text == "auto":
+        return "auto"
+    parts = text.lower().split("x")
+    if len(parts) != 2 or not all(p.strip().isdigit() for p in parts) or any(int(p) < 1 for p in parts):
+        raise ValueError("--tiles: 'auto' or NIxNJ with two counts >= 1 expected, got %r" % text)
+    return int(parts[0]), int(parts[1])
 
 
 def read_list(list_file):
@@ -108,6 +124,10 @@ def parse_args(argv=None):
     from .volume_source import add_prefilter_flag, add_sample_mm_flag, prefilter_from_args, sample_mm_from_args
     add_sample_mm_flag(ap)
     add_prefilter_flag(ap)
+    ap.add_argument("--tiles", default=None, metavar="auto|NIxNJ", help="with --sample-mm: cover the whole (cropped) scan with overlapping "
+                    "planes of the millimetre grid and blend them (auto: as many as the scan needs; NIxNJ: counts per in-plane axis)")
+    ap.add_argument("--tile-overlap", type=float, default=None, metavar="F", help="with --tiles: the least share of a plane that its "
+                    "neighbour repeats, in [0, 0.5] (default 0.25)")
     a = ap.parse_args(argv)
     sample_mm = sample_mm_from_args(ap, a)
     prefilter = prefilter_from_args(ap, a)
@@ -148,11 +168,32 @@ def parse_args(argv=None):
             options["tta"] = tta_entries(tta)
         except ValueError as e:
             ap.error("--tta: %s" % e)
-    from .volume_predict import MAX_MEMBERS
+    tiles = None
+    if a.tiles is not None:
+        try:
+            tiles = parse_tiles(a.tiles)
+        except ValueError as e:
+            ap.error(str(e))
+        if sample_mm is None:
+            ap.error("--tiles needs --sample-mm: the planes of a tiled prediction share one millimetre grid")
+    if a.tile_overlap is not None:
+        if tiles is None:
+            ap.error("--tile-overlap goes with --tiles")
+        if not 0.0 <= a.tile_overlap <= 0.5:
+            ap.error("--tile-overlap: %r outside [0, 0.5]" % a.tile_overlap)
+    from .volume_predict import MAX_MEMBERS, MAX_TILE_MEMBERS
     members = (1 + len(a.ensemble or [])) * len(options.get("tta", [None]))
-    if members > MAX_MEMBERS:
+    planes = 1 if tiles in (None, "auto") else tiles[0] * tiles[1]          # auto: counted per scan, by segment_volume
+    if tiles is None and members > MAX_MEMBERS:
         ap.error("--ensemble / --tta: %d checkpoints x %d views = %d members, at most %d" % (1 + len(a.ensemble or []), len(options.get("tta", [None])),
                                                                                            members, MAX_MEMBERS))
+    if tiles is not None and members * planes > MAX_TILE_MEMBERS:
+        ap.error("--ensemble / --tta / --tiles: %d checkpoints x %d views x %d tiles = %d members, at most %d" % (
+            1 + len(a.ensemble or []), len(options.get("tta", [None])), planes, members * planes, MAX_TILE_MEMBERS))
+    if tiles is not None:
+        options["tiles"] = tiles
+        if a.tile_overlap is not None:
+            options["tile_overlap"] = a.tile_overlap
     if sample_mm is not None:
         options["sample_mm"] = sample_mm
     if prefilter is not None:

@@ -26,9 +26,14 @@ paste writes only the voxel columns inside the plane's field of view (pnp_paste_
 
 Anti-alias prefilter (opt-in): with prefilter= the normalised box is low-passed on the device (pnp_volume_smooth) before
 anything samples it, with volume_source.prefilter_sigmas' rule — the setting the network was trained with.
+
+Tiles (opt-in, needs sample_mm): with tiles= the crop box is covered by several overlapping planes of the same millimetre
+grid (tile_plan), every plane is predicted, and ONE pnp_paste_tiles launch per batch blends them over their union with a window that
+trusts a plane's centre more than its border.  Without the option nothing of this is reached.
 """
 import collections
 import logging
+import math
 import os
 
 import numpy as np
@@ -39,6 +44,7 @@ from .volume_source import (SAMPLE_DTYPE, SAMPLE_Z_DTYPE, AugmentedSliceSource, 
 
 EDGES = ("replicate", "skip")
 MAX_MEMBERS = 8                          # pnp_paste_ensemble's
+MAX_TILE_MEMBERS = 64                    # pnp_paste_tiles'
 TTA_KEYS = ("rotate", "scale", "translate", "flip")      # compose_matrix's keywords
 DEFAULT_TTA = ({}, {"rotate": 7.5}, {"rotate": -7.5}, {"scale": 0.95}, {"scale": 1.05})
 Ensemble = collections.namedtuple("Ensemble", ("label", "prob", "entropy"))
@@ -57,18 +63,77 @@ def invert_matrix(m, dtype=np.float32):
     return out.astype(dtype)
 
 
-def coverage(inv, X, Y, H, W):
-    """the share of the X * Y voxel columns that lie inside the field of view of EVERY given map (inv: six entries, or a list of such):
-    pnp_paste_*_fov's rule — unclamped plane coordinates in [-0.5, H - 0.5] x [-0.5, W - 0.5] — evaluated in float64 on the host from
-    the float32 entries the kernel gets"""
+def coverage(inv, X, Y, H, W, mode="all"):
+    """the share of the X * Y voxel columns that lie inside the field of view of EVERY given map (mode="all": pnp_paste_*_fov's columns)
+    or of AT LEAST ONE of them (mode="any": pnp_paste_tiles' columns); inv: six entries, or a list of such.  The rule — unclamped plane
+    coordinates in [-0.5, H - 0.5] x [-0.5, W - 0.5] — is evaluated in float64 on the host from the float32 entries the kernel gets"""
+    if mode not in ("all", "any"):
+        raise ValueError("coverage: mode must be 'all' or 'any', got %r" % (mode,))
     maps = np.asarray(inv, dtype=np.float32).astype(np.float64).reshape(-1, 6)
     x = np.arange(int(X), dtype=np.float64)[:, None]
     y = np.arange(int(Y), dtype=np.float64)[None, :]
-    ok = np.ones((int(X), int(Y)), dtype=bool)
+    ok = np.full((int(X), int(Y)), mode == "all", dtype=bool)
     for m in maps:
         pi, pj = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
-        ok &= (pi >= -0.5) & (pi <= H - 0.5) & (pj >= -0.5) & (pj <= W - 0.5)
+        inside = (pi >= -0.5) & (pi <= H - 0.5) & (pj >= -0.5) & (pj <= W - 0.5)
+        ok = ok & inside if mode == "all" else ok | inside
     return float(ok.mean())
+
+
+def check_tiles(tiles):
+    """None, "auto" or (ni, nj) with both counts >= 1 -> None / "auto" / a pair of ints; anything else is a ValueError"""
+    if tiles is None or (isinstance(tiles, str) and tiles == "auto"):
+        return tiles
+    try:
+        t = tuple(tiles)
+        ok = not isinstance(tiles, str) and len(t) == 2 and all(isinstance(n, (int, np.integer)) and not isinstance(n, bool) and n >= 1 for n in t)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError("tiles must be None, 'auto' or (ni, nj) with counts >= 1, got %r" % (tiles,))
+    return int(t[0]), int(t[1])
+
+
+def _axis_overlap_mm(L, F, n):
+    """what two neighbouring planes of extent F share when n of them, evenly spaced, lie flush in a box of extent L (n > 1)"""
+    return F - (L - F) / (n - 1)
+
+
+def tile_plan(extent_mm, fov_mm, tiles="auto", overlap=0.25):
+    """-> (offsets_mm, (ni, nj)): the planes that cover a box of extent_mm = (Li, Lj) with a field of view of fov_mm = (Fi, Fj) each.
+    Per in-plane axis n = 1 if L <= F, else ceil((L - o) / (F - o)) with o = overlap * F (overlap in [0, 0.5]: the least share of a plane
+    that its neighbour repeats); tiles = (ni, nj) overrides both counts.  The centres are evenly spaced, the first and the last plane lie
+    flush with the box's edges, a single plane is centred.  offsets_mm lists (ti, tj), the plane centres relative to the box's centre in
+    millimetres, tile-major (i outer, j inner): what is added to compose_matrix's `translate`.  ValueError: an overlap outside [0, 0.5],
+    extents that are not positive and finite, counts with n * F < L (they cannot cover the box)."""
+    tiles = check_tiles(tiles)
+    if tiles is None:
+        raise ValueError("tile_plan: tiles must be 'auto' or (ni, nj)")
+    overlap = float(overlap)
+    if not 0.0 <= overlap <= 0.5:
+        raise ValueError("tile overlap %r outside [0, 0.5]" % (overlap,))
+    L, F = tuple(float(v) for v in extent_mm), tuple(float(v) for v in fov_mm)
+    if len(L) != 2 or len(F) != 2 or not all(0.0 < v < math.inf for v in L + F):
+        raise ValueError("tile_plan: extent_mm %r and fov_mm %r must be two positive finite numbers each" % (extent_mm, fov_mm))
+    counts, centres = [], []
+    for a in range(2):
+        if tiles == "auto":
+            o = overlap * F[a]
+            n = 1 if L[a] <= F[a] else int(math.ceil((L[a] - o) / (F[a] - o)))
+        else:
+            n = tiles[a]
+            if n * F[a] < L[a]:
+                raise ValueError("tiles: %d planes of %g mm cannot cover %g mm along axis %d" % (n, F[a], L[a], a))
+        counts.append(n)
+        centres.append([0.0] if n == 1 else [(L[a] - F[a]) * (k / (n - 1.0) - 0.5) for k in range(n)])
+    return [(ti, tj) for ti in centres[0] for tj in centres[1]], (counts[0], counts[1])
+
+
+def tile_ramp(extent_mm, fov_mm, counts, pixel_mm):
+    """the window's rise in plane pixels for tile_plan's planes: max(1, the overlap of two neighbouring planes in plane pixels), the
+    smallest over the axes that have more than one plane; 1 if none has (or if neighbours only abut)"""
+    over = [_axis_overlap_mm(float(L), float(F), int(n)) / float(p) for L, F, n, p in zip(extent_mm, fov_mm, counts, pixel_mm) if n > 1]
+    return max(1.0, min(over)) if over else 1.0
 
 
 def file_layout(shape, flip_correction=True, axis=2, box=None):
@@ -145,20 +210,20 @@ def tta_entries(tta):
     return out
 
 
-def ensemble_members(logits_fn, tta):
-    """-> (callables, entries): the members are callables x entries, callable-major; more than MAX_MEMBERS is a ValueError"""
+def ensemble_members(logits_fn, tta, limit=MAX_MEMBERS):
+    """-> (callables, entries): the members are callables x entries, callable-major; more than `limit` is a ValueError"""
     fns = list(logits_fn) if isinstance(logits_fn, (list, tuple)) else [logits_fn]
     if not fns:
         raise ValueError("logits_fn: an empty list has no member")
     entries = tta_entries(tta)
-    if len(fns) * len(entries) > MAX_MEMBERS:
-        raise ValueError("%d callables x %d tta entries = %d members, at most %d" % (len(fns), len(entries), len(fns) * len(entries), MAX_MEMBERS))
+    if len(fns) * len(entries) > limit:
+        raise ValueError("%d callables x %d tta entries = %d members, at most %d" % (len(fns), len(entries), len(fns) * len(entries), limit))
     return fns, entries
 
 
 def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
                    out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None,
-                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None):
+                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25):
     """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
       logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
                  checkpoint ensemble
@@ -183,6 +248,16 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
                  are padded (the padding copies smoothed frames), with volume_source.prefilter_sigmas' sigmas from the box extents,
                  out_size, spacing and sample_mm; tta scales are ignored.  "auto" with spacing but without sample_mm is the plain resize's
                  rule.  The fill stays the unsmoothed minimum.  Use the setting the network was trained with.
+      tiles      None, "auto" or (ni, nj): cover the crop box with ni x nj overlapping planes of the millimetre grid (needs
+                 sample_mm) instead of the one centred plane.  tile_plan places them (tile_overlap in [0, 0.5]: the least share of a plane
+                 that its neighbour repeats); every batch gathers once per (tile, view), a tile's offset added in mm to the entry's
+                 translate, runs every callable on every gather and ends in ONE pnp_paste_tiles launch, which writes the columns that at
+                 least one member covers and blends the covering members' softmax with a window that rises over the planes' overlap.
+                 Members = callables x tiles x tta entries (in that order, callable-major), at most 64.  The result is the Ensemble tuple
+                 with the ensemble path's rules for prob, entropy, keep_largest and the short last batch; fov_stats gets the share of the
+                 columns that at least one member covers.  ALL members' logits of a batch are alive at once: members x 4 B H W num_cls
+                 bytes — 21 MB per member at the defaults, 1.3 GB at the limit of 64 members — beside one forward's activations.  On an
+                 MI355X (288 GB) no member count needs a smaller batch_size; where that product nears the free memory, halve batch_size.
       edge       "replicate": the normalised volume is padded with a copy of its first and last frame, every frame is predicted;
                  "skip": frames 1 .. Z - 2 only (the reference's frame set), the two edge frames stay 0
     Frames run in ascending order, batch_size at a time; the last, short batch repeats its last frame and pastes nb < B slices.  Nothing
@@ -205,9 +280,15 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         geom = {"spacing_xy": vox[:2], "pixel_mm": mm[:2]}
     else:
         geom = {}
-    ensemble = isinstance(logits_fn, (list, tuple)) or tta is not None or bool(prob) or bool(entropy)
+    tiles = check_tiles(tiles)
+    if tiles is not None:
+        if mm is None:
+            raise ValueError("tiles needs sample_mm: the planes of a tiled prediction share one millimetre grid")
+        if not 0.0 <= float(tile_overlap) <= 0.5:
+            raise ValueError("tile overlap %r outside [0, 0.5]" % (tile_overlap,))
+    ensemble = tiles is not None or isinstance(logits_fn, (list, tuple)) or tta is not None or bool(prob) or bool(entropy)
     if ensemble:
-        fns, entries = ensemble_members(logits_fn, tta)
+        fns, entries = ensemble_members(logits_fn, tta, MAX_MEMBERS if tiles is None else MAX_TILE_MEMBERS)
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.PnpError("segment_volume: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (device,))
@@ -217,6 +298,20 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     origin, strides, (X, Y, Z) = file_layout(image.shape, flip_correction, axis, box)
     if edge == "skip" and Z < 3:
         raise ValueError("edge='skip' needs at least 3 frames, the box has %d" % Z)
+    ramp = None
+    if tiles is not None:                               # the plan, before any device work: tile-major, then view
+        extent, plane_mm = (X * vox[0], Y * vox[1]), (H * mm[0], W * mm[1])
+        offsets, counts = tile_plan(extent, plane_mm, tiles, tile_overlap)
+        if len(fns) * len(offsets) * len(entries) > MAX_TILE_MEMBERS:
+            raise ValueError("%d callables x %d x %d tiles x %d tta entries = %d members, at most %d" % (
+                len(fns), counts[0], counts[1], len(entries), len(fns) * len(offsets) * len(entries), MAX_TILE_MEMBERS))
+        ramp = tile_ramp(extent, plane_mm, counts, mm[:2])
+        shifted = []
+        for ti, tj in offsets:
+            for e in entries:
+                t = e.get("translate", (0.0, 0.0))
+                shifted.append(dict(e, translate=(t[0] + ti, t[1] + tj)))
+        entries = shifted
     out = torch.zeros(tuple(image.shape), dtype=torch.uint8, device=device)
 
     v = torch.from_numpy(np.ascontiguousarray(img[tuple(slice(a, b) for a, b in box)])).to(device)
@@ -245,7 +340,7 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         maps = [compose_matrix((X, Y), (H, W), **e, **geom) for e in entries]
         invs = [invert_matrix(m) for m in maps] * len(fns)                  # callable-major, like the members
         if fov and fov_stats is not None:
-            fov_stats.append(coverage(invs, X, Y, H, W))
+            fov_stats.append(coverage(invs, X, Y, H, W, mode="all" if ramp is None else "any"))
         out_p = torch.zeros((int(num_cls),) + tuple(image.shape), dtype=torch.float32, device=device) if prob else None
         out_e = torch.zeros(tuple(image.shape), dtype=torch.float32, device=device) if entropy else None
         for k in range(0, count, B):
@@ -262,7 +357,10 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
                     if tuple(logits.shape) != (B, H, W, int(num_cls)):
                         raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
                     members.append(logits.detach().contiguous())
-            K.paste_ensemble(members, nb, first + k + shift, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e, fov=fov)
+            if ramp is not None:
+                K.paste_tiles(members, nb, first + k + shift, invs, ramp, (X, Y), out, origin, strides, prob=out_p, entropy=out_e)
+            else:
+                K.paste_ensemble(members, nb, first + k + shift, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e, fov=fov)
         src.close()
         _filter_components(out, post, num_cls, component_stats)
         return Ensemble(out, out_p, out_e)
@@ -320,7 +418,8 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
     ground truth with labels >= num_cls set to 0).  options: segment_volume's; with prob= / entropy= also prob_<basename> (float32,
     [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine; with keep_largest= every label volume written
     is the filtered one (component_stats=[]: one stats tensor per volume is appended); prefilter= is segment_volume's (the
-    setting the network was trained with); with sample_mm= every image's voxel size is read
+    setting the network was trained with); tiles= / tile_overlap= are segment_volume's (the share logged is then the union
+    of the planes); with sample_mm= every image's voxel size is read
     from its affine, the share of its voxel columns inside the field of view is logged, and a share below 1 is a warning (the voxels
     outside stay 0: choose crop / out_size / sample_mm so that the structure lies inside).  Returns the pred_* paths."""
     from . import nifti
