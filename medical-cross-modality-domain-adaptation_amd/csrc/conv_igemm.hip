@@ -1974,6 +1974,12 @@ bool narrow_fwd_ok(const pnp_conv_geom* g, NarrowArgs* na) {
     static const int off = getenv("PNP_CONV_NONARROW") ? 1 : 0;
     if (off || g->K > 16 || g->stride != 1 || g->pad_mode != PNP_PAD_ZERO || (g->C & 3) != 0 || g->C < 8) return false;
     if ((long long)g->N * g->OH * g->OW < 8192) return false;
+    // launch_narrow puts the images on the grid's z extent.  hipGetDeviceProperties on an MI355X (ROCm 7.2) reports maxGridSize =
+    // (2147483647, 65536, 65536), and hipDeviceAttributeMaxGridDimZ 65536: a launch past that is outside what HIP promises, so such a
+    // batch of tiny maps runs on the implicit GEMM.  The figure is a constant here because the route query must answer on hosts without
+    // a device.  n16_geom_ok (conv_small.hip) stops one short, at the 65535 of the CUDA-style limit it was written against; both are safe,
+    // and (65536, 1, 1, 16 -> 16) is the row of tests/test_gpu_igemm_domain.py that runs this kernel at the bound.
+    if (g->N > 65536) return false;
     // 9..16 outputs: the MFMA tile is half full, the vector ALUs only win while the work per pixel is small (16->16 3x3: 0.154 -> 0.130 ms;
     // 32->16 3x3, twice the work: 0.062 -> 0.071)
     if (g->K > 8 && (long long)g->R * g->S * g->C * g->K > 2304) return false;

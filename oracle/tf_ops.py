@@ -64,7 +64,7 @@ def conv2d(x, w, stride=1, dil=1, padding="SAME"):
     xn = x.permute(0, 3, 1, 2)
     if any(pads):
         xn = F.pad(xn, pads)
-    wn = w.permute(3, 2, 0, 1)
+    wn = w.permute(3, 2, 0, 1).contiguous()      # (float64 backward of some narrow filters: "slow_conv2d: grad_weight must be contiguous")
     y = F.conv2d(xn, wn, None, stride=stride, padding=0, dilation=dil)
     return y.permute(0, 2, 3, 1)
 

@@ -42,16 +42,17 @@ CASES = [
     (1, 14, 14, 32, 64, 5, 3, 1, "SAME"),       # stride 3, 5x5: phases with 2 and 1 taps per axis
     (2, 8, 8, 32, 32, 1, 2, 1, "SAME"),         # filter smaller than the stride: zero-upsampled fallback
     (2, 10, 10, 20, 24, 3, 2, 1, "SAME"),       # stride phases on the generic (C % 32 != 0) loaders
-    (2, 64, 64, 3, 16, 3, 1, 1, "SAME"),        # >= 8192 pixels, K <= 16: direct (vector-ALU) filter gradient, 27 pairs x 9 pixel groups
-    (2, 64, 64, 16, 16, 3, 1, 1, "SAME"),       # direct wgrad, 144 pairs, one group
-    (2, 68, 68, 40, 5, 5, 1, 1, "VALID"),       # direct wgrad, 1000 pairs = 4 per thread, K = 5 (the pre-padded logits conv)
+    (2, 64, 64, 3, 16, 3, 1, 1, "SAME"),        # >= 8192 pixels, 3 -> 16: the first layer's 16x16x4-MFMA kernels (N16 / NARROW over dy / N16_WGRAD: wgrad_c3n16_kernel)
+    (2, 64, 64, 16, 16, 3, 1, 1, "SAME"),       # 16 -> 16 at >= 8192 pixels: N16 forward and data gradient, filter gradient on wgrad_n16_kernel<16>
+    (2, 68, 68, 40, 5, 5, 1, 1, "VALID"),       # direct wgrad, 1000 pairs = 250 quads (wgrad_direct4_kernel), K = 5 (the pre-padded logits conv); NARROW forward
     (2, 128, 128, 5, 16, 3, 2, 1, "SAME"),      # direct wgrad with stride 2 (mask critic m_cls_1)
     (2, 64, 64, 8, 7, 3, 1, 1, "SAME"),         # direct wgrad, K = 7 on the 8-wide instance
     (2, 64, 64, 4, 12, 3, 1, 2, "SAME"),        # direct wgrad, K = 12 on the 16-wide instance, dilation 2
-    (2, 64, 64, 32, 12, 3, 1, 2, "SAME"),       # direct narrow-output forward, K = 12 on the 16-wide instance, dilation 2
-    (2, 64, 64, 16, 32, 3, 1, 1, "SAME"),       # data gradient with 16 INPUT channels: narrow-output kernel over dy (32 channels)
-    (2, 70, 66, 16, 16, 3, 1, 1, "SAME"),       # narrow kernels with ragged 8x32 output patches
-    (2, 33, 45, 64, 96, 3, 1, 1, "SAME"),       # ring filter gradient (rows >= 32 pixels), ragged rows / tiles, K not a tile multiple
+    (2, 64, 64, 32, 12, 3, 1, 2, "SAME"),       # 9 * 32 * 12 > 2304: the forward stays on the MFMA tiles; direct wgrad, K = 12, 288 pairs = 2 per thread, dilation 2
+    (2, 64, 64, 16, 32, 3, 1, 1, "SAME"),       # data gradient with 16 INPUT channels: conv_n16_kernel<32, 1> over dy (32 channels); filter gradient N16_WGRAD
+    (2, 70, 66, 16, 16, 3, 1, 1, "SAME"),       # the N16 kernels (forward, data and filter gradient) with ragged 8x32 output tiles
+    (2, 33, 45, 64, 96, 3, 1, 1, "SAME"),       # ragged rows / tiles, K not a tile multiple; the filter gradient is the Winograd route's under the default switches (the ring kernel
+                                                # with PNP_WINOGRAD=0: tests/test_gpu_igemm_domain.py)
     (2, 67, 65, 32, 48, 3, 2, 1, "SAME"),       # ring filter gradient walking a STRIDED output with odd extents (OW = 33)
     (1, 70, 70, 32, 64, 3, 2, 1, "VALID"),      # same, VALID: the last input row / column is never read (OW = 34)
     (2, 40, 72, 64, 64, 5, 2, 1, "SAME"),       # 5x5 stride 2 on the ring kernel (OW = 36), phases of the data gradient in one launch
