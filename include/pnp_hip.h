@@ -655,6 +655,27 @@ int pnp_paste_tiles(int32_t M, const float* const* logits, const float* inv, flo
                     int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
                     int64_t sz, float* prob /*nullable*/, float* entropy /*nullable*/, void* stream);
 
+/* ---- multi-planar fusion: several probability volumes of one grid -> label, mean probabilities, entropy (csrc/paste.hip) -----
+ *
+ * probs: HOST array of n_views device pointers (1 <= n_views <= 8), each ncls class-major planes of vol_elems float32 — class c of
+ * element e at probs[v][c * vol_elems + e], the layout pnp_paste_ensemble writes; weights: HOST array of n_views positive finite floats,
+ * NULL = all 1.  Per element e, in this order:
+ *   for v ascending: s_v = sum of probs[v][c][e] over ascending c (each step rounded); view v COVERS e iff s_v > 0.5 (a view's
+ *     probabilities sum to 1 within rounding where it predicted, and are exactly 0 where it did not; a NaN sum does not cover);
+ *   no covering view: label[e] = 0, prob[c][e] = 0 for every c, entropy[e] = 0;
+ *   otherwise, over the covering views in ascending v: acc_c += w_v * probs[v][c][e] (the product rounded, then the sum), wsum += w_v;
+ *     P_c = acc_c / wsum;  label[e] = the lowest c with the strictly largest P_c;  prob[c * vol_elems + e] = P_c (nullable);
+ *     entropy[e] from P as pnp_paste_ensemble's (nullable).
+ * EVERY element of label, prob and entropy is written (they may be uninitialised).  One view without weights reproduces its probabilities
+ * bit for bit.  prob may be probs[0] itself (every element's inputs are read before it is written); no atomics, bit-identical from run
+ * to run.  Bases aligned to 4 bytes only are served (16-byte accesses are used where all float bases share one phase of the 16-byte grid
+ * and ncls == 1 or vol_elems % 4 == 0).
+ * Refused on the host before any HIP call: n_views outside [1, 8]; ncls outside [1, 8]; vol_elems < 1; 4 * ncls * vol_elems overflowing
+ * int64; a null probs, view or label; a weight that is not positive and finite; a float pointer not aligned to 4 bytes; any overlap
+ * among the views, prob, entropy and label other than prob == probs[0]. */
+int pnp_fuse_views(int32_t n_views, const float* const* probs, const float* weights /*host, nullable*/, int32_t ncls, int64_t vol_elems,
+                   uint8_t* label, float* prob /*nullable*/, float* entropy /*nullable*/, void* stream);
+
 /* ---- connected components of label volumes (csrc/components.hip): keep the largest 3-D component of every structure -------
  *
  * vol: uint8 labels [D0, D1, D2], C order (D2 fastest: what pnp_paste_labels writes and a NIfTI reader returns), each extent in [1, 4096],

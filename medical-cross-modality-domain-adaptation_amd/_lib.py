@@ -202,6 +202,7 @@ PROTOTYPES = {
                                        c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, _F, _F, c_void_p]),
     "pnp_paste_tiles": (c_int, [c_int32, POINTER(c_void_p), POINTER(c_float), c_float, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                 c_int32, c_int32, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, _F, _F, c_void_p]),
+    "pnp_fuse_views": (c_int, [c_int32, POINTER(c_void_p), POINTER(c_float), c_int32, c_int64, c_void_p, _F, _F, c_void_p]),
     "pnp_components_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "pnp_label_components": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnp_filter_components": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_uint32, c_int32, c_int64, c_void_p, c_void_p,

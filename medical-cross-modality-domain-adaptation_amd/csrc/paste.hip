@@ -29,6 +29,10 @@
 //                         bits (two SGPRs).  Per frame: the wave walks the set bits of the union, so the member's pointer and map are scalar
 //                         loads from the kernel-argument block, and a lane whose own bit is clear skips the member; the covering member's
 //                         corner data and weight are recomputed from its six floats as above.  No accumulator volume, no atomics.
+//
+//   fuse_views_kernel        M <= 8 finished probability volumes of ONE grid (the views of a multi-planar prediction) -> label,
+//                         weighted mean probabilities over the views that cover a voxel, normalised entropy.  Pure streaming, no map: a lane
+//                         owns four consecutive elements (one float4 per plane) where the bases allow it, single elements otherwise.
 #include <algorithm>
 #include <math.h>
 
@@ -218,6 +222,16 @@ __device__ __forceinline__ int ensemble_at(const EnsembleArgs& A, float fx, floa
     return am;
 }
 
+// the normalised entropy of the probabilities P (a term with P_c == 0 contributes 0); inv_logn = 1 / logf(NCLS), 0 for NCLS == 1
+template <int NCLS>
+__device__ __forceinline__ float soft_entropy(const float (&P)[NCLS], float inv_logn) {
+    float h = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c)
+        if (P[c] > 0.f) h = fmaf(P[c], logf(P[c]), h);
+    return NCLS == 1 ? 0.f : -h * inv_logn;
+}
+
 // the probabilities P and their normalised entropy of one voxel at element index e (plain dword stores, one writer per element)
 template <int NCLS>
 __device__ __forceinline__ void store_soft(float* prob, float* entropy, long long vol_elems, long long e, const float (&P)[NCLS], float inv_logn) {
@@ -225,13 +239,7 @@ __device__ __forceinline__ void store_soft(float* prob, float* entropy, long lon
 #pragma unroll
         for (int c = 0; c < NCLS; ++c) prob[(long long)c * vol_elems + e] = P[c];
     }
-    if (entropy) {
-        float h = 0.f;
-#pragma unroll
-        for (int c = 0; c < NCLS; ++c)
-            if (P[c] > 0.f) h = fmaf(P[c], logf(P[c]), h);
-        entropy[e] = NCLS == 1 ? 0.f : -h * inv_logn;
-    }
+    if (entropy) entropy[e] = soft_entropy<NCLS>(P, inv_logn);
 }
 
 // the z-fastest store path of the soft kernels, one label per call in address order (t counts elements from e0, the lowest address): labels
@@ -398,6 +406,136 @@ __global__ void __launch_bounds__(kThreads) paste_tiles_kernel(const TilesArgs A
     }
 }
 
+// ---- multi-planar fusion (pnp_fuse_views) ------------------------------------------------------------------------------------
+constexpr int kMaxViews = 8;
+constexpr int kFuseBlocks = 2048;          // 256 CUs x 8 blocks of 256 threads: the grid of a pass, the rest is the grid's stride
+
+struct FuseArgs {
+    const float* probs[kMaxViews];         // ncls planes of vol_elems floats each
+    float w[kMaxViews];
+    unsigned char* label;
+    float* prob;               // nullable; may be probs[0]
+    float* entropy;            // nullable
+    long long vol_elems;
+    long long head;            // elements before the first 16-byte boundary of the float planes (0 without the wide path)
+    long long nvec;            // groups of four elements from `head` on that go through 16-byte accesses (0: everything is scalar)
+    int n_views;
+    int label_word;            // label + head is 4-byte aligned: a group's four labels go out as one dword
+};
+
+// one element's accumulators: add(p, w) takes view v's NCLS values and its weight, v ascending.  Products are rounded
+// before their sum (no contraction, as in tiles_at): classes that are bit-identical in every view stay bit-identical in acc.
+template <int NCLS>
+struct Fuse {
+    float acc[NCLS];
+    float wsum;
+    __device__ __forceinline__ void clear() {
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) acc[c] = 0.f;
+        wsum = 0.f;
+    }
+    __device__ __forceinline__ void add(const float (&p)[NCLS], float w) {
+#pragma clang fp contract(off)
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) s += p[c];
+        if (s > 0.5f) {                    // the view covers this element (a NaN sum does not)
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) acc[c] += w * p[c];
+            wsum += w;
+        }
+    }
+    // P (all 0 where no view covers) and the first strict maximum of P
+    __device__ __forceinline__ int finish(float (&P)[NCLS]) const {
+        int am = 0;
+        float best = 0.f;
+#pragma unroll
+        for (int c = 0; c < NCLS; ++c) {
+            P[c] = wsum > 0.f ? acc[c] / wsum : 0.f;
+            if (c == 0 || P[c] > best) {
+                best = P[c];
+                am = c;
+            }
+        }
+        return am;
+    }
+    // store_soft's entropy of P; +0 where no view covers
+    __device__ __forceinline__ float entropy(const float (&P)[NCLS], float inv_logn) const {
+        return wsum > 0.f ? soft_entropy<NCLS>(P, inv_logn) : 0.f;
+    }
+};
+
+// Work items of the wide path: group i covers elements head + 4 i .. head + 4 i + 3, every plane read and written as one float4 per lane
+// (consecutive lanes, consecutive groups: 1 KiB per wave and instruction).  The scalar items are the `head` elements before the groups
+// and the tail after them — all elements when the bases or vol_elems do not allow 16-byte accesses — one element per lane and pass.
+// Every lane reads all inputs of its elements before its first store: prob may be probs[0].
+template <int NCLS>
+__global__ void __launch_bounds__(kThreads) fuse_views_kernel(const FuseArgs A) {
+    const long long stride = (long long)gridDim.x * kThreads;
+    const long long gid = (long long)blockIdx.x * kThreads + threadIdx.x;
+    const float inv_logn = NCLS > 1 ? 1.f / logf((float)NCLS) : 0.f;
+    const long long n = A.vol_elems;
+    for (long long i = gid; i < A.nvec; i += stride) {
+        const long long e = A.head + 4 * i;
+        Fuse<NCLS> f[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) f[u].clear();
+        for (int v = 0; v < A.n_views; ++v) {
+            float4 q[NCLS];
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) q[c] = *(const float4*)(A.probs[v] + (long long)c * n + e);
+            const float w = A.w[v];
+            float p[NCLS];
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) p[c] = q[c].x;
+            f[0].add(p, w);
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) p[c] = q[c].y;
+            f[1].add(p, w);
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) p[c] = q[c].z;
+            f[2].add(p, w);
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) p[c] = q[c].w;
+            f[3].add(p, w);
+        }
+        float P[4][NCLS], h[4];
+        unsigned int lab = 0u;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            lab |= (unsigned int)f[u].finish(P[u]) << (8 * u);
+            h[u] = f[u].entropy(P[u], inv_logn);
+        }
+        if (A.prob) {
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) *(float4*)(A.prob + (long long)c * n + e) = make_float4(P[0][c], P[1][c], P[2][c], P[3][c]);
+        }
+        if (A.entropy) *(float4*)(A.entropy + e) = make_float4(h[0], h[1], h[2], h[3]);
+        if (A.label_word) {
+            *(unsigned int*)(A.label + e) = lab;
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) A.label[e + u] = (unsigned char)(lab >> (8 * u));
+        }
+    }
+    const long long body_end = A.head + 4 * A.nvec, nscalar = n - 4 * A.nvec;
+    for (long long i = gid; i < nscalar; i += stride) {
+        const long long e = i < A.head ? i : body_end + (i - A.head);
+        Fuse<NCLS> f;
+        f.clear();
+        for (int v = 0; v < A.n_views; ++v) {
+            float p[NCLS];
+#pragma unroll
+            for (int c = 0; c < NCLS; ++c) p[c] = A.probs[v][(long long)c * n + e];
+            f.add(p, A.w[v]);
+        }
+        float P[NCLS];
+        A.label[e] = (unsigned char)f.finish(P);
+        store_soft<NCLS>(A.prob, nullptr, n, e, P, inv_logn);
+        if (A.entropy) A.entropy[e] = f.entropy(P, inv_logn);
+    }
+}
+
 long long abs_ll(long long v) { return v < 0 ? -v : v; }
 
 // the argument checks both entry points share (everything but the null pointers), with the caller's name in the text
@@ -540,9 +678,78 @@ int paste_tiles_launch(const char* who, int32_t M, const float* const* logits, c
     return PNP_OK;
 }
 
+int fuse_views_launch(const char* who, int32_t n_views, const float* const* probs, const float* weights, int32_t ncls, int64_t vol_elems,
+                      uint8_t* label, float* prob, float* entropy, void* stream) {
+    PNP_REQUIRE(n_views >= 1 && n_views <= kMaxViews, "%s: n_views = %d outside [1, %d]", who, (int)n_views, kMaxViews);
+    PNP_REQUIRE(ncls >= 1 && ncls <= MAXC, "%s: ncls %d outside [1, %d]", who, (int)ncls, MAXC);
+    PNP_REQUIRE(vol_elems >= 1, "%s: vol_elems = %lld, at least one element is needed", who, (long long)vol_elems);
+    PNP_REQUIRE((__int128)ncls * vol_elems * 4 <= (__int128)INT64_MAX, "%s: ncls * vol_elems = %d * %lld floats overflow int64", who, (int)ncls,
+                (long long)vol_elems);
+    PNP_REQUIRE(probs && label, "%s: null pointer", who);
+    for (int v = 0; v < n_views; ++v) {
+        PNP_REQUIRE(probs[v], "%s: view %d of %d is a null pointer", who, v, (int)n_views);
+        if (weights)
+            PNP_REQUIRE(std::isfinite(weights[v]) && weights[v] > 0.f, "%s: weight %d = %g must be positive and finite", who, v, (double)weights[v]);
+    }
+    uintptr_t low = (uintptr_t)prob | (uintptr_t)entropy;             // a null pointer adds no bits
+    for (int v = 0; v < n_views; ++v) low |= (uintptr_t)probs[v];
+    PNP_REQUIRE((low & 3u) == 0, "%s: a float buffer is not aligned to 4 bytes", who);
+    // byte ranges of every buffer: the views, then prob, entropy, label.  prob == probs[0] is the one overlap that is served.
+    struct Range { uintptr_t lo, hi; const char* name; };
+    Range r[kMaxViews + 3];
+    int nr = 0;
+    const uintptr_t planes = (uintptr_t)ncls * (uintptr_t)vol_elems * 4u;
+    for (int v = 0; v < n_views; ++v) r[nr++] = {(uintptr_t)probs[v], (uintptr_t)probs[v] + planes, "a view"};
+    if (prob) r[nr++] = {(uintptr_t)prob, (uintptr_t)prob + planes, "prob"};
+    if (entropy) r[nr++] = {(uintptr_t)entropy, (uintptr_t)entropy + (uintptr_t)vol_elems * 4u, "entropy"};
+    r[nr++] = {(uintptr_t)label, (uintptr_t)label + (uintptr_t)vol_elems, "label"};
+    for (int a = 0; a < nr; ++a)
+        for (int b = a + 1; b < nr; ++b) {
+            if (a == 0 && prob && b == n_views && r[a].lo == r[b].lo) continue;
+            PNP_REQUIRE(r[a].hi <= r[b].lo || r[b].hi <= r[a].lo, "%s: %s overlaps %s (buffers %d and %d; only prob == probs[0] may alias)", who,
+                        r[a].name, r[b].name, a, b);
+        }
+    FuseArgs A;
+    for (int v = 0; v < kMaxViews; ++v) {
+        A.probs[v] = probs[v < n_views ? v : 0];
+        A.w[v] = weights && v < n_views ? weights[v] : 1.f;
+    }
+    A.label = label;
+    A.prob = prob;
+    A.entropy = entropy;
+    A.vol_elems = vol_elems;
+    A.n_views = n_views;
+    // 16-byte accesses need every float plane on one phase of the 16-byte grid: bases that differ from a boundary by the same number of
+    // floats (float-aligned at least), and planes a multiple of four floats apart (or a single plane).  `head` elements lead up to it.
+    bool wide = ncls == 1 || vol_elems % 4 == 0;
+    const uintptr_t phase = (uintptr_t)A.probs[0] & 15u;
+    for (int v = 0; v < n_views && wide; ++v) wide = ((uintptr_t)A.probs[v] & 15u) == phase;
+    if (prob) wide = wide && ((uintptr_t)prob & 15u) == phase;
+    if (entropy) wide = wide && ((uintptr_t)entropy & 15u) == phase;
+    A.head = wide ? (long long)(((16u - phase) & 15u) / 4u) : 0;
+    if (A.head > vol_elems) A.head = vol_elems;
+    A.nvec = wide ? (vol_elems - A.head) / 4 : 0;
+    A.label_word = (((uintptr_t)label + (uintptr_t)A.head) & 3u) == 0;
+    const long long items = std::max(A.nvec, vol_elems - 4 * A.nvec);
+    const unsigned blocks = (unsigned)std::min<long long>((items + kThreads - 1) / kThreads, kFuseBlocks);
+    switch (ncls) {
+#define PNP_FUSE_CASE(n) case n: hipLaunchKernelGGL((fuse_views_kernel<n>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
+        PNP_FUSE_CASE(1) PNP_FUSE_CASE(2) PNP_FUSE_CASE(3) PNP_FUSE_CASE(4)
+        PNP_FUSE_CASE(5) PNP_FUSE_CASE(6) PNP_FUSE_CASE(7) PNP_FUSE_CASE(8)
+#undef PNP_FUSE_CASE
+    }
+    PNP_CHECK_LAUNCH("fuse_views_kernel");
+    return PNP_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pnp_fuse_views(int32_t n_views, const float* const* probs, const float* weights, int32_t ncls, int64_t vol_elems, uint8_t* label,
+                   float* prob, float* entropy, void* stream) {
+    return fuse_views_launch("pnp_fuse_views", n_views, probs, weights, ncls, vol_elems, label, prob, entropy, stream);
+}
 
 int pnp_paste_labels(const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0, const float* inv,
                      int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,

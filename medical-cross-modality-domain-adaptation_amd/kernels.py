@@ -1178,6 +1178,49 @@ def paste_tiles(logits, nb, z0, invs, ramp, src_xy, vol, origin, strides, prob=N
     return vol, prob, entropy
 
 
+def fuse_views(probs, weights=None, label=None, prob=None, entropy=None):
+    """pnp_fuse_views: probs = 1 .. 8 contiguous float32 CUDA tensors [ncls, ...] of one shape (the probability volumes
+    of the views of one scan, class-major as paste_ensemble writes them), weights: None or one positive finite number per view (host).
+    Per voxel, over the views whose probabilities sum to more than 0.5 there: label = the first strict maximum of the weighted mean
+    probabilities, prob = that mean, entropy = its normalised entropy; a voxel no view covers gets 0 in all three.
+    label: a contiguous uint8 CUDA tensor of the voxel count (None: a new one of the views' spatial shape); prob / entropy: True = a new
+    tensor, a tensor = written in place (prob may be probs[0] itself; any other overlap is refused), None / False = not computed.  Every
+    element of the outputs is written.  Stream-ordered, returns (label, prob, entropy)."""
+    probs = list(probs)
+    M = len(probs)
+    if M == 0:                                                  # the library's refusal (as M > 8 is), before anything is read
+        check(_lib.load().pnp_fuse_views(0, None, None, 1, 1, None, None, None, None), "pnp_fuse_views")
+    shape = tuple(probs[0].shape)
+    for t in probs:
+        if not torch.is_tensor(t) or t.dim() < 2 or tuple(t.shape) != shape:
+            raise _lib.PnpError("fuse_views: every view must be [ncls, ...] of one shape, got %s and %s" % (shape, tuple(getattr(t, "shape", ()))))
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.PnpError("fuse_views: views must be contiguous float32 CUDA tensors (got %s %s) — there is no CPU fallback" % (t.device, t.dtype))
+    ncls = int(shape[0])
+    elems = 1
+    for d in shape[1:]:
+        elems *= int(d)
+    if weights is not None and len(weights) != M:
+        raise _lib.PnpError("fuse_views: %d weights for %d views" % (len(weights), M))
+    dev = probs[0].device
+    if label is None:
+        label = torch.empty(shape[1:], dtype=torch.uint8, device=dev)
+    prob = torch.empty(shape, dtype=torch.float32, device=dev) if prob is True else None if prob is False else prob
+    entropy = torch.empty(shape[1:], dtype=torch.float32, device=dev) if entropy is True else None if entropy is False else entropy
+    if not torch.is_tensor(label) or not label.is_cuda or label.dtype != torch.uint8 or not label.is_contiguous() or label.numel() != elems:
+        raise _lib.PnpError("fuse_views: label must be a contiguous uint8 CUDA tensor of %d elements (got %s %s, %d) — there is no CPU fallback"
+                            % (elems, label.device, label.dtype, label.numel()))
+    for name, t, n in (("prob", prob, ncls * elems), ("entropy", entropy, elems)):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise _lib.PnpError("fuse_views: %s must be a contiguous float32 CUDA tensor of %d elements (got %s %s, %d) — there is no CPU fallback"
+                                % (name, n, t.device, t.dtype, t.numel()))
+    ptrs = (ctypes.c_void_p * M)(*[t.data_ptr() for t in probs])
+    w = None if weights is None else (ctypes.c_float * M)(*[float(v) for v in weights])
+    check(_lib.load().pnp_fuse_views(M, ptrs, w, ncls, elems, ctypes.c_void_p(label.data_ptr()), _p(prob), _p(entropy), _stream()),
+          "pnp_fuse_views")
+    return label, prob, entropy
+
+
 # ---- connected components of label volumes (csrc/components.hip, components.py) ------------------------------------------------------------
 def _components_ws(vol):
     D0, D1, D2 = (int(d) for d in vol.shape)

@@ -8,6 +8,7 @@
            [--keep-largest [K]] [--min-size N] [--connectivity 1|2|3]
            [--sample-mm MM|PI,PJ,FRAME] [--prefilter auto|off|SX,SY,SZ]
            [--tiles auto|NIxNJ [--tile-overlap F]]
+           [--axes 0,1,2 [--axis-weights 1,1,2]]
 
 --list holds one `image.nii[.gz]` or `image.nii[.gz] label.nii[.gz]` per line (all lines alike; paths relative to the list's folder unless
 absolute).  The net is built as train_segmenter / train_gan build theirs, with their default configuration: `segmenter` is the source
@@ -33,6 +34,12 @@ Tiles: with --sample-mm the plane covers out_size x pixel size 
 with overlapping planes of the same grid (auto: as many as the scan needs; NIxNJ: that many per in-plane axis) and blends them where
 they overlap, --tile-overlap F in [0, 0.5] being the least share of a plane that its neighbour repeats.  Members = checkpoints x tiles x
 views, at most 64; the share reported per file is then the union of the planes.
+
+Multi-planar fusion: --axes 0,1,2 predicts every scan once per listed slicing axis and fuses the probability volumes,
+per voxel over the views that wrote it, optionally weighted by --axis-weights (one positive number per axis).  It excludes a non-default
+--axis and composes with every option above, each of which applies to every view; the member limits hold per view, --keep-largest filters
+the fused labels, and with --sample-mm one share is reported per view.  --crop stays in the slicing order of the default axis.  Use a
+checkpoint that was trained on all the listed orientations (train_segmenter / train_gan --axes).
 """
 import argparse
 import json
@@ -121,9 +128,10 @@ def parse_args(argv=None):
     ap.add_argument("--ensemble", nargs="+", default=None, metavar="CKPT", help="further checkpoints of the same --net, averaged with --model")
     from . import components
     components.add_cli_arguments(ap)
-    from .volume_source import add_prefilter_flag, add_sample_mm_flag, prefilter_from_args, sample_mm_from_args
+    from .volume_source import add_axes_flag, add_prefilter_flag, add_sample_mm_flag, axes_from_args, prefilter_from_args, sample_mm_from_args
     add_sample_mm_flag(ap)
     add_prefilter_flag(ap)
+    add_axes_flag(ap, weights=True)
     ap.add_argument("--tiles", default=None, metavar="auto|NIxNJ", help="with --sample-mm: cover the whole (cropped) scan with overlapping "
                     "planes of the millimetre grid and blend them (auto: as many as the scan needs; NIxNJ: counts per in-plane axis)")
     ap.add_argument("--tile-overlap", type=float, default=None, metavar="F", help="with --tiles: the least share of a plane that its "
@@ -131,6 +139,9 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     sample_mm = sample_mm_from_args(ap, a)
     prefilter = prefilter_from_args(ap, a)
+    axes, axis_weights = axes_from_args(ap, a)
+    if axes is not None and a.axis != 2:
+        ap.error("--axes and --axis exclude each other")
     if (a.images is None) == (a.list is None):
         ap.error("give either --images or --list")
     try:
@@ -198,6 +209,10 @@ def parse_args(argv=None):
         options["sample_mm"] = sample_mm
     if prefilter is not None:
         options["prefilter"] = prefilter
+    if axes is not None:                     # entered only when given, like the options above
+        options["axes"] = axes
+        if axis_weights is not None:
+            options["axis_weights"] = axis_weights
     if a.prob:
         options["prob"] = True
     if a.entropy:

@@ -599,7 +599,8 @@ class Trainer(object):
         flip_correction, batch_size [default: the net's], percentile, out_size; tta, prob, entropy: DESIGN.md §15, which also write prob_* /
         entropy_* files; keep_largest, component_stats: the connected-component filter of DESIGN.md §16;
         sample_mm: the millimetre grid of DESIGN.md §17, with each file's voxel size read from its affine; prefilter: the anti-alias prefilter of DESIGN.md §19;
-        tiles, tile_overlap: with sample_mm, overlapping planes that cover the whole crop box, blended by pnp_paste_tiles: DESIGN.md §20).  ensemble: further nets of this class, averaged with this trainer's.  Returns the pred_* paths.  test_eval is untouched."""
+        tiles, tile_overlap: with sample_mm, overlapping planes that cover the whole crop box, blended by pnp_paste_tiles: DESIGN.md §20;
+        axes, axis_weights: multi-planar fusion, one prediction per listed slicing axis fused by pnp_fuse_views: DESIGN.md §21).  ensemble: further nets of this class, averaged with this trainer's.  Returns the pred_* paths.  test_eval is untouched."""
         from . import volume_predict as vp
         options.setdefault("batch_size", self.net.batch_size)
         if tiles is not None:              # entered only when given: without it segment_volume takes the path it took before

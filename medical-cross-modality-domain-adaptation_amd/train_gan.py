@@ -4,7 +4,7 @@
   --phase fine-tune : continue from a breakpoint (the reference's `training_config` NameError at train_gan.py:121 is fixed)
 Extra flags: --synthetic N, --batch-size, --iters, --epochs, --output, --baseline (source-segmenter .npz for the pre-train hand-off),
 --mr-nii-train / --mr-nii-val / --ct-nii-train / --ct-nii-val LIST (all four: train from NIfTI volumes kept on the device,
-volume_source.py; --augment JSON / --no-augment), --gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference).
+volume_source.py; --augment JSON / --no-augment; --axes 0,1,2: slices of every listed orientation, one value for MR and CT), --gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference).
 """
 import argparse
 import datetime
@@ -74,11 +74,14 @@ def parse_args(phase, argv=None):
     for flag in NII_FLAGS:
         ap.add_argument("--" + flag.replace("_", "-"), default=None, metavar="LIST", help="NIfTI list file (one `image.nii[.gz] "
                         "label.nii[.gz]` pair per line, volume_source.py); the four --*-nii-* flags go together")
-    from .volume_source import add_augment_flags, add_prefilter_flag, add_sample_mm_flag, prefilter_from_args, sample_mm_from_args
+    from .volume_source import (add_augment_flags, add_axes_flag, add_prefilter_flag, add_sample_mm_flag, axes_from_args, prefilter_from_args,
+                                sample_mm_from_args)
     add_augment_flags(ap)
     add_sample_mm_flag(ap)
     add_prefilter_flag(ap)
+    add_axes_flag(ap)
     args = ap.parse_args(argv)
+    args.axes = axes_from_args(ap, args)                    # one value serves MR and CT
     args.sample_mm = sample_mm_from_args(ap, args)          # one grid for both modalities: that is the point
     args.prefilter = prefilter_from_args(ap, args)          # one setting for both: the per-volume sigmas differ through the spacings
     given = [getattr(args, f) is not None for f in NII_FLAGS]
@@ -90,6 +93,8 @@ def parse_args(phase, argv=None):
         ap.error("--sample-mm goes with the --*-nii-* lists")
     if args.prefilter is not None and not all(given):
         ap.error("--prefilter goes with the --*-nii-* lists")
+    if args.axes is not None and not all(given):
+        ap.error("--axes goes with the --*-nii-* lists")
     if not args.gp_weight >= 0.0:
         ap.error("--gp-weight must be >= 0, got %r" % args.gp_weight)
     if args.gp_weight > 0 and args.dtype != "f32":
@@ -126,9 +131,9 @@ def main(phase, argv=None):
         from .volume_source import augment_from_args, sources_from_lists
         shard = (rank, world) if world > 1 else None
         mr_train, mr_val = sources_from_lists(args.mr_nii_train, args.mr_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
-                                              seed=0, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter)
+                                              seed=0, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter, axes=args.axes)
         ct_train, ct_val = sources_from_lists(args.ct_nii_train, args.ct_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
-                                              seed=2, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter)
+                                              seed=2, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter, axes=args.axes)
     elif args.synthetic:
         from .synthetic import write_dataset
         sets = (("syn_mr_train", args.synthetic, 0, "mr"), ("syn_ct_train", args.synthetic, 1, "ct"),

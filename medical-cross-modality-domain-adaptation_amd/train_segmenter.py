@@ -2,7 +2,8 @@
 source segmenter.  Extra flags (defaults keep the reference behaviour): --synthetic N writes N synthetic tfrecords and trains on
 them, --batch-size, --iters, --epochs, --output; --nii-train LIST --nii-val LIST train from NIfTI volumes kept on the device
 (volume_source.py: one `image.nii[.gz] label.nii[.gz]` pair per line; --augment JSON / --no-augment; --sample-mm MM|PI,PJ,FRAME samples them on
-a millimetre grid; --prefilter auto|off|SX,SY,SZ low-passes them first).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
+a millimetre grid; --prefilter auto|off|SX,SY,SZ low-passes them first; --axes 0,1,2 trains on slices of
+every listed orientation).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
 one process per GPU over RCCL, --batch-size slices PER RANK, file lists sharded by rank, rank 0 writes the checkpoint.
   python -m "medical-cross-modality-domain-adaptation_amd.train_segmenter" --synthetic 8 --batch-size 4 --iters 2 --epochs 1
 """
@@ -33,14 +34,18 @@ def main(argv=None):
     ap.add_argument("--nii-train", default=None, metavar="LIST", help="train from NIfTI volumes resident on the device: a list file with one "
                     "`image.nii[.gz] label.nii[.gz]` pair per line (volume_source.py); needs --nii-val")
     ap.add_argument("--nii-val", default=None, metavar="LIST", help="validation volumes (never augmented)")
-    from .volume_source import (add_augment_flags, add_prefilter_flag, add_sample_mm_flag, augment_from_args, prefilter_from_args,
-                                sample_mm_from_args)
+    from .volume_source import (add_augment_flags, add_axes_flag, add_prefilter_flag, add_sample_mm_flag, augment_from_args, axes_from_args,
+                                prefilter_from_args, sample_mm_from_args)
     add_augment_flags(ap)
     add_sample_mm_flag(ap)
     add_prefilter_flag(ap)
+    add_axes_flag(ap)
     args = ap.parse_args(argv)
     sample_mm = sample_mm_from_args(ap, args)
     prefilter = prefilter_from_args(ap, args)
+    axes = axes_from_args(ap, args)
+    if axes is not None and not args.nii_train:
+        ap.error("--axes goes with --nii-train / --nii-val")
     if sample_mm is not None and not args.nii_train:
         ap.error("--sample-mm goes with --nii-train / --nii-val")
     if prefilter is not None and not args.nii_train:
@@ -73,7 +78,7 @@ def main(argv=None):
         from .volume_source import sources_from_lists
         train_list, val_list = sources_from_lists(args.nii_train, args.nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
                                                   shard=(rank, world) if world > 1 else None, sample_mm=sample_mm,
-                                                  prefilter=prefilter)
+                                                  prefilter=prefilter, axes=axes)
     elif args.synthetic:
         from .synthetic import write_dataset
         # next to (not inside) output_path: Trainer.train(restore=False) clears output_path like the reference (source_segmenter.py:416-418)

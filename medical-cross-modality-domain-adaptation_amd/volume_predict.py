@@ -30,6 +30,10 @@ anything samples it, with volume_source.prefilter_sigmas' rule — the setting t
 Tiles (opt-in, needs sample_mm): with tiles= the crop box is covered by several overlapping planes of the same millimetre
 grid (tile_plan), every plane is predicted, and ONE pnp_paste_tiles launch per batch blends them over their union with a window that
 trusts a plane's centre more than its border.  Without the option nothing of this is reached.
+
+Multi-planar fusion (opt-in): with axes= the scan is predicted once per listed slicing axis by the single-axis path above
+(every other option applies to each view), and ONE pnp_fuse_views launch averages the views' probability volumes over the views that
+cover a voxel (check_axes, view_box, fuse_views).  Without the option nothing of this is reached.
 """
 import collections
 import logging
@@ -39,8 +43,8 @@ import os
 import numpy as np
 
 from . import _lib
-from .volume_source import (SAMPLE_DTYPE, SAMPLE_Z_DTYPE, AugmentedSliceSource, VolumeSet, check_prefilter, check_sample_mm, check_spacing,
-                            compose_matrix, gaussian_weights, label_bounding_box, prefilter_sigmas, prepare_pair, slicing_order)
+from .volume_source import (SAMPLE_DTYPE, SAMPLE_Z_DTYPE, AugmentedSliceSource, VolumeSet, check_axes, check_prefilter, check_sample_mm,
+                            check_spacing, compose_matrix, gaussian_weights, label_bounding_box, prefilter_sigmas, prepare_pair, slicing_order)
 
 EDGES = ("replicate", "skip")
 MAX_MEMBERS = 8                          # pnp_paste_ensemble's
@@ -166,6 +170,50 @@ def _box_of(crop, label, dims):
     return box
 
 
+def view_box(box, axis):
+    """an explicit crop box ((x0, x1), (y0, y1), (z0, z1)) given in the slicing order of the default axis (2: the array's own order after
+    the flips) -> the same voxel set in the slicing order of `axis`: the ranges permuted as prepare_pair's moveaxis(axis, -1) permutes
+    the array's axes"""
+    if axis not in (0, 1, 2):
+        raise ValueError("view_box: axis %r is not one of 0, 1, 2" % (axis,))
+    b = [(int(lo), int(hi)) for lo, hi in box]
+    if len(b) != 3:
+        raise ValueError("crop box %r: three ranges expected" % (box,))
+    return tuple(b[:axis] + b[axis + 1:] + [b[axis]])
+
+
+def fuse_views(views, weights=None, prob=True, entropy=False):
+    """views: the Ensemble tuples (their .prob is used) or bare probability tensors [num_cls, *shape] of several predictions of ONE scan on
+    one device — segment_volume(prob=True) results for different slicing axes, or for groups of checkpoints that do not fit one call's
+    member limit -> Ensemble(label, prob, entropy) by one pnp_fuse_views launch: per voxel the weighted mean over the
+    views that cover it (whose probabilities are not all 0 there), its first strict maximum and its normalised entropy; a voxel that no
+    view covers is 0 in all three.  weights: None or one positive finite number per view.  The inputs are left as they are; prob /
+    entropy: whether those two are computed (None otherwise)."""
+    from . import kernels as K
+    probs = []
+    for n, v in enumerate(views):
+        p = v.prob if isinstance(v, Ensemble) else v
+        if p is None:
+            raise ValueError("fuse_views: view %d carries no probabilities (predict it with prob=True)" % n)
+        probs.append(p)
+    if not probs:
+        raise ValueError("fuse_views: no view")
+    if weights is not None:
+        weights = _check_weights(weights, len(probs))
+    label, p, h = K.fuse_views(probs, weights, prob=bool(prob), entropy=bool(entropy))
+    return Ensemble(label, p, h)
+
+
+def _check_weights(weights, n):
+    try:
+        w = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        raise ValueError("fuse_views: weights must be %d positive finite numbers, got %r" % (n, weights))
+    if len(w) != n or not all(0.0 < v < math.inf for v in w):
+        raise ValueError("fuse_views: weights must be %d positive finite numbers, got %r" % (n, weights))
+    return w
+
+
 def tta_entries(tta):
     """None -> [{}]; "default" -> DEFAULT_TTA; a list of dicts of compose_matrix's keywords -> a list of validated copies.  Raises ValueError
     for an empty list, an entry that is no dict, unknown keys and values compose_matrix cannot take (checked here, on the host)."""
@@ -223,7 +271,7 @@ def ensemble_members(logits_fn, tta, limit=MAX_MEMBERS):
 
 def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
                    out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None,
-                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25):
+                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25, axes=None, axis_weights=None):
     """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
       logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
                  checkpoint ensemble
@@ -258,6 +306,17 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
                  columns that at least one member covers.  ALL members' logits of a batch are alive at once: members x 4 B H W num_cls
                  bytes — 21 MB per member at the defaults, 1.3 GB at the limit of 64 members — beside one forward's activations.  On an
                  MI355X (288 GB) no member count needs a smaller batch_size; where that product nears the free memory, halve batch_size.
+      axes       None, or a sequence of distinct slicing axes from 0, 1, 2 (check_axes): multi-planar fusion.  `axis` must
+                 then be left at its default.  Every listed axis is predicted by the single-axis path with prob=True and every other option
+                 unchanged (tta, lists of callables, tiles, sample_mm, prefilter, edge, batch_size; the member limits hold per view), and
+                 ONE pnp_fuse_views launch averages the views into the first view's probability buffer: per voxel over the views that
+                 wrote it (a view leaves 0 outside its field of view, on the edge frames it skips and outside the crop box), weighted by
+                 axis_weights (None: all 1).  The result is always the Ensemble tuple (prob / entropy None unless asked for);
+                 keep_largest runs once, on the fused label, never on a view; fov_stats gets one share per view, in axes order.  crop: None
+                 and a margin work as they are (a label's bounding box is the same voxel set in every orientation); an explicit box is
+                 given in the slicing order of the default axis (2) and re-expressed per view (view_box).  sample_mm and spacing keep their
+                 meaning per view (slicing_order moves each view's axis last): with an anisotropic scan a single number — an isotropic
+                 grid — is the sensible sample_mm.  Peak memory is len(axes) probability volumes: 262 MB per view at 256 x 256 x 200 x 5.
       edge       "replicate": the normalised volume is padded with a copy of its first and last frame, every frame is predicted;
                  "skip": frames 1 .. Z - 2 only (the reference's frame set), the two edge frames stay 0
     Frames run in ascending order, batch_size at a time; the last, short batch repeats its last frame and pastes nb < B slices.  Nothing
@@ -268,6 +327,27 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         raise ValueError("edge must be one of %s, got %r" % (EDGES, edge))
     from . import components
     post = components.parse_option(keep_largest, num_cls)
+    if axes is not None or axis_weights is not None:
+        if axes is None:
+            raise ValueError("axis_weights %r goes with axes" % (axis_weights,))
+        if axis != 2:
+            raise ValueError("axes=%r and axis=%r exclude each other: leave axis at its default" % (axes, axis))
+        axes, axis_weights = check_axes(axes, axis_weights)
+        explicit = crop is not None and not isinstance(crop, (int, np.integer))          # a box, in the slicing order of axis 2
+        views = []
+        for a in axes:
+            one = segment_volume(logits_fn, image, label=label, flip_correction=flip_correction, axis=a,
+                                 crop=view_box(crop, a) if explicit else crop, edge=edge, batch_size=batch_size, percentile=percentile,
+                                 out_size=out_size, num_cls=num_cls, device=device, tta=tta, prob=True, spacing=spacing, sample_mm=sample_mm,
+                                 fov_stats=fov_stats, prefilter=prefilter, tiles=tiles, tile_overlap=tile_overlap)
+            views.append(one.prob)
+            if len(views) == 1:
+                fused = one.label                       # the first view's label buffer takes the fused labels
+            del one
+        _, out_p, out_e = K.fuse_views(views, axis_weights, label=fused, prob=views[0] if prob else None, entropy=bool(entropy))
+        del views
+        _filter_components(fused, post, num_cls, component_stats)
+        return Ensemble(fused, out_p, out_e)
     B, H, W = int(batch_size), int(out_size[0]), int(out_size[1])
     if B < 1:
         raise ValueError("batch_size must be at least 1")
@@ -419,7 +499,8 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
     [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine; with keep_largest= every label volume written
     is the filtered one (component_stats=[]: one stats tensor per volume is appended); prefilter= is segment_volume's (the
     setting the network was trained with); tiles= / tile_overlap= are segment_volume's (the share logged is then the union
-    of the planes); with sample_mm= every image's voxel size is read
+    of the planes); axes= / axis_weights= are segment_volume's (every image is predicted once per listed slicing axis and
+    the views are fused; one share is then logged per view); with sample_mm= every image's voxel size is read
     from its affine, the share of its voxel columns inside the field of view is logged, and a share below 1 is a warning (the voxels
     outside stay 0: choose crop / out_size / sample_mm so that the structure lies inside).  Returns the pred_* paths."""
     from . import nifti

@@ -13,7 +13,7 @@ the host only draws the parameters.
 A list file holds one `image.nii[.gz] label.nii[.gz]` pair per line (paths relative to the list file's folder unless absolute).
 
   python -m "medical-cross-modality-domain-adaptation_amd.volume_source" --export N OUTDIR --list LIST [--augment JSON | --no-augment]
-         [--sample-mm MM|PI,PJ,FRAME] [--prefilter auto|off|SX,SY,SZ]
+         [--sample-mm MM|PI,PJ,FRAME] [--prefilter auto|off|SX,SY,SZ] [--axes 0,1,2]
 writes N slices in the reference's tfrecord layout (tfrecord.write_slice) plus OUTDIR/slice_list, so that the TensorFlow reference can be
 fed from the same volumes.
 
@@ -215,6 +215,35 @@ def check_spacing(spacing, name="volume"):
     return sp
 
 
+def check_axes(axes, weights=None):
+    """the slicing axes of a multi-planar set or prediction: a non-empty sequence of distinct ints from {0, 1, 2}, and
+    weights = None or as many positive finite numbers -> (tuple of ints, tuple of floats or None); anything else is a ValueError that
+    quotes the offending value"""
+    if isinstance(axes, (str, bytes)) or not hasattr(axes, "__iter__"):
+        raise ValueError("axes must be a sequence of distinct axes from 0, 1, 2, got %r" % (axes,))
+    t = tuple(axes)
+    if not t:
+        raise ValueError("axes: an empty sequence names no slicing axis, got %r" % (axes,))
+    for a in t:
+        if isinstance(a, (bool, np.bool_)) or not isinstance(a, (int, np.integer)) or a not in (0, 1, 2):
+            raise ValueError("axes: %r is not one of the axes 0, 1, 2 (in %r)" % (a, axes))
+    t = tuple(int(a) for a in t)
+    if len(set(t)) != len(t):
+        raise ValueError("axes: %r names an axis twice" % (axes,))
+    if weights is None:
+        return t, None
+    try:
+        w = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        raise ValueError("axis_weights must be one positive finite number per axis, got %r" % (weights,))
+    if len(w) != len(t):
+        raise ValueError("axis_weights: %d weights %r for the %d axes %r" % (len(w), weights, len(t), t))
+    for v in w:
+        if not 0.0 < v < math.inf:
+            raise ValueError("axis_weights: %r is not a positive finite number (in %r)" % (v, weights))
+    return t, w
+
+
 PREFILTER_TRUNCATE = 4.0
 MAX_PREFILTER_RADIUS = 32            # pnp_volume_smooth's
 
@@ -414,16 +443,25 @@ class VolumeSet(object):
     flip volume_eval.test_eval applies (flip_correction), `axis` moved last (the slicing axis), crop=None or a margin in voxels around
     the label bounding box, upload, pnp_volume_preprocess (clip at the `percentile` order statistic, z-score).
     .images / .labels: device tensors [X, Y, Z] float32 / uint8;  .stats: [{clip, mean, std, fill}];  .names: image basenames;
-    .spacings: [(sx, sy, sz)] in mm, slicing order (from the image's affine; from_arrays / from_device: spacings=, default 1 mm)."""
+    .spacings: [(sx, sy, sz)] in mm, slicing order (from the image's affine; from_arrays / from_device: spacings=, default 1 mm).
+    Multi-planar training: `axis` may be a sequence of distinct axes (check_axes).  The set then holds one resident entry
+    per (pair, axis), pair-major and axis-minor, each prepared exactly as above with its own axis and its own slicing_spacing; with more
+    than one axis an entry's name is <basename>@<axis>, with an int or a one-element sequence names are the basenames.  sample_params
+    draws the ENTRY uniformly, so every orientation gets an equal share of every volume's samples.  Residency grows by the number of
+    axes: 20 scans of 256 x 256 x 200 on three axes are about 3 GB of image plus 0.8 GB of label.  .axes: the axes, in order."""
 
     def __init__(self, pairs, device, flip_correction=True, axis=2, crop=None, percentile=98):
         from . import nifti
+        axes = (axis,) if isinstance(axis, (int, np.integer)) and not isinstance(axis, bool) else check_axes(axis)[0]
         arrays, names, spacings = [], [], []
         for image_fid, label_fid in pairs:
             image = nifti.load(image_fid)
-            arrays.append(prepare_pair(image.get_data(), nifti.load(label_fid).get_data(), flip_correction, axis, crop))
-            names.append(os.path.basename(str(image_fid)))
-            spacings.append(slicing_spacing(image.affine, axis, str(image_fid)))
+            data, label = image.get_data(), nifti.load(label_fid).get_data()
+            for ax in axes:
+                arrays.append(prepare_pair(data, label, flip_correction, ax, crop))
+                names.append(os.path.basename(str(image_fid)) + ("@%d" % ax if len(axes) > 1 else ""))
+                spacings.append(slicing_spacing(image.affine, ax, str(image_fid)))
+        self.axes = tuple(int(a) for a in axes)
         self._build(arrays, names, device, percentile)
         self.spacings = spacings
 
@@ -650,13 +688,15 @@ class AugmentedSliceSource(object):
 
 
 def sources_from_lists(train_list, val_list, device, batch_size, num_cls, augment=DEFAULT_AUGMENT, seed=0, shard=None, sample_mm=None,
-                       prefilter=None):
+                       prefilter=None, axes=None):
     """the two sources of a trainer from two list files: the training one augmented, the validation one with augment=None; sample_mm and
-    prefilter (AugmentedSliceSource's) hold for both"""
-    train = AugmentedSliceSource(VolumeSet(read_pairs(train_list), device), batch_size, augment=augment, seed=seed, shard=shard,
+    prefilter (AugmentedSliceSource's) hold for both, and so does axes (None: the default slicing axis; a sequence: VolumeSet's
+    multi-planar set, DESIGN.md §21 — one resident entry per volume and axis)"""
+    which = {} if axes is None else {"axis": check_axes(axes)[0]}
+    train = AugmentedSliceSource(VolumeSet(read_pairs(train_list), device, **which), batch_size, augment=augment, seed=seed, shard=shard,
                                  num_cls=num_cls, sample_mm=sample_mm, prefilter=prefilter)
-    val = AugmentedSliceSource(VolumeSet(read_pairs(val_list), device), batch_size, augment=None, seed=seed + 1, shard=shard, num_cls=num_cls,
-                               sample_mm=sample_mm, prefilter=prefilter)
+    val = AugmentedSliceSource(VolumeSet(read_pairs(val_list), device, **which), batch_size, augment=None, seed=seed + 1, shard=shard,
+                               num_cls=num_cls, sample_mm=sample_mm, prefilter=prefilter)
     return train, val
 
 
@@ -722,6 +762,55 @@ def prefilter_from_args(ap, args):
         ap.error(str(e))
 
 
+def parse_axes(text):
+    """--axes: 'A[,B[,C]]' -> check_axes' tuple of distinct axes from 0, 1, 2 (None stays None)"""
+    if text is None:
+        return None
+    parts = str(text).split(",")
+    if not all(p.strip().lstrip("+").isdigit() for p in parts):
+        raise ValueError("--axes: %r is not a comma-separated list of axes from 0, 1, 2" % (text,))
+    try:
+        return check_axes([int(p) for p in parts])[0]
+    except ValueError as e:
+        raise ValueError("--axes: %s" % e)
+
+
+def parse_axis_weights(text, axes):
+    """--axis-weights: 'W[,W[,W]]', one positive finite number per axis of --axes -> a tuple of floats (None stays None)"""
+    if text is None:
+        return None
+    if axes is None:
+        raise ValueError("--axis-weights goes with --axes")
+    try:
+        vals = [float(p) for p in str(text).split(",")]
+    except ValueError:
+        raise ValueError("--axis-weights: %r is not a comma-separated list of numbers" % (text,))
+    try:
+        return check_axes(axes, vals)[1]
+    except ValueError as e:
+        raise ValueError("--axis-weights: %s" % e)
+
+
+def add_axes_flag(ap, weights=False):
+    ap.add_argument("--axes", default=None, metavar="A[,B[,C]]", help="multi-planar: the slicing axes of the NIfTI volumes, distinct axes from "
+                    "0, 1, 2 (e.g. 0,1,2: sagittal, coronal and axial slices of an RAS file); training holds every volume once per axis, "
+                    "prediction runs once per axis and fuses the probability volumes (default: the one default axis)")
+    if weights:
+        ap.add_argument("--axis-weights", default=None, metavar="W[,W[,W]]", help="with --axes: one positive weight per axis for the fusion "
+                        "(default: all 1)")
+
+
+def axes_from_args(ap, args):
+    """-> the axes, or (axes, weights) for a parser that was given add_axes_flag(weights=True)"""
+    try:
+        axes = parse_axes(args.axes)
+        if hasattr(args, "axis_weights"):
+            return axes, parse_axis_weights(args.axis_weights, axes)
+        return axes
+    except ValueError as e:
+        ap.error(str(e))
+
+
 def add_augment_flags(ap):
     g = ap.add_mutually_exclusive_group()
     g.add_argument("--augment", default=None, metavar="JSON", help="augmentation ranges of the NIfTI training sources, e.g. "
@@ -746,11 +835,13 @@ def augment_from_args(args):
 
 
 def export(n, outdir, list_file, device="cuda", augment=DEFAULT_AUGMENT, seed=0, batch_size=16, out_size=(256, 256), sample_mm=None,
-           prefilter=None):
+           prefilter=None, axes=None):
     """N augmented slices as one-record tfrecords in the reference's layout plus OUTDIR/slice_list.  data_vol is the [H, W, 3] image;
-    label_vol repeats the centre frame's label map in its three channels (the reference's decoder reads channel 1 only)."""
+    label_vol repeats the centre frame's label map in its three channels (the reference's decoder reads channel 1 only).  axes: None, or
+    the slicing axes of a multi-planar set."""
     from .tfrecord import write_slice
-    src = AugmentedSliceSource(VolumeSet(read_pairs(list_file), device), batch_size, out_size=out_size, augment=augment, seed=seed,
+    which = {} if axes is None else {"axis": check_axes(axes)[0]}
+    src = AugmentedSliceSource(VolumeSet(read_pairs(list_file), device, **which), batch_size, out_size=out_size, augment=augment, seed=seed,
                                sample_mm=sample_mm, prefilter=prefilter)
     os.makedirs(outdir, exist_ok=True)
     files = []
@@ -776,9 +867,10 @@ def main(argv=None):
     add_augment_flags(ap)
     add_sample_mm_flag(ap)
     add_prefilter_flag(ap)
+    add_axes_flag(ap)
     args = ap.parse_args(argv)
     files = export(int(args.export[0]), args.export[1], args.list, device=args.device, augment=augment_from_args(args), seed=args.seed,
-                   sample_mm=sample_mm_from_args(ap, args), prefilter=prefilter_from_args(ap, args))
+                   sample_mm=sample_mm_from_args(ap, args), prefilter=prefilter_from_args(ap, args), axes=axes_from_args(ap, args))
     print("wrote %d slices and %s" % (len(files), os.path.join(args.export[1], "slice_list")))
     return files
 
