@@ -7,6 +7,9 @@ scipy.ndimage.gaussian_filter1d in tests/test_prefilter_host.py.
   smooth(v, sigmas)                the passes over the filtered axes (in exact arithmetic they commute; here X, Y, Z)
   auto_sigmas(...)                 the sigma rule: max(0, (r - 1) / 2) for r source voxels per output sample
   bound(sigmas, top)               (n_x + n_y + n_z + 6) 2^-24 max|v|, n_a = 2 R_a + 1 over the filtered axes
+  smooth_taps(v, (wx, wy, wz))     the same passes for ANY 2 r + 1 taps per axis (None: the axis is not filtered), symmetric or not:
+                                   out[a] = sum_k w[k] v[clamp(a - r + k)], pinned to scipy.ndimage.correlate1d(mode="nearest")
+  bound_taps(taps, top)            bound()'s derivation by tap count, for non-negative taps that sum to 1 in float64, rounded once to float32
   stripes() / stripe_map()         the aliasing case: cos(2 pi x 0.35 / 1.0) on 120 x 40 x 6 voxels of 0.35 mm under a 32 x 12 plane of 1 mm pixels
 """
 import numpy as np
@@ -60,6 +63,30 @@ def bound(sigmas, top):
     """first-order fp32 bound of up to three chains of non-negative weights that sum to 1: n_a roundings of at most u max|v| per filtered
     axis (one fmaf per tap), plus 6 u max|v| of slack (the weights' sums are 1 only up to 2R + 1 float32 ulps)"""
     n = sum(2 * radius(s) + 1 for s in sigmas if radius(s) > 0)
+    return (n + 6) * U * float(top)
+
+
+def smooth_taps(v, taps):
+    """taps = (wx, wy, wz), each None or 2 r + 1 float32-convertible weights; the passes run in the order X, Y, Z like smooth()"""
+    out = np.asarray(v, dtype=np.float64)
+    assert len(taps) == 3
+    for axis, w in enumerate(taps):
+        if w is not None:
+            assert len(w) % 2 == 1 and len(w) >= 3
+            out = pass_1d(out, w, axis)
+    return out
+
+
+def bound_taps(taps, top):
+    """bound() by tap count: every filtered axis is one fmaf chain of n_a = len(taps_a) non-negative weights that sum to 1 — one rounding
+    of at most u max|v| per tap, every partial sum being a sub-convex combination of values within max|v| — plus the same 6 u max|v| of
+    slack (the float32 weights sum to 1 only up to n_a ulps).  For Gaussian taps this is bound(sigmas, top) itself."""
+    n = 0
+    for w in taps:
+        if w is not None:
+            w64 = np.asarray(w, dtype=np.float32).astype(np.float64)
+            assert np.all(w64 >= 0) and abs(float(w64.sum()) - 1.0) <= len(w64) * U
+            n += len(w64)
     return (n + 6) * U * float(top)
 
 
