@@ -13,8 +13,13 @@
 //   otherwise (the file stores the slicing axis first)          one byte per frame and lane; with |sy| == 1 a wave's 64 lanes write 64
 //                         adjacent bytes with one store instruction.
 // Every output element has exactly one writer (the host refuses strides under which two voxels collide): no atomics.
+// The destination is one Box in every argument block.  paste_labels_kernel writes its columns with three hand-written loops (head bytes,
+// dwords, tail bytes); the soft kernels share one frame loop with the same store paths, walk_column (with pack_label), one argument
+// block, SoftArgs<MAXM> (8 or 64 members), and one host launcher: after the column prologue that decides whether the lane writes at all
+// they differ in the per-frame functor they hand to the walk.  (The labels kernel on walk_column cuts a column into the same bytes and
+// dwords but ran 19.0 -> 21.1 us per batch: profiles/paste_refactor.txt.)
 //
-//   paste_ensemble_kernel   the same lane layout and the same three store paths for M <= 8 members: per voxel every member's
+//   paste_ensemble_kernel   the same lane layout and the same walk for M <= 8 members: per voxel every member's
 //                         logits are interpolated through that member's own inverse map (the very expressions of label_at), passed
 //                         through softmax and summed in a fixed order; the label is the first strict maximum of the sum, and on request
 //                         the mean probabilities (class-major fp32 planes) and the normalised entropy go to the same element index.
@@ -22,7 +27,7 @@
 //                         per lane would be 64 VGPRs or an indexed private array (scratch); the ~30 VALU operations per member and frame
 //                         stand against 4 * ncls dependent-address loads, ncls expf and ncls divisions.
 //
-//   paste_tiles_kernel       the same lane layout, store paths and one-writer rule for M <= 64 members that each cover a PART of
+//   paste_tiles_kernel       the same lane layout, walk and one-writer rule for M <= 64 members that each cover a PART of
 //                         the box: a column is written iff at least one member covers it (a union), and the covering members' softmax is
 //                         blended with a separable window that trusts a plane's centre more than its border.  Per column, once: every
 //                         member's two coordinate chains, kept as one covering bit per member (two VGPRs), and the wave's union of those
@@ -44,14 +49,20 @@ constexpr int kThreads = 256;
 constexpr int kMaxExtent = 4096;
 constexpr int MAXC = 8;        // loss_optim.hip's
 
-struct PasteArgs {
-    const float* logits;       // [B, H, W, ncls]
+// where a launch writes: the X x Y x nb box of voxel columns and frames z0 .. z0 + nb - 1
+struct Box {
     unsigned char* vol;        // the allocation's first element
     long long origin;          // element offset of voxel (0, 0) of frame 0
     long long sx, sy, sz;      // element strides, any sign
-    long long plane;           // H * W * ncls
+    long long plane;           // H * W * ncls: the floats from one frame's logits to the next
+    int nb, z0, X, Y;
+};
+
+struct PasteArgs {
+    const float* logits;       // [B, H, W, ncls]
+    Box box;
     float inv[6];
-    int H, W, ncls, nb, z0, X, Y;
+    int H, W, ncls;
 };
 
 struct Corners {
@@ -84,8 +95,8 @@ __device__ __forceinline__ bool in_fov(float pi, float pj, int H, int W) {
 template <bool FOV>
 __global__ void __launch_bounds__(kThreads) paste_labels_kernel(const PasteArgs A) {
     const int g = blockIdx.x * kThreads + threadIdx.x;        // flat column index, y fastest (X * Y <= 2^24)
-    if (g >= A.X * A.Y) return;
-    const int x = g / A.Y, y = g - x * A.Y;
+    if (g >= A.box.X * A.box.Y) return;
+    const int x = g / A.box.Y, y = g - x * A.box.Y;
     float pi = fmaf(A.inv[0], (float)x, fmaf(A.inv[1], (float)y, A.inv[2]));
     float pj = fmaf(A.inv[3], (float)x, fmaf(A.inv[4], (float)y, A.inv[5]));
     if constexpr (FOV) {
@@ -105,47 +116,51 @@ __global__ void __launch_bounds__(kThreads) paste_labels_kernel(const PasteArgs 
     k.o01 = (i0 * A.W + j1) * A.ncls;
     k.o10 = (i1 * A.W + j0) * A.ncls;
     k.o11 = (i1 * A.W + j1) * A.ncls;
-    const int nb = A.nb, ncls = A.ncls;
-    const long long col = A.origin + (long long)x * A.sx + (long long)y * A.sy + (long long)A.z0 * A.sz;      // frame z0 of this column
+    const Box& D = A.box;
+    const int nb = D.nb, ncls = A.ncls;
+    const long long col = D.origin + (long long)x * D.sx + (long long)y * D.sy + (long long)D.z0 * D.sz;      // frame z0 of this column
     const float* __restrict__ lg = A.logits;
-    if (A.sz == 1 || A.sz == -1) {
+    if (D.sz == 1 || D.sz == -1) {
         // t counts bytes from the lowest address: frame t (sz = 1) or nb - 1 - t (sz = -1)
-        const bool up = A.sz == 1;
-        unsigned char* dst = A.vol + (up ? col : col - (nb - 1));
+        const bool up = D.sz == 1;
+        unsigned char* dst = D.vol + (up ? col : col - (nb - 1));
         int t = 0;
         for (; t < nb && (((uintptr_t)(dst + t)) & 3u); ++t)
-            dst[t] = (unsigned char)label_at(lg + (long long)(up ? t : nb - 1 - t) * A.plane, k, ncls);
+            dst[t] = (unsigned char)label_at(lg + (long long)(up ? t : nb - 1 - t) * D.plane, k, ncls);
         for (; t + 4 <= nb; t += 4) {
             unsigned int w = 0u;
 #pragma unroll
             for (int u = 0; u < 4; ++u)
-                w |= (unsigned int)label_at(lg + (long long)(up ? t + u : nb - 1 - t - u) * A.plane, k, ncls) << (8 * u);
+                w |= (unsigned int)label_at(lg + (long long)(up ? t + u : nb - 1 - t - u) * D.plane, k, ncls) << (8 * u);
             *(unsigned int*)(dst + t) = w;
         }
         for (; t < nb; ++t)
-            dst[t] = (unsigned char)label_at(lg + (long long)(up ? t : nb - 1 - t) * A.plane, k, ncls);
+            dst[t] = (unsigned char)label_at(lg + (long long)(up ? t : nb - 1 - t) * D.plane, k, ncls);
     } else {
         for (int b = 0; b < nb; ++b)
-            A.vol[col + (long long)b * A.sz] = (unsigned char)label_at(lg + (long long)b * A.plane, k, ncls);
+            D.vol[col + (long long)b * D.sz] = (unsigned char)label_at(lg + (long long)b * D.plane, k, ncls);
     }
 }
 
 constexpr int kMaxMembers = 8;
 constexpr int kGroup = 4;      // members are summed in runs of 4: see ensemble_at
+constexpr int kMaxTiles = 64;
 
-struct EnsembleArgs {
-    const float* logits[kMaxMembers];      // [B, H, W, ncls] each
-    unsigned char* vol;
+// the argument block of the soft kernels: paste_ensemble_kernel's at MAXM = kMaxMembers, paste_tiles_kernel's at kMaxTiles
+template <int MAXM>
+struct SoftArgs {
+    const float* logits[MAXM]; // [B, H, W, ncls] each
+    float inv[6 * MAXM];
+    Box box;
     float* prob;               // nullable: ncls planes of vol_elems floats
     float* entropy;            // nullable: vol_elems floats
     long long vol_elems;
-    long long origin;
-    long long sx, sy, sz;
-    long long plane;
-    float inv[6 * kMaxMembers];
-    float inv_m;               // 1.0f / M
-    int M, H, W, ncls, nb, z0, X, Y;
+    float scale;               // paste_ensemble_kernel: 1.0f / M; paste_tiles_kernel: 1.0f / ramp
+    int M, H, W, ncls;
 };
+using EnsembleArgs = SoftArgs<kMaxMembers>;
+using TilesArgs = SoftArgs<kMaxTiles>;
+static_assert(sizeof(TilesArgs) < 4096, "the member table travels by value in the kernel-argument block");
 
 // the unclamped plane coordinates of voxel column (fx, fy) under the six-entry map iv: the two fmaf chains of the contract
 __device__ __forceinline__ void plane_coords(const float* iv, float fx, float fy, float& pi, float& pj) {
@@ -187,6 +202,20 @@ __device__ __forceinline__ float softmax_at(const float* __restrict__ p, float p
     return s;
 }
 
+// the first strict maximum of v
+template <int NCLS>
+__device__ __forceinline__ int first_max(const float (&v)[NCLS]) {
+    int am = 0;
+    float best = 0.f;
+#pragma unroll
+    for (int c = 0; c < NCLS; ++c)
+        if (c == 0 || v[c] > best) {
+            best = v[c];
+            am = c;
+        }
+    return am;
+}
+
 // acc[c] = sum over the members of softmax_c(interpolated logits), frame offset `off` (floats); returns the first strict maximum of acc.
 // Order of the sum: members 0 .. 3 ascending into one accumulator, members 4 .. 7 ascending into a second one, then first + second.  For
 // M <= 4 that is the plain ascending sum; the split makes M = 8 copies of one member sum to exactly 8 p (p + p + p + p is exact in
@@ -209,6 +238,7 @@ __device__ __forceinline__ int ensemble_at(const EnsembleArgs& A, float fx, floa
             for (int c = 0; c < NCLS; ++c) hi[c] += r[c] / s;
         }
     }
+    // first_max, fused with the second run's add: as two loops the add becomes a branch, and the M = 5 launches measured 0.4 % slower
     int am = 0;
     float best = 0.f;
 #pragma unroll
@@ -259,13 +289,37 @@ __device__ __forceinline__ void pack_label(unsigned char* vol, long long e0, lon
     }
 }
 
+// One voxel column (x, y) of the box: the frame loop of the soft kernels and the three store paths of paste_labels_kernel in one loop.
+// at(off, e) returns the label of the frame whose logits start `off` floats into a member's batch, and stores whatever else the kernel
+// writes at element e itself.  t counts elements from the lowest address when z is fastest: frame t (sz = 1) or nb - 1 - t (sz = -1);
+// otherwise t is the frame.
+template <class At>
+__device__ __forceinline__ void walk_column(const Box& D, int x, int y, At at) {
+    const int nb = D.nb;
+    const long long col = D.origin + (long long)x * D.sx + (long long)y * D.sy + (long long)D.z0 * D.sz;      // frame z0 of this column
+    const bool zfast = D.sz == 1 || D.sz == -1, up = D.sz != -1;
+    const long long e0 = up ? col : col - (nb - 1);
+    unsigned int w = 0u;
+    int first = 0;
+    for (int t = 0; t < nb; ++t) {
+        const int b = up ? t : nb - 1 - t;
+        const long long e = zfast ? e0 + t : col + (long long)b * D.sz;
+        const unsigned int lab = (unsigned int)at((long long)b * D.plane, e);
+        if (!zfast) {
+            D.vol[e] = (unsigned char)lab;
+            continue;
+        }
+        pack_label(D.vol, e0, e, t, nb, lab, w, first);
+    }
+}
+
 // FOV (pnp_paste_ensemble_fov): a column that ANY member's map takes outside its plane writes nothing (the same two fmaf chains as
 // ensemble_at, before the clamp)
 template <int NCLS, bool FOV>
 __global__ void __launch_bounds__(kThreads) paste_ensemble_kernel(const EnsembleArgs A) {
     const int g = blockIdx.x * kThreads + threadIdx.x;        // flat column index, y fastest, as in paste_labels_kernel
-    if (g >= A.X * A.Y) return;
-    const int x = g / A.Y, y = g - x * A.Y;
+    if (g >= A.box.X * A.box.Y) return;
+    const int x = g / A.box.Y, y = g - x * A.box.Y;
     const float fx = (float)x, fy = (float)y;
     if constexpr (FOV) {
         for (int m = 0; m < A.M; ++m) {
@@ -274,54 +328,22 @@ __global__ void __launch_bounds__(kThreads) paste_ensemble_kernel(const Ensemble
             if (!in_fov(pi, pj, A.H, A.W)) return;
         }
     }
-    const int nb = A.nb;
     const bool soft = A.prob || A.entropy;
     const float inv_logn = NCLS > 1 ? 1.f / logf((float)NCLS) : 0.f;
-    const long long col = A.origin + (long long)x * A.sx + (long long)y * A.sy + (long long)A.z0 * A.sz;      // frame z0 of this column
-    float acc[NCLS];
-    // t counts elements from the lowest address when z is fastest: frame t (sz = 1) or nb - 1 - t (sz = -1); otherwise t is the frame.
-    // The three store paths of paste_labels_kernel in one loop: labels collect in `w` at their byte lane; a word that fills all four
-    // lanes goes out as one aligned dword, the head (before the first 4-byte boundary) and the tail as single bytes.
-    const bool zfast = A.sz == 1 || A.sz == -1, up = A.sz != -1;
-    const long long e0 = up ? col : col - (nb - 1);
-    unsigned int w = 0u;
-    int first = 0;
-    for (int t = 0; t < nb; ++t) {
-        const int b = up ? t : nb - 1 - t;
-        const long long e = zfast ? e0 + t : col + (long long)b * A.sz;
-        const unsigned int lab = (unsigned int)ensemble_at<NCLS>(A, fx, fy, (long long)b * A.plane, acc);
+    walk_column(A.box, x, y, [&](long long off, long long e) {
+        float acc[NCLS];
+        const int lab = ensemble_at<NCLS>(A, fx, fy, off, acc);
         if (soft) {
             float P[NCLS];
 #pragma unroll
-            for (int c = 0; c < NCLS; ++c) P[c] = acc[c] * A.inv_m;
+            for (int c = 0; c < NCLS; ++c) P[c] = acc[c] * A.scale;
             store_soft<NCLS>(A.prob, A.entropy, A.vol_elems, e, P, inv_logn);
         }
-        if (!zfast) {
-            A.vol[e] = (unsigned char)lab;
-            continue;
-        }
-        pack_label(A.vol, e0, e, t, nb, lab, w, first);
-    }
+        return lab;
+    });
 }
 
 // ---- tiled inference (pnp_paste_tiles) ---------------------------------------------------------------------------------------
-constexpr int kMaxTiles = 64;
-
-struct TilesArgs {
-    const float* logits[kMaxTiles];        // [B, H, W, ncls] each
-    float inv[6 * kMaxTiles];
-    unsigned char* vol;
-    float* prob;               // nullable: ncls planes of vol_elems floats
-    float* entropy;            // nullable: vol_elems floats
-    long long vol_elems;
-    long long origin;
-    long long sx, sy, sz;
-    long long plane;
-    float inv_ramp;            // 1.0f / ramp
-    int M, H, W, ncls, nb, z0, X, Y;
-};
-static_assert(sizeof(TilesArgs) < 4096, "the member table travels by value in the kernel-argument block");
-
 // g(p; n) = min(1, max(d, 0.5) / ramp), d = min(p + 0.5, (n - 0.5) - p): the distance to the nearer border of the field of view in plane
 // pixels, at least half a pixel, over the ramp.  Inside the field of view 0.5 / ramp <= g <= 1.  (No a * b + c pair here either: see softmax_at.)
 __device__ __forceinline__ float window(float p, int n, float inv_ramp) {
@@ -345,29 +367,21 @@ __device__ __forceinline__ int tiles_at(const TilesArgs& A, unsigned long long w
         if (!((mine >> m) & 1ull)) continue;
         float pi, pj;
         plane_coords(A.inv + 6 * m, fx, fy, pi, pj);
-        const float wm = window(pi, A.H, A.inv_ramp) * window(pj, A.W, A.inv_ramp);
+        const float wm = window(pi, A.H, A.scale) * window(pj, A.W, A.scale);
         float r[NCLS];
         const float s = softmax_at<NCLS>(A.logits[m] + off, pi, pj, A.H, A.W, r);
 #pragma unroll
         for (int c = 0; c < NCLS; ++c) acc[c] += wm * (r[c] / s);
         wsum += wm;
     }
-    int am = 0;
-    float best = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCLS; ++c)
-        if (c == 0 || acc[c] > best) {
-            best = acc[c];
-            am = c;
-        }
-    return am;
+    return first_max<NCLS>(acc);
 }
 
 template <int NCLS>
 __global__ void __launch_bounds__(kThreads) paste_tiles_kernel(const TilesArgs A) {
     const int g = blockIdx.x * kThreads + threadIdx.x;        // flat column index, y fastest, as in paste_labels_kernel
-    if (g >= A.X * A.Y) return;
-    const int x = g / A.Y, y = g - x * A.Y;
+    if (g >= A.box.X * A.box.Y) return;
+    const int x = g / A.box.Y, y = g - x * A.box.Y;
     const float fx = (float)x, fy = (float)y;
     // coverage depends on the column only: one bit per member, once
     unsigned long long mine = 0ull, wave = 0ull;
@@ -379,31 +393,19 @@ __global__ void __launch_bounds__(kThreads) paste_tiles_kernel(const TilesArgs A
         if (__builtin_amdgcn_ballot_w64(in)) wave |= 1ull << m;
     }
     if (!mine) return;                                        // covered by no member: nothing of vol, prob, entropy is written
-    const int nb = A.nb;
     const bool soft = A.prob || A.entropy;
     const float inv_logn = NCLS > 1 ? 1.f / logf((float)NCLS) : 0.f;
-    const long long col = A.origin + (long long)x * A.sx + (long long)y * A.sy + (long long)A.z0 * A.sz;      // frame z0 of this column
-    float acc[NCLS], wsum;
-    const bool zfast = A.sz == 1 || A.sz == -1, up = A.sz != -1;      // t, e0, w, first: as in paste_ensemble_kernel
-    const long long e0 = up ? col : col - (nb - 1);
-    unsigned int w = 0u;
-    int first = 0;
-    for (int t = 0; t < nb; ++t) {
-        const int b = up ? t : nb - 1 - t;
-        const long long e = zfast ? e0 + t : col + (long long)b * A.sz;
-        const unsigned int lab = (unsigned int)tiles_at<NCLS>(A, wave, mine, fx, fy, (long long)b * A.plane, acc, wsum);
+    walk_column(A.box, x, y, [&](long long off, long long e) {
+        float acc[NCLS], wsum;
+        const int lab = tiles_at<NCLS>(A, wave, mine, fx, fy, off, acc, wsum);
         if (soft) {
             float P[NCLS];
 #pragma unroll
             for (int c = 0; c < NCLS; ++c) P[c] = acc[c] / wsum;
             store_soft<NCLS>(A.prob, A.entropy, A.vol_elems, e, P, inv_logn);
         }
-        if (!zfast) {
-            A.vol[e] = (unsigned char)lab;
-            continue;
-        }
-        pack_label(A.vol, e0, e, t, nb, lab, w, first);
-    }
+        return lab;
+    });
 }
 
 // ---- multi-planar fusion (pnp_fuse_views) ------------------------------------------------------------------------------------
@@ -447,17 +449,9 @@ struct Fuse {
     }
     // P (all 0 where no view covers) and the first strict maximum of P
     __device__ __forceinline__ int finish(float (&P)[NCLS]) const {
-        int am = 0;
-        float best = 0.f;
 #pragma unroll
-        for (int c = 0; c < NCLS; ++c) {
-            P[c] = wsum > 0.f ? acc[c] / wsum : 0.f;
-            if (c == 0 || P[c] > best) {
-                best = P[c];
-                am = c;
-            }
-        }
-        return am;
+        for (int c = 0; c < NCLS; ++c) P[c] = wsum > 0.f ? acc[c] / wsum : 0.f;
+        return first_max<NCLS>(P);
     }
     // store_soft's entropy of P; +0 where no view covers
     __device__ __forceinline__ float entropy(const float (&P)[NCLS], float inv_logn) const {
@@ -585,6 +579,28 @@ int check_paste(const char* who, int32_t B, int32_t H, int32_t W, int32_t ncls, 
     return PNP_OK;
 }
 
+// the destination of a checked call, and its grid: one lane per voxel column
+Box make_box(uint8_t* vol, int64_t origin, int64_t sx, int64_t sy, int64_t sz, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0,
+             int32_t X, int32_t Y) {
+    Box D;
+    D.vol = vol;
+    D.origin = origin;
+    D.sx = sx; D.sy = sy; D.sz = sz;
+    D.plane = (long long)H * W * ncls;
+    D.nb = nb; D.z0 = z0; D.X = X; D.Y = Y;
+    return D;
+}
+unsigned column_blocks(const Box& D) { return (unsigned)(((long long)D.X * D.Y + kThreads - 1) / kThreads); }
+
+// launches KERNEL<ncls, ...> (the further template arguments follow the kernel's name) on `blocks` blocks with the argument block A
+#define PNP_LAUNCH_CASE(n, KERNEL, ...) \
+    case n: hipLaunchKernelGGL((KERNEL<n, ##__VA_ARGS__>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
+#define PNP_LAUNCH_NCLS(...)                                                                                                \
+    switch (ncls) {                                                                                                         \
+        PNP_LAUNCH_CASE(1, __VA_ARGS__) PNP_LAUNCH_CASE(2, __VA_ARGS__) PNP_LAUNCH_CASE(3, __VA_ARGS__) PNP_LAUNCH_CASE(4, __VA_ARGS__) \
+        PNP_LAUNCH_CASE(5, __VA_ARGS__) PNP_LAUNCH_CASE(6, __VA_ARGS__) PNP_LAUNCH_CASE(7, __VA_ARGS__) PNP_LAUNCH_CASE(8, __VA_ARGS__) \
+    }
+
 // the two label entry points: the same checks, arguments and launch, with and without the field-of-view rule
 template <bool FOV>
 int paste_labels_launch(const char* who, const float* logits, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb, int32_t z0,
@@ -594,87 +610,51 @@ int paste_labels_launch(const char* who, const float* logits, int32_t B, int32_t
     if (const int rc = check_paste(who, B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
     PasteArgs A;
     A.logits = logits;
-    A.vol = vol;
-    A.origin = origin;
-    A.sx = sx; A.sy = sy; A.sz = sz;
-    A.plane = (long long)H * W * ncls;
+    A.box = make_box(vol, origin, sx, sy, sz, H, W, ncls, nb, z0, X, Y);
     for (int i = 0; i < 6; ++i) A.inv[i] = inv[i];
-    A.H = H; A.W = W; A.ncls = ncls; A.nb = nb; A.z0 = z0; A.X = X; A.Y = Y;
-    const unsigned blocks = (unsigned)(((long long)X * Y + kThreads - 1) / kThreads);
-    hipLaunchKernelGGL(paste_labels_kernel<FOV>, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A);
+    A.H = H; A.W = W; A.ncls = ncls;
+    hipLaunchKernelGGL(paste_labels_kernel<FOV>, dim3(column_blocks(A.box)), dim3(kThreads), 0, (hipStream_t)stream, A);
     PNP_CHECK_LAUNCH("paste_labels_kernel");
     return PNP_OK;
 }
 
-template <bool FOV>
-int paste_ensemble_launch(const char* who, int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls,
-                          int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
-                          int64_t sz, float* prob, float* entropy, void* stream) {
-    PNP_REQUIRE(M >= 1 && M <= kMaxMembers, "%s: M = %d members outside [1, %d]", who, (int)M, kMaxMembers);
+// the three soft entry points: the same checks, member table, box and grid.  pnp_paste_tiles alone has 64 member slots, takes `ramp`
+// (checked between the member checks and check_paste; 1 / ramp is its `scale`, 1 / M the ensemble's, whose entry points pass a ramp
+// that is not read) and launches paste_tiles_kernel.
+enum class Soft { Ensemble, EnsembleFov, Tiles };
+template <Soft KIND>
+int paste_soft_launch(const char* who, int32_t M, const float* const* logits, const float* inv, float ramp, int32_t B, int32_t H, int32_t W,
+                      int32_t ncls, int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx,
+                      int64_t sy, int64_t sz, float* prob, float* entropy, void* stream) {
+    constexpr bool tiles = KIND == Soft::Tiles;
+    constexpr int MAXM = tiles ? kMaxTiles : kMaxMembers;
+    PNP_REQUIRE(M >= 1 && M <= MAXM, "%s: M = %d members outside [1, %d]", who, (int)M, MAXM);
     PNP_REQUIRE(logits && vol, "%s: null pointer", who);
     PNP_REQUIRE(inv, "%s: null inv (6 floats per member)", who);
     for (int m = 0; m < M; ++m) PNP_REQUIRE(logits[m], "%s: member %d of %d is a null pointer", who, m, (int)M);
+    if constexpr (tiles)
+        PNP_REQUIRE(std::isfinite(ramp) && ramp >= 1.f, "%s: ramp = %g must be finite and at least 1 (plane pixels)", who, (double)ramp);
     if (const int rc = check_paste(who, B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
     PNP_REQUIRE((__int128)ncls * vol_elems <= (__int128)INT64_MAX, "%s: ncls * vol_elems = %d * %lld overflows int64", who, (int)ncls,
                 (long long)vol_elems);
-    EnsembleArgs A;
-    for (int m = 0; m < kMaxMembers; ++m) {
+    SoftArgs<MAXM> A;
+    for (int m = 0; m < MAXM; ++m) {                          // unused slots repeat member 0
         A.logits[m] = logits[m < M ? m : 0];
         for (int i = 0; i < 6; ++i) A.inv[6 * m + i] = inv[6 * (m < M ? m : 0) + i];
     }
-    A.vol = vol;
+    A.box = make_box(vol, origin, sx, sy, sz, H, W, ncls, nb, z0, X, Y);
     A.prob = prob;
     A.entropy = entropy;
     A.vol_elems = vol_elems;
-    A.origin = origin;
-    A.sx = sx; A.sy = sy; A.sz = sz;
-    A.plane = (long long)H * W * ncls;
-    A.inv_m = 1.0f / (float)M;
-    A.M = M; A.H = H; A.W = W; A.ncls = ncls; A.nb = nb; A.z0 = z0; A.X = X; A.Y = Y;
-    const unsigned blocks = (unsigned)(((long long)X * Y + kThreads - 1) / kThreads);
-    switch (ncls) {
-#define PNP_ENSEMBLE_CASE(n) case n: hipLaunchKernelGGL((paste_ensemble_kernel<n, FOV>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
-        PNP_ENSEMBLE_CASE(1) PNP_ENSEMBLE_CASE(2) PNP_ENSEMBLE_CASE(3) PNP_ENSEMBLE_CASE(4)
-        PNP_ENSEMBLE_CASE(5) PNP_ENSEMBLE_CASE(6) PNP_ENSEMBLE_CASE(7) PNP_ENSEMBLE_CASE(8)
-#undef PNP_ENSEMBLE_CASE
+    A.scale = 1.0f / (tiles ? ramp : (float)M);
+    A.M = M; A.H = H; A.W = W; A.ncls = ncls;
+    const unsigned blocks = column_blocks(A.box);
+    if constexpr (tiles) {
+        PNP_LAUNCH_NCLS(paste_tiles_kernel)
+    } else {
+        PNP_LAUNCH_NCLS(paste_ensemble_kernel, KIND == Soft::EnsembleFov)
     }
-    PNP_CHECK_LAUNCH("paste_ensemble_kernel");
-    return PNP_OK;
-}
-
-int paste_tiles_launch(const char* who, int32_t M, const float* const* logits, const float* inv, float ramp, int32_t B, int32_t H, int32_t W,
-                       int32_t ncls, int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx,
-                       int64_t sy, int64_t sz, float* prob, float* entropy, void* stream) {
-    PNP_REQUIRE(M >= 1 && M <= kMaxTiles, "%s: M = %d members outside [1, %d]", who, (int)M, kMaxTiles);
-    PNP_REQUIRE(logits && vol, "%s: null pointer", who);
-    PNP_REQUIRE(inv, "%s: null inv (6 floats per member)", who);
-    for (int m = 0; m < M; ++m) PNP_REQUIRE(logits[m], "%s: member %d of %d is a null pointer", who, m, (int)M);
-    PNP_REQUIRE(std::isfinite(ramp) && ramp >= 1.f, "%s: ramp = %g must be finite and at least 1 (plane pixels)", who, (double)ramp);
-    if (const int rc = check_paste(who, B, H, W, ncls, nb, z0, X, Y, vol_elems, origin, sx, sy, sz)) return rc;
-    PNP_REQUIRE((__int128)ncls * vol_elems <= (__int128)INT64_MAX, "%s: ncls * vol_elems = %d * %lld overflows int64", who, (int)ncls,
-                (long long)vol_elems);
-    TilesArgs A;
-    for (int m = 0; m < kMaxTiles; ++m) {
-        A.logits[m] = logits[m < M ? m : 0];
-        for (int i = 0; i < 6; ++i) A.inv[6 * m + i] = inv[6 * (m < M ? m : 0) + i];
-    }
-    A.vol = vol;
-    A.prob = prob;
-    A.entropy = entropy;
-    A.vol_elems = vol_elems;
-    A.origin = origin;
-    A.sx = sx; A.sy = sy; A.sz = sz;
-    A.plane = (long long)H * W * ncls;
-    A.inv_ramp = 1.0f / ramp;
-    A.M = M; A.H = H; A.W = W; A.ncls = ncls; A.nb = nb; A.z0 = z0; A.X = X; A.Y = Y;
-    const unsigned blocks = (unsigned)(((long long)X * Y + kThreads - 1) / kThreads);
-    switch (ncls) {
-#define PNP_TILES_CASE(n) case n: hipLaunchKernelGGL((paste_tiles_kernel<n>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
-        PNP_TILES_CASE(1) PNP_TILES_CASE(2) PNP_TILES_CASE(3) PNP_TILES_CASE(4)
-        PNP_TILES_CASE(5) PNP_TILES_CASE(6) PNP_TILES_CASE(7) PNP_TILES_CASE(8)
-#undef PNP_TILES_CASE
-    }
-    PNP_CHECK_LAUNCH("paste_tiles_kernel");
+    PNP_CHECK_LAUNCH(tiles ? "paste_tiles_kernel" : "paste_ensemble_kernel");
     return PNP_OK;
 }
 
@@ -732,12 +712,7 @@ int fuse_views_launch(const char* who, int32_t n_views, const float* const* prob
     A.label_word = (((uintptr_t)label + (uintptr_t)A.head) & 3u) == 0;
     const long long items = std::max(A.nvec, vol_elems - 4 * A.nvec);
     const unsigned blocks = (unsigned)std::min<long long>((items + kThreads - 1) / kThreads, kFuseBlocks);
-    switch (ncls) {
-#define PNP_FUSE_CASE(n) case n: hipLaunchKernelGGL((fuse_views_kernel<n>), dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, A); break;
-        PNP_FUSE_CASE(1) PNP_FUSE_CASE(2) PNP_FUSE_CASE(3) PNP_FUSE_CASE(4)
-        PNP_FUSE_CASE(5) PNP_FUSE_CASE(6) PNP_FUSE_CASE(7) PNP_FUSE_CASE(8)
-#undef PNP_FUSE_CASE
-    }
+    PNP_LAUNCH_NCLS(fuse_views_kernel)
     PNP_CHECK_LAUNCH("fuse_views_kernel");
     return PNP_OK;
 }
@@ -766,22 +741,22 @@ int pnp_paste_labels_fov(const float* logits, int32_t B, int32_t H, int32_t W, i
 int pnp_paste_ensemble(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
                        int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
                        float* prob, float* entropy, void* stream) {
-    return paste_ensemble_launch<false>("pnp_paste_ensemble", M, logits, inv, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy, sz, prob,
-                                        entropy, stream);
+    return paste_soft_launch<Soft::Ensemble>("pnp_paste_ensemble", M, logits, inv, 0.f, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy,
+                                             sz, prob, entropy, stream);
 }
 
 int pnp_paste_ensemble_fov(int32_t M, const float* const* logits, const float* inv, int32_t B, int32_t H, int32_t W, int32_t ncls, int32_t nb,
                            int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy, int64_t sz,
                            float* prob, float* entropy, void* stream) {
-    return paste_ensemble_launch<true>("pnp_paste_ensemble_fov", M, logits, inv, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy, sz,
-                                       prob, entropy, stream);
+    return paste_soft_launch<Soft::EnsembleFov>("pnp_paste_ensemble_fov", M, logits, inv, 0.f, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin,
+                                                sx, sy, sz, prob, entropy, stream);
 }
 
 int pnp_paste_tiles(int32_t M, const float* const* logits, const float* inv, float ramp, int32_t B, int32_t H, int32_t W, int32_t ncls,
                     int32_t nb, int32_t z0, int32_t X, int32_t Y, uint8_t* vol, int64_t vol_elems, int64_t origin, int64_t sx, int64_t sy,
                     int64_t sz, float* prob, float* entropy, void* stream) {
-    return paste_tiles_launch("pnp_paste_tiles", M, logits, inv, ramp, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy, sz, prob,
-                              entropy, stream);
+    return paste_soft_launch<Soft::Tiles>("pnp_paste_tiles", M, logits, inv, ramp, B, H, W, ncls, nb, z0, X, Y, vol, vol_elems, origin, sx, sy, sz,
+                                          prob, entropy, stream);
 }
 
 }  // extern "C"

@@ -1110,6 +1110,31 @@ def paste_labels(logits, nb, z0, inv, src_xy, vol, origin, strides, fov=False):
     return vol
 
 
+def _paste_soft_args(who, logits, invs, nb, z0, src_xy, vol, origin, strides, prob, entropy):
+    """what paste_ensemble and paste_tiles share: the checks of the member and output tensors, in the order the calls are refused in, and
+    the arguments of the entry points -> ((B, H, W, ncls), member pointers, maps, the arguments from nb on).  No member: the shape is
+    (1, 1, 1, 1) and the outputs are not looked at — M = 0 is the caller's or the library's refusal, before anything is read."""
+    shape = tuple(logits[0].shape) if logits else (1, 1, 1, 1)
+    for t in logits:
+        if t.dim() != 4 or tuple(t.shape) != shape:
+            raise _lib.PnpError("%s: every member must be [B, H, W, ncls] of one shape, got %s and %s" % (who, shape, tuple(t.shape)))
+        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
+            raise _lib.PnpError("%s: logits must be contiguous float32 CUDA tensors (got %s %s) — there is no CPU fallback" % (who, t.device, t.dtype))
+    if not vol.is_cuda or vol.dtype != torch.uint8 or not vol.is_contiguous():
+        raise _lib.PnpError("%s: vol must be a contiguous uint8 CUDA tensor (got %s %s) — there is no CPU fallback" % (who, vol.device, vol.dtype))
+    dims = tuple(int(d) for d in shape)
+    for name, t, n in (("prob", prob, dims[3] * vol.numel()), ("entropy", entropy, vol.numel())) if logits else ():
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
+            raise _lib.PnpError("%s: %s must be a contiguous float32 CUDA tensor of %d elements (got %s %s, %d) — there is no CPU fallback"
+                                % (who, name, n, t.device, t.dtype, t.numel()))
+    M = len(logits)
+    ptrs = (ctypes.c_void_p * M)(*[t.data_ptr() for t in logits])
+    m = (ctypes.c_float * (6 * M))(*[float(v) for inv in invs for v in inv])
+    tail = (int(nb), int(z0), int(src_xy[0]), int(src_xy[1]), ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]),
+            int(strides[1]), int(strides[2]), _p(prob), _p(entropy), _stream())
+    return dims, ptrs, m, tail
+
+
 def paste_ensemble(logits, nb, z0, invs, src_xy, vol, origin, strides, prob=None, entropy=None, fov=False):
     """fov=True: pnp_paste_ensemble_fov — a voxel column that any member's map takes outside its plane is written in none
     of vol, prob, entropy; otherwise
@@ -1121,28 +1146,11 @@ def paste_ensemble(logits, nb, z0, invs, src_xy, vol, origin, strides, prob=None
     logits = list(logits)
     if not logits or len(invs) != len(logits):
         raise _lib.PnpError("paste_ensemble: %d members with %d maps" % (len(logits), len(invs)))
-    shape = tuple(logits[0].shape)
-    for t in logits:
-        if t.dim() != 4 or tuple(t.shape) != shape:
-            raise _lib.PnpError("paste_ensemble: every member must be [B, H, W, ncls] of one shape, got %s and %s" % (shape, tuple(t.shape)))
-        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.PnpError("paste_ensemble: logits must be contiguous float32 CUDA tensors (got %s %s) — there is no CPU fallback" % (t.device, t.dtype))
-    if not vol.is_cuda or vol.dtype != torch.uint8 or not vol.is_contiguous():
-        raise _lib.PnpError("paste_ensemble: vol must be a contiguous uint8 CUDA tensor (got %s %s) — there is no CPU fallback" % (vol.device, vol.dtype))
-    B, H, W, ncls = (int(d) for d in shape)
-    for name, t, n in (("prob", prob, ncls * vol.numel()), ("entropy", entropy, vol.numel())):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
-            raise _lib.PnpError("paste_ensemble: %s must be a contiguous float32 CUDA tensor of %d elements (got %s %s, %d) — there is no CPU fallback"
-                                % (name, n, t.device, t.dtype, t.numel()))
-    M = len(logits)
-    ptrs = (ctypes.c_void_p * M)(*[t.data_ptr() for t in logits])
-    m = (ctypes.c_float * (6 * M))(*[float(v) for inv in invs for v in inv])
-    if len(m) != 6 * M:
+    dims, ptrs, m, tail = _paste_soft_args("paste_ensemble", logits, invs, nb, z0, src_xy, vol, origin, strides, prob, entropy)
+    if len(m) != 6 * len(logits):
         raise _lib.PnpError("paste_ensemble: every map has six entries")
     entry = "pnp_paste_ensemble_fov" if fov else "pnp_paste_ensemble"
-    check(getattr(_lib.load(), entry)(M, ptrs, m, B, H, W, ncls, int(nb), int(z0), int(src_xy[0]), int(src_xy[1]),
-                                      ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
-                                      int(strides[2]), _p(prob), _p(entropy), _stream()), entry)
+    check(getattr(_lib.load(), entry)(len(logits), ptrs, m, *dims, *tail), entry)
     return vol, prob, entropy
 
 
@@ -1156,25 +1164,8 @@ def paste_tiles(logits, nb, z0, invs, ramp, src_xy, vol, origin, strides, prob=N
         raise _lib.PnpError("paste_tiles: %d members with %d maps" % (len(logits), len(invs)))
     if any(len(inv) != 6 for inv in invs):
         raise _lib.PnpError("paste_tiles: every map has six entries")
-    shape = tuple(logits[0].shape) if logits else (1, 1, 1, 1)          # M = 0 (and M > 64) is the library's refusal, before anything is read
-    for t in logits:
-        if t.dim() != 4 or tuple(t.shape) != shape:
-            raise _lib.PnpError("paste_tiles: every member must be [B, H, W, ncls] of one shape, got %s and %s" % (shape, tuple(t.shape)))
-        if not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous():
-            raise _lib.PnpError("paste_tiles: logits must be contiguous float32 CUDA tensors (got %s %s) — there is no CPU fallback" % (t.device, t.dtype))
-    if not vol.is_cuda or vol.dtype != torch.uint8 or not vol.is_contiguous():
-        raise _lib.PnpError("paste_tiles: vol must be a contiguous uint8 CUDA tensor (got %s %s) — there is no CPU fallback" % (vol.device, vol.dtype))
-    B, H, W, ncls = (int(d) for d in shape)
-    for name, t, n in (("prob", prob, ncls * vol.numel()), ("entropy", entropy, vol.numel())) if logits else ():
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n):
-            raise _lib.PnpError("paste_tiles: %s must be a contiguous float32 CUDA tensor of %d elements (got %s %s, %d) — there is no CPU fallback"
-                                % (name, n, t.device, t.dtype, t.numel()))
-    M = len(logits)
-    ptrs = (ctypes.c_void_p * M)(*[t.data_ptr() for t in logits])
-    m = (ctypes.c_float * (6 * M))(*[float(v) for inv in invs for v in inv])
-    check(_lib.load().pnp_paste_tiles(M, ptrs, m, float(ramp), B, H, W, ncls, int(nb), int(z0), int(src_xy[0]), int(src_xy[1]),
-                                      ctypes.c_void_p(vol.data_ptr()), vol.numel(), int(origin), int(strides[0]), int(strides[1]),
-                                      int(strides[2]), _p(prob), _p(entropy), _stream()), "pnp_paste_tiles")
+    dims, ptrs, m, tail = _paste_soft_args("paste_tiles", logits, invs, nb, z0, src_xy, vol, origin, strides, prob, entropy)
+    check(_lib.load().pnp_paste_tiles(len(logits), ptrs, m, float(ramp), *dims, *tail), "pnp_paste_tiles")
     return vol, prob, entropy
 
 

@@ -416,50 +416,41 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     if mm is not None:
         rec["dz"] = np.float32(mm[2] / vox[2])
     fov = mm is not None
+    # one batch loop for every path: the default one is one callable, one map and pnp_paste_labels[_fov] (the maximum of the interpolated
+    # logits, not the M = 1 ensemble kernel's maximum of their softmax)
     if ensemble:
         maps = [compose_matrix((X, Y), (H, W), **e, **geom) for e in entries]
-        invs = [invert_matrix(m) for m in maps] * len(fns)                  # callable-major, like the members
-        if fov and fov_stats is not None:
-            fov_stats.append(coverage(invs, X, Y, H, W, mode="all" if ramp is None else "any"))
-        out_p = torch.zeros((int(num_cls),) + tuple(image.shape), dtype=torch.float32, device=device) if prob else None
-        out_e = torch.zeros(tuple(image.shape), dtype=torch.float32, device=device) if entropy else None
-        for k in range(0, count, B):
-            nb = min(B, count - k)
-            rec["frame"] = np.minimum(first + k + np.arange(B), first + k + nb - 1)
-            xs = []
-            for m in maps:                                                  # one gather per distinct map, shared by the callables
-                rec["m"][:] = m
-                xs.append(src.gather_records(rec, num_cls, want_onehot=False)[0])
-            members = []
-            for fn in fns:
-                for x in xs:
-                    logits = fn(x)
-                    if tuple(logits.shape) != (B, H, W, int(num_cls)):
-                        raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
-                    members.append(logits.detach().contiguous())
-            if ramp is not None:
-                K.paste_tiles(members, nb, first + k + shift, invs, ramp, (X, Y), out, origin, strides, prob=out_p, entropy=out_e)
-            else:
-                K.paste_ensemble(members, nb, first + k + shift, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e, fov=fov)
-        src.close()
-        _filter_components(out, post, num_cls, component_stats)
-        return Ensemble(out, out_p, out_e)
-    m = compose_matrix((X, Y), (H, W), **geom)
-    inv = invert_matrix(m)
+    else:
+        fns, maps = [logits_fn], [compose_matrix((X, Y), (H, W), **geom)]
+    invs = [invert_matrix(m) for m in maps] * len(fns)                      # callable-major, like the members
     if fov and fov_stats is not None:
-        fov_stats.append(coverage(inv, X, Y, H, W))
-    rec["m"][:] = m
+        fov_stats.append(coverage(invs, X, Y, H, W, mode="all" if ramp is None else "any"))
+    out_p = torch.zeros((int(num_cls),) + tuple(image.shape), dtype=torch.float32, device=device) if prob else None
+    out_e = torch.zeros(tuple(image.shape), dtype=torch.float32, device=device) if entropy else None
+    if not ensemble:
+        paste = lambda members, nb, z: K.paste_labels(members[0], nb, z, invs[0], (X, Y), out, origin, strides, fov=fov)
+    elif ramp is not None:
+        paste = lambda members, nb, z: K.paste_tiles(members, nb, z, invs, ramp, (X, Y), out, origin, strides, prob=out_p, entropy=out_e)
+    else:
+        paste = lambda members, nb, z: K.paste_ensemble(members, nb, z, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e, fov=fov)
     for k in range(0, count, B):
         nb = min(B, count - k)
         rec["frame"] = np.minimum(first + k + np.arange(B), first + k + nb - 1)
-        x, _, _ = src.gather_records(rec, num_cls, want_onehot=False)
-        logits = logits_fn(x)
-        if tuple(logits.shape) != (B, H, W, int(num_cls)):
-            raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
-        K.paste_labels(logits.detach().contiguous(), nb, first + k + shift, inv, (X, Y), out, origin, strides, fov=fov)
+        xs = []
+        for m in maps:                                                      # one gather per distinct map, shared by the callables
+            rec["m"][:] = m
+            xs.append(src.gather_records(rec, num_cls, want_onehot=False)[0])
+        members = []
+        for fn in fns:
+            for x in xs:
+                logits = fn(x)
+                if tuple(logits.shape) != (B, H, W, int(num_cls)):
+                    raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
+                members.append(logits.detach().contiguous())
+        paste(members, nb, first + k + shift)
     src.close()
     _filter_components(out, post, num_cls, component_stats)
-    return out
+    return Ensemble(out, out_p, out_e) if ensemble else out
 
 
 def _filter_components(label, post, num_cls, component_stats):
