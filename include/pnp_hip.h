@@ -723,6 +723,19 @@ int pnp_volume_smooth(const float* src, float* dst, int32_t X, int32_t Y, int32_
                       const float* wy /*host, nullable*/, int32_t ry, const float* wz /*host, nullable*/, int32_t rz, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---- per-frame class statistics of a resident label volume (csrc/frame_stats.hip): where the classes are ---------------------
+ *
+ * pnp_label_frame_stats: label uint8 [X, Y, Z] in C order (z fastest: pnp_aug_volume's label), at ANY byte address (a misaligned base or a
+ * Z that is no multiple of 4 takes byte loads, anything else 4-, 8- or 16-byte loads).  stats [Z, ncls, 5] int32:
+ *   stats[z][c] = (count, xmin, xmax, ymin, ymax) over the voxels of frame z whose label equals c, c in [0, ncls); a label >= ncls counts
+ *   nowhere (as it gives an all-zero one-hot row in pnp_aug_slices); a class absent from a frame is (0, X, -1, Y, -1).
+ * The call initialises the table itself: stats may be uninitialised memory.  One stream-ordered call (two launches), no host
+ * synchronisation, no workspace.  int32 add / min / max atomics only: bit-identical from run to run.
+ * Refused on the host before any HIP call: null pointers; X or Y outside [1, 4096]; Z < 1; X * Y * Z >= 2^31; ncls outside [1, 8]; stats not
+ * 4-byte aligned. */
+int pnp_label_frame_stats(const uint8_t* label, int32_t X, int32_t Y, int32_t Z, int32_t ncls, int32_t* stats /* [Z, ncls, 5] */,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -210,6 +210,7 @@ PROTOTYPES = {
     "pnp_volume_smooth_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "pnp_volume_smooth": (c_int, [_F, _F, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_size_t,
                                   c_void_p]),
+    "pnp_label_frame_stats": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

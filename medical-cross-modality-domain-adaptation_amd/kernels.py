@@ -1000,6 +1000,26 @@ def volume_preprocess(v, percentile=98, out=None):
     return out, stats
 
 
+def label_frame_stats(label, ncls):
+    """pnp_label_frame_stats of a contiguous uint8 CUDA label volume [X, Y, Z] (any storage offset: a misaligned base is
+    served) -> int32 [Z, ncls, 5] on the device: per frame z and class c in [0, ncls) the voxel count and the bounding box (xmin, xmax, ymin,
+    ymax) of the voxels of frame z with label c; (0, X, -1, Y, -1) for a class absent from the frame.  Stream-ordered, no host
+    synchronisation, no workspace."""
+    if not label.is_cuda:
+        raise _lib.PnpError("label_frame_stats: pnp kernels need CUDA/HIP tensors (got a CPU tensor) — there is no CPU fallback")
+    if label.dtype != torch.uint8 or label.dim() != 3 or not label.is_contiguous():
+        raise _lib.PnpError("label_frame_stats: a contiguous uint8 volume [X, Y, Z] expected, got %s %s contiguous=%s"
+                            % (label.dtype, tuple(label.shape), label.is_contiguous()))
+    X, Y, Z = (int(d) for d in label.shape)
+    ncls = int(ncls)
+    if not 1 <= ncls <= 8 or Z < 1:              # before the table is sized from them
+        raise _lib.PnpError("label_frame_stats: ncls = %d outside [1, 8] or an empty volume %s" % (ncls, (X, Y, Z)))
+    stats = torch.empty((Z, ncls, 5), dtype=torch.int32, device=label.device)
+    check(_lib.load().pnp_label_frame_stats(_u8p(label), X, Y, Z, ncls, ctypes.c_void_p(stats.data_ptr()), _stream()),
+          "pnp_label_frame_stats")
+    return stats
+
+
 def volume_smooth(v, weights, out=None):
     """pnp_volume_smooth of a contiguous float32 CUDA volume [X, Y, Z]: weights = (wx, wy, wz), each None (the axis is not
     filtered) or 2 r + 1 float32-convertible taps, r <= 32 (volume_source.gaussian_weights); borders replicated.  out=None: a new tensor;

@@ -74,16 +74,19 @@ def parse_args(phase, argv=None):
     for flag in NII_FLAGS:
         ap.add_argument("--" + flag.replace("_", "-"), default=None, metavar="LIST", help="NIfTI list file (one `image.nii[.gz] "
                         "label.nii[.gz]` pair per line, volume_source.py); the four --*-nii-* flags go together")
-    from .volume_source import (add_augment_flags, add_axes_flag, add_prefilter_flag, add_sample_mm_flag, axes_from_args, prefilter_from_args,
-                                sample_mm_from_args)
+    from .volume_source import (add_augment_flags, add_axes_flag, add_prefilter_flag, add_sample_mm_flag, add_sampling_flags, axes_from_args,
+                                prefilter_from_args, sample_mm_from_args, sampling_from_args)
     add_augment_flags(ap)
     add_sample_mm_flag(ap)
     add_prefilter_flag(ap)
     add_axes_flag(ap)
+    add_sampling_flags(ap, what="the source-domain (MR) training volumes ONLY: the target's labels must not steer an unsupervised adaptation, "
+                                "so the CT volumes and both validation sets stay uniform")
     args = ap.parse_args(argv)
     args.axes = axes_from_args(ap, args)                    # one value serves MR and CT
     args.sample_mm = sample_mm_from_args(ap, args)          # one grid for both modalities: that is the point
     args.prefilter = prefilter_from_args(ap, args)          # one setting for both: the per-volume sigmas differ through the spacings
+    args.sampling = sampling_from_args(ap, args)            # the MR training set's alone
     given = [getattr(args, f) is not None for f in NII_FLAGS]
     if any(given) and not all(given):
         ap.error("--mr-nii-train, --mr-nii-val, --ct-nii-train and --ct-nii-val go together")
@@ -95,6 +98,8 @@ def parse_args(phase, argv=None):
         ap.error("--prefilter goes with the --*-nii-* lists")
     if args.axes is not None and not all(given):
         ap.error("--axes goes with the --*-nii-* lists")
+    if args.foreground is not None and not all(given):
+        ap.error("--foreground goes with the --*-nii-* lists")
     if not args.gp_weight >= 0.0:
         ap.error("--gp-weight must be >= 0, got %r" % args.gp_weight)
     if args.gp_weight > 0 and args.dtype != "f32":
@@ -131,7 +136,8 @@ def main(phase, argv=None):
         from .volume_source import augment_from_args, sources_from_lists
         shard = (rank, world) if world > 1 else None
         mr_train, mr_val = sources_from_lists(args.mr_nii_train, args.mr_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
-                                              seed=0, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter, axes=args.axes)
+                                              seed=0, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter, axes=args.axes,
+                                              sampling=args.sampling)
         ct_train, ct_val = sources_from_lists(args.ct_nii_train, args.ct_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
                                               seed=2, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter, axes=args.axes)
     elif args.synthetic:

@@ -34,16 +34,20 @@ def main(argv=None):
     ap.add_argument("--nii-train", default=None, metavar="LIST", help="train from NIfTI volumes resident on the device: a list file with one "
                     "`image.nii[.gz] label.nii[.gz]` pair per line (volume_source.py); needs --nii-val")
     ap.add_argument("--nii-val", default=None, metavar="LIST", help="validation volumes (never augmented)")
-    from .volume_source import (add_augment_flags, add_axes_flag, add_prefilter_flag, add_sample_mm_flag, augment_from_args, axes_from_args,
-                                prefilter_from_args, sample_mm_from_args)
+    from .volume_source import (add_augment_flags, add_axes_flag, add_prefilter_flag, add_sample_mm_flag, add_sampling_flags, augment_from_args,
+                                axes_from_args, prefilter_from_args, sample_mm_from_args, sampling_from_args)
     add_augment_flags(ap)
     add_sample_mm_flag(ap)
     add_prefilter_flag(ap)
     add_axes_flag(ap)
+    add_sampling_flags(ap)
     args = ap.parse_args(argv)
     sample_mm = sample_mm_from_args(ap, args)
     prefilter = prefilter_from_args(ap, args)
     axes = axes_from_args(ap, args)
+    sampling = sampling_from_args(ap, args)
+    if args.foreground is not None and not args.nii_train:
+        ap.error("--foreground goes with --nii-train / --nii-val")
     if axes is not None and not args.nii_train:
         ap.error("--axes goes with --nii-train / --nii-val")
     if sample_mm is not None and not args.nii_train:
@@ -78,7 +82,7 @@ def main(argv=None):
         from .volume_source import sources_from_lists
         train_list, val_list = sources_from_lists(args.nii_train, args.nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
                                                   shard=(rank, world) if world > 1 else None, sample_mm=sample_mm,
-                                                  prefilter=prefilter, axes=axes)
+                                                  prefilter=prefilter, axes=axes, sampling=sampling)
     elif args.synthetic:
         from .synthetic import write_dataset
         # next to (not inside) output_path: Trainer.train(restore=False) clears output_path like the reference (source_segmenter.py:416-418)
