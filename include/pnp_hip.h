@@ -302,6 +302,12 @@ int pnp_sympad_fwd(const float* x, float* xp, int32_t N, int32_t H, int32_t W, i
 /* backward of tf.pad(x, p, 'SYMMETRIC') in H and W: dx[N,H,W,C] from dxp[N,H+2p,W+2p,C] */
 int pnp_sympad_bwd(const float* dxp, float* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t p, void* stream);
 
+/* pnp_sympad_fwd(pnp_ps_fwd(x)) in one pass (the segmenter head: PS(r = 8), then the mirror pad of the 5x5 logits convolution):
+ * x [N,A,B,nc*r*r] -> xp [N,A*r+2p,B*r+2p,nc]; and its backward pnp_ps_bwd(pnp_sympad_bwd(dxp)), summed in pnp_sympad_bwd's order.
+ * Both are bit-identical to the two-kernel sequence.  Needs nc*r*r <= 4096 and p <= r. */
+int pnp_ps_pad_fwd(const float* x, float* xp, int32_t N, int32_t A, int32_t B, int32_t r, int32_t nc, int32_t p, void* stream);
+int pnp_ps_pad_bwd(const float* dxp, float* dx, int32_t N, int32_t A, int32_t B, int32_t r, int32_t nc, int32_t p, void* stream);
+
 /* Segmentation loss of source_segmenter.py:211-273 (weighted cross-entropy + soft Dice), 5..8 classes.
  * logits, y (one-hot float, lib._label_decomp) : [P, ncls].
  * out[0]=miu_cross*xent + miu_dice*dice, out[1]=xent, out[2]=dice ; dlogits = d out[0] / d logits * gscale.
@@ -393,6 +399,15 @@ int pnp_critic_input_fwd(const float* a, int32_t Ca, int32_t tile_a, const float
                          const float* d, int32_t Cd, const float* logits, int32_t ncls, float* out, int64_t P, void* stream);
 int pnp_critic_input_bwd(const float* dout, float* da, int32_t Ca, int32_t tile_a, float* db, int32_t Cb, float* dc, int32_t Cc,
                          float* dd, int32_t Cd, float* dlogits, int32_t ncls, int64_t P, void* stream);
+/* The same from the COARSE tensors: a..d are [N,A,B,C*r*r] and are read through pnp_ps_fwd's permutation, logits and out are
+ * [N,A*r,B*r,.]; C* are the channel counts after PS.  Bit-identical to four pnp_ps_fwd + pnp_critic_input_fwd, and to
+ * pnp_critic_input_bwd + four pnp_ps_bwd (da..dd come out coarse; NULL outputs are skipped).
+ * Needs (Ca+Cb+Cc+Cd)*r*r <= 4096 and, backward, r*(r*(Ctot+8)+1) <= 6144 with Ctot = Ca*tile_a+Cb+Cc+Cd+ncls+1. */
+int pnp_critic_input_ps_fwd(const float* a, int32_t Ca, int32_t tile_a, const float* b, int32_t Cb, const float* c, int32_t Cc,
+                            const float* d, int32_t Cd, const float* logits, int32_t ncls, float* out, int32_t N, int32_t A, int32_t B,
+                            int32_t r, void* stream);
+int pnp_critic_input_ps_bwd(const float* dout, float* da, int32_t Ca, int32_t tile_a, float* db, int32_t Cb, float* dc, int32_t Cc,
+                            float* dd, int32_t Cd, float* dlogits, int32_t ncls, int32_t N, int32_t A, int32_t B, int32_t r, void* stream);
 
 /* WGAN critic losses (adversarial.py:455-459): out[0] = sum_i coef[i] * mean(logit_i[0..B)) over the (up to 4) non-NULL
  * critic-logit vectors  {ct_cls, mr_cls, ct_mask, mr_mask};  e.g. dis_loss: coef = {+miu, -miu, +lambda*miu, -lambda*miu}. */

@@ -131,6 +131,8 @@ PROTOTYPES = {
     "pnp_ps_bwd": (c_int, [_F, _F, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "pnp_sympad_fwd": (c_int, [_F, _F, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "pnp_sympad_bwd": (c_int, [_F, _F, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "pnp_ps_pad_fwd": (c_int, [_F, _F, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "pnp_ps_pad_bwd": (c_int, [_F, _F, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "pnp_seg_loss_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "pnp_seg_loss_fwd": (c_int, [_F, _F, _F, c_int64, c_int32, c_float, c_float, c_void_p, c_size_t, c_void_p]),
     "pnp_seg_loss_bwd": (c_int, [_F, _F, _F, c_int64, c_int32, c_float, c_float, c_float, c_void_p, c_size_t, c_void_p]),
@@ -145,6 +147,10 @@ PROTOTYPES = {
     "pnp_reduce_workspace_bytes": (c_size_t, [c_size_t]),
     "pnp_critic_input_fwd": (c_int, [_F, c_int32, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, _F, c_int64, c_void_p]),
     "pnp_critic_input_bwd": (c_int, [_F, _F, c_int32, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, c_int64, c_void_p]),
+    "pnp_critic_input_ps_fwd": (c_int, [_F, c_int32, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, c_int32, c_int32,
+                                        c_int32, c_void_p]),
+    "pnp_critic_input_ps_bwd": (c_int, [_F, _F, c_int32, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, _F, c_int32, c_int32, c_int32, c_int32,
+                                        c_int32, c_void_p]),
     "pnp_axpby": (c_int, [_F, _F, c_size_t, c_float, c_float, c_void_p]),
     "pnp_add": (c_int, [_F, _F, _F, c_size_t, c_void_p]),
     "pnp_wgan_loss": (c_int, [_F, _F, _F, _F, c_int32, c_float, c_float, c_float, c_float, _F, c_void_p]),

@@ -18,12 +18,13 @@ import time
 import numpy as np
 import torch
 
+from . import functional as Fn
 from . import kernels as K
-from .functional import Conv2dDropFn, CriticInputFn, WganLossFn, fan_out, wgrad_overlap
+from .functional import Conv2dDropFn, CriticInputFn, CriticInputPsFn, WganLossFn, fan_out, wgrad_overlap
 from .gradient_penalty import critic_gradient_penalty, critic_table
 from .layers import (DR_block, conv2d, conv_bn_relu2d, max_pool2d, residual_block, sharable_weight_variable, weight_variable)
 from .lib import _dice_eval, _label_decomp
-from .ops import PS
+from .ops import PS, PS_conv2d
 from .parallel import barrier, rank_seed
 from .variables import VariableStore
 
@@ -189,10 +190,10 @@ class Full_DRN(object):
             w10_1 = sw([3, 3, fb * 32, 8 * 8 * num_cls * 8], "Variable")
             conv10_1 = conv2d(c9_seg, w10_1, keep_prob_=keep_prob, padding='SYMMETRIC')
             wl.append(w10_1)
-            flat_conv10_1 = PS(conv10_1, r=8, n_channel=num_cls * 8, batch_size=self.batch_size)
         with st.variable_scope('output'):
             w11_1 = sw([5, 5, num_cls * 8, num_cls], "Variable")
-            logits = conv2d(flat_conv10_1, w11_1, keep_prob_=1., padding='SYMMETRIC')
+            # PS(conv10_1, r=8) and the logits convolution's mirror pad in one kernel
+            logits = PS_conv2d(conv10_1, w11_1, r=8, n_channel=num_cls * 8, keep_prob_=1., batch_size=self.batch_size)
         return conv9_2, block8_2, block7_2, logits
 
     # ---- adversarial.py:320-400 ------------------------------------------------------------------------------------------
@@ -201,14 +202,18 @@ class Full_DRN(object):
         st = self.store
         fb = feature_base
         with st.variable_scope('cls_0'):
-            f4 = PS(input_conv4, r=8, n_channel=2, batch_size=self.batch_size)
-            f6 = PS(input_conv6, r=8, n_channel=4, batch_size=self.batch_size)
-            f7 = PS(input_b7, r=8, n_channel=8, batch_size=self.batch_size)
-            f9 = PS(input_conv9, r=8, n_channel=8, batch_size=self.batch_size)
-            # tile(f4, 3) | f6 | f7 | f9 | logits | float(argmax logits): one fused kernel instead of 5 concats (adversarial.py:326-335)
+            coarse, chans = (input_conv4, input_conv6, input_b7, input_conv9), (2, 4, 8, 8)
+            # tile(f4, 3) | f6 | f7 | f9 | logits | float(argmax logits) with f* = PS(coarse, r=8): one fused kernel instead of 5 concats
+            # (adversarial.py:326-335), reading the coarse tensors through the PS permutation instead of four PS kernels in front of it
             if seg_logits.is_meta:
+                for t, c in zip(coarse, chans):
+                    PS(t, r=8, n_channel=c, batch_size=self.batch_size)      # the channel check
                 input_comp = torch.empty(tuple(seg_logits.shape[:3]) + (2 * 3 + 4 + 8 + 8 + seg_logits.shape[3] + 1,), device="meta")
+            elif (Fn.PS_FUSE and all(t.shape[-1] == c * 64 for t, c in zip(coarse, chans))
+                  and K.critic_input_ps_served(chans, 3, seg_logits.shape[3], 8)):
+                input_comp = CriticInputPsFn.apply(*coarse, seg_logits, 3, 8)
             else:
+                f4, f6, f7, f9 = (PS(t, r=8, n_channel=c, batch_size=self.batch_size) for t, c in zip(coarse, chans))
                 input_comp = CriticInputFn.apply(f4, f6, f7, f9, seg_logits, 3)
         self._critic_input = input_comp
         return self._critic_body(critic_table("cls", fb), input_comp, keep_prob, cls_bn, cls_trainable, self._lists["cls_weights"])

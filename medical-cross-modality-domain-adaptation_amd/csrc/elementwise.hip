@@ -983,6 +983,281 @@ __global__ void __launch_bounds__(NT) critic_input_bwd_kernel(CriticBwdArgs k) {
     }
 }
 
+// ---- PS fused into its consumers ----------------------------------------------------------------
+// The two places where the model leaves the 32 x 32 grid through PS(r = 8) — the segmenter head (PS, mirror pad, 5x5 logits convolution)
+// and the feature critic's input (four PS, then critic_input) — wrote the fine tensors only for the next kernel to read them again.  These
+// kernels keep ps_tile_kernel's shape (a workgroup owns T coarse pixels jj0 .. jj0+T-1 of coarse row ii, moves them through LDS at slot
+// x + x/64 and is coalesced on both sides) and do the consumer's work on the way.  They move values and, where they sum, keep the order of
+// the kernel they replace: every result is bit-identical to the unfused sequence.
+
+// f / d for the small non-negative integers of a tile (f < 2^14, quotient x divisor far below 2^21): (f + 0.5) / d is at least 0.5 / d
+// away from an integer, the float product is not
+__device__ __forceinline__ int tdiv(int f, float inv) { return (int)(((float)f + 0.5f) * inv); }
+__device__ __forceinline__ int mirror(int h, int H) { return h < 0 ? -1 - h : (h >= H ? 2 * H - 1 - h : h); }
+
+struct PsTile {
+    int n, ii, jb, bpr;
+};
+__device__ __forceinline__ PsTile ps_tile_of(int b, int A, int B, int T) {
+    PsTile q;
+    q.bpr = B / T;
+    q.jb = b % q.bpr;
+    b /= q.bpr;
+    q.ii = b % A;
+    q.n = b / A;
+    return q;
+}
+// cnt contiguous floats (a multiple of 4 when VEC) from src into the LDS image at coarse index x0 ..
+template <bool VEC>
+__device__ __forceinline__ void ps_stage_in(float* tile, int x0, const float* __restrict__ src, int cnt) {
+    if constexpr (VEC) {
+        for (int i = threadIdx.x; i < (cnt >> 2); i += NT) {
+            const f32x4 v = ld4(src + 4 * i);
+            const int x = x0 + 4 * i;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) tile[x + e + ((x + e) >> 6)] = v[e];
+        }
+    } else {
+        for (int i = threadIdx.x; i < cnt; i += NT) tile[x0 + i + ((x0 + i) >> 6)] = src[i];
+    }
+}
+
+// PS + mirror pad: the workgroup writes the part of the padded image whose source pixels it holds — its r x T*r fine pixels, plus the
+// border rows / columns that mirror onto them when it sits at an edge (p <= r: only the first and last tile of a row or column do).
+// VW = 4: one 16-byte store per thread (nc % 4 == 0)
+template <int VW>
+__global__ void __launch_bounds__(NT) ps_pad_fwd_kernel(const float* __restrict__ src, float* __restrict__ dst, int A, int B, int r, int nc,
+                                                        int p, int T) {
+    __shared__ float tile[4096 + 64];
+    const PsTile q = ps_tile_of(blockIdx.x, A, B, T);
+    const int rr = r * r, Cin = nc * rr;
+    const int H = A * r, W = B * r, Wp = W + 2 * p;
+    const int h0 = q.ii * r, w0 = q.jb * T * r;
+    const float* in = src + (((size_t)q.n * A + q.ii) * B + (size_t)q.jb * T) * Cin;
+    if ((Cin & 3) == 0) ps_stage_in<true>(tile, 0, in, T * Cin);
+    else ps_stage_in<false>(tile, 0, in, T * Cin);
+    __syncthreads();
+    // the region in padded coordinates: rows [rlo, rhi), columns [clo, chi)
+    const int rlo = h0 + (q.ii == 0 ? 0 : p), rhi = h0 + r + p + (q.ii == A - 1 ? p : 0);
+    const int clo = w0 + (q.jb == 0 ? 0 : p), chi = w0 + T * r + p + (q.jb == q.bpr - 1 ? p : 0);
+    const int ncv = nc / VW, rowv = (chi - clo) * ncv, total = (rhi - rlo) * rowv;
+    const float inv_rowv = 1.0f / (float)rowv, inv_ncv = 1.0f / (float)ncv, inv_r = 1.0f / (float)r;
+    float* out = dst + ((size_t)q.n * (H + 2 * p) * Wp) * nc;
+    for (int f = threadIdx.x; f < total; f += NT) {
+        const int ro = tdiv(f, inv_rowv), rem = f - ro * rowv;
+        const int co = tdiv(rem, inv_ncv), cv = rem - co * ncv;
+        const int u = mirror(rlo + ro - p, H) - h0, lc = mirror(clo + co - p, W) - w0;
+        const int tj = tdiv(lc, inv_r), v = lc - tj * r;
+        const int x = tj * Cin + cv * VW * rr + v * r + u;
+        float* o = out + ((size_t)(rlo + ro) * Wp + (clo + co)) * nc + cv * VW;
+        if constexpr (VW == 4) {
+            f32x4 val;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) val[e] = tile[x + e * rr + ((x + e * rr) >> 6)];
+            st4(o, val);
+        } else {
+            *o = tile[x + (x >> 6)];
+        }
+    }
+}
+
+// backward: every fine pixel of the tile sums the padded positions that mirror onto it in sympad_bwd_kernel's order (rows h+p, the top
+// mirror, the bottom mirror; inside each, the columns likewise) and lands in the coarse layout through LDS
+template <int VW>
+__global__ void __launch_bounds__(NT) ps_pad_bwd_kernel(const float* __restrict__ dxp, float* __restrict__ dx, int A, int B, int r, int nc,
+                                                        int p, int T) {
+    __shared__ float tile[4096 + 64];
+    const PsTile q = ps_tile_of(blockIdx.x, A, B, T);
+    const int rr = r * r, Cin = nc * rr;
+    const int H = A * r, W = B * r, Wp = W + 2 * p;
+    const int h0 = q.ii * r, w0 = q.jb * T * r;
+    const int ncv = nc / VW, rowv = T * r * ncv, total = r * rowv;
+    const float inv_rowv = 1.0f / (float)rowv, inv_ncv = 1.0f / (float)ncv, inv_r = 1.0f / (float)r;
+    const float* in = dxp + ((size_t)q.n * (H + 2 * p) * Wp) * nc;
+    for (int f = threadIdx.x; f < total; f += NT) {
+        const int u = tdiv(f, inv_rowv), rem = f - u * rowv;
+        const int lc = tdiv(rem, inv_ncv), cv = rem - lc * ncv;
+        const int h = h0 + u, w = w0 + lc;
+        float s[VW];
+#pragma unroll
+        for (int e = 0; e < VW; ++e) s[e] = 0.f;
+        for (int i = 0; i < 3; ++i) {
+            if ((i == 1 && h >= p) || (i == 2 && h < H - p)) continue;
+            const int hs = i == 0 ? h + p : (i == 1 ? p - 1 - h : 2 * H - 1 - h + p);
+            for (int j = 0; j < 3; ++j) {
+                if ((j == 1 && w >= p) || (j == 2 && w < W - p)) continue;
+                const int ws = j == 0 ? w + p : (j == 1 ? p - 1 - w : 2 * W - 1 - w + p);
+                const float* g = in + ((size_t)hs * Wp + ws) * nc + cv * VW;
+                if constexpr (VW == 4) {
+                    const f32x4 gv = ld4(g);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) s[e] += gv[e];
+                } else {
+                    s[0] += *g;
+                }
+            }
+        }
+        const int tj = tdiv(lc, inv_r), v = lc - tj * r;
+        const int x = tj * Cin + cv * VW * rr + v * r + u;
+#pragma unroll
+        for (int e = 0; e < VW; ++e) tile[x + e * rr + ((x + e * rr) >> 6)] = s[e];
+    }
+    __syncthreads();
+    float* out = dx + (((size_t)q.n * A + q.ii) * B + (size_t)q.jb * T) * Cin;
+    for (int x = threadIdx.x; x < T * Cin; x += NT) out[x] = tile[x + (x >> 6)];
+}
+
+// largest divisor T of B with T <= cap (cap >= 1)
+inline int ps_fused_T(int B, int cap) {
+    int T = cap < B ? cap : B;
+    while (T > 1 && (B % T) != 0) --T;
+    return T;
+}
+
+// critic input from the coarse tensors.  C[s]: channels of source s AFTER PS; the LDS image holds, per coarse pixel, the sources' coarse
+// channels back to back (Cs = sum C[s] fine channels, Cs * r * r floats: 1408 at the model's sizes)
+struct CriticPsArgs {
+    const float* src[4];
+    const float* logits;
+    float* out;
+    int A, B, r, T, C[4], tile_a, ncls, Ctot;
+};
+constexpr int CRITIC_PS_RAW = 6144;     // floats of the backward's LDS image of dout
+// VEC: one 16-byte store per thread (Ctot % 4 == 0: the reference's 32 channels), a fine row of the tile = T * r * Ctot contiguous floats.
+// The argmax is taken by the one thread of a pixel that stores the last channel
+template <bool VEC>
+__global__ void __launch_bounds__(NT) critic_ps_fwd_kernel(CriticPsArgs k) {
+    __shared__ float tile[4096 + 64];
+    const PsTile q = ps_tile_of(blockIdx.x, k.A, k.B, k.T);
+    const int r = k.r, rr = r * r, T = k.T;
+    const int Cs = k.C[0] + k.C[1] + k.C[2] + k.C[3], Xp = Cs * rr;
+    const size_t cpix = ((size_t)q.n * k.A + q.ii) * k.B + (size_t)q.jb * T;
+    int off = 0;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        const int cnt = k.C[s] * rr;
+        for (int tj = 0; tj < T; ++tj) {
+            const float* in = k.src[s] + (cpix + tj) * cnt;
+            if ((rr & 3) == 0) ps_stage_in<true>(tile, tj * Xp + off * rr, in, cnt);
+            else ps_stage_in<false>(tile, tj * Xp + off * rr, in, cnt);
+        }
+        off += k.C[s];
+    }
+    __syncthreads();
+    const int o1 = k.C[0] * k.tile_a, o2 = o1 + k.C[1], o3 = o2 + k.C[2], o4 = o3 + k.C[3], o5 = o4 + k.ncls;
+    const int CV = VEC ? (k.Ctot >> 2) : k.Ctot, rowv = T * r * CV, total = r * rowv;
+    const float inv_rowv = 1.0f / (float)rowv, inv_cv = 1.0f / (float)CV, inv_r = 1.0f / (float)r;
+    const size_t Wf = (size_t)k.B * r;
+    auto channel = [&](int ch, int xpix, size_t pix) -> float {
+        int sc;
+        if (ch < o1) sc = ch % k.C[0];
+        else if (ch < o2) sc = k.C[0] + (ch - o1);
+        else if (ch < o3) sc = k.C[0] + k.C[1] + (ch - o2);
+        else if (ch < o4) sc = k.C[0] + k.C[1] + k.C[2] + (ch - o3);
+        else {
+            const float* z = k.logits + pix * k.ncls;
+            if (ch < o5) return z[ch - o4];
+            int am = 0;
+            float m = z[0];
+            for (int j = 1; j < k.ncls; ++j)
+                if (z[j] > m) { m = z[j]; am = j; }
+            return (float)am;
+        }
+        const int x = xpix + sc * rr;
+        return tile[x + (x >> 6)];
+    };
+    for (int f = threadIdx.x; f < total; f += NT) {
+        const int u = tdiv(f, inv_rowv), rem = f - u * rowv;
+        const int lc = tdiv(rem, inv_cv), cv = rem - lc * CV;
+        const int tj = tdiv(lc, inv_r), v = lc - tj * r;
+        const size_t pix = ((size_t)q.n * k.A * r + (size_t)q.ii * r + u) * Wf + (size_t)q.jb * T * r + lc;
+        const int xpix = tj * Xp + v * r + u;
+        if constexpr (VEC) {
+            f32x4 val;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) val[e] = channel(4 * cv + e, xpix, pix);
+            st4(k.out + pix * k.Ctot + 4 * cv, val);
+        } else {
+            k.out[pix * k.Ctot + cv] = channel(cv, xpix, pix);
+        }
+    }
+}
+
+struct CriticPsBwdArgs {
+    const float* dout;
+    float* dsrc[4];
+    float* dlogits;
+    int A, B, r, T, C[4], tile_a, ncls, Ctot, any_src;
+};
+// backward: the tile's r fine rows of dout (T * r * Ctot contiguous floats each) go to LDS as they are — pixel stride Ctot + 8, row stride
+// + 1, so that the 64 pixels of a coarse pixel fall on different banks — and are read back in the coarse order of every wanted source;
+// the tile_a copies of `a` are summed t = 0, 1, 2 as in critic_input_bwd_kernel.  dlogits is a plain strided copy
+template <bool VEC>
+__global__ void __launch_bounds__(NT) critic_ps_bwd_kernel(CriticPsBwdArgs k) {
+    __shared__ float raw[CRITIC_PS_RAW];
+    const PsTile q = ps_tile_of(blockIdx.x, k.A, k.B, k.T);
+    const int r = k.r, rr = r * r, T = k.T, Ctot = k.Ctot;
+    const int Ps = Ctot + 8, Rs = T * r * Ps + 1;
+    const size_t Wf = (size_t)k.B * r;
+    const size_t pix0 = ((size_t)q.n * k.A * r + (size_t)q.ii * r) * Wf + (size_t)q.jb * T * r;    // + u * Wf + lc
+    const int o1 = k.C[0] * k.tile_a, o2 = o1 + k.C[1], o3 = o2 + k.C[2], o4 = o3 + k.C[3];
+    const float inv_r = 1.0f / (float)r;
+    if (k.dlogits) {
+        const int rown = T * r * k.ncls, total = r * rown;
+        const float inv_rown = 1.0f / (float)rown, inv_ncls = 1.0f / (float)k.ncls;
+        for (int f = threadIdx.x; f < total; f += NT) {
+            const int u = tdiv(f, inv_rown), rem = f - u * rown;
+            const int lc = tdiv(rem, inv_ncls), j = rem - lc * k.ncls;
+            const size_t pix = pix0 + (size_t)u * Wf + lc;
+            k.dlogits[pix * k.ncls + j] = k.dout[pix * Ctot + o4 + j];
+        }
+    }
+    if (!k.any_src) return;
+    {
+        const int CV = VEC ? (Ctot >> 2) : Ctot, rowv = T * r * CV, total = r * rowv;
+        const float inv_rowv = 1.0f / (float)rowv, inv_cv = 1.0f / (float)CV;
+        for (int f = threadIdx.x; f < total; f += NT) {
+            const int u = tdiv(f, inv_rowv), rem = f - u * rowv;
+            const int lc = tdiv(rem, inv_cv), cv = rem - lc * CV;
+            const float* g = k.dout + (pix0 + (size_t)u * Wf + lc) * Ctot;
+            float* dst = raw + u * Rs + lc * Ps;
+            if constexpr (VEC) {
+                const f32x4 gv = ld4(g + 4 * cv);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) dst[4 * cv + e] = gv[e];
+            } else {
+                dst[cv] = g[cv];
+            }
+        }
+    }
+    __syncthreads();
+    const int Cs = k.C[0] + k.C[1] + k.C[2] + k.C[3], Xp = Cs * rr;
+    const float inv_xp = 1.0f / (float)Xp, inv_rr = 1.0f / (float)rr;
+    const size_t cpix = ((size_t)q.n * k.A + q.ii) * k.B + (size_t)q.jb * T;
+    for (int x = threadIdx.x; x < T * Xp; x += NT) {
+        const int tj = tdiv(x, inv_xp), y = x - tj * Xp;
+        int sc = tdiv(y, inv_rr);
+        const int vu = y - sc * rr;
+        const int v = tdiv(vu, inv_r), u = vu - v * r;
+        const float* g = raw + u * Rs + (tj * r + v) * Ps;
+        int s = 0, o = 0;       // source, its first channel in dout
+        if (sc >= k.C[0]) { sc -= k.C[0]; s = 1; o = o1; }
+        if (s == 1 && sc >= k.C[1]) { sc -= k.C[1]; s = 2; o = o2; }
+        if (s == 2 && sc >= k.C[2]) { sc -= k.C[2]; s = 3; o = o3; }
+        float* d = s == 0 ? k.dsrc[0] : (s == 1 ? k.dsrc[1] : (s == 2 ? k.dsrc[2] : k.dsrc[3]));
+        if (!d) continue;
+        const int Cn = s == 0 ? k.C[0] : (s == 1 ? k.C[1] : (s == 2 ? k.C[2] : k.C[3]));
+        float val;
+        if (s == 0) {
+            val = 0.f;
+            for (int t = 0; t < k.tile_a; ++t) val += g[t * Cn + sc];
+        } else {
+            val = g[o + sc];
+        }
+        d[((cpix + tj) * Cn + sc) * rr + vu] = val;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -1222,6 +1497,65 @@ int pnp_critic_input_bwd(const float* dout, float* da, int32_t Ca, int32_t tile_
     hipLaunchKernelGGL(critic_input_bwd_kernel, dim3(grid_for((size_t)P * (Ca + Cb + Cc + Cd + ncls), 256 * 16)), dim3(NT), 0,
                        (hipStream_t)stream, k);
     PNP_CHECK_LAUNCH("pnp_critic_input_bwd");
+    return PNP_OK;
+}
+
+int pnp_ps_pad_fwd(const float* x, float* xp, int32_t N, int32_t A, int32_t B, int32_t r, int32_t nc, int32_t p, void* stream) {
+    PNP_REQUIRE(x && xp && N > 0 && A > 0 && B > 0 && r > 0 && nc > 0 && p >= 0, "pnp_ps_pad_fwd: bad argument");
+    PNP_REQUIRE(nc * r * r <= 4096 && p <= r, "pnp_ps_pad_fwd: needs nc*r*r <= 4096 and p <= r");
+    const int T = ps_fused_T(B, 4096 / (nc * r * r));
+    const dim3 grid((unsigned)(N * A * (B / T)));
+    if ((nc & 3) == 0) hipLaunchKernelGGL(ps_pad_fwd_kernel<4>, grid, dim3(NT), 0, (hipStream_t)stream, x, xp, A, B, r, nc, p, T);
+    else hipLaunchKernelGGL(ps_pad_fwd_kernel<1>, grid, dim3(NT), 0, (hipStream_t)stream, x, xp, A, B, r, nc, p, T);
+    PNP_CHECK_LAUNCH("pnp_ps_pad_fwd");
+    return PNP_OK;
+}
+
+int pnp_ps_pad_bwd(const float* dxp, float* dx, int32_t N, int32_t A, int32_t B, int32_t r, int32_t nc, int32_t p, void* stream) {
+    PNP_REQUIRE(dxp && dx && N > 0 && A > 0 && B > 0 && r > 0 && nc > 0 && p >= 0, "pnp_ps_pad_bwd: bad argument");
+    PNP_REQUIRE(nc * r * r <= 4096 && p <= r, "pnp_ps_pad_bwd: needs nc*r*r <= 4096 and p <= r");
+    const int T = ps_fused_T(B, 4096 / (nc * r * r));
+    const dim3 grid((unsigned)(N * A * (B / T)));
+    if ((nc & 3) == 0) hipLaunchKernelGGL(ps_pad_bwd_kernel<4>, grid, dim3(NT), 0, (hipStream_t)stream, dxp, dx, A, B, r, nc, p, T);
+    else hipLaunchKernelGGL(ps_pad_bwd_kernel<1>, grid, dim3(NT), 0, (hipStream_t)stream, dxp, dx, A, B, r, nc, p, T);
+    PNP_CHECK_LAUNCH("pnp_ps_pad_bwd");
+    return PNP_OK;
+}
+
+int pnp_critic_input_ps_fwd(const float* a, int32_t Ca, int32_t tile_a, const float* b, int32_t Cb, const float* c, int32_t Cc,
+                            const float* d, int32_t Cd, const float* logits, int32_t ncls, float* out, int32_t N, int32_t A, int32_t B,
+                            int32_t r, void* stream) {
+    PNP_REQUIRE(a && b && c && d && logits && out && N > 0 && A > 0 && B > 0 && r > 0 && Ca > 0 && tile_a > 0 && Cb > 0 && Cc > 0 && Cd > 0 &&
+                    ncls > 0, "pnp_critic_input_ps_fwd: bad argument");
+    const int Xp = (Ca + Cb + Cc + Cd) * r * r;
+    PNP_REQUIRE(Xp <= 4096, "pnp_critic_input_ps_fwd: needs (Ca+Cb+Cc+Cd)*r*r <= 4096");
+    CriticPsArgs k{{a, b, c, d}, logits, out, A, B, r, ps_fused_T(B, 4096 / Xp), {Ca, Cb, Cc, Cd}, tile_a, ncls,
+                   Ca * tile_a + Cb + Cc + Cd + ncls + 1};
+    const dim3 grid((unsigned)(N * A * (B / k.T)));
+    if ((k.Ctot & 3) == 0) hipLaunchKernelGGL(critic_ps_fwd_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL(critic_ps_fwd_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, k);
+    PNP_CHECK_LAUNCH("pnp_critic_input_ps_fwd");
+    return PNP_OK;
+}
+
+int pnp_critic_input_ps_bwd(const float* dout, float* da, int32_t Ca, int32_t tile_a, float* db, int32_t Cb, float* dc, int32_t Cc,
+                            float* dd, int32_t Cd, float* dlogits, int32_t ncls, int32_t N, int32_t A, int32_t B, int32_t r, void* stream) {
+    PNP_REQUIRE(dout && N > 0 && A > 0 && B > 0 && r > 0 && Ca > 0 && tile_a > 0 && Cb > 0 && Cc > 0 && Cd > 0 && ncls > 0,
+                "pnp_critic_input_ps_bwd: bad argument");
+    const int Ctot = Ca * tile_a + Cb + Cc + Cd + ncls + 1;
+    const int Xp = (Ca + Cb + Cc + Cd) * r * r;
+    // LDS: r rows of T*r pixels at stride Ctot+8, + 1 per row
+    const int capT = (CRITIC_PS_RAW / r - 1) / (r * (Ctot + 8));
+    PNP_REQUIRE(Xp <= 4096 && capT >= 1, "pnp_critic_input_ps_bwd: needs (Ca+Cb+Cc+Cd)*r*r <= 4096 and r*(r*(Ctot+8)+1) <= %d", CRITIC_PS_RAW);
+    const int any_src = (da || db || dc || dd) ? 1 : 0;
+    if (!any_src && !dlogits) return PNP_OK;
+    const int cap_x = 4096 / Xp;
+    CriticPsBwdArgs k{dout, {da, db, dc, dd}, dlogits, A, B, r, ps_fused_T(B, capT < cap_x ? capT : cap_x), {Ca, Cb, Cc, Cd}, tile_a, ncls,
+                      Ctot, any_src};
+    const dim3 grid((unsigned)(N * A * (B / k.T)));
+    if ((Ctot & 3) == 0) hipLaunchKernelGGL(critic_ps_bwd_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, k);
+    else hipLaunchKernelGGL(critic_ps_bwd_kernel<false>, grid, dim3(NT), 0, (hipStream_t)stream, k);
+    PNP_CHECK_LAUNCH("pnp_critic_input_ps_bwd");
     return PNP_OK;
 }
 

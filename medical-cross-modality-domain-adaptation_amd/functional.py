@@ -6,6 +6,8 @@ Fused units (what TF-1.4 lowers layers.py's chains to, restated as one forward +
   ConvBNActFn     : conv -> dropout -> batch_norm [-> + shortcut] [-> leaky_relu]
                     (layers.py:9-45 and the tails of residual_block / DR_block, 145-189)
   MaxPool2Fn, PSFn, SegLossFn, CriticInputFn
+  PSPadFn         : PS -> tf.pad(SYMMETRIC)                                  (the segmenter head, in front of the logits convolution)
+  CriticInputPsFn : four PS -> critic input                                 (adversarial.py:325-335)
 
 Sums that TF's autodiff emits as AddN are done by the kernels, not by the engine: parameter gradients go straight into the
 variable's slot of the gradient arena (gradsink.py -> pnp_conv2d_wgrad_acc / pnp_bn_bwd_acc), the gradient arriving at a block input
@@ -33,6 +35,9 @@ FUSE_BN_STATS = os.environ.get("PNP_FUSE_BN_STATS", "1") != "0"
 # the value the forward activated) instead of read back from the saved output — one activation-sized read less in the reduction and in
 # the apply kernel, and the unit's output is not kept for its own backward pass
 BN_RECOMPUTE_SIGN = os.environ.get("PNP_BN_RECOMPUTE_SIGN", "1") != "0"
+# PS fused into its consumers: the segmenter head's PS + mirror pad in one kernel (PSPadFn) and the feature critic's input straight from
+# the coarse tensors (CriticInputPsFn); False: PSFn, SymPadFn and CriticInputFn as separate kernels.  Same bits either way
+PS_FUSE = os.environ.get("PNP_PS_FUSE", "1") != "0"
 
 
 def sync_now():
@@ -448,6 +453,20 @@ class PSFn(Function):
         return K.ps_bwd(_contig(dy), ctx.r, ctx.nc), None, None
 
 
+class PSPadFn(Function):
+    """SymPadFn(PSFn(x, r, nc), p) in one kernel each way (the segmenter head: PS(r = 8), then the 5x5 logits convolution's mirror pad);
+    bit-identical to the pair (PNP_PS_FUSE=0 runs the pair)."""
+
+    @staticmethod
+    def forward(ctx, x, r, nc, p):
+        ctx.r, ctx.nc, ctx.p = r, nc, p
+        return K.ps_pad_fwd(_contig(x), r, nc, p)
+
+    @staticmethod
+    def backward(ctx, dxp):
+        return K.ps_pad_bwd(_contig(dxp), ctx.r, ctx.nc, ctx.p), None, None, None
+
+
 class SegLossFn(Function):
     """returns tensor [3] = (miu_cross*xent + miu_dice*dice, xent, dice).
 
@@ -490,6 +509,24 @@ class CriticInputFn(Function):
         need = tuple(ctx.needs_input_grad[:5])
         da, db, dc, dd, dl = K.critic_input_bwd(_contig(dout), ctx.shapes, ctx.tile_a, need)
         return da, db, dc, dd, dl, None
+
+
+class CriticInputPsFn(Function):
+    """CriticInputFn over PSFn(a), PSFn(b), PSFn(c), PSFn(d) in one kernel each way: a..d are the COARSE tensors [N,A,B,C*r*r], the four
+    fine tensors are never written; bit-identical to the five Functions (PNP_PS_FUSE=0 runs those)."""
+
+    @staticmethod
+    def forward(ctx, a, b, c, d, logits, tile_a, r):
+        a, b, c, d, logits = map(_contig, (a, b, c, d, logits))
+        ctx.shapes = tuple(tuple(t.shape) for t in (a, b, c, d, logits))
+        ctx.tile_a, ctx.r = tile_a, r
+        return K.critic_input_ps_fwd(a, tile_a, b, c, d, logits, r)
+
+    @staticmethod
+    def backward(ctx, dout):
+        need = tuple(ctx.needs_input_grad[:5])
+        da, db, dc, dd, dl = K.critic_input_ps_bwd(_contig(dout), ctx.shapes, ctx.tile_a, ctx.r, need)
+        return da, db, dc, dd, dl, None, None
 
 
 class FanOutFn(Function):

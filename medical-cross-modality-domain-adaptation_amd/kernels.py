@@ -704,6 +704,33 @@ def sympad_bwd(dxp, p):
     return dx
 
 
+def ps_pad_served(r, nc, p):
+    """the geometries pnp_ps_pad_fwd / _bwd take: a coarse pixel's nc*r*r channels fit the kernels' LDS tile, the mirror stays inside the
+    first / last coarse pixel"""
+    return nc * r * r <= 4096 and 0 <= p <= r
+
+
+def ps_pad_fwd(x, r, nc, p):
+    """sympad_fwd(ps_fwd(x, r, nc), p) in one pass (bit-identical)"""
+    lib = _lib.load()
+    N, A, B, Cin = x.shape
+    if Cin != nc * r * r:
+        raise ValueError("PS: %d channels != n_channel*r*r = %d" % (Cin, nc * r * r))
+    xp = torch.empty((N, A * r + 2 * p, B * r + 2 * p, nc), dtype=torch.float32, device=x.device)
+    check(lib.pnp_ps_pad_fwd(_p(x), _p(xp), N, A, B, r, nc, p, _stream()), "pnp_ps_pad_fwd")
+    return xp
+
+
+def ps_pad_bwd(dxp, r, nc, p):
+    """ps_bwd(sympad_bwd(dxp, p), r, nc) in one pass (bit-identical: the mirrored positions are summed in sympad_bwd's order)"""
+    lib = _lib.load()
+    N, Hp, Wp, _ = dxp.shape
+    A, B = (Hp - 2 * p) // r, (Wp - 2 * p) // r
+    dx = torch.empty((N, A, B, nc * r * r), dtype=torch.float32, device=dxp.device)
+    check(lib.pnp_ps_pad_bwd(_p(dxp), _p(dx), N, A, B, r, nc, p, _stream()), "pnp_ps_pad_bwd")
+    return dx
+
+
 def seg_loss_fwd(logits, y, miu_cross=1.0, miu_dice=1.0):
     """returns (out[3] = total, xent, dice ; workspace tensor to hand to seg_loss_bwd)"""
     lib = _lib.load()
@@ -965,6 +992,45 @@ def critic_input_bwd(dout, shapes, tile_a, need=(True,) * 5):
     da, db, dc, dd, dl = mk(sa, need[0]), mk(sb, need[1]), mk(sc, need[2]), mk(sd, need[3]), mk(sl, need[4])
     check(lib.pnp_critic_input_bwd(_p(dout), _p(da), sa[-1], tile_a, _p(db), sb[-1], _p(dc), sc[-1], _p(dd), sd[-1], _p(dl), sl[-1],
                                    P, _stream()), "pnp_critic_input_bwd")
+    return da, db, dc, dd, dl
+
+
+def critic_input_ps_served(channels, tile_a, ncls, r):
+    """the sizes pnp_critic_input_ps_fwd / _bwd take (channels: of a, b, c, d AFTER PS): the four sources' coarse pixel fits the forward's
+    LDS tile, one coarse pixel's r x r fine pixels of dout the backward's"""
+    ctot = channels[0] * tile_a + sum(channels[1:]) + ncls + 1
+    return sum(channels) * r * r <= 4096 and r * (r * (ctot + 8) + 1) <= 6144
+
+
+def critic_input_ps_fwd(a, tile_a, b, c, d, logits, r):
+    """critic_input_fwd(ps_fwd(a), tile_a, ps_fwd(b), ps_fwd(c), ps_fwd(d), logits) from the coarse a..d [N,A,B,C*r*r] (bit-identical)"""
+    lib = _lib.load()
+    N, A, B, _ = a.shape
+    rr = r * r
+    Ca, Cb, Cc, Cd, ncls = a.shape[-1] // rr, b.shape[-1] // rr, c.shape[-1] // rr, d.shape[-1] // rr, logits.shape[-1]
+    for t, C in ((a, Ca), (b, Cb), (c, Cc), (d, Cd)):
+        if tuple(t.shape) != (N, A, B, C * rr):
+            raise ValueError("critic_input_ps_fwd: coarse tensor %r, expected [%d,%d,%d,C*%d]" % (tuple(t.shape), N, A, B, rr))
+    if tuple(logits.shape[:3]) != (N, A * r, B * r):
+        raise ValueError("critic_input_ps_fwd: logits %r on a grid other than [%d,%d,%d]" % (tuple(logits.shape), N, A * r, B * r))
+    Ct = Ca * tile_a + Cb + Cc + Cd + ncls + 1
+    out = torch.empty((N, A * r, B * r, Ct), dtype=torch.float32, device=logits.device)
+    check(lib.pnp_critic_input_ps_fwd(_p(a), Ca, tile_a, _p(b), Cb, _p(c), Cc, _p(d), Cd, _p(logits), ncls, _p(out), N, A, B, r, _stream()),
+          "pnp_critic_input_ps_fwd")
+    return out
+
+
+def critic_input_ps_bwd(dout, shapes, tile_a, r, need=(True,) * 5):
+    """the coarse gradients of a..d and dlogits from dout [N,A*r,B*r,Ctot]; shapes: of the coarse a..d and of logits (bit-identical to
+    critic_input_bwd + ps_bwd x4)"""
+    lib = _lib.load()
+    (sa, sb, sc, sd, sl) = shapes
+    N, A, B, _ = sa
+    rr = r * r
+    mk = lambda s, n: torch.empty(s, dtype=torch.float32, device=dout.device) if n else None
+    da, db, dc, dd, dl = mk(sa, need[0]), mk(sb, need[1]), mk(sc, need[2]), mk(sd, need[3]), mk(sl, need[4])
+    check(lib.pnp_critic_input_ps_bwd(_p(dout), _p(da), sa[-1] // rr, tile_a, _p(db), sb[-1] // rr, _p(dc), sc[-1] // rr, _p(dd), sd[-1] // rr,
+                                      _p(dl), sl[-1], N, A, B, r, _stream()), "pnp_critic_input_ps_bwd")
     return da, db, dc, dd, dl
 
 

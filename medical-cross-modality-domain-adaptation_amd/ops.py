@@ -8,7 +8,10 @@ batch_size >= 2 is the closed form
 """
 import torch
 
-from .functional import PSFn
+from . import functional as Fn
+from . import kernels as K
+from .functional import PSFn, PSPadFn
+from .layers import conv2d
 
 
 def PS(X, r, n_channel=8, batch_size=10):
@@ -19,6 +22,17 @@ def PS(X, r, n_channel=8, batch_size=10):
     if X.is_meta:   # symbolic build pass
         return torch.empty((X.shape[0], X.shape[1] * r, X.shape[2] * r, n_channel), device="meta")
     return PSFn.apply(X, r, n_channel)
+
+
+def PS_conv2d(X, W, r, n_channel, keep_prob_, batch_size=10):
+    """conv2d(PS(X, r, n_channel), W, keep_prob_, padding='SYMMETRIC') — the segmenter head (adversarial.py:312-316,
+    source_segmenter.py:202-206).  The mirror pad of the convolution is written by the PS kernel (pnp_ps_pad_fwd), the convolution then
+    runs VALID on that image exactly as it does behind layers._prepad; PNP_PS_FUSE=0: the two calls as written."""
+    p = int(W.shape[0]) // 2
+    if (Fn.PS_FUSE and not X.is_meta and W.shape[0] == W.shape[1] and X.shape[-1] == n_channel * r * r
+            and K.ps_pad_served(r, n_channel, p)):
+        return conv2d(PSPadFn.apply(X, r, n_channel, p), W, keep_prob_=keep_prob_, padding='VALID')
+    return conv2d(PS(X, r, n_channel=n_channel, batch_size=batch_size), W, keep_prob_=keep_prob_, padding='SYMMETRIC')
 
 
 def _phase_shift(I, r, batch_size=10):

@@ -20,7 +20,7 @@ from . import lib
 from .functional import SegLossFn, sync_now, wgrad_overlap
 from .layers import (DR_block, conv2d, conv_bn_relu2d, max_pool2d, pixel_wise_softmax_2, residual_block, weight_variable)
 from .lib import _dice_eval, _indicator_eval, _label_decomp
-from .ops import PS
+from .ops import PS_conv2d
 from .parallel import barrier, rank_seed
 from .variables import VariableStore
 
@@ -203,11 +203,11 @@ class Full_DRN(object):
             w10_1 = wv([3, 3, fb * 32, local_size * num_cls * 8], main_trainable)
             conv10_1 = conv2d(conv9_2, w10_1, keep_prob_=keep_prob, padding='SYMMETRIC')
             cw.append(w10_1)
-            flat_conv10_1 = PS(conv10_1, r=8, n_channel=num_cls * 8, batch_size=self.batch_size)
 
         with st.name_scope('output'):
             w11_1 = wv([5, 5, num_cls * 8, num_cls], main_trainable)
-            logits = conv2d(flat_conv10_1, w11_1, keep_prob_=1., padding='SYMMETRIC')
+            # PS(conv10_1, r=8) and the logits convolution's mirror pad in one kernel
+            logits = PS_conv2d(conv10_1, w11_1, r=8, n_channel=num_cls * 8, keep_prob_=1., batch_size=self.batch_size)
             cw.append(w11_1)
 
         self.conv_weights = cw
