@@ -751,6 +751,27 @@ int pnp_volume_smooth(const float* src, float* dst, int32_t X, int32_t Y, int32_
 int pnp_label_frame_stats(const uint8_t* label, int32_t X, int32_t Y, int32_t Z, int32_t ncls, int32_t* stats /* [Z, ncls, 5] */,
                           void* stream);
 
+/* ---- label-free body crop of a resident volume (csrc/body.hip): histogram between min and max, mask of the upper bins --------
+ *
+ * The bin of a voxel x of a volume with minimum lo and maximum hi, lo < hi, is
+ *   bin(x) = min(nbins - 1, (int)((x - lo) * scale)),   scale = (float)nbins / (hi - lo),
+ * every operation one float32 IEEE round-to-nearest operation, nothing contracted or reassociated; both calls compute it with the same
+ * device function, so they never disagree about a voxel on a bin edge.  2 <= nbins <= 1024.
+ * pnp_volume_histogram: v = n finite float32 voxels at ANY 4-byte address (a base that is no multiple of 16 costs up to three scalar loads
+ *   at either end, the rest are 16-byte loads).  range [2] float32 <- (lo, hi) = (min v, max v), bit-exact; hist [nbins] uint32 <- the voxel
+ *   count per bin, sum = n.  hi == lo (a constant volume): hist[0] = n, every other bin 0.  The call initialises range and hist itself;
+ *   one stream-ordered call (four launches), no host synchronisation, no workspace.  Integer atomics only (min / max of the order-preserving
+ *   uint32 key of a float, one pair per workgroup; LDS histograms, one global add per non-empty bin and workgroup): bit-identical from run
+ *   to run.
+ * pnp_volume_threshold_mask: mask [n] uint8 (any address) <- bin(v[i]) > k ? 1 : 0 with (lo, hi) read from `range` ON THE DEVICE (what
+ *   pnp_volume_histogram wrote for the same v) — the threshold is a bin index, a float threshold is never compared.  hi == lo: all zeros.
+ *   One launch, no host synchronisation.
+ * Refused on the host before any HIP call: null pointers; n < 1; n >= 2^31; nbins outside [2, 1024]; k outside [0, nbins - 1]; v, range or
+ * hist not 4-byte aligned; mask overlapping v. */
+int pnp_volume_histogram(const float* v, int64_t n, int32_t nbins, float* range /* [2] */, uint32_t* hist /* [nbins] */, void* stream);
+int pnp_volume_threshold_mask(const float* v, int64_t n, const float* range /* [2], device */, int32_t nbins, int32_t k, uint8_t* mask,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif

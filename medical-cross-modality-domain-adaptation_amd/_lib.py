@@ -217,6 +217,8 @@ PROTOTYPES = {
     "pnp_volume_smooth": (c_int, [_F, _F, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_size_t,
                                   c_void_p]),
     "pnp_label_frame_stats": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "pnp_volume_histogram": (c_int, [_F, c_int64, c_int32, _F, c_void_p, c_void_p]),
+    "pnp_volume_threshold_mask": (c_int, [_F, c_int64, _F, c_int32, c_int32, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -383,20 +383,24 @@ class Full_DRN(object):
         self.critic_scores = {k: o[k].detach() for k in ("ct_cls", "ct_mask") if o.get(k) is not None}
         return self.ct_gen_loss
 
-    def evaluate(self, ct, ct_y, mr, mr_y, keep_prob=1.0, detail=False):
+    def evaluate(self, ct, ct_y, mr, mr_y, keep_prob=1.0, detail=False, ct_labelled=True):
         """monitoring fetches that are not TensorBoard summaries (adversarial.py:101-116, 948-991): CT / MR hard Dice of the current
         segmenter, with `detail` the CT confusion matrix.  Every segmenter BN in inference mode; the critics are not evaluated (nothing
-        here consumes their scores), so the forward has no side effect on any variable."""
+        here consumes their scores), so the forward has no side effect on any variable.  ct_labelled=False (the CT batch comes from
+        unlabelled volumes, DESIGN.md §24: ct_y is class 0 everywhere): no CT Dice and no confusion matrix, the CT Dice returned is None."""
         from . import lib
         with torch.no_grad():
             o = self._graph(mr, ct, keep_prob, mr_front_bn=False, joint_bn=False, ct_front_bn=False, critics=False)
             self.predicter, self.compact_pred = K.softmax_argmax(o["ct_logits"].contiguous())
             self.mr_seg_valid, self.compact_mr_valid = K.softmax_argmax(o["mr_logits"].contiguous())
-            self.ct_dice_eval, self.ct_dice_eval_arr = _dice_eval(self.compact_pred, ct_y, self.n_class)
+            if ct_labelled:
+                self.ct_dice_eval, self.ct_dice_eval_arr = _dice_eval(self.compact_pred, ct_y, self.n_class)
+            else:
+                self.ct_dice_eval = self.ct_dice_eval_arr = None
             self.mr_dice_eval, self.mr_dice_eval_arr = _dice_eval(self.compact_mr_valid, mr_y, self.n_class)
-            if detail:
+            if detail and ct_labelled:
                 self.compact_y, self.confusion_matrix = lib.compact_and_confusion(ct_y, self.compact_pred)
-        return float(self.ct_dice_eval), float(self.mr_dice_eval)
+        return float(self.ct_dice_eval) if ct_labelled else None, float(self.mr_dice_eval)
 
     def predict_ct(self, ct, ct_y):
         """sess.run([compact_pred, confusion_matrix], {ct, ct_y, keep_prob: 1, *_bn: False}) of adversarial.py:1035-1037"""
@@ -716,8 +720,10 @@ class Trainer(object):
                     self.scalars.write("gan_step", step=step, epoch=epoch, host_time_s=self.step_times[-1], dis_updates=n_dis, gen_updates=n_gen)
                     logging.info("Training step %s epoch %s has been finished! Time elapsed %s seconds" % (step, epoch, time.time() - start))
                     if step % display_step == 0:
-                        self.output_minibatch_stats(step, *ct_feed.next()[:2], *mr_feed.next()[:2])                # a training batch ...
-                        self.output_minibatch_stats(step, *ct_val.next()[:2], *mr_val.next()[:2], detail=True)     # ... and a validation batch
+                        # a source of unlabelled CT volumes (AugmentedSliceSource.labelled is False) says so: no CT Dice
+                        unl = [{} if getattr(src, "labelled", True) else {"ct_labelled": False} for src in (self.ct_train_list, self.ct_val_list)]
+                        self.output_minibatch_stats(step, *ct_feed.next()[:2], *mr_feed.next()[:2], **unl[0])                # a training batch ...
+                        self.output_minibatch_stats(step, *ct_val.next()[:2], *mr_val.next()[:2], detail=True, **unl[1])     # ... and a validation batch
                     if step % tc.get("checkpoint_space", 100) == 0 and step != 0:
                         if self.rank == 0:
                             self.save_checkpoint(output_path)
@@ -733,10 +739,14 @@ class Trainer(object):
         barrier()
         return save_path
 
-    def output_minibatch_stats(self, step, ct_batch, ct_batch_y, mr_batch, mr_batch_y, detail=False):
-        """adversarial.py:948-991 without the TensorBoard writers: Dice of both domains, confusion matrix + per-organ report on `detail`"""
+    def output_minibatch_stats(self, step, ct_batch, ct_batch_y, mr_batch, mr_batch_y, detail=False, ct_labelled=True):
+        """adversarial.py:948-991 without the TensorBoard writers: Dice of both domains, confusion matrix + per-organ report on `detail`.
+        ct_labelled=False (the CT source holds unlabelled volumes: AugmentedSliceSource.labelled): the CT Dice and the CT confusion report
+        are skipped, the scalar log gets ct_dice = null; the MR side is unchanged"""
         from .lib import _indicator_eval
-        ct_d, mr_d = self.net.evaluate(ct_batch, ct_batch_y, mr_batch, mr_batch_y, detail=detail)
+        ct_d, mr_d = self.net.evaluate(ct_batch, ct_batch_y, mr_batch, mr_batch_y, detail=detail, **({} if ct_labelled else {"ct_labelled": False}))
+        if not ct_labelled:
+            logging.info("step %d %s batch: ct_dice n/a (unlabelled CT volumes), mr_dice %.4f" % (step, "validation" if detail else "training", mr_d))
         self.loss_dict["val" if detail else "train"] = (step, ct_d, mr_d)
         gp = {}
         if _gp_weight(self.net) > 0 and getattr(self.net, "gp_value", None) is not None:
@@ -747,7 +757,7 @@ class Trainer(object):
         if getattr(self, "scalars", None) is not None:      # evaluate() has just synchronised: the last losses cost nothing to read here
             self.scalars.write("val_eval" if detail else "train_eval", step=step, ct_dice=ct_d, mr_dice=mr_d,
                                dis_loss=_host(getattr(self.net, "dis_loss", None)), gen_loss=_host(getattr(self.net, "ct_gen_loss", None)), **gp)
-        if detail:
+        if detail and ct_labelled:
             _indicator_eval(self.net.confusion_matrix, verbose=verbose)
 
     # -- volume inference -------------------------------------------------------------------------------
@@ -779,7 +789,8 @@ class Trainer(object):
     def predict_volumes(self, nii_list, output_path, label_list=None, ensemble=None, tiles=None, tile_overlap=0.25, **options):
         """volume_predict.predict_volumes with this trainer's net (no counterpart in the reference): every image ->
         <output_path>/pred_<basename>, a uint8 label volume on the image's own grid with its affine; with label_list also the
-        dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  options: volume_predict.segment_volume's (edge, crop, axis,
+        dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  options: volume_predict.segment_volume's (edge, crop [a box, or "body" /
+        ("body", margin): the label-free body crop of DESIGN.md §24], axis,
         flip_correction, batch_size [default: the net's], percentile, out_size; tta, prob, entropy: DESIGN.md §15, which also write prob_* /
         entropy_* files; keep_largest, component_stats: the connected-component filter of DESIGN.md §16;
         sample_mm: the millimetre grid of DESIGN.md §17, with each file's voxel size read from its affine; prefilter: the anti-alias prefilter of DESIGN.md §19;

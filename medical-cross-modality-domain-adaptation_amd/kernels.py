@@ -1086,6 +1086,59 @@ def label_frame_stats(label, ncls):
     return stats
 
 
+def _flat_f32_volume(v, what):
+    if not isinstance(v, torch.Tensor) or not v.is_cuda:
+        raise _lib.PnpError("%s: pnp kernels need CUDA/HIP tensors (got a CPU tensor) — there is no CPU fallback" % what)
+    if v.dtype != torch.float32 or not v.is_contiguous() or v.numel() < 1:
+        raise _lib.PnpError("%s: a non-empty contiguous float32 tensor expected, got %s %s contiguous=%s"
+                            % (what, v.dtype, tuple(v.shape), v.is_contiguous()))
+    return v
+
+
+def _check_nbins(nbins, what):
+    if isinstance(nbins, bool) or int(nbins) != nbins or not 2 <= int(nbins) <= 1024:
+        raise _lib.PnpError("%s: nbins = %r outside [2, 1024]" % (what, nbins))
+    return int(nbins)
+
+
+def volume_histogram_packed(v, nbins=256):
+    """pnp_volume_histogram into ONE int32 device buffer of 2 + nbins words, so that one copy brings both results to the
+    host: words 0:2 are the bits of the float32 (lo, hi) = (min v, max v), words 2: the voxel count per bin (< 2^31 each)"""
+    _flat_f32_volume(v, "volume_histogram")
+    nbins = _check_nbins(nbins, "volume_histogram")
+    buf = torch.empty(2 + nbins, dtype=torch.int32, device=v.device)
+    check(_lib.load().pnp_volume_histogram(_p(v), v.numel(), nbins, ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(buf.data_ptr() + 8),
+                                           _stream()), "pnp_volume_histogram")
+    return buf
+
+
+def volume_histogram(v, nbins=256):
+    """pnp_volume_histogram of a contiguous float32 CUDA tensor of finite values (any shape, any storage offset) ->
+    (range: float32 [2] = (min, max), bit-exact; hist: int32 [nbins], the voxel count of bin
+    min(nbins - 1, int((v - lo) * (float32(nbins) / (hi - lo)))) in float32 round-to-nearest operations; a constant tensor counts in bin 0).
+    Both are views of one device buffer.  Stream-ordered, no host synchronisation, no workspace; bit-identical from run to run."""
+    buf = volume_histogram_packed(v, nbins)
+    return buf[:2].view(torch.float32), buf[2:]
+
+
+def volume_threshold_mask(v, range, k, nbins=256, out=None):
+    """pnp_volume_threshold_mask: uint8 tensor of v's shape, 1 where the bin of v (volume_histogram's, with `range` = its
+    float32 [2] device tensor, read on the device) is above k, 0 elsewhere; all zeros for a constant tensor.  out: a contiguous uint8 CUDA
+    tensor of v's shape to write into.  Stream-ordered, no host synchronisation."""
+    _flat_f32_volume(v, "volume_threshold_mask")
+    nbins = _check_nbins(nbins, "volume_threshold_mask")
+    if not isinstance(range, torch.Tensor) or not range.is_cuda or range.dtype != torch.float32 or range.numel() != 2 or not range.is_contiguous():
+        raise _lib.PnpError("volume_threshold_mask: range must be volume_histogram's float32 [2] CUDA tensor")
+    if isinstance(k, bool) or int(k) != k or not 0 <= int(k) <= nbins - 1:
+        raise _lib.PnpError("volume_threshold_mask: k = %r outside [0, %d]" % (k, nbins - 1))
+    if out is None:
+        out = torch.empty(v.shape, dtype=torch.uint8, device=v.device)
+    elif not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != tuple(v.shape) or not out.is_contiguous():
+        raise _lib.PnpError("volume_threshold_mask: out must be a contiguous uint8 CUDA tensor of shape %s" % (tuple(v.shape),))
+    check(_lib.load().pnp_volume_threshold_mask(_p(v), v.numel(), _p(range), nbins, int(k), _u8p(out), _stream()), "pnp_volume_threshold_mask")
+    return out
+
+
 def volume_smooth(v, weights, out=None):
     """pnp_volume_smooth of a contiguous float32 CUDA volume [X, Y, Z]: weights = (wx, wy, wz), each None (the axis is not
     filtered) or 2 r + 1 float32-convertible taps, r <= 32 (volume_source.gaussian_weights); borders replicated.  out=None: a new tensor;

@@ -595,7 +595,8 @@ class Trainer(object):
     def predict_volumes(self, nii_list, output_path, label_list=None, ensemble=None, tiles=None, tile_overlap=0.25, **options):
         """volume_predict.predict_volumes with this trainer's net (no counterpart in the reference): every image ->
         <output_path>/pred_<basename>, a uint8 label volume on the image's own grid with its affine; with label_list also the
-        dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  options: volume_predict.segment_volume's (edge, crop, axis,
+        dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  options: volume_predict.segment_volume's (edge, crop [a box, or "body" /
+        ("body", margin): the label-free body crop of DESIGN.md §24], axis,
         flip_correction, batch_size [default: the net's], percentile, out_size; tta, prob, entropy: DESIGN.md §15, which also write prob_* /
         entropy_* files; keep_largest, component_stats: the connected-component filter of DESIGN.md §16;
         sample_mm: the millimetre grid of DESIGN.md §17, with each file's voxel size read from its affine; prefilter: the anti-alias prefilter of DESIGN.md §19;

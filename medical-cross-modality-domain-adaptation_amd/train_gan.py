@@ -4,7 +4,8 @@
   --phase fine-tune : continue from a breakpoint (the reference's `training_config` NameError at train_gan.py:121 is fixed)
 Extra flags: --synthetic N, --batch-size, --iters, --epochs, --output, --baseline (source-segmenter .npz for the pre-train hand-off),
 --mr-nii-train / --mr-nii-val / --ct-nii-train / --ct-nii-val LIST (all four: train from NIfTI volumes kept on the device,
-volume_source.py; --augment JSON / --no-augment; --axes 0,1,2: slices of every listed orientation, one value for MR and CT), --gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference).
+volume_source.py; the two CT lists may name images alone — unlabelled target scans; --crop-body [N] / --crop-margin N crop
+every volume of both domains to its body / label box; --augment JSON / --no-augment; --axes 0,1,2: slices of every listed orientation, one value for MR and CT), --gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference).
 """
 import argparse
 import datetime
@@ -82,12 +83,15 @@ def parse_args(phase, argv=None):
     add_axes_flag(ap)
     add_sampling_flags(ap, what="the source-domain (MR) training volumes ONLY: the target's labels must not steer an unsupervised adaptation, "
                                 "so the CT volumes and both validation sets stay uniform")
+    from . import body
+    body.add_crop_flags(ap)
     args = ap.parse_args(argv)
     args.axes = axes_from_args(ap, args)                    # one value serves MR and CT
     args.sample_mm = sample_mm_from_args(ap, args)          # one grid for both modalities: that is the point
     args.prefilter = prefilter_from_args(ap, args)          # one setting for both: the per-volume sigmas differ through the spacings
     args.sampling = sampling_from_args(ap, args)            # the MR training set's alone
     given = [getattr(args, f) is not None for f in NII_FLAGS]
+    args.crop = body.crop_from_args(ap, args, have_lists=all(given))         # one crop for both domains
     if any(given) and not all(given):
         ap.error("--mr-nii-train, --mr-nii-val, --ct-nii-train and --ct-nii-val go together")
     if all(given) and args.synthetic:
@@ -137,9 +141,11 @@ def main(phase, argv=None):
         shard = (rank, world) if world > 1 else None
         mr_train, mr_val = sources_from_lists(args.mr_nii_train, args.mr_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
                                               seed=0, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter, axes=args.axes,
-                                              sampling=args.sampling)
+                                              sampling=args.sampling, crop=args.crop)
+        # the target lists may name images alone: dis_step and gen_step never read a CT label, the Dice monitor skips such a source
         ct_train, ct_val = sources_from_lists(args.ct_nii_train, args.ct_nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
-                                              seed=2, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter, axes=args.axes)
+                                              seed=2, shard=shard, sample_mm=args.sample_mm, prefilter=args.prefilter, axes=args.axes,
+                                              crop=args.crop, labels="optional")
     elif args.synthetic:
         from .synthetic import write_dataset
         sets = (("syn_mr_train", args.synthetic, 0, "mr"), ("syn_ct_train", args.synthetic, 1, "ct"),

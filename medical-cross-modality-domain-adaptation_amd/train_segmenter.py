@@ -3,7 +3,8 @@ source segmenter.  Extra flags (defaults keep the reference behaviour): --synthe
 them, --batch-size, --iters, --epochs, --output; --nii-train LIST --nii-val LIST train from NIfTI volumes kept on the device
 (volume_source.py: one `image.nii[.gz] label.nii[.gz]` pair per line; --augment JSON / --no-augment; --sample-mm MM|PI,PJ,FRAME samples them on
 a millimetre grid; --prefilter auto|off|SX,SY,SZ low-passes them first; --axes 0,1,2 trains on slices of
-every listed orientation).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
+every listed orientation; --crop-body [N] crops every volume to its body, found without a label, --crop-margin N to its
+label bounding box).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
 one process per GPU over RCCL, --batch-size slices PER RANK, file lists sharded by rank, rank 0 writes the checkpoint.
   python -m "medical-cross-modality-domain-adaptation_amd.train_segmenter" --synthetic 8 --batch-size 4 --iters 2 --epochs 1
 """
@@ -41,7 +42,10 @@ def main(argv=None):
     add_prefilter_flag(ap)
     add_axes_flag(ap)
     add_sampling_flags(ap)
+    from . import body
+    body.add_crop_flags(ap)
     args = ap.parse_args(argv)
+    crop = body.crop_from_args(ap, args, have_lists=bool(args.nii_train))
     sample_mm = sample_mm_from_args(ap, args)
     prefilter = prefilter_from_args(ap, args)
     axes = axes_from_args(ap, args)
@@ -82,7 +86,7 @@ def main(argv=None):
         from .volume_source import sources_from_lists
         train_list, val_list = sources_from_lists(args.nii_train, args.nii_val, device, batch_size, num_cls, augment=augment_from_args(args),
                                                   shard=(rank, world) if world > 1 else None, sample_mm=sample_mm,
-                                                  prefilter=prefilter, axes=axes, sampling=sampling)
+                                                  prefilter=prefilter, axes=axes, sampling=sampling, crop=crop)
     elif args.synthetic:
         from .synthetic import write_dataset
         # next to (not inside) output_path: Trainer.train(restore=False) clears output_path like the reference (source_segmenter.py:416-418)

@@ -271,7 +271,7 @@ def ensemble_members(logits_fn, tta, limit=MAX_MEMBERS):
 
 def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
                    out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None,
-                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25, axes=None, axis_weights=None):
+                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25, axes=None, axis_weights=None, crop_box=None):
     """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
       logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
                  checkpoint ensemble
@@ -281,7 +281,12 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     crop box all three are 0) and every batch ends in one pnp_paste_ensemble launch; with the defaults it is the label
     tensor alone, through pnp_paste_labels.
       label      optional ground truth of the same shape: only its bounding box is used (crop = a margin in voxels)
-      crop       None, a margin around the label's bounding box, or a box ((x0, x1), (y0, y1), (z0, z1)) in slicing order; outside it: 0
+      crop       None, a margin around the label's bounding box, or a box ((x0, x1), (y0, y1), (z0, z1)) in slicing order; outside it: 0.
+                 "body" or ("body", margin): the label-free body crop of DESIGN.md §24 — the prepared full volume is uploaded,
+                 body.body_box finds the patient's bounding box on the device (two host synchronisations), the crop is taken on the device
+                 and everything after that is the path of an explicit box: the result equals crop=<that box> bit for bit.  With axes the
+                 box is found once, in the default axis's order, and handed to the views through view_box.
+      crop_box   optional list: the box used, ((x0, x1), (y0, y1), (z0, z1)) in slicing order (with axes: of the default axis), is appended
       keep_largest   None, an int K (keep the K largest 3-D components of every class) or a dict of components.keep_largest's keywords
                  (keep, min_size, connectivity, classes): applied in place to the finished label volume on the device.  On
                  the ensemble path only Ensemble.label is filtered: prob and entropy are returned as computed, also where the label became 0.
@@ -327,13 +332,25 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         raise ValueError("edge must be one of %s, got %r" % (EDGES, edge))
     from . import components
     post = components.parse_option(keep_largest, num_cls)
+    body_margin = _body_margin(crop)                            # None unless crop is "body" / ("body", margin)
     if axes is not None or axis_weights is not None:
         if axes is None:
             raise ValueError("axis_weights %r goes with axes" % (axis_weights,))
         if axis != 2:
             raise ValueError("axes=%r and axis=%r exclude each other: leave axis at its default" % (axes, axis))
         axes, axis_weights = check_axes(axes, axis_weights)
+        if body_margin is not None:                             # found once, in the slicing order of axis 2; the views get it as a box
+            full = _upload_prepared(image, flip_correction, 2, device)
+            from . import body
+            crop = body.body_box(full, percentile=int(percentile), margin=body_margin)
+            del full
         explicit = crop is not None and not isinstance(crop, (int, np.integer))          # a box, in the slicing order of axis 2
+        if crop_box is not None:
+            if explicit:
+                crop_box.append(tuple((int(a), int(b)) for a, b in crop))
+            else:
+                lab2 = None if label is None else prepare_pair(image, label, flip_correction, 2, None)[1]
+                crop_box.append(_box_of(crop, lab2, file_layout(np.shape(image), flip_correction, 2)[2]))
         views = []
         for a in axes:
             one = segment_volume(logits_fn, image, label=label, flip_correction=flip_correction, axis=a,
@@ -374,7 +391,15 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         raise _lib.PnpError("segment_volume: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (device,))
     image = np.asarray(image)
     img, lab = prepare_pair(image, np.zeros(image.shape, np.uint8) if label is None else label, flip_correction, axis, None)
-    box = _box_of(crop, None if label is None else lab, img.shape)
+    full = None
+    if body_margin is not None:
+        from . import body
+        full = torch.from_numpy(img).to(device)
+        box = body.body_box(full, percentile=int(percentile), margin=body_margin)
+    else:
+        box = _box_of(crop, None if label is None else lab, img.shape)
+    if crop_box is not None:
+        crop_box.append(box)
     origin, strides, (X, Y, Z) = file_layout(image.shape, flip_correction, axis, box)
     if edge == "skip" and Z < 3:
         raise ValueError("edge='skip' needs at least 3 frames, the box has %d" % Z)
@@ -394,7 +419,11 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         entries = shifted
     out = torch.zeros(tuple(image.shape), dtype=torch.uint8, device=device)
 
-    v = torch.from_numpy(np.ascontiguousarray(img[tuple(slice(a, b) for a, b in box)])).to(device)
+    if full is not None:                                # the body crop, taken on the device
+        v = full[tuple(slice(a, b) for a, b in box)].contiguous()
+        del full
+    else:
+        v = torch.from_numpy(np.ascontiguousarray(img[tuple(slice(a, b) for a, b in box)])).to(device)
     _, stats = K.volume_preprocess(v, int(percentile), out=v)
     fill = float(stats[3].item())                       # the one read before the loop: the fill enters the gather's descriptor table
     if pre is not None:
@@ -453,6 +482,24 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     return Ensemble(out, out_p, out_e) if ensemble else out
 
 
+def _body_margin(crop):
+    """the margin of crop="body" / ("body", margin), None for every other crop; a malformed body crop is a ValueError"""
+    if isinstance(crop, str) or (isinstance(crop, (tuple, list)) and len(crop) > 0 and isinstance(crop[0], str)):
+        from . import body
+        return body.parse_crop(crop)[1]
+    return None
+
+
+def _upload_prepared(image, flip_correction, axis, device):
+    """prepare_pair's image (flips, `axis` last, finite check) on the device, whole"""
+    import torch
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.PnpError("segment_volume: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (device,))
+    image = np.asarray(image)
+    return torch.from_numpy(prepare_pair(image, np.zeros(image.shape, np.uint8), flip_correction, axis, None)[0]).to(device)
+
+
 def _filter_components(label, post, num_cls, component_stats):
     """components.keep_largest on the finished label volume, in place; post: components.parse_option's keywords or None (nothing runs)"""
     if post is None:
@@ -486,7 +533,8 @@ def adapted_logits(net):
 def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5, device="cuda", **options):
     """every image of nii_list -> <output_path>/pred_<basename>: uint8 NIfTI on the input's grid with the input's affine.  With
     label_list (same order) also the dense_pred_<name>.nii.gz / gth_dense_pred_<name>.nii.gz pair that `evaluate --pred-dir` reads (the
-    ground truth with labels >= num_cls set to 0).  options: segment_volume's; with prob= / entropy= also prob_<basename> (float32,
+    ground truth with labels >= num_cls set to 0).  options: segment_volume's; with crop="body" / ("body", margin) the box
+    found for every image is logged (crop_box=[] also collects them, one per image); with prob= / entropy= also prob_<basename> (float32,
     [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine; with keep_largest= every label volume written
     is the filtered one (component_stats=[]: one stats tensor per volume is appended); prefilter= is segment_volume's (the
     setting the network was trained with); tiles= / tile_overlap= are segment_volume's (the share logged is then the union
@@ -507,7 +555,13 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
         if options.get("sample_mm") is not None:
             from .surface import spacing_of
             extra = {"spacing": check_spacing(spacing_of(img.affine), str(fid)), "fov_stats": []}
-        res = segment_volume(logits_fn, img.get_data(), label=gt, num_cls=num_cls, device=device, **options, **extra)
+        if _body_margin(options.get("crop")) is not None:
+            extra["crop_box"] = options["crop_box"] if options.get("crop_box") is not None else []
+        res = segment_volume(logits_fn, img.get_data(), label=gt, num_cls=num_cls, device=device,
+                             **{k: v for k, v in options.items() if k not in extra}, **extra)
+        if "crop_box" in extra:
+            logging.info("%s: body box %s of the volume %s (slicing order, half-open)" % (
+                fid, " x ".join("[%d, %d)" % b for b in extra["crop_box"][-1]), tuple(img.get_data().shape)))
         for share in extra.get("fov_stats", ()):
             log = logging.warning if share < 1.0 else logging.info
             log("%s: %.1f %% of the voxel columns lie inside the field of view (pixels of %s mm)%s" % (

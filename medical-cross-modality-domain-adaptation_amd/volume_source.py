@@ -11,10 +11,13 @@ the host only draws the parameters.
                         [B, H, W, 4] numpy protocol
 
 A list file holds one `image.nii[.gz] label.nii[.gz]` pair per line (paths relative to the list file's folder unless absolute).
+With read_pairs(..., labels="optional") a line may name the image alone: an unlabelled target scan.  It gets an all-zero
+label volume, VolumeSet.has_labels / AugmentedSliceSource.labelled say so, and VolumeSet(crop="body" | ("body", margin)) crops every volume
+to the bounding box of the patient found on the device without a label (body.body_box) instead of the label bounding box.
 
   python -m "medical-cross-modality-domain-adaptation_amd.volume_source" --export N OUTDIR --list LIST [--augment JSON | --no-augment]
          [--sample-mm MM|PI,PJ,FRAME] [--prefilter auto|off|SX,SY,SZ] [--axes 0,1,2]
-         [--foreground P [--foreground-classes C[,C..]] [--foreground-centre]]
+         [--foreground P [--foreground-classes C[,C..]] [--foreground-centre]] [--crop-body [N] | --crop-margin N]
 writes N slices in the reference's tfrecord layout (tfrecord.write_slice) plus OUTDIR/slice_list, so that the TensorFlow reference can be
 fed from the same volumes.
 
@@ -65,8 +68,11 @@ DEFAULT_ELASTIC_GRID = 4
 MAX_ELASTIC_GRID = 16
 
 
-def read_pairs(list_file):
-    """list file -> [(image path, label path)]; blank lines and lines starting with # are skipped"""
+def read_pairs(list_file, labels="required"):
+    """list file -> [(image path, label path)]; blank lines and lines starting with # are skipped.  labels="optional": a line may name
+    the image alone (an unlabelled target scan) and gives (image path, None)"""
+    if labels not in ("required", "optional"):
+        raise ValueError("read_pairs: labels must be \"required\" or \"optional\", got %r" % (labels,))
     if not os.path.isfile(list_file):
         raise IOError("volume list %s does not exist" % list_file)
     base = os.path.dirname(os.path.abspath(list_file))
@@ -77,7 +83,7 @@ def read_pairs(list_file):
             if not line or line.startswith("#"):
                 continue
             parts = line.split()
-            if len(parts) != 2:
+            if len(parts) != 2 and not (labels == "optional" and len(parts) == 1):
                 raise ValueError("%s:%d: expected `image.nii[.gz] label.nii[.gz]`, got %d fields" % (list_file, no, len(parts)))
             for p in parts:
                 if not p.endswith((".nii", ".nii.gz")):
@@ -86,7 +92,7 @@ def read_pairs(list_file):
             for p in pair:
                 if not os.path.isfile(p):
                     raise IOError("%s:%d: %s does not exist" % (list_file, no, p))
-            pairs.append(pair)
+            pairs.append(pair if len(pair) == 2 else (pair[0], None))
     if not pairs:
         raise ValueError("%s: no volume pair listed" % list_file)
     return pairs
@@ -512,9 +518,10 @@ def label_bounding_box(label, margin):
     return tuple(slice(max(int(a.min()) - margin, 0), min(int(a.max()) + 1 + margin, n)) for a, n in zip(nz, label.shape))
 
 
-def prepare_pair(image, label, flip_correction=True, axis=2, crop=None):
+def prepare_pair(image, label, flip_correction=True, axis=2, crop=None, box_out=None):
     """host numpy, once per volume: the double flip of volume_eval.test_eval, `axis` moved last, the optional crop to the label bounding
-    box plus `crop` voxels -> (float32 image [X, Y, Z], uint8 label [X, Y, Z]), both C-contiguous"""
+    box plus `crop` voxels -> (float32 image [X, Y, Z], uint8 label [X, Y, Z]), both C-contiguous.  box_out: a list that receives the
+    box of a crop, ((x0, x1), (y0, y1), (z0, z1)) half-open"""
     image, label = np.asarray(image), np.asarray(label)
     if image.ndim != 3 or image.shape != label.shape:
         raise ValueError("image %s / label %s: a 3-D pair of equal shape expected" % (image.shape, label.shape))
@@ -529,15 +536,33 @@ def prepare_pair(image, label, flip_correction=True, axis=2, crop=None):
     if crop is not None:
         box = label_bounding_box(label, int(crop))
         image, label = image[box], label[box]
+        if box_out is not None:
+            box_out.append(tuple((sl.start, sl.stop) for sl in box))
     if not np.all(np.isfinite(image)):
         raise ValueError("the image holds non-finite voxels")
     return np.ascontiguousarray(image, dtype=np.float32), np.ascontiguousarray(label, dtype=np.uint8)
+
+
+def _device_body_box(img, device, percentile, margin):
+    """body.body_box of a prepared host volume: uploaded whole, released when the box is known"""
+    import torch
+    from . import body
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.PnpError("VolumeSet: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (dev,))
+    return body.body_box(torch.from_numpy(img).to(dev), percentile=percentile, margin=margin)
 
 
 class VolumeSet(object):
     """Normalised volumes resident on `device`.  pairs: [(image path, label path)] (read_pairs).  Per volume, in this order: the double
     flip volume_eval.test_eval applies (flip_correction), `axis` moved last (the slicing axis), crop=None or a margin in voxels around
     the label bounding box, upload, pnp_volume_preprocess (clip at the `percentile` order statistic, z-score).
+    Unlabelled volumes and the body crop: a pair's label path may be None — the entry then gets an all-zero uint8 label
+    volume (the gather kernels and their descriptor table do not change) and .has_labels, one bool per entry, says so.  crop="body" or
+    ("body", margin): the prepared full volume is uploaded, body.body_box finds the patient on the device without a label, image and label
+    are cropped to that box and pnp_volume_preprocess runs on the crop (the stats are the crop's).  .boxes: per entry the box used,
+    ((x0, x1), (y0, y1), (z0, z1)) half-open in the entry's order, for either crop; None without a crop.  With several axes the box of a
+    pair is found once, on its first axis, and permuted for the others.  An int crop needs a label: ValueError for an entry without one.
     .images / .labels: device tensors [X, Y, Z] float32 / uint8;  .stats: [{clip, mean, std, fill}];  .names: image basenames;
     .spacings: [(sx, sy, sz)] in mm, slicing order (from the image's affine; from_arrays / from_device: spacings=, default 1 mm).
     Multi-planar training: `axis` may be a sequence of distinct axes (check_axes).  The set then holds one resident entry
@@ -548,26 +573,51 @@ class VolumeSet(object):
 
     def __init__(self, pairs, device, flip_correction=True, axis=2, crop=None, percentile=98):
         from . import nifti
+        from . import body
         axes = (axis,) if isinstance(axis, (int, np.integer)) and not isinstance(axis, bool) else check_axes(axis)[0]
-        arrays, names, spacings = [], [], []
+        kind = body.parse_crop(crop)
+        arrays, names, spacings, has_labels, boxes = [], [], [], [], []
         for image_fid, label_fid in pairs:
             image = nifti.load(image_fid)
-            data, label = image.get_data(), nifti.load(label_fid).get_data()
+            data = image.get_data()
+            if label_fid is None and kind is not None and kind[0] == "label":
+                raise ValueError("%s has no label: crop=%r is a margin around the label bounding box (crop=\"body\" needs none)" % (image_fid, crop))
+            label = np.zeros(np.shape(data), dtype=np.uint8) if label_fid is None else nifti.load(label_fid).get_data()
+            file_box = None          # the pair's body box in file order (after the flips), found on its first axis
             for ax in axes:
-                arrays.append(prepare_pair(data, label, flip_correction, ax, crop))
+                if kind is None:
+                    img, lab = prepare_pair(data, label, flip_correction, ax, None)
+                    boxes.append(None)
+                elif kind[0] == "label":
+                    img, lab = prepare_pair(data, label, flip_correction, ax, crop, box_out=boxes)
+                else:
+                    img, lab = prepare_pair(data, label, flip_correction, ax, None)
+                    if file_box is None:
+                        file_box = body.unpermute_box(_device_body_box(img, device, percentile, kind[1]), ax)
+                    box = body.permute_box(file_box, ax)
+                    img, lab = np.ascontiguousarray(img[body.box_slices(box)]), np.ascontiguousarray(lab[body.box_slices(box)])
+                    boxes.append(box)
+                arrays.append((img, lab))
+                has_labels.append(label_fid is not None)
                 names.append(os.path.basename(str(image_fid)) + ("@%d" % ax if len(axes) > 1 else ""))
                 spacings.append(slicing_spacing(image.affine, ax, str(image_fid)))
         self.axes = tuple(int(a) for a in axes)
         self._build(arrays, names, device, percentile)
         self.spacings = spacings
+        self.has_labels = has_labels
+        self.boxes = boxes if kind is not None else None
 
     @classmethod
     def from_arrays(cls, images, labels, names, device, percentile=98, spacings=None):
         """volumes already in slicing order [X, Y, Z] (no flip, no crop): float32-convertible images, integer labels in [0, 255];
-        spacings: one (sx, sy, sz) in mm per volume (default: 1 mm)"""
+        spacings: one (sx, sy, sz) in mm per volume (default: 1 mm).  A label may be None: an unlabelled volume (all-zero labels,
+        has_labels False)"""
         self = cls.__new__(cls)
-        arrays = [prepare_pair(i, l, flip_correction=False, axis=2, crop=None) for i, l in zip(images, labels)]
+        arrays = [prepare_pair(i, np.zeros(np.shape(i), dtype=np.uint8) if l is None else l, flip_correction=False, axis=2, crop=None)
+                  for i, l in zip(images, labels)]
         self._build(arrays, [str(n) for n in names], device, percentile)
+        self.has_labels = [l is not None for l in labels]
+        self.boxes = None
         self._set_spacings(spacings)
         return self
 
@@ -601,6 +651,8 @@ class VolumeSet(object):
         self.images, self.labels = list(images), list(labels)
         self.dims = [tuple(int(d) for d in v.shape) for v in self.images]
         self.stats = [{"clip": None, "mean": None, "std": None, "fill": float(f)} for f in fills]
+        self.has_labels = [True] * len(self.images)
+        self.boxes = None
         self.set_fill(None)
         return self
 
@@ -708,7 +760,9 @@ class AugmentedSliceSource(object):
                 random class present in its volume (and with `centre` the plane centred on that class in the frame) instead of a uniform
                 frame.  The draws come from a third generator, default_rng([seed + rank_seed(rank), 2]): the volumes and augment draws of
                 a seed do not depend on the option.  The set's class tables (VolumeSet.frame_stats) are computed here, once;
-                sampling_report() counts what was drawn; last_draw holds the raw draws of the last batch (sample_params' dict)."""
+                sampling_report() counts what was drawn; last_draw holds the raw draws of the last batch (sample_params' dict).
+    .labelled: every entry of the set has a label (VolumeSet.has_labels); a source that is not labelled delivers label 0 / one-hot class 0
+    everywhere, the trainers skip the Dice of its batches, and foreground sampling on it is a ValueError."""
 
     def __init__(self, volumes, batch_size, out_size=(256, 256), augment=DEFAULT_AUGMENT, seed=0, shard=None, num_cls=5, sample_mm=None,
                  prefilter=None, sampling=None):
@@ -728,6 +782,10 @@ class AugmentedSliceSource(object):
         self.rng2 = np.random.default_rng([int(seed) + rank_seed(self.rank), 1]) if self.warp else None
         check_elastic_fold(self.augment, self.out_size)
         self.sampling = check_sampling(sampling, self.num_cls)
+        self.labelled = all(getattr(volumes, "has_labels", None) or [True])
+        if self.sampling and not self.labelled:
+            raise ValueError("sampling: foreground-aware sampling reads the labels, and the set holds unlabelled volumes (%s)"
+                             % ", ".join(n for n, h in zip(volumes.names, volumes.has_labels) if not h))
         self.rng3 = np.random.default_rng([int(seed) + rank_seed(self.rank), 2]) if self.sampling else None
         self._frame_stats = volumes.frame_stats(self.num_cls) if self.sampling else None
         self._drawn, self._fallbacks, self._fg = 0, 0, {c: 0 for c in (self.sampling or {}).get("classes", ())}
@@ -822,15 +880,18 @@ class AugmentedSliceSource(object):
 
 
 def sources_from_lists(train_list, val_list, device, batch_size, num_cls, augment=DEFAULT_AUGMENT, seed=0, shard=None, sample_mm=None,
-                       prefilter=None, axes=None, sampling=None):
+                       prefilter=None, axes=None, sampling=None, crop=None, labels="required"):
     """the two sources of a trainer from two list files: the training one augmented, the validation one with augment=None; sample_mm and
     prefilter (AugmentedSliceSource's) hold for both, and so does axes (None: the default slicing axis; a sequence: VolumeSet's
     multi-planar set, DESIGN.md §21 — one resident entry per volume and axis); sampling (foreground-aware frames) goes to
-    the training source only: validation stays uniform"""
+    the training source only: validation stays uniform; crop (VolumeSet's: None, a label margin, "body" or ("body", margin)) and labels
+    (read_pairs': "optional" admits image-only lines) hold for both lists"""
     which = {} if axes is None else {"axis": check_axes(axes)[0]}
-    train = AugmentedSliceSource(VolumeSet(read_pairs(train_list), device, **which), batch_size, augment=augment, seed=seed, shard=shard,
+    if crop is not None:
+        which["crop"] = crop
+    train = AugmentedSliceSource(VolumeSet(read_pairs(train_list, labels), device, **which), batch_size, augment=augment, seed=seed, shard=shard,
                                  num_cls=num_cls, sample_mm=sample_mm, prefilter=prefilter, sampling=sampling)
-    val = AugmentedSliceSource(VolumeSet(read_pairs(val_list), device, **which), batch_size, augment=None, seed=seed + 1, shard=shard,
+    val = AugmentedSliceSource(VolumeSet(read_pairs(val_list, labels), device, **which), batch_size, augment=None, seed=seed + 1, shard=shard,
                                num_cls=num_cls, sample_mm=sample_mm, prefilter=prefilter)
     return train, val
 
@@ -1003,12 +1064,15 @@ def augment_from_args(args):
 
 
 def export(n, outdir, list_file, device="cuda", augment=DEFAULT_AUGMENT, seed=0, batch_size=16, out_size=(256, 256), sample_mm=None,
-           prefilter=None, axes=None, sampling=None):
+           prefilter=None, axes=None, sampling=None, crop=None):
     """N augmented slices as one-record tfrecords in the reference's layout plus OUTDIR/slice_list.  data_vol is the [H, W, 3] image;
     label_vol repeats the centre frame's label map in its three channels (the reference's decoder reads channel 1 only).  axes: None, or
-    the slicing axes of a multi-planar set.  sampling: None, or AugmentedSliceSource's foreground sampling."""
+    the slicing axes of a multi-planar set.  sampling: None, or AugmentedSliceSource's foreground sampling.
+    crop: None, or VolumeSet's crop (a label margin, "body" or ("body", margin): DESIGN.md §24)."""
     from .tfrecord import write_slice
     which = {} if axes is None else {"axis": check_axes(axes)[0]}
+    if crop is not None:
+        which["crop"] = crop
     src = AugmentedSliceSource(VolumeSet(read_pairs(list_file), device, **which), batch_size, out_size=out_size, augment=augment, seed=seed,
                                sample_mm=sample_mm, prefilter=prefilter, sampling=sampling)
     os.makedirs(outdir, exist_ok=True)
@@ -1039,10 +1103,13 @@ def main(argv=None):
     add_prefilter_flag(ap)
     add_axes_flag(ap)
     add_sampling_flags(ap)
+    from . import body
+    body.add_crop_flags(ap)
     args = ap.parse_args(argv)
+    crop = body.crop_from_args(ap, args)
     files = export(int(args.export[0]), args.export[1], args.list, device=args.device, augment=augment_from_args(args), seed=args.seed,
                    sample_mm=sample_mm_from_args(ap, args), prefilter=prefilter_from_args(ap, args), axes=axes_from_args(ap, args),
-                   sampling=sampling_from_args(ap, args))
+                   sampling=sampling_from_args(ap, args), crop=crop)
     print("wrote %d slices and %s" % (len(files), os.path.join(args.export[1], "slice_list")))
     return files
 
