@@ -132,6 +132,7 @@ int32_t pnp_conv2d_wino_chosen(const pnp_conv_geom* g, int32_t kind);   /* 0: di
 #define PNP_ROUTE_N16_WGRAD 9    /* filter gradient: 16x16x4-MFMA kernel */
 #define PNP_ROUTE_WGD 10         /* filter gradient: vector-ALU kernel */
 #define PNP_ROUTE_RING 11        /* filter gradient: MFMA ring kernel */
+#define PNP_ROUTE_X3N 12         /* direct split-bf16, the 5x5 40 -> 5 logits layer: forward and data gradient (conv_x3_narrow.hip) */
 int32_t pnp_conv2d_route(const pnp_conv_geom* g, int32_t kind);
 /* sets the route policy at run time (0 / 1 / 2 as PNP_WINOGRAD; < 0: read only) and returns the previous one */
 int32_t pnp_conv2d_wino_mode(int32_t mode);
@@ -168,6 +169,14 @@ int32_t pnp_conv2d_x3_strided(int32_t mode);
  * kernels.  Taken under pnp_conv2d_x3_direct's mode (1: >= 256 tiles) while this switch is 1 (default; environment PNP_X3_WGRAD); 0: off.
  * Returns the previous value (mode < 0: read only). */
 int32_t pnp_conv2d_x3_wgrad(int32_t mode);
+/* The segmenter head's logits layer on the same arithmetic (csrc/conv_x3_narrow.hip: 5x5, stride 1, dilation 1, 40 -> 5 channels, fp32
+ * geometry, zero or no padding), forward (output a multiple of 8 x 16; dropout as the vector-ALU kernel's, same masks) and data gradient
+ * (any extent; honours the residual of pnp_conv2d_dgrad_add): the 5-channel side is the 16-row operand of v_mfma_f32_16x16x32_bf16, the
+ * taps are LDS offsets of one split patch, the split filter image goes through pnp_conv2d_{fwd,dgrad}_workspace_bytes(g) of workspace.
+ * Route PNP_ROUTE_X3N.  0: off, 1 (default; environment PNP_X3_NARROW): where a launch fills the chip (>= 256 tiles) and the direction
+ * measured faster at B = 16, 2: wherever the shapes allow; pnp_conv2d_x3_direct(0) turns it off as well.  Frozen-BN forwards, bf16
+ * geometries and the filter gradient keep their kernels.  Returns the previous mode (mode < 0: read only). */
+int32_t pnp_conv2d_x3_narrow(int32_t mode);
 /* Transformed-filter cache of the route.  U = G g G^T (36 C K values per filter and pass: fp32, or three bf16 planes) only changes when the filter does: the caller
  * lends one buffer per (filter, pass) and reports weight writes; a launch whose filter has a valid entry skips wino_filter_kernel (the
  * frozen source segmenter / shared half of adversarial.py:839-882 never pay it again, a trained layer once per update instead of once per

@@ -24,7 +24,7 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F64 = 0, 1, 2
 COMM_ID_BYTES = 128
 # PNP_ROUTE_* (pnp_conv2d_route)
 (ROUTE_IGEMM, ROUTE_N16, ROUTE_NARROW, ROUTE_WINO, ROUTE_X3D, ROUTE_X3S, ROUTE_PHASES,
- ROUTE_WINO_WGRAD, ROUTE_X3W, ROUTE_N16_WGRAD, ROUTE_WGD, ROUTE_RING) = range(12)
+ ROUTE_WINO_WGRAD, ROUTE_X3W, ROUTE_N16_WGRAD, ROUTE_WGD, ROUTE_RING, ROUTE_X3N) = range(13)
 ABI_VERSION = 4
 
 
@@ -107,6 +107,7 @@ PROTOTYPES = {
     "pnp_conv2d_x3_direct": (c_int32, [c_int32]),
     "pnp_conv2d_x3_strided": (c_int32, [c_int32]),
     "pnp_conv2d_x3_wgrad": (c_int32, [c_int32]),
+    "pnp_conv2d_x3_narrow": (c_int32, [c_int32]),
     "pnp_conv2d_wino_filter_bytes": (c_size_t, [c_int32, c_int32]),
     "pnp_conv2d_wino_filter_bind": (c_int, [c_void_p, c_int32, c_void_p, c_size_t]),
     "pnp_weights_changed": (None, [c_void_p, c_void_p]),

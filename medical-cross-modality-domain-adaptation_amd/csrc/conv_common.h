@@ -400,6 +400,12 @@ int x3d_route_mode();
 bool x3w_chosen(const pnp_conv_geom* g);
 size_t x3w_workspace_bytes(const pnp_conv_geom* g);
 int launch_x3_wgrad(const float* x, const float* dy, float* dw, const pnp_conv_geom* g, int accumulate, void* ws, size_t ws_bytes, hipStream_t st);
+// conv_x3_narrow.hip: the 5x5, 40 -> 5 logits layer on the same arithmetic (PNP_X3_NARROW, under x3d_route_mode()), forward (kind 0) and
+// data gradient (kind 1; honours res_add); g = the FORWARD geometry.  x3n_chosen: can / should the family take the layer (route X3N); the
+// launch writes its split filter image into x3n_filter_bytes(kind) of workspace
+bool x3n_chosen(const pnp_conv_geom* g, int kind);
+size_t x3n_filter_bytes(int kind);
+int launch_x3_narrow(const ConvArgs& a, int kind, void* ws, size_t ws_bytes, hipStream_t st);
 int wino_tile(const pnp_conv_geom* g);
 size_t wino_workspace_bytes(const pnp_conv_geom* g);
 int wino_stats_parts(const pnp_conv_geom* g);

@@ -2172,7 +2172,7 @@ int launch_phase_group(const float* dy, const float* wt, float* outp, const pnp_
 
 // ---- one plan per pass ---------------------------------------------------------------------------------------------------------
 // plan_fwd / plan_dgrad / plan_wgrad are the ONLY code that combines the families' predicates (n16_geom_ok, narrow_fwd_ok, wino_tile,
-// x3d_chosen, x3s_chosen, plan_phases, x3w_chosen, n16_wgrad_ok, wgd_plan, choose_tile / choose_split, wgrad_plan_split): each states the
+// x3d_chosen, x3s_chosen, x3n_chosen, plan_phases, x3w_chosen, n16_wgrad_ok, wgd_plan, choose_tile / choose_split, wgrad_plan_split): each states the
 // precedence of its pass once, top to bottom.  The workspace / partial-row / route queries read the plan, and the entry points take the
 // first candidate whose workspace the caller brought and switch on its route.
 struct ConvPlan {
@@ -2211,11 +2211,22 @@ static ConvPlan plan_fwd(const pnp_conv_geom* g, unsigned ep) {
     const int ns = fwd_split(g);
     const size_t split = ns > 1 ? (size_t)ns * M * g->K * sizeof(float) : 0;
     p.ws_bytes = split;
+    // the logits layer on the split-bf16 kernel (conv_x3_narrow.hip: dropout, neither statistics nor the fused BN), ahead of whatever else
+    // serves it: the vector-ALU kernel, or below its floor of 8 192 pixels (mode 2 only) the implicit GEMM
+    const bool x3n = !bn && !stats && x3n_chosen(g, 0);
+    auto add_x3n = [&]() {
+        if (x3n_filter_bytes(0) > p.ws_bytes) p.ws_bytes = x3n_filter_bytes(0);
+        if (ws) p.add(PNP_ROUTE_X3N, x3n_filter_bytes(0));
+    };
     if (n16_geom_ok(g)) p.add(PNP_ROUTE_N16, 0);
-    else if (!bn && narrow_fwd_ok(g, nullptr)) p.add(PNP_ROUTE_NARROW, 0);      // (no fused BN in the vector-ALU kernel)
+    else if (!bn && narrow_fwd_ok(g, nullptr)) {                                // (no fused BN in the vector-ALU kernel)
+        if (x3n) add_x3n();
+        p.add(PNP_ROUTE_NARROW, 0);
+    }
     else {
         // the direct split-bf16 kernels (conv_x3_direct.hip) have dropout, statistics and the residual add, not the fused BN
         const bool x3d = x3d_chosen(g);
+        if (x3n) add_x3n();
         if (p.tile) {
             // the Winograd planner's layer: transformed filter + input + product (conv_wino.hip) — ALSO where the narrow layers then run on
             // the direct split-bf16 kernel, whose filter image is smaller
@@ -2295,8 +2306,10 @@ static ConvPlan plan_dgrad(const pnp_conv_geom* g) {
         if (!sym && n16_geom_ok(&d)) route = PNP_ROUTE_N16;                            // 16 INPUT channels: a 16-output conv of dy
         else if (g->stride == 1 && narrow_fwd_ok(&d, nullptr)) route = PNP_ROUTE_NARROW;    // few INPUT channels: a narrow-output conv of dy
         else if (plain && x3d_chosen(&d)) route = PNP_ROUTE_X3D;
+        else if (plain && x3n_chosen(g, 1)) route = PNP_ROUTE_X3N;                     // the logits layer's (conv_x3_narrow.hip)
         else route = PNP_ROUTE_IGEMM;                                                  // (stride > 1 without phases: dy zero-upsampled)
         if (route == PNP_ROUTE_X3D) x3 = x3d_filter_bytes(d.C, d.K);
+        if (route == PNP_ROUTE_X3N) x3 = x3n_filter_bytes(1);
     }
     p.ws_bytes = b > x3 ? b : x3;
     p.add(route, p.ws_bytes);
@@ -2344,6 +2357,7 @@ static int launch_fwd_cand(const ConvPlan::Cand& c, ConvArgs& a, const pnp_conv_
     case PNP_ROUTE_WINO: return launch_wino(a, 0, false, ws, ws_bytes, st);
     case PNP_ROUTE_X3D: return launch_x3_direct(a, 0, false, ws, ws_bytes, st);
     case PNP_ROUTE_X3S: return launch_x3_strided(a, g, 0, ws, ws_bytes, st);
+    case PNP_ROUTE_X3N: return launch_x3_narrow(a, 0, ws, ws_bytes, st);
     default: return launch_fwd<0>(a, st, c.need ? (float*)ws : nullptr);
     }
 }
@@ -2487,9 +2501,10 @@ static int dgrad_impl(const float* dy, const float* w, float* dx, const pnp_conv
         if (int e = launch_x3_strided(a, g, 1, workspace, workspace_bytes, st)) return e;
         return residual ? pnp_axpby(residual, dx, (size_t)g->N * g->H * g->W * g->C, 1.f, 1.f, stream) : PNP_OK;
     }
-    if (route == PNP_ROUTE_WINO || route == PNP_ROUTE_X3D) {      // the filter transform / image flips and transposes on the way (no flip launch)
+    if (route == PNP_ROUTE_WINO || route == PNP_ROUTE_X3D || route == PNP_ROUTE_X3N) {      // the filter transform / image flips and transposes on the way (no flip launch)
         ConvArgs a = make_args(dy, w, dx, &d);
         a.res_add = residual;
+        if (route == PNP_ROUTE_X3N) return launch_x3_narrow(a, 1, workspace, workspace_bytes, st);
         return route == PNP_ROUTE_WINO ? launch_wino(a, 1, true, workspace, workspace_bytes, st)
                                        : launch_x3_direct(a, 1, true, workspace, workspace_bytes, st);
     }

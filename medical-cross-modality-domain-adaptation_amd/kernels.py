@@ -175,6 +175,13 @@ def x3_wgrad(mode=-1):
     return int(_lib.load().pnp_conv2d_x3_wgrad(int(mode)))
 
 
+def x3_narrow(mode=-1):
+    """the 5x5, 40 -> 5 logits layer's forward and data gradient on the direct split-bf16 kernels (csrc/conv_x3_narrow.hip), under
+    x3_direct's mode: 0 off, 1 where a launch fills the chip (>= 256 tiles), 2 wherever the shapes allow; returns the previous mode
+    (mode < 0: read only)"""
+    return int(_lib.load().pnp_conv2d_x3_narrow(int(mode)))
+
+
 def wino_chosen(g, kind=0):
     """pnp_conv2d_fwd* (kind 0) / pnp_conv2d_dgrad* (kind 1) / pnp_conv2d_wgrad* (kind 2) of this layer (g = the forward geometry): 0 = the
     direct kernels, else the output tile edge of the Winograd route (2 or 4) — truthy exactly when the layer is on the route"""
