@@ -727,6 +727,28 @@ int pnp_filter_components(const uint8_t* vol, const int32_t* roots, int64_t D0, 
                           int32_t keep, int64_t min_size, uint8_t* out, int64_t* stats, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- hole filling of label volumes (csrc/components.hip): close the enclosed background holes of every structure -----------
+ *
+ * vol, the extents and ncls as above.  A voxel is BACKGROUND when its label is 0 or >= ncls.  A CAVITY is a maximal set of background voxels
+ * joined by face steps (6 neighbours) without a voxel at index 0 or D - 1 of any axis: scipy.ndimage.binary_fill_holes with its default
+ * structure fills exactly the union of the cavities (a volume with an extent <= 2 has none).  For a cavity and a class c in [1, ncls) the
+ * contacts are the pairs (v in the cavity, u a face neighbour of v) with label(u) == c; the WINNER is the class with the most contacts,
+ * ties going to the lower class.  A cavity is filled with its winner when the winner's bit is set in class_mask and max_size == 0 or its
+ * size <= max_size; otherwise it is left (the mask never redirects a cavity to a runner-up).
+ *   out [n] uint8 (may be vol itself) = the winner on filled cavities, 0 on every other background voxel (labels >= ncls included), vol
+ *   elsewhere: only background is ever rewritten, a class enclosed by another class is never touched.
+ *   stats [ncls, 4] int64: row c >= 1 = cavities filled with c, voxels filled with c, size of the largest cavity filled with c, cavities
+ *   won by c and left; row 0 = cavities found, voxels in them, cavities left, voxels left.
+ * Integers only, bit-identical from run to run; 10 launches whatever the data, no host read.
+ * Workspace: pnp_fill_holes_workspace_bytes (0 for unsupported extents or ncls) = 2 048 + 4 n + 4 n + n + 4 n (ncls - 1) bytes, every block
+ * rounded up to 256.  Its first two uint32 are the labelling's and the size count's error counters (see above), the uint32 at byte 1 024
+ * counts cavities without a contact and cavity voxels on a face (neither can happen); all are zeroed by the call and read by the caller.
+ * Refused on the host before any HIP call: null pointers; an extent outside [1, 4096]; n >= 2^31; ncls outside [2, 8]; class_mask with bit 0
+ * or a bit >= ncls; max_size < 0; a short workspace. */
+size_t pnp_fill_holes_workspace_bytes(int64_t D0, int64_t D1, int64_t D2, int32_t ncls);
+int pnp_fill_holes(const uint8_t* vol, int64_t D0, int64_t D1, int64_t D2, int32_t ncls, uint32_t class_mask, int64_t max_size, uint8_t* out,
+                   int64_t* stats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- anti-alias prefilter of a resident volume (csrc/smooth.hip) ---------------------------------------------------------------
  *
  * pnp_volume_smooth: dst = the separable filter of src, both float32 [X, Y, Z] in C order (z fastest), borders replicated (the index of

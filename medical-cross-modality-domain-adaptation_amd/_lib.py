@@ -214,6 +214,8 @@ PROTOTYPES = {
     "pnp_label_components": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnp_filter_components": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_uint32, c_int32, c_int64, c_void_p, c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
+    "pnp_fill_holes_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int32]),
+    "pnp_fill_holes": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int32, c_uint32, c_int64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnp_volume_smooth_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
     "pnp_volume_smooth": (c_int, [_F, _F, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_size_t,
                                   c_void_p]),

@@ -792,7 +792,7 @@ class Trainer(object):
         dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  options: volume_predict.segment_volume's (edge, crop [a box, or "body" /
         ("body", margin): the label-free body crop of DESIGN.md §24], axis,
         flip_correction, batch_size [default: the net's], percentile, out_size; tta, prob, entropy: DESIGN.md §15, which also write prob_* /
-        entropy_* files; keep_largest, component_stats: the connected-component filter of DESIGN.md §16;
+        entropy_* files; keep_largest, component_stats: the connected-component filter of DESIGN.md §16; fill_holes, hole_stats: the hole filling of DESIGN.md §26;
         sample_mm: the millimetre grid of DESIGN.md §17, with each file's voxel size read from its affine; prefilter: the anti-alias prefilter of DESIGN.md §19;
         tiles, tile_overlap: with sample_mm, overlapping planes that cover the whole crop box, blended by pnp_paste_tiles: DESIGN.md §20;
         axes, axis_weights: multi-planar fusion, one prediction per listed slicing axis fused by pnp_fuse_views: DESIGN.md §21).  ensemble: further nets of this class, averaged with this trainer's.  Returns the pred_* paths.  test_eval is untouched."""

@@ -6,6 +6,9 @@ and evaluation — keep the largest 3-D component of every structure, drop the i
   keep_largest(vol, num_cls, keep, min_size, ...)   (filtered uint8 volume, int64 stats [num_cls, 4]: components found, voxels before,
                                                     voxels kept, size of the largest component)
   parse_option(arg, num_cls)                        the keep_largest= argument of volume_predict.segment_volume / evaluate.evaluate -> keywords
+  fill_holes(vol, num_cls, max_size, classes, ...)  (filled uint8 volume, int64 stats [num_cls, 4]): every enclosed background hole takes the
+                                                    class with the most face contacts to it
+  parse_fill_option(arg, num_cls)                   the fill_holes= argument of the same functions -> keywords
 
 vol is a contiguous uint8 [D0, D1, D2] CUDA tensor (what segment_volume returns); a label >= num_cls counts as background.  A component is
 a maximal set of voxels of one non-zero label joined by steps of scipy's generate_binary_structure(3, connectivity).  There is no CPU
@@ -20,6 +23,8 @@ from . import _lib
 OPTION_KEYS = ("keep", "min_size", "connectivity", "classes")
 MAX_KEEP = 8                         # pnp_filter_components'
 last_errors = (0, 0)                 # the counters the most recent call read: (labelling, filter)
+FILL_OPTION_KEYS = ("max_size", "classes")        # fill_holes' 
+last_fill_errors = (0, 0, 0)         # the counters the most recent fill_holes read: (labelling, size count, fill)
 
 
 def class_mask(num_cls, classes=None):
@@ -123,6 +128,72 @@ def keep_largest(vol, num_cls=5, keep=1, min_size=0, connectivity=1, classes=Non
     return out, stats
 
 
+def check_fill_options(num_cls, max_size=0, classes=None):
+    """the host checks of fill_holes' keywords -> (max_size, class mask); ValueError otherwise"""
+    if isinstance(max_size, bool) or not isinstance(max_size, numbers.Integral):
+        raise ValueError("max_size must be an int, got %r" % (max_size,))
+    if int(max_size) < 0:
+        raise ValueError("max_size = %d is negative" % max_size)
+    return int(max_size), class_mask(num_cls, classes)
+
+
+def parse_fill_option(arg, num_cls=5):
+    """None / False -> None; True -> {}; a positive int N -> {"max_size": N}; a dict of fill_holes' keywords -> a checked copy.  ValueError
+    for anything else."""
+    if arg is None or arg is False:
+        return None
+    if arg is True:
+        opts = {}
+    elif isinstance(arg, dict):
+        unknown = sorted(set(arg) - set(FILL_OPTION_KEYS))
+        if unknown:
+            raise ValueError("fill_holes: unknown keys %s (known: %s)" % (unknown, list(FILL_OPTION_KEYS)))
+        opts = dict(arg)
+    elif isinstance(arg, numbers.Integral):
+        if arg < 1:
+            raise ValueError("fill_holes = %d is no positive size limit (True fills cavities of any size)" % arg)
+        opts = {"max_size": int(arg)}
+    else:
+        raise ValueError("fill_holes must be None, a bool, a positive int or a dict of %s, got %r" % (list(FILL_OPTION_KEYS), arg))
+    try:
+        check_fill_options(num_cls, **opts)
+    except ValueError as e:
+        raise ValueError("fill_holes: %s" % e)
+    return opts
+
+
+def fill_holes(vol, num_cls=5, max_size=0, classes=None, out=None):
+    """-> (filled, stats).  Every cavity — a 6-connected set of background voxels (label 0 or >= num_cls) that touches no face of the volume:
+    what scipy.ndimage.binary_fill_holes fills — takes the class with the most face contacts to it (ties: the lower class) when that class
+    is in `classes` (None = all) and max_size == 0 or the cavity has at most max_size voxels; all other background becomes 0, everything
+    else stays.  stats int64 [num_cls, 4]: row c = cavities filled with c, voxels filled, largest cavity filled, cavities
+    won by c and left; row 0 = cavities found, their voxels, cavities left, voxels left.  out: a uint8 tensor like vol — vol itself fills
+    in place."""
+    global last_fill_errors
+    from . import kernels as K
+    _volume(vol, "fill_holes")
+    max_size, mask = check_fill_options(num_cls, max_size, classes)
+    if out is None:
+        out = torch.empty_like(vol)
+    elif _volume(out, "fill_holes: out").shape != vol.shape or out.device != vol.device:
+        raise ValueError("fill_holes: out %s on %s does not match the volume %s on %s" % (tuple(out.shape), out.device, tuple(vol.shape), vol.device))
+    _, stats, ws = K.fill_holes(vol, int(num_cls), mask, max_size, out)
+    last_fill_errors = K.fill_holes_errors(ws)
+    if last_fill_errors[0]:
+        raise _lib.PnpError("fill_holes: %d union-find loops reached their cap (the labelling's error counter)" % last_fill_errors[0])
+    if last_fill_errors[1] or last_fill_errors[2]:
+        raise _lib.PnpError("fill_holes: inconsistent roots or cavities (pnp_fill_holes' error counters: %d, %d)" % last_fill_errors[1:])
+    return out, stats
+
+
+def fill_stats_line(stats):
+    """one printable line of fill_holes' stats tensor / array / nested list"""
+    rows = stats.cpu().tolist() if isinstance(stats, torch.Tensor) else [list(r) for r in stats]
+    head = "%d cavities, %d voxels, left %d / %d" % tuple(rows[0])
+    return head + "".join("   class %d: %d filled, %d voxels, largest %d, left %d" % (c, r[0], r[1], r[2], r[3])
+                          for c, r in enumerate(rows) if c > 0 and (r[0] or r[3]))
+
+
 def stats_line(stats, num_cls=None):
     """one printable line of a stats tensor / array / nested list: per class found, before -> kept, largest"""
     rows = stats.cpu().tolist() if isinstance(stats, torch.Tensor) else [list(r) for r in stats]
@@ -135,6 +206,10 @@ def add_cli_arguments(ap):
                     help="keep the K largest 3-D connected components of every class (a bare flag: 1), on the device")
     ap.add_argument("--min-size", type=int, default=None, metavar="N", help="drop components of fewer than N voxels (alone: no rank rule)")
     ap.add_argument("--connectivity", type=int, default=None, choices=(1, 2, 3), help="6, 18 or 26 neighbours (default 1)")
+    ap.add_argument("--fill-holes", nargs="?", type=int, const=0, default=None, metavar="MAX",
+                    help="fill the enclosed background holes of the label volume with the class around them, on the device, after "
+                         "--keep-largest (a bare flag: holes of any size; MAX: holes of at most MAX voxels)")
+    ap.add_argument("--fill-classes", default=None, metavar="C,C", help="the classes that may grow into holes (default: all)")
 
 
 def cli_option(ap, a, num_cls=5):
@@ -149,3 +224,25 @@ def cli_option(ap, a, num_cls=5):
         return parse_option(opts, num_cls)
     except ValueError as e:
         ap.error("--keep-largest / --min-size: %s" % e)
+
+
+def cli_fill_option(ap, a, num_cls=5):
+    """the fill_holes= option of the parsed arguments, or None without --fill-holes; argument errors end in ap.error"""
+    if a.fill_holes is None:
+        if a.fill_classes is not None:
+            ap.error("--fill-classes goes with --fill-holes")
+        return None
+    opts = {}
+    try:
+        if a.fill_holes < 0:
+            raise ValueError("max_size = %d is negative" % a.fill_holes)
+        if a.fill_holes > 0:
+            opts["max_size"] = a.fill_holes
+        if a.fill_classes is not None:
+            try:
+                opts["classes"] = [int(c) for c in a.fill_classes.split(",")]
+            except ValueError:
+                raise ValueError("classes: %r is no comma-separated list of ints" % a.fill_classes)
+        return parse_fill_option(opts, num_cls)
+    except ValueError as e:
+        ap.error("--fill-holes / --fill-classes: %s" % e)

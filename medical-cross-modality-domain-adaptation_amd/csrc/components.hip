@@ -31,6 +31,9 @@
 // met: ONE atomic add for 4 096 voxels inside a structure.  cc_rank_kernel (one launch per rank, max(keep, 1) launches) finds per class the largest key (size << 32 | ~root) below the
 // previous rank's: ties go to the lower root.  cc_apply_kernel writes the filtered labels (out may be vol: a lane reads and writes its own
 // voxel only) and cc_stats_kernel writes the int64 rows.  Integer atomics only: exact in any order.
+//
+// Hole filling (pnp_fill_holes) labels the BACKGROUND with the same three launches and counts its components' sizes with
+// cc_count_kernel; its own kernels (fh_*) stand further down, before the entry points.
 #include "pnp_common.h"
 
 namespace {
@@ -361,6 +364,185 @@ int check_dims(const char* who, int64_t D0, int64_t D1, int64_t D2, int32_t ncls
 
 size_t ws_bytes_of(long long n) { return kHeaderBytes + (size_t)((4 * n + 255) / 256 * 256); }
 
+// ---- hole filling -----------------------------------------------------------------------------------------------------------
+// The background (label 0 or >= ncls) is labelled at connectivity 1 by the three launches above, as the one class of a 2-class volume
+// `state`; a CAVITY is a background component without a voxel on a face of the volume.  A cavity's winner is the class with the most
+// contacts (pairs of a cavity voxel and a face neighbour of class c; ties to the lower class); it is filled with its winner when
+// class_mask holds the winner and max_size == 0 or size <= max_size.  After the labelling:
+//   fh_open_kernel      one lane per FACE voxel: state[root] = kOpen, a plain store of a constant (racing stores write the same byte)
+//   fh_prepare_kernel   roots only: sizes[root] = 0, and for closed roots the contact row = 0 (no clear of the whole table)
+//   cc_count_kernel     sizes, merged in LDS: the open background of a scan costs one global add per workgroup
+//   fh_contact_kernel   voxels of CLOSED components only: up to six neighbour labels, packed 4 bits per class, one global add per class met
+//   fh_apply_kernel     every voxel of a cavity reads its root's row and size and decides alike; out may be vol (a lane reads and writes its
+//                       own voxel only; the neighbours were read by the launch before); the root reports to the sums, merged in LDS
+//   fh_stats_kernel     the int64 rows
+// Each stage reads what an EARLIER launch wrote; integer atomics only, exact in any order.
+constexpr unsigned char kBackground = 1, kOpen = 2;       // state: 0 = a class, 1 = background, 2 = background and the root of an open component
+
+struct FillHeader {                        // the second kHeaderBytes of the fill workspace (the first are the Header above)
+    unsigned int err_fill;                 // cavities without a contact, neighbours outside the volume (neither can happen)
+    unsigned int pad;
+    unsigned long long filled[MAXC], left[MAXC];          // per winner (cavities << 32) + voxels: filled / left as they are
+    unsigned int largest[MAXC];            // the largest cavity filled with the class
+};
+static_assert(sizeof(FillHeader) <= kHeaderBytes, "fill header");
+
+__global__ void __launch_bounds__(kThreads) fh_state_kernel(const unsigned char* __restrict__ vol, unsigned char* __restrict__ state, int n,
+                                                            int ncls) {
+    const long long v = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (v >= n) return;
+    const unsigned char l = vol[v];
+    state[v] = (l == 0 || l >= ncls) ? kBackground : 0;
+}
+
+__global__ void __launch_bounds__(kThreads) fh_open_kernel(const int* __restrict__ roots, unsigned char* state, int D0, int D1, int D2, int n) {
+    int i = blockIdx.x * kThreads + threadIdx.x;          // < 2 (D1 D2 + D0 D2 + D0 D1) <= 6 * 2^24
+    const int a0 = D1 * D2, a1 = D0 * D2, a2 = D0 * D1;
+    int x, y, z;
+    if (i < 2 * a0) {
+        x = i < a0 ? 0 : D0 - 1;
+        const int j = i < a0 ? i : i - a0;
+        y = j / D2;
+        z = j % D2;
+    } else if ((i -= 2 * a0) < 2 * a1) {
+        y = i < a1 ? 0 : D1 - 1;
+        const int j = i < a1 ? i : i - a1;
+        x = j / D2;
+        z = j % D2;
+    } else if ((i -= 2 * a1) < 2 * a2) {
+        z = i < a2 ? 0 : D2 - 1;
+        const int j = i < a2 ? i : i - a2;
+        x = j / D1;
+        y = j % D1;
+    } else {
+        return;
+    }
+    const int r = roots[(x * D1 + y) * D2 + z];
+    if (r >= 0 && r < n) state[r] = kOpen;
+}
+
+__global__ void __launch_bounds__(kThreads) fh_prepare_kernel(const int* __restrict__ roots, const unsigned char* __restrict__ state,
+                                                              int* __restrict__ sizes, int* __restrict__ contacts, int n, int nc1) {
+    const long long v = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (v >= n || roots[v] != (int)v) return;
+    sizes[v] = 0;
+    if (state[v] == kOpen) return;
+    for (int c = 0; c < nc1; ++c) contacts[(size_t)v * nc1 + c] = 0;
+}
+
+__global__ void __launch_bounds__(kThreads) fh_contact_kernel(const unsigned char* __restrict__ vol, const int* __restrict__ roots,
+                                                              const unsigned char* __restrict__ state, int* contacts, FillHeader* fh,
+                                                              int D0, int D1, int D2, int n, int ncls) {
+    const long long v = (long long)blockIdx.x * kThreads + threadIdx.x;
+    if (v >= n) return;
+    const int r = roots[v];
+    if (r < 0 || r >= n || state[r] == kOpen) return;
+    const int z = (int)(v % D2), t = (int)(v / D2), y = t % D1, x = t / D1;
+    if (x < 1 || y < 1 || z < 1 || x > D0 - 2 || y > D1 - 2 || z > D2 - 2) {       // a closed component has no voxel on a face
+        atomicAdd(&fh->err_fill, 1u);
+        return;
+    }
+    const int sy = D2, sx = D1 * D2;
+    const unsigned char nb[6] = {vol[v - sx], vol[v + sx], vol[v - sy], vol[v + sy], vol[v - 1], vol[v + 1]};
+    unsigned int packed = 0;               // 4 bits per class: at most 6 contacts of a voxel
+#pragma unroll
+    for (int j = 0; j < 6; ++j)
+        if (nb[j] >= 1 && nb[j] < ncls) packed += 1u << (4 * nb[j]);
+    const int nc1 = ncls - 1;
+    for (int c = 1; c < ncls; ++c) {
+        const int k = (int)((packed >> (4 * c)) & 15u);
+        if (k) atomicAdd(&contacts[(size_t)r * nc1 + c - 1], k);
+    }
+}
+
+__global__ void __launch_bounds__(kThreads) fh_apply_kernel(const unsigned char* vol, const int* __restrict__ roots,
+                                                            const unsigned char* __restrict__ state, const int* __restrict__ sizes,
+                                                            const int* __restrict__ contacts, unsigned char* out, FillHeader* fh, int n, int ncls,
+                                                            unsigned int mask, long long max_size) {
+    __shared__ unsigned long long s_filled[MAXC], s_left[MAXC];
+    __shared__ unsigned int s_largest[MAXC];
+    if (threadIdx.x < MAXC) {
+        s_filled[threadIdx.x] = s_left[threadIdx.x] = 0ull;
+        s_largest[threadIdx.x] = 0u;
+    }
+    __syncthreads();
+    const long long v = (long long)blockIdx.x * kThreads + threadIdx.x;
+    bool bad = false;
+    if (v < n) {
+        unsigned char l = vol[v];
+        if (l >= ncls) l = 0;
+        const int r = roots[v];
+        if (r >= 0 && r < n) {             // background
+            l = 0;
+            if (state[r] != kOpen) {       // a cavity
+                const int nc1 = ncls - 1;
+                int best = 0, win = 0;
+                for (int c = 1; c < ncls; ++c) {
+                    const int k = contacts[(size_t)r * nc1 + c - 1];
+                    if (k > best) {        // ties stay with the lower class
+                        best = k;
+                        win = c;
+                    }
+                }
+                const int s = sizes[r];
+                const bool fill = win != 0 && ((mask >> win) & 1u) && (max_size == 0 || (long long)s <= max_size);
+                if (fill) l = (unsigned char)win;
+                if (r == (int)v) {         // the root reports its cavity
+                    bad = win == 0;
+                    const unsigned long long one = (1ull << 32) + (unsigned long long)(unsigned int)s;
+                    if (fill) {
+                        atomicAdd(&s_filled[win], one);
+                        atomicMax(&s_largest[win], (unsigned int)s);
+                    } else {
+                        atomicAdd(&s_left[win], one);        // win == 0 (never): row 0 still counts it
+                    }
+                }
+            }
+        }
+        out[v] = l;
+    }
+    __syncthreads();
+    const int c = threadIdx.x;
+    if (c < ncls) {
+        if (s_filled[c] != 0ull) atomicAdd(&fh->filled[c], s_filled[c]);
+        if (s_left[c] != 0ull) atomicAdd(&fh->left[c], s_left[c]);
+        if (s_largest[c] != 0u) atomicMax(&fh->largest[c], s_largest[c]);
+    }
+    if (bad) atomicAdd(&fh->err_fill, 1u);
+}
+
+__global__ void fh_stats_kernel(const FillHeader* __restrict__ fh, long long* __restrict__ stats, int ncls) {
+    const int c = threadIdx.x;
+    if (c >= ncls) return;
+    const unsigned long long lo = 0xffffffffull;
+    if (c > 0) {
+        stats[4 * c + 0] = (long long)(fh->filled[c] >> 32);
+        stats[4 * c + 1] = (long long)(fh->filled[c] & lo);
+        stats[4 * c + 2] = (long long)fh->largest[c];
+        stats[4 * c + 3] = (long long)(fh->left[c] >> 32);
+        return;
+    }
+    long long nf = 0, vf = 0, nl = 0, vl = 0;
+    for (int k = 0; k < ncls; ++k) {
+        nf += (long long)(fh->filled[k] >> 32);
+        vf += (long long)(fh->filled[k] & lo);
+        nl += (long long)(fh->left[k] >> 32);
+        vl += (long long)(fh->left[k] & lo);
+    }
+    stats[0] = nf + nl;
+    stats[1] = vf + vl;
+    stats[2] = nl;
+    stats[3] = vl;
+}
+
+// the fill workspace: Header, FillHeader, parent / sizes int32 [n], roots int32 [n], state uint8 [n], contacts int32 [n, ncls - 1];
+// every block rounded up to 256 bytes
+size_t round256(size_t b) { return (b + 255) / 256 * 256; }
+
+size_t fill_ws_bytes_of(long long n, int ncls) {
+    return 2 * kHeaderBytes + 2 * round256(4 * (size_t)n) + round256((size_t)n) + round256(4 * (size_t)n * (size_t)(ncls - 1));
+}
+
 }  // namespace
 
 extern "C" {
@@ -429,6 +611,67 @@ int pnp_filter_components(const uint8_t* vol, const int32_t* roots, int64_t D0, 
     PNP_CHECK_LAUNCH("cc_apply_kernel");
     hipLaunchKernelGGL(cc_stats_kernel, dim3(1), dim3(64), 0, st, h, (long long*)stats, (int)ncls);
     PNP_CHECK_LAUNCH("cc_stats_kernel");
+    return PNP_OK;
+}
+
+size_t pnp_fill_holes_workspace_bytes(int64_t D0, int64_t D1, int64_t D2, int32_t ncls) {
+    long long n;
+    return dims_ok(D0, D1, D2, &n) && ncls >= 2 && ncls <= MAXC ? fill_ws_bytes_of(n, (int)ncls) : 0;
+}
+
+int pnp_fill_holes(const uint8_t* vol, int64_t D0, int64_t D1, int64_t D2, int32_t ncls, uint32_t class_mask, int64_t max_size, uint8_t* out,
+                   int64_t* stats, void* ws, size_t ws_bytes, void* stream) {
+    PNP_REQUIRE(vol && out && stats && ws, "pnp_fill_holes: null pointer");
+    long long n;
+    if (const int rc = check_dims("pnp_fill_holes", D0, D1, D2, ncls, &n)) return rc;
+    PNP_REQUIRE((class_mask & 1u) == 0 && (class_mask >> ncls) == 0, "pnp_fill_holes: class_mask 0x%x selects class 0 or a class >= ncls = %d",
+                (unsigned)class_mask, (int)ncls);
+    PNP_REQUIRE(max_size >= 0, "pnp_fill_holes: max_size %lld is negative", (long long)max_size);
+    PNP_REQUIRE(ws_bytes >= fill_ws_bytes_of(n, (int)ncls), "pnp_fill_holes: workspace too small (%zu < %zu bytes)", ws_bytes,
+                fill_ws_bytes_of(n, (int)ncls));
+    hipStream_t st = (hipStream_t)stream;
+    Header* h = (Header*)ws;
+    FillHeader* fh = (FillHeader*)((char*)ws + kHeaderBytes);
+    char* p = (char*)ws + 2 * kHeaderBytes;
+    int* parent = (int*)p;                 // sizes once the roots stand
+    int* roots = (int*)(p += round256(4 * (size_t)n));
+    unsigned char* state = (unsigned char*)(p += round256(4 * (size_t)n));
+    int* contacts = (int*)(p += round256((size_t)n));
+    if (hipMemsetAsync(ws, 0, 2 * kHeaderBytes, st) != hipSuccess) {
+        pnp_set_error("pnp_fill_holes: clearing the headers failed");
+        return PNP_ELAUNCH;
+    }
+    Dims d;
+    d.D0 = (int)D0; d.D1 = (int)D1; d.D2 = (int)D2;
+    d.nt1 = pnp_cdiv(D1, T1);
+    d.nt2 = pnp_cdiv(D2, T2);
+    const unsigned tiles = (unsigned)((long long)pnp_cdiv(D0, T0) * d.nt1 * d.nt2);
+    const unsigned flat = (unsigned)pnp_cdiv(n, kThreads);
+    const long long faces = 2 * (D1 * D2 + D0 * D2 + D0 * D1);
+    hipLaunchKernelGGL(fh_state_kernel, dim3(flat), dim3(kThreads), 0, st, vol, state, (int)n, (int)ncls);
+    PNP_CHECK_LAUNCH("fh_state_kernel");
+    // the background as the one class of a 2-class volume, 6 neighbours
+    hipLaunchKernelGGL(cc_tile_kernel, dim3(tiles), dim3(kThreads), 0, st, state, parent, h, d, 2, 3);
+    PNP_CHECK_LAUNCH("cc_tile_kernel");
+    hipLaunchKernelGGL(cc_border_kernel, dim3(tiles), dim3(kThreads), 0, st, state, parent, h, d, 2, 3, (int)n);
+    PNP_CHECK_LAUNCH("cc_border_kernel");
+    hipLaunchKernelGGL(cc_flatten_kernel, dim3(flat), dim3(kThreads), 0, st, parent, roots, h, (int)n);
+    PNP_CHECK_LAUNCH("cc_flatten_kernel");
+    hipLaunchKernelGGL(fh_open_kernel, dim3((unsigned)pnp_cdiv(faces, kThreads)), dim3(kThreads), 0, st, roots, state, (int)D0, (int)D1, (int)D2,
+                       (int)n);
+    PNP_CHECK_LAUNCH("fh_open_kernel");
+    hipLaunchKernelGGL(fh_prepare_kernel, dim3(flat), dim3(kThreads), 0, st, roots, state, parent, contacts, (int)n, (int)ncls - 1);
+    PNP_CHECK_LAUNCH("fh_prepare_kernel");
+    hipLaunchKernelGGL(cc_count_kernel, dim3((unsigned)pnp_cdiv(n, kThreads * kRun)), dim3(kThreads), 0, st, roots, parent, h, (int)n);
+    PNP_CHECK_LAUNCH("cc_count_kernel");
+    hipLaunchKernelGGL(fh_contact_kernel, dim3(flat), dim3(kThreads), 0, st, vol, roots, state, contacts, fh, (int)D0, (int)D1, (int)D2, (int)n,
+                       (int)ncls);
+    PNP_CHECK_LAUNCH("fh_contact_kernel");
+    hipLaunchKernelGGL(fh_apply_kernel, dim3(flat), dim3(kThreads), 0, st, vol, roots, state, parent, contacts, out, fh, (int)n, (int)ncls,
+                       (unsigned int)class_mask, (long long)max_size);
+    PNP_CHECK_LAUNCH("fh_apply_kernel");
+    hipLaunchKernelGGL(fh_stats_kernel, dim3(1), dim3(64), 0, st, fh, (long long*)stats, (int)ncls);
+    PNP_CHECK_LAUNCH("fh_stats_kernel");
     return PNP_OK;
 }
 

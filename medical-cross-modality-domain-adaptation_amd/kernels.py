@@ -1394,3 +1394,27 @@ def filter_components(vol, roots, ncls, class_mask, keep, min_size, out):
     check(lib.pnp_filter_components(vp(vol), vp(roots), D0, D1, D2, int(ncls), int(class_mask), int(keep), int(min_size), vp(out), vp(stats),
                                     vp(ws), ws.numel(), _stream()), "pnp_filter_components")
     return out, stats, ws
+
+
+def fill_holes_errors(ws):
+    """the three device error counters of a fill workspace (labelling, size count, fill): one host read"""
+    e = ws[:1032].cpu()
+    a, b = e[:8].view(torch.int32), e[1024:1032].view(torch.int32)
+    return int(a[0]), int(a[1]), int(b[0])
+
+
+def fill_holes(vol, ncls, class_mask, max_size, out):
+    """pnp_fill_holes: vol a contiguous uint8 [D0, D1, D2] CUDA tensor, out a uint8 tensor of vol's shape (vol itself fills in place)
+    -> (out, stats int64 [ncls, 4], the workspace: its head holds the error counters, fill_holes_errors).  Stream-ordered."""
+    D0, D1, D2 = (int(d) for d in vol.shape)
+    lib = _lib.load()
+    need = lib.pnp_fill_holes_workspace_bytes(D0, D1, D2, int(ncls))
+    if need == 0:
+        raise _lib.PnpError("fill_holes: unsupported volume %s or ncls %d (each extent in [1, 4096], fewer than 2^31 voxels, ncls in [2, 8])"
+                            % ((D0, D1, D2), int(ncls)))
+    ws = workspace(need, vol.device, slot="components")
+    stats = torch.empty((int(ncls), 4), dtype=torch.int64, device=vol.device)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    check(lib.pnp_fill_holes(vp(vol), D0, D1, D2, int(ncls), int(class_mask), int(max_size), vp(out), vp(stats), vp(ws), ws.numel(), _stream()),
+          "pnp_fill_holes")
+    return out, stats, ws

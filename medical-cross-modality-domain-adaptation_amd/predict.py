@@ -26,6 +26,9 @@ checkpoints x views, at most 8.  --prob / --entropy also write prob_<basename> (
 Connected components: --keep-largest [K] keeps the K largest 3-D components of every class (a bare flag: 1), --min-size N
 drops components of fewer than N voxels, --connectivity picks 6, 18 or 26 neighbours; the label volumes written (and scored) are the
 filtered ones, and one line per volume reports per class the components found, the voxels before and after and the largest component.
+Hole filling: --fill-holes [MAX] fills every enclosed background hole (of at most MAX voxels; a bare flag: of any size) with
+the class that touches it most, after --keep-largest; --fill-classes C,C names the classes that may grow; one line per volume reports the
+cavities found, filled and left.
 
 Millimetre grid: --sample-mm shows the network every scan at one pixel size and one distance between its three frames,
 taken from the voxel size in each file's header (--spacing is something else: the units of --score).  The plane is centred on the
@@ -231,6 +234,9 @@ def parse_args(argv=None):
     post = components.cli_option(ap, a)
     if post is not None:
         options["keep_largest"] = post
+    fill = components.cli_fill_option(ap, a)
+    if fill is not None:
+        options["fill_holes"] = fill
     return a, images, labels, options
 
 
@@ -251,7 +257,7 @@ def build_trainer(kind, model, batch_size, device="cuda", num_cls=5):
 
 def main(argv=None):
     """-> {"paths": [pred_* files], "score": evaluate.evaluate's result or None}; with the component filter also "component_stats": one
-    [num_cls][4] list per volume, with --crop-body also "crop_box": the box found per volume"""
+    [num_cls][4] list per volume, with --fill-holes also "hole_stats" (likewise), with --crop-body also "crop_box": the box found per volume"""
     a, images, labels, options = parse_args(argv)
     trainer = build_trainer(a.net, a.model, a.batch_size, a.device)
     if a.ensemble:
@@ -259,6 +265,9 @@ def main(argv=None):
     stats = [] if "keep_largest" in options else None
     if stats is not None:
         options["component_stats"] = stats
+    holes = [] if "fill_holes" in options else None
+    if holes is not None:
+        options["hole_stats"] = holes
     boxes = [] if a.crop_body is not None else None
     if boxes is not None:
         options["crop_box"] = boxes
@@ -270,6 +279,9 @@ def main(argv=None):
         if stats is not None:
             from . import components
             print("  components  %s" % components.stats_line(stats[n]))
+        if holes is not None:
+            from . import components
+            print("  holes  %s" % components.fill_stats_line(holes[n]))
     score = None
     if a.score:
         from . import evaluate as ev
@@ -284,6 +296,8 @@ def main(argv=None):
     res = {"paths": paths, "score": score}
     if stats is not None:
         res["component_stats"] = [t.cpu().tolist() for t in stats]
+    if holes is not None:
+        res["hole_stats"] = [t.cpu().tolist() for t in holes]
     if boxes is not None:
         res["crop_box"] = [[list(b) for b in box] for box in boxes]
     return res

@@ -17,6 +17,7 @@ segment_volume gathers once per distinct map, runs one forward per member and ma
 interpolates every member's logits through that member's own inverse map, averages the softmax and writes the label, the mean
 probabilities and the normalised entropy in the file's array order.  With the defaults nothing of this is reached.
 
+Hole filling (opt-in): fill_holes= runs components.fill_holes on the finished label volume, on the device, after keep_largest.
 Connected-component filtering (opt-in): keep_largest= runs components.keep_largest on the finished label volume, on the
 device, before it is returned.
 
@@ -271,7 +272,8 @@ def ensemble_members(logits_fn, tta, limit=MAX_MEMBERS):
 
 def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
                    out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None,
-                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25, axes=None, axis_weights=None, crop_box=None):
+                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25, axes=None, axis_weights=None, crop_box=None,
+                   fill_holes=None, hole_stats=None):
     """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
       logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
                  checkpoint ensemble
@@ -291,6 +293,11 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
                  (keep, min_size, connectivity, classes): applied in place to the finished label volume on the device.  On
                  the ensemble path only Ensemble.label is filtered: prob and entropy are returned as computed, also where the label became 0.
       component_stats   optional list: the filter's int64 [num_cls, 4] stats tensor is appended to it
+      fill_holes     None / False, True (holes of any size), a positive int (the largest hole filled, in voxels) or a dict of
+                 components.fill_holes' keywords (max_size, classes): every enclosed background hole of the finished label volume takes
+                 the class that touches it most, in place on the device, after keep_largest.  On the ensemble and tiles
+                 paths only Ensemble.label changes; with axes it runs once, on the fused label.
+      hole_stats     optional list: the fill's int64 [num_cls, 4] stats tensor is appended to it
       sample_mm  None, or a number / (pi_mm, pj_mm, frame_mm): sample on that millimetre grid.  Needs `spacing`, the voxel
                  size in mm per ARRAY axis of `image` (surface.spacing_of(affine)).  The plane is centred on the crop box; a voxel column
                  outside its field of view (for any member) stays 0 in label, prob and entropy, like outside the crop box; tta
@@ -332,6 +339,7 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         raise ValueError("edge must be one of %s, got %r" % (EDGES, edge))
     from . import components
     post = components.parse_option(keep_largest, num_cls)
+    holes = components.parse_fill_option(fill_holes, num_cls)
     body_margin = _body_margin(crop)                            # None unless crop is "body" / ("body", margin)
     if axes is not None or axis_weights is not None:
         if axes is None:
@@ -364,6 +372,7 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         _, out_p, out_e = K.fuse_views(views, axis_weights, label=fused, prob=views[0] if prob else None, entropy=bool(entropy))
         del views
         _filter_components(fused, post, num_cls, component_stats)
+        _fill_holes(fused, holes, num_cls, hole_stats)
         return Ensemble(fused, out_p, out_e)
     B, H, W = int(batch_size), int(out_size[0]), int(out_size[1])
     if B < 1:
@@ -479,6 +488,7 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
         paste(members, nb, first + k + shift)
     src.close()
     _filter_components(out, post, num_cls, component_stats)
+    _fill_holes(out, holes, num_cls, hole_stats)
     return Ensemble(out, out_p, out_e) if ensemble else out
 
 
@@ -510,6 +520,16 @@ def _filter_components(label, post, num_cls, component_stats):
         component_stats.append(stats)
 
 
+def _fill_holes(label, holes, num_cls, hole_stats):
+    """components.fill_holes on the finished label volume, in place; holes: components.parse_fill_option's keywords or None (nothing runs)"""
+    if holes is None:
+        return
+    from . import components
+    _, stats = components.fill_holes(label, num_cls=num_cls, out=label, **holes)
+    if hole_stats is not None:
+        hole_stats.append(stats)
+
+
 def segmenter_logits(net):
     """logits_fn of source_segmenter.Full_DRN: every BN in inference mode, no dropout"""
     import torch
@@ -536,7 +556,8 @@ def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5
     ground truth with labels >= num_cls set to 0).  options: segment_volume's; with crop="body" / ("body", margin) the box
     found for every image is logged (crop_box=[] also collects them, one per image); with prob= / entropy= also prob_<basename> (float32,
     [*shape, num_cls]) and entropy_<basename> (float32) on the same grid with the same affine; with keep_largest= every label volume written
-    is the filtered one (component_stats=[]: one stats tensor per volume is appended); prefilter= is segment_volume's (the
+    is the filtered one (component_stats=[]: one stats tensor per volume is appended), with fill_holes= its enclosed holes are filled after
+    that (hole_stats=[] likewise); prefilter= is segment_volume's (the
     setting the network was trained with); tiles= / tile_overlap= are segment_volume's (the share logged is then the union
     of the planes); axes= / axis_weights= are segment_volume's (every image is predicted once per listed slicing axis and
     the views are fused; one share is then logged per view); with sample_mm= every image's voxel size is read
