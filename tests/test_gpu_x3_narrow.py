@@ -1,7 +1,8 @@
 """-m gpu: the 5x5, 40 -> 5 logits layer's forward and data gradient on the split-bf16 kernels of csrc/conv_x3_narrow.hip (route X3N,
 kernels.x3_narrow; mode 2 unless stated), on the smallest shapes that can still go wrong: one forward tile with a data gradient ragged on
-both axes, several tiles wider than high and higher than wide (a swapped tiles_x / tiles_y fails the latter), zero-padded borders.  Every
-case checks which kernel symbols ran, so a silent hand-back cannot pass.
+both axes, several tiles wider than high and higher than wide (a swapped tiles_x / tiles_y fails the latter), zero-padded borders, and
+(ROUNDS) launches with more items than the 512 persistent workgroups whose last round is partial.  Every case checks which kernel symbols
+ran, so a silent hand-back cannot pass.  Per element, one product per output: tests/test_gpu_split_bf16_exact.py.
 
 Bar (the rule of tests/test_gpu_x3_wgrad.py): err_new <= 2 x max(err of the fp32 route of the same tree on the same tensors, 1e-6) of
 max|ref|, ref = the float64 convolution of the same float32 operands — the factor 2 covers a different but equally long fp32 chain.
@@ -54,13 +55,14 @@ def _case(dev, K, shape, kind="normal", seed=0):
     return g, (x, w, dy, res)
 
 
-def _both_routes(dev, K, L, g, host):
-    """forward, data gradient and data gradient + residual with the route off (the fp32 kernels of the same tree) and on"""
+def _both_routes(dev, K, L, g, host, fwd_cls=None):
+    """forward, data gradient and data gradient + residual with the route off (the fp32 kernels of the same tree) and on.  fwd_cls: the
+    profiler classes of the forward (from 8192 output pixels on, the fp32 forward is conv_fwd_narrow_kernel, of the class PROF_CONV_DIRECT)"""
     xd, wd, dyd, resd = (torch.from_numpy(a).to(dev) for a in host)
     out = {}
     for mode in (0, 2):
         K.x3_narrow(mode)
-        y, nf = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD)
+        y, nf = _ran(L, lambda: K.conv2d_fwd(xd, wd, g), L.PROF_CONV_FWD if fwd_cls is None else fwd_cls)
         dx, nd = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g), L.PROF_CONV_DGRAD)
         dxr, ndr = _ran(L, lambda: K.conv2d_dgrad(dyd, wd, g, residual=resd), L.PROF_CONV_DGRAD)
         if mode == 0:
@@ -128,6 +130,68 @@ def test_dropout_masks_equal_the_vector_alu_kernel(dev, route):
         ref = torch.where(kept, yo, torch.zeros_like(yo))
         e_new, e_old = _rel(y1, ref), _rel(y0, ref)
         print("x3 narrow dropout seed %d sid %d: split-bf16 %.2e, fp32 route %.2e of max|ref|, dropped %.3f" % (seed, sid, e_new, e_old, frac))
+        assert e_new <= _bar(e_old), (e_new, e_old)
+
+
+# Past the first round of the persistent grid: conv_x3_direct_kernel_narrow launches min(items, 512) workgroups, and SHAPES above stop at 64
+# forward / 50 data-gradient items.  Here every launch walks the `id += gridDim.x` loop, prefetches the next tile under the MFMAs, stores a
+# prefetched patch and ends on a PARTIAL last round (the `id + gridDim.x < nitems` guard).  shape -> (forward items, data-gradient items)
+ROUNDS = [
+    ((65, 20, 100, "VALID"), (780, 910)),
+    ((48, 32, 96, "SAME"), (1152, 576)),
+]
+GRID = 512
+
+
+def _items(g):
+    """x3n_items() of csrc/conv_x3_narrow.hip: 8 x 16 forward tiles of y, 16 x 16 data-gradient tiles of dx (ragged ones included)"""
+    return g.N * (g.OH // 8) * (g.OW // 16), g.N * -(-g.H // 16) * -(-g.W // 16)
+
+
+@pytest.mark.parametrize("shape,items", ROUNDS, ids=lambda v: "x".join(str(i) for i in v))
+def test_more_items_than_workgroups_vs_float64(dev, route, shape, items):
+    """the bar of test_fwd_dgrad_vs_float64 on launches of two and three rounds, and two launches bit-identical"""
+    K, L = route, pkg("_lib")
+    g, host = _case(dev, K, shape)
+    assert _items(g) == items and all(n > GRID and n % GRID for n in items), (_items(g), items)
+    x, w, dy, res = host
+    yo, dxo, _ = _oracle(x, w, dy, 1, shape[3])
+    old, new = _both_routes(dev, K, L, g, host, fwd_cls=L.PROF_CONV_FWD | L.PROF_CONV_DIRECT)
+    refs = (yo, dxo, dxo + torch.from_numpy(res).double())
+    for name, a_old, a_new, ref in zip(("y", "dx", "dx+res"), old, new, refs):
+        e_new, e_old = _rel(a_new, ref), _rel(a_old, ref)
+        print("x3 narrow rounds %s %s: split-bf16 %.2e, fp32 route %.2e of max|ref|" % (shape, name, e_new, e_old))
+        assert e_new <= _bar(e_old), (name, e_new, e_old)
+    xd, wd, dyd, resd = (torch.from_numpy(a).to(dev) for a in host)
+    again = (K.conv2d_fwd(xd, wd, g), K.conv2d_dgrad(dyd, wd, g), K.conv2d_dgrad(dyd, wd, g, residual=resd))
+    assert all(torch.equal(a, b) for a, b in zip(new, again)), "two launches differ"
+
+
+@pytest.mark.parametrize("shape,items", ROUNDS, ids=lambda v: "x".join(str(i) for i in v))
+def test_more_items_than_workgroups_dropout(dev, route, shape, items):
+    """keep 0.75 past the first round: the zero pattern of the mode-0 route of the same tree (conv_fwd_narrow_kernel<5, true>, which
+    takes both shapes: >= 8192 output pixels) for the same seed and stream id; kept values within the bar"""
+    K, L = route, pkg("_lib")
+    g, host = _case(dev, K, shape)
+    assert _items(g)[0] == items[0]
+    x, w, _, _ = host
+    xd, wd = torch.from_numpy(x).to(dev), torch.from_numpy(w).to(dev)
+    yo = T.conv2d(torch.from_numpy(x).double(), torch.from_numpy(w).double(), 1, 1, shape[3]) / 0.75
+    for seed, sid in ((5, 3), (1 << 40, 0)):
+        K.x3_narrow(0)
+        y0, n0 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g, keep_prob=0.75, seed=seed, stream_id=sid), L.PROF_CONV_FWD | L.PROF_CONV_DIRECT)
+        assert n0 == ["conv_fwd_narrow_kernel<5, true>"], n0
+        K.x3_narrow(2)
+        y1, n1 = _ran(L, lambda: K.conv2d_fwd(xd, wd, g, keep_prob=0.75, seed=seed, stream_id=sid), L.PROF_CONV_FWD)
+        assert n1 == FWD, n1
+        assert torch.equal(y0 == 0, y1 == 0), "dropout masks differ"
+        frac = float((y1 == 0).double().mean())
+        assert 0.2 < frac < 0.3, frac
+        kept = (y1 != 0).cpu()
+        ref = torch.where(kept, yo, torch.zeros_like(yo))
+        e_new, e_old = _rel(y1, ref), _rel(y0, ref)
+        print("x3 narrow rounds dropout %s seed %d sid %d: split-bf16 %.2e, fp32 route %.2e of max|ref|, dropped %.3f" % (
+            shape, seed, sid, e_new, e_old, frac))
         assert e_new <= _bar(e_old), (e_new, e_old)
 
 
