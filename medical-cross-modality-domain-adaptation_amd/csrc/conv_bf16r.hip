@@ -17,27 +17,11 @@
 //   tiles: 256 x 128 / 8 waves (64 x 64 per wave), 128 x 128 and 128 x 64 / 4 waves; NBUF LDS stages, ONE raw s_barrier per stage,
 //   loads of stage j + NBUF - 1 in flight under the MFMAs of stage j (counted s_waitcnt vmcnt, never a drain inside the loop).
 // fp32 accumulation, fp32 output (+ optional bf16 copy of the output from the same epilogue: the next convolution's operand).
-#include "conv_common.h"
+#include "conv_x3_common.h"      // (the wait-count and LDS-DMA helpers of the loader waves)
 
 using namespace pnpconv;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-// one LDS-DMA piece: 16 bytes per lane, global (buffer descriptor + per-lane voffset + scalar soffset) -> LDS (wave-uniform dst + 16 x lane).
-// The builtin only exists in the device pass (in the host pass clang silently drops the whole kernel's launch stub over it).
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, lds_void* dst, unsigned voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
-#endif
-}
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // 16-byte chunk swizzle of an LDS row (see the file header)
 template <int BKC>

@@ -34,7 +34,7 @@
 #include <atomic>
 #include <map>
 #include <mutex>
-#include "conv_common.h"
+#include "conv_x3_common.h"
 #include "conv_mma.h"
 
 using namespace pnpconv;
@@ -49,24 +49,11 @@ __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4
 // ---- split-bf16 ("x3") operands of the GEMMs (conv_wino_x3.hip): v = hi + mid + lo EXACTLY, hi = bf16(v), mid = bf16(v - hi),
 // lo = bf16(v - hi - mid) (round-to-nearest-even: v_cvt_pk_bf16_f32; both differences are exact in fp32).  Operand layout ("stage-major":
 // what ONE stage of the GEMM reads of one plane is contiguous): [pos][C / X3_SW][plane][rows][X3_SW]; pstride = rows * X3_SW elements between planes.
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split3(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
-    hi = (__bf16)v;
-    const float r = v - (float)hi;
-    mid = (__bf16)r;
-    lo = (__bf16)(r - (float)mid);
-}
+// The split itself is conv_x3_common.h's.
 __device__ __forceinline__ void st4x3(__bf16* p, size_t pstride, f32x4 v) {
     bf16x4 h, m, l;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        __bf16 a, b, c;
-        split3(v[e], a, b, c);
-        h[e] = a; m[e] = b; l[e] = c;
-    }
-    *reinterpret_cast<bf16x4*>(p) = h;
-    *reinterpret_cast<bf16x4*>(p + pstride) = m;
-    *reinterpret_cast<bf16x4*>(p + 2 * pstride) = l;
+    split3(v, h, m, l);
+    store3(p, pstride * sizeof(__bf16), h, m, l);
 }
 
 // Hi x Wi: the input image, Ho x Wo = Hi + 2 pad - 2 dil: the output; ps = pad / dil in {0, 1, 2} (VALID on a pre-padded image, SAME, the

@@ -30,28 +30,15 @@
 // Chunked accumulation: every 64 channels the MFMA accumulator is added into `total` and restarted from zero (first MFMA with C = 0); the
 // adds cost the consumer ~25 % of its time, which the data-bound stage hides.
 #include <type_traits>
-#include "conv_common.h"
+#include "conv_x3_common.h"
 
 using namespace pnpconv;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void;
 #ifndef PNP_X3_AUX
 #define PNP_X3_AUX 0      // cache policy bits of the LDS-DMA loads (experiment: 1 = sc0, 2 = nt, 3 = both: no measurable difference, tools/experiments/README.md)
 #endif
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, lds_void* dst, unsigned voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, PNP_X3_AUX);
-#endif
-}
 
 struct X3Args {
     const unsigned short* V;      // [npos][C / X3_SW][3][T][X3_SW]
@@ -82,7 +69,6 @@ template <int BM, int BN, int KIND>
 __global__ void __launch_bounds__(64 * (BM / 32 + PNP_X3_NL), (BM / 32 + PNP_X3_NL) / 4) wino_gemm_x3_kernel(X3Args g) {
     constexpr int SW = X3_SW;
     constexpr int NCW = BM / 32;               // consumer waves
-    constexpr int kTermA[6] = {2, 1, 0, 1, 0, 0}, kTermB[6] = {0, 1, 2, 0, 1, 0};      // the kept products, smallest first: (plane of A, plane of B)
     constexpr int NL = PNP_X3_NL;              // loader waves
     constexpr int ROWB = 2 * SW;               // bytes per LDS row
     constexpr int LPR = ROWB / 16;             // 16-byte chunks (= lanes of a DMA piece) per row
@@ -181,8 +167,8 @@ __global__ void __launch_bounds__(64 * (BM / 32 + PNP_X3_NL), (BM / 32 + PNP_X3_
             const int cc = c_s0 + c_j;
 #pragma unroll
             for (int i = 0; i < LPS; ++i) {
-                if (pisa[i]) dma16(rv, (lds_void*)(bp + pdst[i]), pvo[i], cc * sstrideV);
-                else dma16(ru, (lds_void*)(bp + pdst[i]), pvo[i], cc * sstrideU);
+                if (pisa[i]) dma16<PNP_X3_AUX>(rv, (lds_void*)(bp + pdst[i]), pvo[i], cc * sstrideV);
+                else dma16<PNP_X3_AUX>(ru, (lds_void*)(bp + pdst[i]), pvo[i], cc * sstrideU);
             }
             if (c_j + 1 < c_nst) {
                 ++c_j;
@@ -235,7 +221,7 @@ __global__ void __launch_bounds__(64 * (BM / 32 + PNP_X3_NL), (BM / 32 + PNP_X3_
         for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
             for (int tr = 0; tr < 6; ++tr) {
-                const int pa = kTermA[tr], pb = kTermB[tr];
+                const int pa = kTermX[tr], pb = kTermW[tr];      // (plane of A, plane of B)
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
 #pragma unroll

@@ -24,17 +24,15 @@
 // The strided layers (conv_x3_direct_kernel_strided below, PNP_X3_STRIDED): forward and stride-phase data gradient as sums of stride-1
 // sub-convolutions on the same LDS layout, MFMA order and epilogue; the plan's route X3S, through x3s_chosen().
 // The FILTER gradient of the stride-1 layers with 64 filters is conv_x3_wgrad.hip (PNP_X3_WGRAD), under this file's mode (x3d_route_mode()).
-#include <atomic>
-#include <cstdlib>
-#include "conv_common.h"
+// Where the shared pieces live: the split, the kept-products table, the wait-count / LDS-DMA helpers and the run-time switch of a route are
+// conv_x3_common.h's (for the whole split-bf16 family); the two kernels below differ only in how they enumerate items, patch slots and
+// filter stages (static and unrolled / run-time cursors) and call ONE copy of everything else — filter_lane_offsets / filter_dma /
+// filter_pipeline, patch_store, consumer_lanes / consumer_stage, tile_epilogue — written once in front of them.
+#include "conv_x3_common.h"
 
 using namespace pnpconv;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void lds_void;
 
 constexpr int TH = 16, TW = 16, PH = TH + 2, PW = TW + 2, NPX = PH * PW;      // 324 patch pixels
 constexpr int ROWB = 64;                           // bytes per LDS row: 32 channels of one plane
@@ -46,17 +44,6 @@ constexpr int NPL = 192;                           // patch-loader lanes (3 wave
 constexpr int NPI = (NPX * 8 + NPL - 1) / NPL;     // float4 loads per patch-loader lane: 14
 
 __device__ __forceinline__ int swz(int row) { return (row >> 2) & 3; }
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t r, lds_void* dst, unsigned voff, int soff) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, dst, 16, voff, soff, 0, 0);
-#endif
-}
 
 struct X3dArgs {
     const float* x;               // [N][H][W][C]
@@ -74,15 +61,219 @@ struct X3dArgs {
     const float* stat_shift;
 };
 
+// ============================ the pieces both kernels are built from ============================
+// a (half, tap) filter stage of a block of KW filters: [plane][KW filters][64 B]
+template <int KW>
+struct FStage {
+    static constexpr int PLANE = KW * ROWB;        // bytes per filter plane of a stage
+    static constexpr int BYTES = 3 * PLANE;        // bytes per stage
+    static constexpr int NPC = BYTES / 1024;       // LDS-DMA pieces per stage (1 KiB each)
+    static constexpr int TN = KW / 32;             // 32-filter MFMA blocks
+};
+
+// filter loader: the lane's source offsets of the pieces of a stage.  Piece i (1 KiB = 16 rows of 64 B): lane (lrow = lane / 4,
+// lchk = lane % 4) fetches chunk lchk ^ swz(row) of its row
+template <int KW>
+__device__ __forceinline__ void filter_lane_offsets(int lane, unsigned (&vo)[FStage<KW>::NPC]) {
+    const int lrow = lane >> 2, lchk = lane & 3;
+    constexpr int PPP = KW / 16;                   // pieces per plane
+#pragma unroll
+    for (int i = 0; i < FStage<KW>::NPC; ++i) {
+        const int row = (i % PPP) * 16 + lrow;     // row within the plane (filter index); plane = i / PPP
+        vo[i] = (unsigned)((i / PPP) * FStage<KW>::PLANE + row * ROWB + ((lchk ^ swz(row)) << 4));
+    }
+}
+// ... and the DMA of image stage `stg` into the buffer of global stage g
+template <int KW>
+__device__ __forceinline__ void filter_dma(__amdgpu_buffer_rsrc_t rw, unsigned char* filt0, int g, const unsigned (&vo)[FStage<KW>::NPC], int stg) {
+    unsigned char* bp = filt0 + (g % NF) * FStage<KW>::BYTES;
+#pragma unroll
+    for (int i = 0; i < FStage<KW>::NPC; ++i) dma16(rw, (lds_void*)(bp + i * 1024), vo[i], stg * FStage<KW>::BYTES);
+}
+// ... and its pipeline: issue(g) starts global stage g (NPC loads); one barrier per stage, NF - 1 stages ahead of the consumers
+template <int NPC, class Issue>
+__device__ __forceinline__ void filter_pipeline(int gstages, Issue&& issue) {
+#pragma unroll
+    for (int b = 0; b < NF - 1; ++b)
+        if (b < gstages) issue(b);
+    for (int g = 0; g < gstages; ++g) {
+        // stage g has landed; up to NF - 2 younger stages stay in flight (the tail issues nothing: drain)
+        if (g + NF - 2 < gstages) wait_vm<NPC * (NF - 2)>();
+        else wait_vm0();
+        __builtin_amdgcn_s_barrier();
+        if (g + NF - 1 < gstages) issue(g + NF - 1);                 // into the buffer of stage g - 1: every consumer is past it
+    }
+    wait_vm0();
+}
+
+// patch loader: float4 i0 .. i1 - 1 of lane pl's share of a patch, split into the three planes of the patch buffer pb
+__device__ __forceinline__ void patch_store(unsigned char* pb, int pl, const f32x4 (&st)[NPI], int i0, int i1) {
+#pragma unroll
+    for (int i = 0; i < NPI; ++i) {
+        if (i < i0 || i >= i1) continue;
+        const int e = pl + i * NPL;
+        if (e >= NPX * 8) continue;
+        const int q = e >> 3, j = e & 7;
+        bf16x4 hi, mi, lo;
+        split3(st[i], hi, mi, lo);
+        store3(pb + q * ROWB + (((j >> 1) ^ swz(q)) << 4) + (j & 1) * 8, PLANE_P, hi, mi, lo);
+    }
+}
+
+// consumers: 64 pixels (4 output rows x 16) x KW filters per wave.
+// MFMA: A = pixels (rows), B = filters (columns): D[pixel][filter], lane = filter l31 of block tn, rows (i & 3) + 8 (i >> 2) + 4 h.
+// Pixel of MFMA row r in 32-pixel block tm: r < 16: image row 4 w + 2 tm, column r; else the next image row, column (r - 2) mod 16 — the
+// rotation makes the patch index q of the second row congruent (mod 16) to the first row's: 16 distinct bank slots per lane group.
+__device__ __forceinline__ int tile_col(int r) { return (r < 16) ? r : ((r - 16 + 14) & 15); }
+// ... and the pixel of accumulator element i of block tm, in a tile at (oh0, ow0).  (The sums keep this order: another association of the
+// same terms costs the stride-1 kernels six registers.)
+__device__ __forceinline__ void tile_pixel(int oh0, int ow0, int wave, int h, int tm, int i, int& orow, int& ocol) {
+    const int r = (i & 3) + 8 * (i >> 2) + 4 * h;
+    orow = oh0 + 4 * wave + 2 * tm + (r >> 4);
+    ocol = ow0 + tile_col(r);
+}
+template <int TN>
+struct Lanes {
+    int l31, h;
+    int aq[2];                                     // [tm]: the lane's patch pixel at tap (0, 0)
+    int woff[TN][2];                               // [tn][ks]: the lane's fragment within a plane of a filter stage
+};
+template <int TN>
+__device__ __forceinline__ Lanes<TN> consumer_lanes(int lane, int wave) {
+    Lanes<TN> L;
+    L.l31 = lane & 31;
+    L.h = lane >> 5;
+#pragma unroll
+    for (int tm = 0; tm < 2; ++tm) L.aq[tm] = (4 * wave + 2 * tm + (L.l31 >> 4)) * PW + tile_col(L.l31);
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) L.woff[tn][ks] = (tn * 32 + L.l31) * ROWB + (((2 * ks + L.h) ^ swz(tn * 32 + L.l31)) << 4);
+    return L;
+}
+// 16-channel slice ks of plane p of patch pixel q
+__device__ __forceinline__ bf16x8 x_frag(const unsigned char* A, int q, int h, int ks, int p) {
+    return *reinterpret_cast<const bf16x8*>(A + p * PLANE_P + q * ROWB + (((2 * ks + h) ^ swz(q)) << 4));
+}
+
+// One stage: the tap at patch offset dq of patch A against filter stage B.  12 filter-fragment reads after the barrier, the 12
+// pixel-fragment reads of the NEXT tap (patch offset dqn; < 0: this is the patch's last) issued before the MFMAs — same patch, no barrier
+// in between — and 6 x 2 x 2 x TN MFMAs.  first: the patch only became visible with this barrier, nothing was prefetched.
+// xf [ks][plane][tm]: this tap's pixel fragments; xn [plane][tm]: the next tap's first slice, read one stage ahead
+template <int KW>
+__device__ __forceinline__ void consumer_stage(const Lanes<FStage<KW>::TN>& L, const unsigned char* A, const unsigned char* B, int dq, int dqn, bool first,
+                                               f32x16 (&acc)[2][FStage<KW>::TN], bf16x8 (&xf)[2][3][2], bf16x8 (&xn)[3][2]) {
+    constexpr int TN = FStage<KW>::TN, PLANE_F = FStage<KW>::PLANE;
+    wait_lgkm0();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (first) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm) xf[0][p][tm] = x_frag(A, L.aq[tm] + dq, L.h, 0, p);
+    } else {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm) xf[0][p][tm] = xn[p][tm];
+    }
+    bf16x8 wf[2][3][TN];                           // [ks][plane][tn]
+#pragma unroll
+    for (int p = 0; p < 3; ++p)
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) wf[0][p][tn] = *reinterpret_cast<const bf16x8*>(B + p * PLANE_F + L.woff[tn][0]);
+#pragma unroll
+    for (int p = 0; p < 3; ++p) {
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) xf[1][p][tm] = x_frag(A, L.aq[tm] + dq, L.h, 1, p);
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) wf[1][p][tn] = *reinterpret_cast<const bf16x8*>(B + p * PLANE_F + L.woff[tn][1]);
+    }
+    if (dqn >= 0) {
+#pragma unroll
+        for (int p = 0; p < 3; ++p)
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm) xn[p][tm] = x_frag(A, L.aq[tm] + dqn, L.h, 0, p);
+    }
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+        for (int trm = 0; trm < 6; ++trm)
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                for (int tn = 0; tn < TN; ++tn)
+                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[ks][kTermX[trm]][tm], wf[ks][kTermW[trm]][tn], acc[tm][tn], 0, 0, 0);
+}
+
+// Epilogue (conv_common.h: conv_epilogue, for the tiled pixel order): phases of pure loads / arithmetic, then stores.  mlin_of(tm, i) = the
+// linear output pixel of accumulator element i of pixel block tm (recomputed where it is used: no index arrays kept live); n0 = the
+// block's first filter, part = the statistics partial of this wave, out_bytes = the extent of y (and of res_add, which may be null)
+template <int TN, class Args, class MLin>
+__device__ __forceinline__ void tile_epilogue(f32x16 (&acc)[2][TN], const Args& a, uint32_t dkey, const float* res_add, unsigned out_bytes, int n0, int part,
+                                              int l31, int h, MLin&& mlin_of) {
+    int ncol[TN];
+#pragma unroll
+    for (int tn = 0; tn < TN; ++tn) ncol[tn] = n0 + tn * 32 + l31;
+#define X3_FOR                                                       \
+    _Pragma("unroll") for (int tm = 0; tm < 2; ++tm)                 \
+        _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)            \
+            _Pragma("unroll") for (int i = 0; i < 16; ++i)
+    if (a.do_drop) {
+        X3_FOR {
+            const uint32_t idx = (uint32_t)((size_t)mlin_of(tm, i) * a.K + ncol[tn]);
+            const float kept = acc[tm][tn][i] / a.drop_keep;         // (divided whether kept or not: a select, no branch per element)
+            acc[tm][tn][i] = pnp_drop_keep(idx, dkey, a.drop_thresh) ? kept : 0.f;
+        }
+    }
+    if (res_add) {
+        const __amdgpu_buffer_rsrc_t rr = make_rsrc(res_add, out_bytes);
+#pragma unroll
+        for (int tm = 0; tm < 2; ++tm) {              // (one pixel block at a time: all loads, then all adds)
+            f32x16 rv[TN];
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) rv[tn][i] = bload1(rr, (unsigned)(mlin_of(tm, i) * a.K + ncol[tn]) * 4u);
+#pragma unroll
+            for (int tn = 0; tn < TN; ++tn)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[tm][tn][i] += rv[tn][i];
+        }
+    }
+    if (a.stat_ws) {
+#pragma unroll
+        for (int tn = 0; tn < TN; ++tn) {
+            const float shift = a.stat_shift ? a.stat_shift[ncol[tn]] : 0.f;
+            float ssum = 0.f, ssq = 0.f;
+#pragma unroll
+            for (int tm = 0; tm < 2; ++tm)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float d = acc[tm][tn][i] - shift;
+                    ssum += d;
+                    ssq = fmaf(d, d, ssq);
+                }
+            const float s_ = ssum + __shfl_xor(ssum, 32, 64);      // the two half-waves hold the same filter, disjoint pixels
+            const float q_ = ssq + __shfl_xor(ssq, 32, 64);
+            if (h == 0) {
+                a.stat_ws[((size_t)part * 2 + 0) * a.K + ncol[tn]] = s_;
+                a.stat_ws[((size_t)part * 2 + 1) * a.K + ncol[tn]] = q_;
+            }
+        }
+    }
+    const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.y, out_bytes);
+    X3_FOR bstore1(ry, (unsigned)(mlin_of(tm, i) * a.K + ncol[tn]) * 4u, acc[tm][tn][i]);
+#undef X3_FOR
+}
+
 // NH = C / 32 channel halves (1 or 2); KW = filters per block (64; 32 for the 32-filter layers: the data gradient of a 32 -> 64 layer);
 // KIND 0 / 1 only names the symbol (forward / data gradient: the difference is the filter image)
 template <int NH, int KW, int KIND>
 __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel(X3dArgs a) {
     constexpr int NSTG = 9 * NH;
-    constexpr int PLANE_F = KW * ROWB;             // bytes per filter plane of a stage
-    constexpr int FSTG = 3 * PLANE_F;              // bytes per (half, tap) stage
-    constexpr int NPC = FSTG / 1024;               // LDS-DMA pieces per stage (1 KiB each)
-    constexpr int TN = KW / 32;
+    constexpr int FSTG = FStage<KW>::BYTES, NPC = FStage<KW>::NPC, TN = FStage<KW>::TN;
     static_assert(NSTG % NF == 0, "the filter buffer of a stage must not depend on the item");
     __shared__ __attribute__((aligned(256))) unsigned char lds[LDS_BYTES];
     unsigned char* const patch0 = lds;
@@ -109,33 +300,13 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel(X3dArgs a) {
     if (wave == 4) {
         // ============================ filter loader: one 12 KB stage per barrier, LDS-DMA ============================
         const __amdgpu_buffer_rsrc_t rw = make_rsrc(reinterpret_cast<const float*>(a.w3), (unsigned)(KB * NSTG * FSTG));
-        // piece i (1 KiB = 16 rows of 64 B): lane (lrow = lane / 4, lchk = lane % 4) fetches chunk lchk ^ swz(row) of its row
-        const int lrow = lane >> 2, lchk = lane & 3;
-        constexpr int PPP = KW / 16;                                   // pieces per plane
         unsigned vo[NPC];
-#pragma unroll
-        for (int i = 0; i < NPC; ++i) {
-            const int row = (i % PPP) * 16 + lrow;                    // row within the plane (filter index); plane = i / PPP
-            vo[i] = (unsigned)((i / PPP) * PLANE_F + row * ROWB + ((lchk ^ swz(row)) << 4));
-        }
-        auto issue = [&](int g) {
+        filter_lane_offsets<KW>(lane, vo);
+        filter_pipeline<NPC>(gstages, [&](int g) {
             const int it = g / NSTG, s = g - it * NSTG;
             const int kb = (int)((blockIdx.x + it * gridDim.x) % KB);
-            unsigned char* bp = filt0 + (g % NF) * FSTG;
-#pragma unroll
-            for (int i = 0; i < NPC; ++i) dma16(rw, (lds_void*)(bp + i * 1024), vo[i], (kb * NSTG + s) * FSTG);
-        };
-#pragma unroll
-        for (int b = 0; b < NF - 1; ++b)
-            if (b < gstages) issue(b);
-        for (int g = 0; g < gstages; ++g) {
-            // stage g has landed; up to NF - 2 younger stages stay in flight (the tail issues nothing: drain)
-            if (g + NF - 2 < gstages) wait_vm<NPC * (NF - 2)>();
-            else wait_vm0();
-            __builtin_amdgcn_s_barrier();
-            if (g + NF - 1 < gstages) issue(g + NF - 1);             // into the buffer of stage g - 1: every consumer is past it
-        }
-        wait_vm0();
+            filter_dma<KW>(rw, filt0, g, vo, kb * NSTG + s);
+        });
         return;
     }
     if (wave > 4) {
@@ -158,30 +329,7 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel(X3dArgs a) {
                 st[i] = v;
             }
         };
-        auto store = [&](int slot, int i0, int i1) {
-            unsigned char* pb = patch0 + (slot & 1) * PATCH;
-#pragma unroll
-            for (int i = 0; i < NPI; ++i) {
-                if (i < i0 || i >= i1) continue;
-                const int e = pl + i * NPL;
-                if (e >= NPX * 8) continue;
-                const int q = e >> 3, j = e & 7;
-                bf16x4 hi, mi, lo;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float v = st[i][c];
-                    const __bf16 h = (__bf16)v;
-                    const float r1 = v - (float)h;
-                    const __bf16 m = (__bf16)r1;
-                    const float r2 = r1 - (float)m;
-                    hi[c] = h; mi[c] = m; lo[c] = (__bf16)r2;
-                }
-                const int off = q * ROWB + (((j >> 1) ^ swz(q)) << 4) + (j & 1) * 8;
-                *reinterpret_cast<bf16x4*>(pb + off) = hi;
-                *reinterpret_cast<bf16x4*>(pb + PLANE_P + off) = mi;
-                *reinterpret_cast<bf16x4*>(pb + 2 * PLANE_P + off) = lo;
-            }
-        };
+        auto store = [&](int slot, int i0, int i1) { patch_store(patch0 + (slot & 1) * PATCH, pl, st, i0, i1); };
         const int nslots = myitems * NH;
         load(0);
         wait_vm0();
@@ -205,28 +353,9 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel(X3dArgs a) {
         return;
     }
     // ============================ consumers: 64 pixels (4 output rows x 16) x 64 filters per wave ============================
-    // MFMA: A = pixels (rows), B = filters (columns): D[pixel][filter], lane = filter l31 of block tn, rows (i & 3) + 8 (i >> 2) + 4 h.
-    // Pixel of MFMA row r in 32-pixel block tm: r < 16: image row 4 w + 2 tm, column r; else the next image row, column (r - 2) mod 16 — the
-    // rotation makes the patch index q of the second row congruent (mod 16) to the first row's: 16 distinct bank slots per lane group.
-    const int l31 = lane & 31, h = lane >> 5;
-    const int prow = l31 >> 4, pcol = (l31 < 16) ? l31 : ((l31 - 16 + 14) & 15);
-    int aq[2];
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) aq[tm] = (4 * wave + 2 * tm + prow) * PW + pcol;
-    int woff[TN][2];                                // [tn][ks]
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) woff[tn][ks] = (tn * 32 + l31) * ROWB + (((2 * ks + h) ^ swz(tn * 32 + l31)) << 4);
-    constexpr int kTermX[6] = {2, 1, 0, 1, 0, 0}, kTermW[6] = {0, 1, 2, 0, 1, 0};      // the kept plane products, smallest first
+    const Lanes<TN> L = consumer_lanes<TN>(lane, wave);
     f32x16 acc[2][TN];                              // [tm (pixel block)][tn (filter block)]
-    bf16x8 xf[2][3][2];                             // [ks][plane][tm]: this tap's pixel fragments
-    bf16x8 xn[3][2];                                // [plane][tm]: the NEXT tap's first 16-channel slice, read one stage ahead
-    auto x_frag = [&](int pbuf, int tap, int ks, int p, int tm) {
-        const unsigned char* A = patch0 + pbuf * PATCH;
-        const int q = aq[tm] + (tap / 3) * PW + (tap % 3);
-        return *reinterpret_cast<const bf16x8*>(A + p * PLANE_P + q * ROWB + (((2 * ks + h) ^ swz(q)) << 4));
-    };
+    bf16x8 xf[2][3][2], xn[3][2];
     const uint32_t dkey = a.do_drop ? pnp_eff_drop_key(a.drop_key, a.sp, a.drop_sid) : 0u;
     for (int it = 0; it < myitems; ++it) {
 #pragma unroll
@@ -239,109 +368,17 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel(X3dArgs a) {
 #pragma unroll
         for (int s = 0; s < NSTG; ++s) {
             const int hsel = s / 9, tap = s % 9;     // (static after unrolling; the filter buffer of global stage NSTG it + s is s mod NF)
-            const int fb = s % NF;
             const int pbuf = (slot0 + hsel) & 1;
-            wait_lgkm0();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            // this tap's first slice: prefetched by the previous stage, or (first tap of a half: the patch only became visible with this
-            // barrier) read now
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm) xf[0][p][tm] = (tap == 0) ? x_frag(pbuf, 0, 0, p, tm) : xn[p][tm];
-            const unsigned char* B = filt0 + fb * FSTG;
-            bf16x8 wf[2][3][TN];                     // [ks][plane][tn]
-#pragma unroll
-            for (int p = 0; p < 3; ++p)
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) wf[0][p][tn] = *reinterpret_cast<const bf16x8*>(B + p * PLANE_F + woff[tn][0]);
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm) xf[1][p][tm] = x_frag(pbuf, tap, 1, p, tm);
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) wf[1][p][tn] = *reinterpret_cast<const bf16x8*>(B + p * PLANE_F + woff[tn][1]);
-            }
-            if (tap != 8) {                          // the next tap's first slice: same patch, no barrier in between
-#pragma unroll
-                for (int p = 0; p < 3; ++p)
-#pragma unroll
-                    for (int tm = 0; tm < 2; ++tm) xn[p][tm] = x_frag(pbuf, tap + 1, 0, p, tm);
-            }
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                for (int trm = 0; trm < 6; ++trm)
-#pragma unroll
-                    for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn)
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[ks][kTermX[trm]][tm], wf[ks][kTermW[trm]][tn], acc[tm][tn], 0, 0, 0);
+            consumer_stage<KW>(L, patch0 + pbuf * PATCH, filt0 + (s % NF) * FSTG, (tap / 3) * PW + tap % 3,
+                               tap != 8 ? ((tap + 1) / 3) * PW + (tap + 1) % 3 : -1, tap == 0, acc, xf, xn);
         }
-        // ---------------- epilogue (conv_common.h: conv_epilogue, for the tiled pixel order): phases of pure loads / arithmetic, then stores
         int kb, tile, n, oh0, ow0;
         item_origin(it, kb, tile, n, oh0, ow0);
-        // MFMA row (i & 3) + 8 (i >> 2) + 4 h of block tm -> linear output pixel (recomputed where it is used: no index arrays kept live)
-        auto mlin_of = [&](int tm, int i) {
-            const int r = (i & 3) + 8 * (i >> 2) + 4 * h;
-            const int orow = oh0 + 4 * wave + 2 * tm + (r >> 4);
-            const int ocol = ow0 + ((r < 16) ? r : ((r - 16 + 14) & 15));
+        tile_epilogue<TN>(acc, a, dkey, a.res_add, (unsigned)((size_t)a.M * a.K * 4), kb * KW, tile * 4 + wave, L.l31, L.h, [&](int tm, int i) {
+            int orow, ocol;
+            tile_pixel(oh0, ow0, wave, L.h, tm, i, orow, ocol);
             return (n * a.OH + orow) * a.OW + ocol;
-        };
-        int ncol[TN];
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) ncol[tn] = kb * KW + tn * 32 + l31;
-#define X3D_FOR                                                      \
-    _Pragma("unroll") for (int tm = 0; tm < 2; ++tm)                 \
-        _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)            \
-            _Pragma("unroll") for (int i = 0; i < 16; ++i)
-        if (a.do_drop) {
-            X3D_FOR {
-                const uint32_t idx = (uint32_t)((size_t)mlin_of(tm, i) * a.K + ncol[tn]);
-                acc[tm][tn][i] = pnp_drop_keep(idx, dkey, a.drop_thresh) ? acc[tm][tn][i] / a.drop_keep : 0.f;
-            }
-        }
-        if (a.res_add) {
-            const __amdgpu_buffer_rsrc_t rr = make_rsrc(a.res_add, (unsigned)((size_t)a.M * a.K * 4));
-#pragma unroll
-            for (int tm = 0; tm < 2; ++tm) {          // (one pixel block at a time: all loads, then all adds)
-                f32x16 rv[TN];
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) rv[tn][i] = bload1(rr, (unsigned)(mlin_of(tm, i) * a.K + ncol[tn]) * 4u);
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[tm][tn][i] += rv[tn][i];
-            }
-        }
-        if (a.stat_ws) {
-            const int part = tile * 4 + wave;
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) {
-                const float shift = a.stat_shift ? a.stat_shift[ncol[tn]] : 0.f;
-                float ssum = 0.f, ssq = 0.f;
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const float d = acc[tm][tn][i] - shift;
-                        ssum += d;
-                        ssq = fmaf(d, d, ssq);
-                    }
-                const float s_ = ssum + __shfl_xor(ssum, 32, 64);      // the two half-waves hold the same filter, disjoint pixels
-                const float q_ = ssq + __shfl_xor(ssq, 32, 64);
-                if (h == 0) {
-                    a.stat_ws[((size_t)part * 2 + 0) * a.K + ncol[tn]] = s_;
-                    a.stat_ws[((size_t)part * 2 + 1) * a.K + ncol[tn]] = q_;
-                }
-            }
-        }
-        const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.y, (unsigned)((size_t)a.M * a.K * 4));
-        X3D_FOR bstore1(ry, (unsigned)(mlin_of(tm, i) * a.K + ncol[tn]) * 4u, acc[tm][tn][i]);
-#undef X3D_FOR
+        });
     }
 }
 
@@ -359,15 +396,8 @@ __global__ void __launch_bounds__(256) x3d_filter_kernel(const float* __restrict
     const int hf = r % NH, kb = r / NH;
     const int ic = hf * 32 + i, oc = kb * KW + o;
     const float v = FLIP ? w[((size_t)(8 - tap) * K + oc) * C + ic] : w[((size_t)tap * C + ic) * K + oc];
-    const __bf16 b0 = (__bf16)v;
-    const float r1 = v - (float)b0;
-    const __bf16 b1 = (__bf16)r1;
-    const float r2 = r1 - (float)b1;
-    const __bf16 b2 = (__bf16)r2;
     const size_t base = ((((size_t)kb * NH + hf) * 9 + tap) * 3) * ((size_t)KW * 32) + (size_t)o * 32 + i;
-    w3[base] = __builtin_bit_cast(unsigned short, b0);
-    w3[base + (size_t)KW * 32] = __builtin_bit_cast(unsigned short, b1);
-    w3[base + 2 * (size_t)KW * 32] = __builtin_bit_cast(unsigned short, b2);
+    split3_write(w3 + base, (size_t)KW * 32, v);
 }
 
 // ============================ strided layers: sums of stride-1 sub-convolutions over the input's stride phases ============================
@@ -419,8 +449,8 @@ __device__ __forceinline__ int x3s_group(const X3sArgs& a, int id) {
 // KIND 0 / 1 only names the symbol (forward / data gradient)
 template <int KIND>
 __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel_strided(X3sArgs a) {
-    constexpr int KW = 64, TN = 2;
-    constexpr int PLANE_F = KW * ROWB, FSTG = 3 * PLANE_F, NPC = FSTG / 1024;
+    constexpr int KW = 64;
+    constexpr int FSTG = FStage<KW>::BYTES, NPC = FStage<KW>::NPC, TN = FStage<KW>::TN;
     __shared__ __attribute__((aligned(256))) unsigned char lds[LDS_BYTES];
     unsigned char* const patch0 = lds;
     unsigned char* const filt0 = lds + 2 * PATCH;
@@ -454,23 +484,14 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel_strided(X3sArgs 
     if (wave == 4) {
         // ============================ filter loader: one 12 KB stage per barrier, LDS-DMA ============================
         const __amdgpu_buffer_rsrc_t rw = make_rsrc(reinterpret_cast<const float*>(a.w3), a.w3_bytes);
-        const int lrow = lane >> 2, lchk = lane & 3;
-        constexpr int PPP = KW / 16;
         unsigned vo[NPC];
-#pragma unroll
-        for (int i = 0; i < NPC; ++i) {
-            const int row = (i % PPP) * 16 + lrow;
-            vo[i] = (unsigned)((i / PPP) * PLANE_F + row * ROWB + ((lchk ^ swz(row)) << 4));
-        }
+        filter_lane_offsets<KW>(lane, vo);
         Cur c{0, 0, 0};
         int gi, kb, tile, n, oh0, ow0;
         item_origin(0, gi, kb, tile, n, oh0, ow0);
-        auto issue = [&](int g) {
+        filter_pipeline<NPC>(gstages, [&](int g) {
             const X3sGroup& G = a.grp[gi];
-            const int stg = G.fbase + (kb * NH + c.hh) * G.nst + c.k;
-            unsigned char* bp = filt0 + (g % NF) * FSTG;
-#pragma unroll
-            for (int i = 0; i < NPC; ++i) dma16(rw, (lds_void*)(bp + i * 1024), vo[i], stg * FSTG);
+            filter_dma<KW>(rw, filt0, g, vo, G.fbase + (kb * NH + c.hh) * G.nst + c.k);
             if (++c.k == G.nst) {
                 c.k = 0;
                 if (++c.hh == NH) {
@@ -478,17 +499,7 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel_strided(X3sArgs 
                     if (++c.it < myitems) item_origin(c.it, gi, kb, tile, n, oh0, ow0);
                 }
             }
-        };
-#pragma unroll
-        for (int b = 0; b < NF - 1; ++b)
-            if (b < gstages) issue(b);
-        for (int g = 0; g < gstages; ++g) {
-            if (g + NF - 2 < gstages) wait_vm<NPC * (NF - 2)>();
-            else wait_vm0();
-            __builtin_amdgcn_s_barrier();
-            if (g + NF - 1 < gstages) issue(g + NF - 1);
-        }
-        wait_vm0();
+        });
         return;
     }
     if (wave > 4) {
@@ -522,29 +533,7 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel_strided(X3sArgs 
                 if (++c.hh == NH) { c.hh = 0; ++c.it; }
             }
         };
-        auto store = [&](int slot) {
-            unsigned char* pb = patch0 + (slot & 1) * PATCH;
-#pragma unroll
-            for (int i = 0; i < NPI; ++i) {
-                const int e = pl + i * NPL;
-                if (e >= NPX * 8) continue;
-                const int q = e >> 3, j = e & 7;
-                bf16x4 hi, mi, lo;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const float v = st[i][c];
-                    const __bf16 h = (__bf16)v;
-                    const float r1 = v - (float)h;
-                    const __bf16 m = (__bf16)r1;
-                    const float r2 = r1 - (float)m;
-                    hi[c] = h; mi[c] = m; lo[c] = (__bf16)r2;
-                }
-                const int off = q * ROWB + (((j >> 1) ^ swz(q)) << 4) + (j & 1) * 8;
-                *reinterpret_cast<bf16x4*>(pb + off) = hi;
-                *reinterpret_cast<bf16x4*>(pb + PLANE_P + off) = mi;
-                *reinterpret_cast<bf16x4*>(pb + 2 * PLANE_P + off) = lo;
-            }
-        };
+        auto store = [&](int slot) { patch_store(patch0 + (slot & 1) * PATCH, pl, st, 0, NPI); };
         auto taps_of = [&](const Cur& c) {
             const int id = blockIdx.x + c.it * gridDim.x;
             const X3sPhase& P = a.ph[a.grp[x3s_group(a, id)].ph0 + c.k];
@@ -578,24 +567,9 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel_strided(X3sArgs 
         return;
     }
     // ============================ consumers: 64 pixels (4 output rows x 16) x 64 filters per wave ============================
-    const int l31 = lane & 31, h = lane >> 5;
-    const int prow = l31 >> 4, pcol = (l31 < 16) ? l31 : ((l31 - 16 + 14) & 15);
-    int aq[2];
-#pragma unroll
-    for (int tm = 0; tm < 2; ++tm) aq[tm] = (4 * wave + 2 * tm + prow) * PW + pcol;
-    int woff[TN][2];
-#pragma unroll
-    for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) woff[tn][ks] = (tn * 32 + l31) * ROWB + (((2 * ks + h) ^ swz(tn * 32 + l31)) << 4);
-    constexpr int kTermX[6] = {2, 1, 0, 1, 0, 0}, kTermW[6] = {0, 1, 2, 0, 1, 0};
+    const Lanes<TN> L = consumer_lanes<TN>(lane, wave);
     f32x16 acc[2][TN];
-    bf16x8 xf[2][3][2];
-    bf16x8 xn[3][2];
-    auto x_frag = [&](const unsigned char* A, int dq, int ks, int p, int tm) {
-        const int q = aq[tm] + dq;
-        return *reinterpret_cast<const bf16x8*>(A + p * PLANE_P + q * ROWB + (((2 * ks + h) ^ swz(q)) << 4));
-    };
+    bf16x8 xf[2][3][2], xn[3][2];
     const uint32_t dkey = a.do_drop ? pnp_eff_drop_key(a.drop_key, a.sp, a.drop_sid) : 0u;
     int g = 0, slot = 0;
     for (int it = 0; it < myitems; ++it) {
@@ -612,100 +586,22 @@ __global__ void __launch_bounds__(512, 1) conv_x3_direct_kernel_strided(X3sArgs 
             for (int pk = 0; pk < G.nph; ++pk, ++slot) {
                 const X3sPhase P = a.ph[G.ph0 + pk];
                 const unsigned char* A = patch0 + (slot & 1) * PATCH;
-                for (int tap = 0, ntap = P.T * P.U; tap < ntap; ++tap, ++g) {
-                    const int tr = tap / P.U, tc = tap - tr * P.U;
-                    const int dq = tr * PW + tc;
-                    wait_lgkm0();
-                    __builtin_amdgcn_s_barrier();
-                    asm volatile("" ::: "memory");
-                    if (tap == 0) {
-#pragma unroll
-                        for (int p = 0; p < 3; ++p)
-#pragma unroll
-                            for (int tm = 0; tm < 2; ++tm) xf[0][p][tm] = x_frag(A, 0, 0, p, tm);
-                    } else {
-#pragma unroll
-                        for (int p = 0; p < 3; ++p)
-#pragma unroll
-                            for (int tm = 0; tm < 2; ++tm) xf[0][p][tm] = xn[p][tm];
-                    }
-                    const unsigned char* B = filt0 + (g % NF) * FSTG;
-                    bf16x8 wf[2][3][TN];
-#pragma unroll
-                    for (int p = 0; p < 3; ++p)
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn) wf[0][p][tn] = *reinterpret_cast<const bf16x8*>(B + p * PLANE_F + woff[tn][0]);
-#pragma unroll
-                    for (int p = 0; p < 3; ++p) {
-#pragma unroll
-                        for (int tm = 0; tm < 2; ++tm) xf[1][p][tm] = x_frag(A, dq, 1, p, tm);
-#pragma unroll
-                        for (int tn = 0; tn < TN; ++tn) wf[1][p][tn] = *reinterpret_cast<const bf16x8*>(B + p * PLANE_F + woff[tn][1]);
-                    }
-                    if (tap + 1 < ntap) {                // the next tap's first slice: same patch, no barrier in between
-                        const int nr = (tap + 1) / P.U, nc = tap + 1 - nr * P.U;
-#pragma unroll
-                        for (int p = 0; p < 3; ++p)
-#pragma unroll
-                            for (int tm = 0; tm < 2; ++tm) xn[p][tm] = x_frag(A, nr * PW + nc, 0, p, tm);
-                    }
-#pragma unroll
-                    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                        for (int trm = 0; trm < 6; ++trm)
-#pragma unroll
-                            for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                                for (int tn = 0; tn < TN; ++tn)
-                                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[ks][kTermX[trm]][tm], wf[ks][kTermW[trm]][tn], acc[tm][tn], 0, 0, 0);
+                // taps row by row: (tr, tc) and its patch offset dq walk along with tap
+                for (int tap = 0, ntap = P.T * P.U, tc = 0, dq = 0; tap < ntap; ++tap, ++g) {
+                    const bool wrap = tc + 1 == P.U;
+                    const int dqn = wrap ? dq + PW - tc : dq + 1;
+                    consumer_stage<KW>(L, A, filt0 + (g % NF) * FSTG, dq, tap + 1 < ntap ? dqn : -1, tap == 0, acc, xf, xn);
+                    tc = wrap ? 0 : tc + 1;
+                    dq = dqn;
                 }
             }
         }
-        // ---------------- epilogue: as conv_x3_direct_kernel's, the output pixel scattered by the group's (o_s, o_h0, o_w0)
-        auto mlin_of = [&](int tm, int i) {
-            const int r = (i & 3) + 8 * (i >> 2) + 4 * h;
-            const int orow = oh0 + 4 * wave + 2 * tm + (r >> 4);
-            const int ocol = ow0 + ((r < 16) ? r : ((r - 16 + 14) & 15));
+        // the output pixel scattered by the group's (o_s, o_h0, o_w0); no residual on this route
+        tile_epilogue<TN>(acc, a, dkey, nullptr, (unsigned)((size_t)a.N * a.OHt * a.OWt * a.K * 4), kb * KW, tile * 4 + wave, L.l31, L.h, [&](int tm, int i) {
+            int orow, ocol;
+            tile_pixel(oh0, ow0, wave, L.h, tm, i, orow, ocol);
             return (n * a.OHt + G.o_h0 + a.o_s * orow) * a.OWt + G.o_w0 + a.o_s * ocol;
-        };
-        int ncol[TN];
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn) ncol[tn] = kb * KW + tn * 32 + l31;
-#define X3S_FOR                                                      \
-    _Pragma("unroll") for (int tm = 0; tm < 2; ++tm)                 \
-        _Pragma("unroll") for (int tn = 0; tn < TN; ++tn)            \
-            _Pragma("unroll") for (int i = 0; i < 16; ++i)
-        if (a.do_drop) {
-            X3S_FOR {
-                const uint32_t idx = (uint32_t)((size_t)mlin_of(tm, i) * a.K + ncol[tn]);
-                acc[tm][tn][i] = pnp_drop_keep(idx, dkey, a.drop_thresh) ? acc[tm][tn][i] / a.drop_keep : 0.f;
-            }
-        }
-        if (a.stat_ws) {
-            const int part = tile * 4 + wave;
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) {
-                const float shift = a.stat_shift ? a.stat_shift[ncol[tn]] : 0.f;
-                float ssum = 0.f, ssq = 0.f;
-#pragma unroll
-                for (int tm = 0; tm < 2; ++tm)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const float d = acc[tm][tn][i] - shift;
-                        ssum += d;
-                        ssq = fmaf(d, d, ssq);
-                    }
-                const float s_ = ssum + __shfl_xor(ssum, 32, 64);
-                const float q_ = ssq + __shfl_xor(ssq, 32, 64);
-                if (h == 0) {
-                    a.stat_ws[((size_t)part * 2 + 0) * a.K + ncol[tn]] = s_;
-                    a.stat_ws[((size_t)part * 2 + 1) * a.K + ncol[tn]] = q_;
-                }
-            }
-        }
-        const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.y, (unsigned)((size_t)a.N * a.OHt * a.OWt * a.K * 4));
-        X3S_FOR bstore1(ry, (unsigned)(mlin_of(tm, i) * a.K + ncol[tn]) * 4u, acc[tm][tn][i]);
-#undef X3S_FOR
+        });
     }
 }
 
@@ -735,27 +631,11 @@ __global__ void __launch_bounds__(256) x3s_filter_kernel(const float* __restrict
     const int r = tp.tr[tp.st0[gi] + s], c = tp.tc[tp.st0[gi] + s];
     const int ic = hf * 32 + i, oc = kb * 64 + o;
     const float v = FLIP ? w[(((size_t)r * tp.S + c) * K + oc) * C + ic] : w[(((size_t)r * tp.S + c) * C + ic) * K + oc];
-    const __bf16 b0 = (__bf16)v;
-    const float r1 = v - (float)b0;
-    const __bf16 b1 = (__bf16)r1;
-    const float r2 = r1 - (float)b1;
-    const __bf16 b2 = (__bf16)r2;
-    const size_t base = (size_t)simg * 3 * 64 * 32 + (size_t)o * 32 + i;
-    w3[base] = __builtin_bit_cast(unsigned short, b0);
-    w3[base + 64 * 32] = __builtin_bit_cast(unsigned short, b1);
-    w3[base + 2 * 64 * 32] = __builtin_bit_cast(unsigned short, b2);
+    split3_write(w3 + (size_t)simg * 3 * 64 * 32 + (size_t)o * 32 + i, 64 * 32, v);
 }
 
-std::atomic<int> g_x3d_mode{-1};
-
-int x3d_mode() {
-    int m = g_x3d_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = getenv("PNP_X3_DIRECT") ? atoi(getenv("PNP_X3_DIRECT")) : 1;
-        g_x3d_mode.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+// PNP_X3_DIRECT / pnp_conv2d_x3_direct() and the strided layers' share of the route, PNP_X3_STRIDED / pnp_conv2d_x3_strided()
+ModeSwitch x3d_switch{"PNP_X3_DIRECT", 1, 2, false}, x3s_switch{"PNP_X3_STRIDED", 1, 1, false};
 
 // mode 1: layers with at least one (tile, filter block) item per CU — a persistent launch of fewer leaves CUs idle and the old route wins;
 // mode 2: wherever the shapes allow (tests)
@@ -763,18 +643,7 @@ bool dims_ok(int R, int S, int stride, int dil, int C, int K, int OH, int OW, lo
     if (!(R == 3 && S == 3 && stride == 1 && dil == 1 && (C == 32 || C == 64) && (K == 32 || K == 64 || K == 128) && (OH % TH) == 0 && (OW % TW) == 0 &&
           M * (long long)K < (1ll << 30)))
         return false;
-    return x3d_mode() >= 2 || (M / (TH * TW)) * (K == 32 ? 1 : K / 64) >= 256;
-}
-
-std::atomic<int> g_x3s_mode{-1};
-
-int x3s_mode() {
-    int m = g_x3s_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = getenv("PNP_X3_STRIDED") ? atoi(getenv("PNP_X3_STRIDED")) : 1;
-        g_x3s_mode.store(m, std::memory_order_relaxed);
-    }
-    return m;
+    return x3d_switch.get() >= 2 || (M / (TH * TW)) * (K == 32 ? 1 : K / 64) >= 256;
 }
 
 // a strided layer's groups, phases and filter stages (kind 0: the forward of g; 1: its data gradient); false: not this route
@@ -786,7 +655,7 @@ struct X3sPlan {
 };
 
 bool x3s_plan(const pnp_conv_geom* g, int kind, X3sPlan* pl) {
-    if (x3d_mode() <= 0 || x3s_mode() <= 0 || g->dtype != PNP_DTYPE_F32 || g->pad_mode != PNP_PAD_ZERO || g->dil != 1) return false;
+    if (x3d_switch.get() <= 0 || x3s_switch.get() <= 0 || g->dtype != PNP_DTYPE_F32 || g->pad_mode != PNP_PAD_ZERO || g->dil != 1) return false;
     const int s = g->stride;
     if (s < 2 || s > 4 || g->R < s || g->S < s || g->R > 3 * s || g->S > 3 * s) return false;
     const int Cin = kind == 0 ? g->C : g->K, Kout = kind == 0 ? g->K : g->C;      // channels of the convolution this kernel computes
@@ -845,16 +714,39 @@ bool x3s_plan(const pnp_conv_geom* g, int kind, X3sPlan* pl) {
     // kernels — phase patches that serve >= 4 taps on average (k5s2: 25 taps over 4 patches), or data gradients of <= 64 dy channels (k3s2
     // 64@256, whose 1x1 / 1x2 phases run at 40-65 TF/s on the fp32 pipe); k3s2 with 2.25 taps per patch is bound by its patch loads
     // elsewhere (256@64, 512@32: 0.8-0.9x).  Mode 2: wherever the shapes allow (tests)
-    if (x3d_mode() < 2 && (items < 256 || !(g->R * g->S >= 4 * s * s || (kind == 1 && Cin <= 64)))) return false;
+    if (x3d_switch.get() < 2 && (items < 256 || !(g->R * g->S >= 4 * s * s || (kind == 1 && Cin <= 64)))) return false;
     if (pl) *pl = p;
     return true;
+}
+
+// The pre-split filter image (6 bytes per filter value) at the head of the caller's workspace: the workspace is checked and
+// launch(image, blocks) — the route's filter kernel, one thread of 256 per value — runs under its own profile row.  Returns the image, or
+// null with the error in rc.
+template <class Launch>
+unsigned short* filter_image(const char* who, const char* kernel, int cls, bool flip, size_t fbytes, void* ws, size_t ws_bytes, hipStream_t st, int& rc, Launch&& launch) {
+    rc = PNP_EWORKSPACE;
+    if (!ws || ws_bytes < fbytes) {
+        pnp_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, fbytes);
+        return nullptr;
+    }
+    const long long total = (long long)(fbytes / 6);
+    PnpProfScope ps(cls, st, 0.0, 4.0 * total + 6.0 * total, "%s<%s>", kernel, flip ? "true" : "false");
+    launch((unsigned short*)ws, dim3((unsigned)pnp_cdiv(total, 256)));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        pnp_set_error("%s: launch failed: %s", kernel, hipGetErrorString(e));
+        rc = PNP_ELAUNCH;
+        return nullptr;
+    }
+    rc = PNP_OK;
+    return (unsigned short*)ws;
 }
 
 }  // namespace
 
 namespace pnpconv {
 
-int x3d_route_mode() { return x3d_mode(); }
+int x3d_route_mode() { return x3d_switch.get(); }
 
 bool x3s_chosen(const pnp_conv_geom* g, int kind) { return x3s_plan(g, kind, nullptr); }
 
@@ -869,21 +761,14 @@ int launch_x3_strided(const ConvArgs& a, const pnp_conv_geom* g, int kind, void*
         return PNP_EINVAL;
     }
     const size_t fbytes = x3s_filter_bytes(g);
-    if (!ws || ws_bytes < fbytes) {
-        pnp_set_error("launch_x3_strided: workspace too small (%zu < %zu)", ws_bytes, fbytes);
-        return PNP_EWORKSPACE;
-    }
-    unsigned short* w3 = (unsigned short*)ws;
     const int cls = prof_class(kind);
     const int Cin = kind == 0 ? g->C : g->K, Kout = kind == 0 ? g->K : g->C;
-    {
-        const long long total = (long long)g->R * g->S * g->C * g->K;
-        PnpProfScope ps(cls, st, 0.0, 4.0 * total + 6.0 * total, "x3s_filter_kernel<%s>", kind ? "true" : "false");
-        const unsigned blocks = (unsigned)pnp_cdiv(total, 256);
-        if (kind) hipLaunchKernelGGL((x3s_filter_kernel<true>), dim3(blocks), dim3(256), 0, st, a.w, w3, Cin, Kout, pl.taps);
-        else hipLaunchKernelGGL((x3s_filter_kernel<false>), dim3(blocks), dim3(256), 0, st, a.w, w3, Cin, Kout, pl.taps);
-        PNP_CHECK_LAUNCH("x3s_filter_kernel");
-    }
+    int rc;
+    unsigned short* w3 = filter_image("launch_x3_strided", "x3s_filter_kernel", cls, kind != 0, fbytes, ws, ws_bytes, st, rc, [&](unsigned short* img, dim3 blocks) {
+        if (kind) hipLaunchKernelGGL((x3s_filter_kernel<true>), blocks, dim3(256), 0, st, a.w, img, Cin, Kout, pl.taps);
+        else hipLaunchKernelGGL((x3s_filter_kernel<false>), blocks, dim3(256), 0, st, a.w, img, Cin, Kout, pl.taps);
+    });
+    if (!w3) return rc;
     X3sArgs x{};
     x.x = a.x; x.w3 = w3; x.y = a.y;
     x.N = g->N; x.C = Cin; x.K = Kout; x.NH = Cin / 32;
@@ -893,7 +778,7 @@ int launch_x3_strided(const ConvArgs& a, const pnp_conv_geom* g, int kind, void*
     x.w3_bytes = (unsigned)fbytes;
     for (int i = 0; i < pl.ngroups; ++i) x.grp[i] = pl.grp[i];
     for (int i = 0; i < X3S_MAXPH; ++i) x.ph[i] = pl.ph[i];
-    x.do_drop = a.do_drop; x.drop_thresh = a.drop_thresh; x.drop_key = a.drop_key; x.drop_keep = a.drop_keep; x.sp = a.sp; x.drop_sid = a.drop_sid;
+    copy_dropout(x, a);
     x.stat_ws = kind == 0 ? a.stat_ws : nullptr; x.stat_shift = a.stat_shift;
     const dim3 grid((unsigned)(pl.nitems > 256 ? 256 : pl.nitems));
     // flops = the bf16 MFMA flops the kernel EXECUTES: six plane products per useful fp32 multiply-add (every forward tap exactly once per
@@ -908,7 +793,7 @@ int launch_x3_strided(const ConvArgs& a, const pnp_conv_geom* g, int kind, void*
 }
 
 bool x3d_chosen(const pnp_conv_geom* g) {
-    return x3d_mode() > 0 && g->dtype == PNP_DTYPE_F32 && (g->pad_mode == PNP_PAD_ZERO || (g->pad_t == 0 && g->pad_l == 0)) && dims_ok(g->R, g->S, g->stride, g->dil, g->C, g->K, g->OH, g->OW, (long long)g->N * g->OH * g->OW);
+    return x3d_switch.get() > 0 && g->dtype == PNP_DTYPE_F32 && (g->pad_mode == PNP_PAD_ZERO || (g->pad_t == 0 && g->pad_l == 0)) && dims_ok(g->R, g->S, g->stride, g->dil, g->C, g->K, g->OH, g->OW, (long long)g->N * g->OH * g->OW);
 }
 
 // one partial per consumer wave: 64 pixels (4 rows x 16) — M / 64 of them
@@ -918,25 +803,18 @@ size_t x3d_filter_bytes(int C, int K) { return (size_t)9 * C * K * 6; }
 
 int launch_x3_direct(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st) {
     PNP_REQUIRE(a.ep_scale == nullptr && a.y_h == nullptr && a.o_s == 0 && a.ups == 1, "launch_x3_direct: unsupported epilogue");
-    const size_t fbytes = x3d_filter_bytes(a.C, a.K);
-    if (!ws || ws_bytes < fbytes) {
-        pnp_set_error("launch_x3_direct: workspace too small (%zu < %zu)", ws_bytes, fbytes);
-        return PNP_EWORKSPACE;
-    }
-    unsigned short* w3 = (unsigned short*)ws;
     const int cls = prof_class(kind);
     const int KW = a.K == 32 ? 32 : 64;
-    {
-        const int total = 9 * a.C * a.K;
-        PnpProfScope ps(cls, st, 0.0, 4.0 * total + 6.0 * total, "x3d_filter_kernel<%s>", flip_transpose ? "true" : "false");
-        if (flip_transpose) hipLaunchKernelGGL((x3d_filter_kernel<true>), dim3((unsigned)pnp_cdiv(total, 256)), dim3(256), 0, st, a.w, w3, a.C, a.K, KW);
-        else hipLaunchKernelGGL((x3d_filter_kernel<false>), dim3((unsigned)pnp_cdiv(total, 256)), dim3(256), 0, st, a.w, w3, a.C, a.K, KW);
-        PNP_CHECK_LAUNCH("x3d_filter_kernel");
-    }
+    int rc;
+    unsigned short* w3 = filter_image("launch_x3_direct", "x3d_filter_kernel", cls, flip_transpose, x3d_filter_bytes(a.C, a.K), ws, ws_bytes, st, rc, [&](unsigned short* img, dim3 blocks) {
+        if (flip_transpose) hipLaunchKernelGGL((x3d_filter_kernel<true>), blocks, dim3(256), 0, st, a.w, img, a.C, a.K, KW);
+        else hipLaunchKernelGGL((x3d_filter_kernel<false>), blocks, dim3(256), 0, st, a.w, img, a.C, a.K, KW);
+    });
+    if (!w3) return rc;
     X3dArgs x{};
     x.x = a.x; x.w3 = w3; x.y = a.y;
     x.N = a.N; x.H = a.H; x.W = a.W; x.C = a.C; x.K = a.K; x.OH = a.OH; x.OW = a.OW; x.pad_t = a.pad_t; x.pad_l = a.pad_l; x.M = a.M;
-    x.do_drop = a.do_drop; x.drop_thresh = a.drop_thresh; x.drop_key = a.drop_key; x.drop_keep = a.drop_keep; x.sp = a.sp; x.drop_sid = a.drop_sid;
+    copy_dropout(x, a);
     x.res_add = a.res_add; x.stat_ws = a.stat_ws; x.stat_shift = a.stat_shift;
     const long long nitems = (long long)a.N * (a.OH / TH) * (a.OW / TW) * (a.K / KW);
     const dim3 grid((unsigned)(nitems > 256 ? 256 : nitems));
@@ -959,15 +837,7 @@ int launch_x3_direct(const ConvArgs& a, int kind, bool flip_transpose, void* ws,
 
 }  // namespace pnpconv
 
-extern "C" int32_t pnp_conv2d_x3_direct(int32_t mode) {
-    const int prev = x3d_mode();
-    if (mode >= 0) g_x3d_mode.store(mode > 2 ? 2 : mode, std::memory_order_relaxed);
-    return prev;
-}
+extern "C" int32_t pnp_conv2d_x3_direct(int32_t mode) { return x3d_switch.set(mode); }
 
 // the strided layers' share of that route (PNP_X3_STRIDED): 0 off, 1 on (where pnp_conv2d_x3_direct's mode allows)
-extern "C" int32_t pnp_conv2d_x3_strided(int32_t mode) {
-    const int prev = x3s_mode();
-    if (mode >= 0) g_x3s_mode.store(mode > 0 ? 1 : 0, std::memory_order_relaxed);
-    return prev;
-}
+extern "C" int32_t pnp_conv2d_x3_strided(int32_t mode) { return x3s_switch.set(mode); }

@@ -24,16 +24,11 @@
 // The filter images are written by x3n_filter_kernel into the caller's workspace (forward as is, data gradient flipped and transposed).
 // PNP_X3_NARROW / pnp_conv2d_x3_narrow(): 0 off, 1 where a launch fills the chip (>= 256 tiles) and the direction measured faster at
 // B = 16, 2 wherever the shapes allow; PNP_X3_DIRECT=0 turns the route off as well.
-#include <atomic>
-#include <cstdlib>
-#include "conv_common.h"
+#include "conv_x3_common.h"
 
 using namespace pnpconv;
 
 namespace {
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int XC = 40, XK = 5, XR = 5;             // the layer class: 5x5, 40 -> 5
 constexpr int NCU = 256;
@@ -65,15 +60,6 @@ constexpr int D_NPI = D_P / 2;                     // patch rows per loader thre
 #define PNP_X3N_ABLATE 0
 #endif
 constexpr int kX3nAblate = PNP_X3N_ABLATE;
-
-constexpr int kTermX[6] = {2, 1, 0, 1, 0, 0}, kTermW[6] = {0, 1, 2, 0, 1, 0};      // the kept plane products, smallest first
-
-__device__ __forceinline__ void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)v;
-    const float r1 = v - (float)h;
-    m = (__bf16)r1;
-    l = (__bf16)(r1 - (float)m);
-}
 
 struct X3nArgs {
     const float* x;               // forward: x [N][H][W][40]; data gradient: dy [N][H][W][5]
@@ -147,12 +133,7 @@ __global__ void __launch_bounds__(256, 2) conv_x3_direct_kernel_narrow(X3nArgs a
 #pragma unroll
             for (int i = 0; i < F_PH; ++i) {
                 bf16x4 hi, mi, lo;
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    __bf16 h, m, l;
-                    split3(st[i][c], h, m, l);
-                    hi[c] = h; mi[c] = m; lo[c] = l;
-                }
+                split3(st[i], hi, mi, lo);
                 unsigned char* d = d0 + i * F_PW * F_PXB;
                 *reinterpret_cast<bf16x4*>(d) = hi;
                 *reinterpret_cast<bf16x4*>(d + F_PLANE) = mi;
@@ -358,23 +339,10 @@ __global__ void __launch_bounds__(256) x3n_filter_kernel(const float* __restrict
         base = ((size_t)(j * 3) * XC + row) * 32 + kk;
         pstride = (size_t)XC * 32;
     }
-    __bf16 h, m, l;
-    split3(v, h, m, l);
-    w3[base] = __builtin_bit_cast(unsigned short, h);
-    w3[base + pstride] = __builtin_bit_cast(unsigned short, m);
-    w3[base + 2 * pstride] = __builtin_bit_cast(unsigned short, l);
+    split3_write(w3 + base, pstride, v);
 }
 
-std::atomic<int> g_x3n_mode{-1};
-
-int x3n_mode() {
-    int m = g_x3n_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = getenv("PNP_X3_NARROW") ? atoi(getenv("PNP_X3_NARROW")) : 1;
-        g_x3n_mode.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+ModeSwitch x3n_switch{"PNP_X3_NARROW", 1, 2, false};
 
 // mode 1 takes a direction only if it measured faster than the old kernel at B = 16 (profiles/x3_narrow_joint_ab.txt)
 constexpr bool kShips[2] = {true, true};
@@ -389,7 +357,7 @@ namespace pnpconv {
 
 // g = the FORWARD geometry; kind 0: forward, 1: data gradient.  Geometry only: every epilogue the old kernels of this layer have is here.
 bool x3n_chosen(const pnp_conv_geom* g, int kind) {
-    const int mode = x3n_mode();
+    const int mode = x3n_switch.get();
     if (x3d_route_mode() <= 0 || mode <= 0) return false;
     if (g->dtype != PNP_DTYPE_F32 || g->pad_mode != PNP_PAD_ZERO || g->R != XR || g->S != XR || g->stride != 1 || g->dil != 1 || g->C != XC || g->K != XK)
         return false;
@@ -429,7 +397,7 @@ int launch_x3_narrow(const ConvArgs& a, int kind, void* ws, size_t ws_bytes, hip
     x.tiles_y = kind ? pnp_cdiv(a.OH, D_T) : a.OH / F_TH;
     const long long nitems = (long long)a.N * x.tiles_x * x.tiles_y;
     x.nitems = (int)nitems;
-    x.do_drop = a.do_drop; x.drop_thresh = a.drop_thresh; x.drop_key = a.drop_key; x.drop_keep = a.drop_keep; x.sp = a.sp; x.drop_sid = a.drop_sid;
+    copy_dropout(x, a);
     const dim3 grid((unsigned)(nitems > 2 * NCU ? 2 * NCU : nitems));
     // flops = six plane products per useful fp32 multiply-add of the layer (§10.1): priced against the dense bf16 peak
     const double fl = 6.0 * 2.0 * (double)a.M * XR * XR * XC * XK;
@@ -443,8 +411,4 @@ int launch_x3_narrow(const ConvArgs& a, int kind, void* ws, size_t ws_bytes, hip
 
 }  // namespace pnpconv
 
-extern "C" int32_t pnp_conv2d_x3_narrow(int32_t mode) {
-    const int prev = x3n_mode();
-    if (mode >= 0) g_x3n_mode.store(mode > 2 ? 2 : mode, std::memory_order_relaxed);
-    return prev;
-}
+extern "C" int32_t pnp_conv2d_x3_narrow(int32_t mode) { return x3n_switch.set(mode); }

@@ -28,16 +28,12 @@
 // Entry: plan_wgrad (conv_igemm.hip) asks x3w_chosen() after the Winograd filter-gradient planner and before the fp32-pipe ring kernel;
 // x3w_workspace_bytes() is what wgrad_ws() reports for the layers the predicate takes.  PNP_X3_WGRAD / pnp_conv2d_x3_wgrad(): 0 off, 1 on,
 // under PNP_X3_DIRECT's mode (0 there: off; 1: layers with >= 256 tiles; 2: wherever the shapes allow).
-#include <atomic>
-#include <cstdlib>
-#include "conv_common.h"
+#include "conv_x3_common.h"
 
 using namespace pnpconv;
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
@@ -53,13 +49,6 @@ constexpr int NLD = 256;                           // loader lanes (4 waves)
 constexpr int ND4 = UH * TW * (KF / 4);            // float4 of a dy unit: 1 024
 constexpr int NDI = ND4 / NLD;                     // 4 per loader lane
 
-__device__ __forceinline__ void wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 struct X3wArgs {
     const float* x;               // [N][H][W][C]
     const float* dy;              // [N][OH][OW][64]
@@ -74,18 +63,14 @@ struct X3wArgs {
 #define PNP_X3W_ABLATE 0
 #endif
 
-__device__ __forceinline__ void split3(const f32x4 v, bf16x4& hi, bf16x4& mi, bf16x4& lo) {
+// the shared split, with the ablation hook.  (The three plane stores behind it stay spelled out in the loaders: through store3() the kernel
+// came out with another register allocation, 1.3 % slower at NH = 1 — profiles/x3_shared_pieces_ab.txt)
+__device__ __forceinline__ void split3a(const f32x4 v, bf16x4& hi, bf16x4& mi, bf16x4& lo) {
+    if (PNP_X3W_ABLATE & 1) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (PNP_X3W_ABLATE & 1) {
-            hi[c] = mi[c] = lo[c] = (__bf16)v[c];
-            continue;
-        }
-        const __bf16 h = (__bf16)v[c];
-        const float r1 = v[c] - (float)h;
-        const __bf16 m = (__bf16)r1;
-        const float r2 = r1 - (float)m;
-        hi[c] = h; mi[c] = m; lo[c] = (__bf16)r2;
+        for (int c = 0; c < 4; ++c) hi[c] = mi[c] = lo[c] = (__bf16)v[c];
+    } else {
+        split3(v, hi, mi, lo);
     }
 }
 
@@ -157,7 +142,7 @@ __global__ void __launch_bounds__(512, 1) conv_x3_wgrad_kernel(X3wArgs a) {
                 const int q = e / (8 * NH), j = e % (8 * NH);
                 const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
                 bf16x4 hi, mi, lo;
-                split3(((okm >> i) & 1u) ? sx[i] : zero, hi, mi, lo);
+                split3a(((okm >> i) & 1u) ? sx[i] : zero, hi, mi, lo);
                 unsigned char* p = xb + (j >> 3) * (3 * XPL) + q * ROWB + (j & 7) * 8;
                 *reinterpret_cast<bf16x4*>(p) = hi;
                 *reinterpret_cast<bf16x4*>(p + XPL) = mi;
@@ -168,7 +153,7 @@ __global__ void __launch_bounds__(512, 1) conv_x3_wgrad_kernel(X3wArgs a) {
                 const int e = pl + i * NLD;
                 const int q = e >> 4, j = e & 15;
                 bf16x4 hi, mi, lo;
-                split3(sd[i], hi, mi, lo);
+                split3a(sd[i], hi, mi, lo);
                 unsigned char* p = db + (j >> 3) * (3 * DPL) + q * ROWB + (j & 7) * 8;
                 *reinterpret_cast<bf16x4*>(p) = hi;
                 *reinterpret_cast<bf16x4*>(p + DPL) = mi;
@@ -213,7 +198,6 @@ __global__ void __launch_bounds__(512, 1) conv_x3_wgrad_kernel(X3wArgs a) {
     const int lbase = ((g16 >> 1) * 8 + e4) * ROWB + (g16 & 1) * 32 + q4 * 8;
     const int xoff = lbase + cm * (3 * XPL) + sl * (PW * ROWB);
     const int doff = lbase + XB + kn * (3 * DPL) + sl * (TW * ROWB);
-    constexpr int kTermX[6] = {2, 1, 0, 1, 0, 0}, kTermD[6] = {0, 1, 2, 0, 1, 0};      // the kept plane products, smallest first
     f32x16 acc[9];
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
@@ -255,7 +239,7 @@ __global__ void __launch_bounds__(512, 1) conv_x3_wgrad_kernel(X3wArgs a) {
                 if (r < 0 || r >= NS) continue;
 #pragma unroll
                 for (int trm = 0; trm < 6; ++trm)
-                    acc[tr * 3 + ts] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[step & 1][kTermX[trm]], df[r][kTermD[trm]], acc[tr * 3 + ts], 0, 0, 0);
+                    acc[tr * 3 + ts] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[step & 1][kTermX[trm]], df[r][kTermW[trm]], acc[tr * 3 + ts], 0, 0, 0);
             }
             // three reads behind each of the step's first MFMAs, the rest of the MFMAs behind them
             const int nrd = (step + 1 < NSTEP ? 6 : 0) + (ts == 0 && rho + 1 < NS ? 6 : 0);
@@ -298,16 +282,7 @@ __global__ void __launch_bounds__(256) x3w_reduce_kernel(const float* __restrict
     }
 }
 
-std::atomic<int> g_x3w_mode{-1};
-
-int x3w_mode() {
-    int m = g_x3w_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = getenv("PNP_X3_WGRAD") ? (atoi(getenv("PNP_X3_WGRAD")) > 0 ? 1 : 0) : 1;
-        g_x3w_mode.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+ModeSwitch x3w_switch{"PNP_X3_WGRAD", 1, 1, true};
 
 int x3w_grid(const pnp_conv_geom* g) {
     const long long ntiles = (long long)g->N * (g->OH / TH) * (g->OW / TW);
@@ -324,7 +299,7 @@ namespace pnpconv {
 // shapes allow (tests)
 bool x3w_chosen(const pnp_conv_geom* g) {
     const int mode = x3d_route_mode();
-    if (mode <= 0 || x3w_mode() <= 0 || g->dtype != PNP_DTYPE_F32 || g->pad_mode != PNP_PAD_ZERO) return false;
+    if (mode <= 0 || x3w_switch.get() <= 0 || g->dtype != PNP_DTYPE_F32 || g->pad_mode != PNP_PAD_ZERO) return false;
     if (!(g->R == 3 && g->S == 3 && g->stride == 1 && g->dil == 1 && (g->C == 32 || g->C == 64) && g->K == KF)) return false;
     if (g->OH <= 0 || g->OW <= 0 || (g->OH % TH) != 0 || (g->OW % TW) != 0) return false;
     const long long M = (long long)g->N * g->OH * g->OW;
@@ -368,8 +343,4 @@ int launch_x3_wgrad(const float* x, const float* dy, float* dw, const pnp_conv_g
 }  // namespace pnpconv
 
 // the filter gradients' share of the direct split-bf16 route (PNP_X3_WGRAD): 0 off, 1 on (where pnp_conv2d_x3_direct's mode allows)
-extern "C" int32_t pnp_conv2d_x3_wgrad(int32_t mode) {
-    const int prev = x3w_mode();
-    if (mode >= 0) g_x3w_mode.store(mode > 0 ? 1 : 0, std::memory_order_relaxed);
-    return prev;
-}
+extern "C" int32_t pnp_conv2d_x3_wgrad(int32_t mode) { return x3w_switch.set(mode); }
