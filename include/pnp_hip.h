@@ -422,6 +422,15 @@ int pnp_critic_input_ps_bwd(const float* dout, float* da, int32_t Ca, int32_t ti
  * critic-logit vectors  {ct_cls, mr_cls, ct_mask, mr_mask};  e.g. dis_loss: coef = {+miu, -miu, +lambda*miu, -lambda*miu}. */
 int pnp_wgan_loss(const float* ct_cls, const float* mr_cls, const float* ct_mask, const float* mr_mask, int32_t B,
                   float c_ct_cls, float c_mr_cls, float c_ct_mask, float c_mr_mask, float* out, void* stream);
+/* Entropy minimisation on unlabelled predictions (csrc/entropy.hip; not in the reference).  logits [P, ncls], fp32,
+ * 1 <= ncls <= 8:  out[0] = L = sum_i H_i / (P ln ncls),  H_i = -sum_k p_ik log p_ik of p_i = softmax(logits_i)  (0 for ncls == 1);
+ * dlogits (nullable: value only) = coef * dL/dlogits = -coef * p_ij (log p_ij + H_i) / (P ln ncls)  — fold 1/world_size into coef.
+ * out[0] is NOT scaled by coef.  log p is taken from the log-softmax, so rows with margins of hundreds give finite values.  One
+ * streaming pass plus a one-block sum of its per-block partials in a fixed order, in double: stream-ordered, capturable, bit-identical
+ * from run to run.  ws: pnp_softmax_entropy_workspace_bytes(P, ncls). */
+size_t pnp_softmax_entropy_workspace_bytes(int64_t P, int32_t ncls);
+int pnp_softmax_entropy(const float* logits, int64_t P, int32_t ncls, float coef, float* dlogits, float* out, void* workspace,
+                        size_t workspace_bytes, void* stream);
 /* p[0..n) = value  (constant gradient of a mean: coef / B) */
 int pnp_fill(float* p, size_t n, float value, void* stream);
 

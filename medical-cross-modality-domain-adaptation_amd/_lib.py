@@ -154,6 +154,8 @@ PROTOTYPES = {
                                         c_int32, c_void_p]),
     "pnp_axpby": (c_int, [_F, _F, c_size_t, c_float, c_float, c_void_p]),
     "pnp_add": (c_int, [_F, _F, _F, c_size_t, c_void_p]),
+    "pnp_softmax_entropy_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "pnp_softmax_entropy": (c_int, [_F, c_int64, c_int32, c_float, _F, _F, c_void_p, c_size_t, c_void_p]),
     "pnp_wgan_loss": (c_int, [_F, _F, _F, _F, c_int32, c_float, c_float, c_float, c_float, _F, c_void_p]),
     "pnp_fill": (c_int, [_F, c_size_t, c_float, c_void_p]),
     "pnp_label_decomp": (c_int, [_F, _F, c_int64, c_int32, c_void_p]),

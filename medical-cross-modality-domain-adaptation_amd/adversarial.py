@@ -20,7 +20,7 @@ import torch
 
 from . import functional as Fn
 from . import kernels as K
-from .functional import Conv2dDropFn, CriticInputFn, CriticInputPsFn, WganLossFn, fan_out, wgrad_overlap
+from .functional import Conv2dDropFn, CriticInputFn, CriticInputPsFn, EntropyLossFn, WganLossFn, fan_out, wgrad_overlap
 from .gradient_penalty import critic_gradient_penalty, critic_table
 from .layers import (DR_block, conv2d, conv_bn_relu2d, max_pool2d, residual_block, sharable_weight_variable, weight_variable)
 from .lib import _dice_eval, _label_decomp
@@ -61,6 +61,7 @@ class Full_DRN(object):
         # last fetched values
         self.dis_loss = self.ct_gen_loss = None
         self.ct_logits = self.mr_logits = None
+        self.ent_value = None
 
     # ---- helpers ----------------------------------------------------------------------------------------------------
     def _names_of(self, tensors):
@@ -79,6 +80,10 @@ class Full_DRN(object):
         self.gp_weight = float(ck.pop("gp_weight", 0.0) or 0.0)
         if not self.gp_weight >= 0.0:
             raise ValueError("cost_kwargs gp_weight must be >= 0, got %r" % (self.gp_weight,))
+        # opt-in entropy minimisation on the CT predictions in the gen step (not in the reference): 0 = the reference
+        self.ent_weight = float(ck.pop("ent_weight", 0.0) or 0.0)
+        if not self.ent_weight >= 0.0:
+            raise ValueError("cost_kwargs ent_weight must be >= 0, got %r" % (self.ent_weight,))
 
     def _fc(self, x, w):
         """tf.matmul(tf.reshape(x, [-1, D]), w) (adversarial.py:395-397, 438-440) as a 1x1 'convolution' on the MFMA kernel"""
@@ -249,7 +254,8 @@ class Full_DRN(object):
                                  self._lists["m_cls_weights"])
 
     # ---- the graph of adversarial.py:82-119, executed eagerly ---------------------------------------------------------------
-    def _graph(self, mr, ct, keep_prob, mr_front_bn, joint_bn, ct_front_bn, record=False, segmenter_no_grad=False, drop_seed=0, critics=True, critic_keep=None):
+    def _graph(self, mr, ct, keep_prob, mr_front_bn, joint_bn, ct_front_bn, record=False, segmenter_no_grad=False, drop_seed=0, critics=True, critic_keep=None,
+               entropy=False):
         """mr / ct: [B,256,256,3] (either may be None: pruned branch).  Returns dict of critic logits and segmenter logits."""
         st = self.store
         ckw = {} if critic_keep is None else {"keep_prob": critic_keep}     # None: the builders' own default (0.75, adversarial.py:320,402)
@@ -278,7 +284,10 @@ class Full_DRN(object):
                 for br in ("ct", "mr"):
                     if br in feats:
                         c9, b8, b7, lg = feats[br]
-                        lg_cls, lg_mask = fan_out(lg)          # the logits feed both critics
+                        lg_c = lg
+                        if entropy and br == "ct":      # a third consumer of the CT logits: the entropy term (its edge comes first)
+                            out["ct_entropy_in"], lg_c = fan_out(lg)
+                        lg_cls, lg_mask = fan_out(lg_c)          # the logits feed both critics
                         feats[br] = (c9, b8, b7, lg_mask)
                         out[br + "_cls"] = self.create_classifier(z[br + "_c4"], z[br + "_c6"], b7, c9, lg_cls, feature_base=self.feature_base,
                                                                   cls_trainable=self.cls_trainable, **ckw)
@@ -372,26 +381,42 @@ class Full_DRN(object):
         """generator step graph (adversarial.py:875-881): CT front in BN-training mode, gradients to `adapt_*` only."""
         self._activate("adapt")
         self.store.zero_grad()
-        o = self._graph(None, ct, keep_prob, mr_front_bn=False, joint_bn=False, ct_front_bn=True, drop_seed=drop_seed)
+        o = self._graph(None, ct, keep_prob, mr_front_bn=False, joint_bn=False, ct_front_bn=True, drop_seed=drop_seed,
+                        entropy=self.ent_weight > 0)
         lam, mu = self.lambda_mask_loss, self.miu_gen
         use_mask = lam != 0.0
         loss = WganLossFn.apply(o["ct_cls"], None, o["ct_mask"] if use_mask else None, None, (-mu, 0.0, -lam * mu, 0.0), 1.0 / self.world_size)
-        with wgrad_overlap():
-            loss.backward(self.store.unit_grad(1))
-        self.ct_gen_loss = loss.detach()
+        if self.ent_weight > 0:
+            # + ent_weight * normalised mean entropy of the CT predictions: a second root of the same backward; its gradient and the
+            # critics' meet in the logits' fan_out (pnp_add)
+            ent = EntropyLossFn.apply(o["ct_entropy_in"], self.ent_weight, 1.0 / self.world_size)
+            with wgrad_overlap():
+                torch.autograd.backward([loss, ent], [self.store.unit_grad(1), self.store.unit_grad(1)])
+            self.ent_value = ent.detach()
+            self.ct_gen_loss = K.axpby(self.ent_value, loss.detach(), self.ent_weight, 1.0)      # (in place: nothing else reads `loss`)
+        else:
+            with wgrad_overlap():
+                loss.backward(self.store.unit_grad(1))
+            self.ent_value = None
+            self.ct_gen_loss = loss.detach()
         self.ct_logits = o["ct_logits"]
         self.critic_scores = {k: o[k].detach() for k in ("ct_cls", "ct_mask") if o.get(k) is not None}
         return self.ct_gen_loss
 
-    def evaluate(self, ct, ct_y, mr, mr_y, keep_prob=1.0, detail=False, ct_labelled=True):
+    def evaluate(self, ct, ct_y, mr, mr_y, keep_prob=1.0, detail=False, ct_labelled=True, entropy=False):
         """monitoring fetches that are not TensorBoard summaries (adversarial.py:101-116, 948-991): CT / MR hard Dice of the current
         segmenter, with `detail` the CT confusion matrix.  Every segmenter BN in inference mode; the critics are not evaluated (nothing
         here consumes their scores), so the forward has no side effect on any variable.  ct_labelled=False (the CT batch comes from
-        unlabelled volumes, DESIGN.md §24: ct_y is class 0 everywhere): no CT Dice and no confusion matrix, the CT Dice returned is None."""
+        unlabelled volumes, DESIGN.md §24: ct_y is class 0 everywhere): no CT Dice and no confusion matrix, the CT Dice returned is None.
+        entropy=True: one more launch pair leaves the normalised mean entropy of the CT predictions in ct_entropy_eval [1]
+        and the logits it was taken from in ct_logits_eval — the label-free monitor; the return value does not change."""
         from . import lib
         with torch.no_grad():
             o = self._graph(mr, ct, keep_prob, mr_front_bn=False, joint_bn=False, ct_front_bn=False, critics=False)
             self.predicter, self.compact_pred = K.softmax_argmax(o["ct_logits"].contiguous())
+            if entropy:
+                self.ct_logits_eval = o["ct_logits"].contiguous()
+                self.ct_entropy_eval = K.softmax_entropy(self.ct_logits_eval)[0]
             self.mr_seg_valid, self.compact_mr_valid = K.softmax_argmax(o["mr_logits"].contiguous())
             if ct_labelled:
                 self.ct_dice_eval, self.ct_dice_eval_arr = _dice_eval(self.compact_pred, ct_y, self.n_class)
@@ -463,6 +488,10 @@ verbose = True
 
 def _host(t):
     return None if t is None else float(t)
+
+
+def _ent_weight(net):
+    return getattr(net, "ent_weight", 0.0)
 
 
 def _gp_weight(net):
@@ -744,7 +773,9 @@ class Trainer(object):
         ct_labelled=False (the CT source holds unlabelled volumes: AugmentedSliceSource.labelled): the CT Dice and the CT confusion report
         are skipped, the scalar log gets ct_dice = null; the MR side is unchanged"""
         from .lib import _indicator_eval
-        ct_d, mr_d = self.net.evaluate(ct_batch, ct_batch_y, mr_batch, mr_batch_y, detail=detail, **({} if ct_labelled else {"ct_labelled": False}))
+        monitor = bool(self.train_config.get("monitor_entropy")) or _ent_weight(self.net) > 0
+        ekw = dict({} if ct_labelled else {"ct_labelled": False}, **({"entropy": True} if monitor else {}))
+        ct_d, mr_d = self.net.evaluate(ct_batch, ct_batch_y, mr_batch, mr_batch_y, detail=detail, **ekw)
         if not ct_labelled:
             logging.info("step %d %s batch: ct_dice n/a (unlabelled CT volumes), mr_dice %.4f" % (step, "validation" if detail else "training", mr_d))
         self.loss_dict["val" if detail else "train"] = (step, ct_d, mr_d)
@@ -754,6 +785,9 @@ class Trainer(object):
             gp.update(("gp_norm_" + k, _host(v)) for k, v in self.net.gp_norms.items())
             logging.info("step %d gradient penalty %.6g, mean critic-gradient norms %s" % (
                 step, gp["gp"], ", ".join("%s %.4g" % (k[8:], v) for k, v in gp.items() if k != "gp")))
+        if monitor:      # the label-free proxy of target quality: labelled and unlabelled CT sources alike
+            gp["ct_entropy"] = _host(self.net.ct_entropy_eval)
+            logging.info("step %d %s batch: ct_entropy %.4f" % (step, "validation" if detail else "training", gp["ct_entropy"]))
         if getattr(self, "scalars", None) is not None:      # evaluate() has just synchronised: the last losses cost nothing to read here
             self.scalars.write("val_eval" if detail else "train_eval", step=step, ct_dice=ct_d, mr_dice=mr_d,
                                dis_loss=_host(getattr(self.net, "dis_loss", None)), gen_loss=_host(getattr(self.net, "ct_gen_loss", None)), **gp)

@@ -586,6 +586,23 @@ class WganLossFn(Function):
         return grads[0], grads[1], grads[2], grads[3], None, None
 
 
+class EntropyLossFn(Function):
+    """scalar = normalised mean entropy of softmax(logits) (kernels.softmax_entropy).  A ROOT of backward like WganLossFn:
+    the upstream gradient is taken to be `gscale` (1/world_size under data parallelism) and `coef * gscale * dL/dlogits` is written by
+    the forward's own pass over the logits; backward hands it on.  Run it together with the step's other root in ONE
+    torch.autograd.backward([...], [...]); where the logits feed other branches too, take them through fan_out so that pnp_add sums."""
+
+    @staticmethod
+    def forward(ctx, logits, coef, gscale):
+        value, dl = K.softmax_entropy(_contig(logits), coef * gscale, want_grad=True)
+        ctx.save_for_backward(dl)
+        return value
+
+    @staticmethod
+    def backward(ctx, dout):
+        return ctx.saved_tensors[0], None, None
+
+
 # ---- arithmetic type of the convolution operands (BASELINE configs[4]) ----------------------------------------------------------
 CONV_DTYPE = "f32"
 

@@ -1050,6 +1050,21 @@ def wgan_loss(ct_cls, mr_cls, ct_mask, mr_mask, coefs):
     return out
 
 
+def softmax_entropy(logits, coef=1.0, want_grad=False):
+    """normalised mean entropy of softmax(logits [..., ncls]) (csrc/entropy.hip, DESIGN.md §27) -> (value [1], not scaled by coef;
+    coef * d value / d logits, or None without want_grad).  One streaming pass, stream-ordered, bit-identical from run to run."""
+    lib = _lib.load()
+    pl = _p(logits)
+    ncls = logits.shape[-1]
+    P = logits.numel() // max(ncls, 1)
+    out = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    ws = workspace(lib.pnp_softmax_entropy_workspace_bytes(P, ncls), logits.device)      # per-block partials, read by the second launch
+    check(lib.pnp_softmax_entropy(pl, P, ncls, float(coef), _p(dl), _p(out), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+          "pnp_softmax_entropy")
+    return out, dl
+
+
 def filled(shape, value, device):
     t = torch.empty(shape, dtype=torch.float32, device=device)
     check(_lib.load().pnp_fill(_p(t), t.numel(), float(value), _stream()), "pnp_fill")

@@ -5,7 +5,9 @@
 Extra flags: --synthetic N, --batch-size, --iters, --epochs, --output, --baseline (source-segmenter .npz for the pre-train hand-off),
 --mr-nii-train / --mr-nii-val / --ct-nii-train / --ct-nii-val LIST (all four: train from NIfTI volumes kept on the device,
 volume_source.py; the two CT lists may name images alone — unlabelled target scans; --crop-body [N] / --crop-margin N crop
-every volume of both domains to its body / label box; --augment JSON / --no-augment; --axes 0,1,2: slices of every listed orientation, one value for MR and CT), --gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference).
+every volume of both domains to its body / label box; --augment JSON / --no-augment; --axes 0,1,2: slices of every listed orientation, one value for MR and CT), --gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference),
+--ent-weight W (opt-in entropy minimisation on the CT predictions in the gen step: gen loss + W * normalised mean entropy, DESIGN.md §27;
+default 0 = the reference), --monitor-entropy (log ct_entropy, the label-free monitor, with every Dice report; implied by --ent-weight > 0).
 """
 import argparse
 import datetime
@@ -72,6 +74,10 @@ def parse_args(phase, argv=None):
                     "(default); bf16 = BASELINE configs[4]: bf16 MFMA operands, fp32 accumulation / master weights / BN")
     ap.add_argument("--gp-weight", type=float, default=0.0, help="WGAN-GP gradient penalty weight of the critics (f = miu_dis * D; 10 = "
                     "the WGAN-GP paper's value); > 0 replaces the +-0.03 weight clip.  fp32, without --sync-stats; default 0")
+    ap.add_argument("--ent-weight", type=float, default=0.0, help="weight of the normalised mean entropy of the CT predictions in the "
+                    "generator loss (entropy minimisation on the unlabelled target, DESIGN.md §27); default 0 = the reference")
+    ap.add_argument("--monitor-entropy", action="store_true", help="log ct_entropy (normalised mean entropy of the CT batch, BN in "
+                    "inference mode) next to the Dice monitor and write it to the scalar log; implied by --ent-weight > 0")
     for flag in NII_FLAGS:
         ap.add_argument("--" + flag.replace("_", "-"), default=None, metavar="LIST", help="NIfTI list file (one `image.nii[.gz] "
                         "label.nii[.gz]` pair per line, volume_source.py); the four --*-nii-* flags go together")
@@ -106,6 +112,8 @@ def parse_args(phase, argv=None):
         ap.error("--foreground goes with the --*-nii-* lists")
     if not args.gp_weight >= 0.0:
         ap.error("--gp-weight must be >= 0, got %r" % args.gp_weight)
+    if not args.ent_weight >= 0.0:
+        ap.error("--ent-weight must be >= 0, got %r" % args.ent_weight)
     if args.gp_weight > 0 and args.dtype != "f32":
         ap.error("--gp-weight > 0 runs fp32 convolutions only: the gradient penalty is not implemented for --dtype %s" % args.dtype)
     if args.gp_weight > 0 and args.sync_stats:
@@ -115,10 +123,14 @@ def parse_args(phase, argv=None):
 
 
 def configure_args(args):
-    """configure(args.phase) plus the flags that change the cost: gp_weight enters cost_kwargs only when it is > 0"""
+    """configure(args.phase) plus the flags that change the cost: gp_weight and ent_weight enter cost_kwargs only when they are > 0"""
     ck, nc, tc = configure(args.phase)
     if args.gp_weight > 0:
         ck["gp_weight"] = float(args.gp_weight)
+    if args.ent_weight > 0:
+        ck["ent_weight"] = float(args.ent_weight)
+    if args.monitor_entropy:
+        tc["monitor_entropy"] = True
     return ck, nc, tc
 
 
