@@ -431,6 +431,25 @@ int pnp_wgan_loss(const float* ct_cls, const float* mr_cls, const float* ct_mask
 size_t pnp_softmax_entropy_workspace_bytes(int64_t P, int32_t ncls);
 int pnp_softmax_entropy(const float* logits, int64_t P, int32_t ncls, float coef, float* dlogits, float* out, void* workspace,
                         size_t workspace_bytes, void* stream);
+/* Boundary loss of Kervadec et al. (MIDL 2019) on the segmenter's logits (csrc/boundary.hip; not in the reference).
+ * pnp_signed_distance_2d: onehot [B, H, W, ncls] fp32 (a pixel is in class c iff its entry is > 0.5) -> phi [B, H, W, ncls].  For a class
+ * whose bit is set in class_mask, per slice: d = Euclidean distance in pixels to the nearest pixel of the slice whose membership in c
+ * differs; phi = d outside the class, -(d - 1) inside it (one_hot2dist of the paper's code), 0 on a slice the class is absent from or
+ * fills.  phi = 0 for a class whose bit is clear.  Exact: integer squared distances, one sqrtf.  1 <= H, W <= 1024, 1 <= ncls <= 8, B >= 1,
+ * no bit of class_mask at or above ncls; anything else is refused before any launch.  Two launches, no atomics, no host read:
+ * stream-ordered, capturable, bit-identical from run to run.  ws: pnp_signed_distance_2d_workspace_bytes(B, H, W, ncls, class_mask)
+ * (one int16 per pixel and selected class; may be NULL when that is 0). */
+size_t pnp_signed_distance_2d_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t ncls, uint32_t class_mask);
+int pnp_signed_distance_2d(const float* onehot, int32_t B, int32_t H, int32_t W, int32_t ncls, uint32_t class_mask, float* phi,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* pnp_boundary_loss: logits, phi [P, ncls], fp32, 1 <= ncls <= 8, 0 <= nsel <= ncls (the number of selected classes: it only enters the
+ * normaliser):  out[0] = L = sum_i s_i / (P nsel),  s_i = sum_k p_ik phi_ik of p_i = softmax(logits_i);  dlogits (nullable: value only,
+ * bit-identical) = coef * dL/dlogits = coef * p_ij (phi_ij - s_i) / (P nsel)  — fold 1/world_size into coef.  out[0] is NOT scaled by
+ * coef.  nsel == 0: value and gradient are 0.  One streaming pass plus a one-block sum of its per-block partials in a fixed order, in
+ * double.  ws: pnp_boundary_loss_workspace_bytes(P, ncls). */
+size_t pnp_boundary_loss_workspace_bytes(int64_t P, int32_t ncls);
+int pnp_boundary_loss(const float* logits, const float* phi, int64_t P, int32_t ncls, int32_t nsel, float coef, float* dlogits, float* out,
+                      void* workspace, size_t workspace_bytes, void* stream);
 /* p[0..n) = value  (constant gradient of a mean: coef / B) */
 int pnp_fill(float* p, size_t n, float value, void* stream);
 

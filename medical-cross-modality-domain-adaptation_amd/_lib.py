@@ -156,6 +156,10 @@ PROTOTYPES = {
     "pnp_add": (c_int, [_F, _F, _F, c_size_t, c_void_p]),
     "pnp_softmax_entropy_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "pnp_softmax_entropy": (c_int, [_F, c_int64, c_int32, c_float, _F, _F, c_void_p, c_size_t, c_void_p]),
+    "pnp_signed_distance_2d_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_uint32]),
+    "pnp_signed_distance_2d": (c_int, [_F, c_int32, c_int32, c_int32, c_int32, c_uint32, _F, c_void_p, c_size_t, c_void_p]),
+    "pnp_boundary_loss_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "pnp_boundary_loss": (c_int, [_F, _F, c_int64, c_int32, c_int32, c_float, _F, _F, c_void_p, c_size_t, c_void_p]),
     "pnp_wgan_loss": (c_int, [_F, _F, _F, _F, c_int32, c_float, c_float, c_float, c_float, _F, c_void_p]),
     "pnp_fill": (c_int, [_F, c_size_t, c_float, c_void_p]),
     "pnp_label_decomp": (c_int, [_F, _F, c_int64, c_int32, c_void_p]),

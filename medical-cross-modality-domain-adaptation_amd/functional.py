@@ -603,7 +603,27 @@ class EntropyLossFn(Function):
         return ctx.saved_tensors[0], None, None
 
 
-# ---- arithmetic type of the convolution operands (BASELINE configs[4]) ----------------------------------------------------------
+class BoundaryLossFn(Function):
+    """scalar = boundary loss of softmax(logits) against the signed distance maps of the one-hot labels y over `classes` (None: every class
+    but the background) — kernels.signed_distance_2d + kernels.boundary_loss; DESIGN.md §28.  A ROOT of backward exactly like
+    EntropyLossFn: the forward computes the maps, the value and `coef * gscale * dL/dlogits`, backward hands the latter on.  Run it with
+    the step's other root in ONE torch.autograd.backward([...], [...]), the logits going through fan_out so that pnp_add sums."""
+
+    @staticmethod
+    def forward(ctx, logits, y, classes, coef, gscale):
+        y = _contig(y)
+        nsel = bin(K.class_mask(classes, y.shape[-1])).count("1")
+        phi = K.signed_distance_2d(y, classes)
+        value, dl = K.boundary_loss(_contig(logits), phi, nsel, coef * gscale, want_grad=True)
+        ctx.save_for_backward(dl)
+        return value
+
+    @staticmethod
+    def backward(ctx, dout):
+        return ctx.saved_tensors[0], None, None, None, None
+
+
+# ---- arithmetic type of the convolution operands (BASELINE configs[4])----------------------------------------------------------
 CONV_DTYPE = "f32"
 
 

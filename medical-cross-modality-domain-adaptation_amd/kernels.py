@@ -1065,6 +1065,54 @@ def softmax_entropy(logits, coef=1.0, want_grad=False):
     return out, dl
 
 
+def class_mask(classes, ncls):
+    """bit mask of an iterable of class indices; None = every class but the background (1 ... ncls-1).  ValueError out of range."""
+    if classes is None:
+        classes = range(1, ncls)
+    mask = 0
+    for c in classes:
+        if int(c) != c or not 0 <= int(c) < ncls:
+            raise ValueError("class index %r is not one of 0 ... %d" % (c, ncls - 1))
+        mask |= 1 << int(c)
+    return mask
+
+
+def signed_distance_2d(y, classes=None):
+    """signed distance maps of one-hot labels y [B, H, W, ncls] (csrc/boundary.hip) -> phi [B, H, W, ncls]: per slice and
+    selected class the Euclidean distance in pixels to the nearest pixel of the other membership, d outside the class and -(d - 1) inside
+    it; 0 for a class that is absent from or fills the slice and for a class that is not selected.  classes: iterable of class indices,
+    default every class but the background.  Exact, stream-ordered, bit-identical from run to run."""
+    lib = _lib.load()
+    py = _p(y)
+    if y.dim() != 4:
+        raise _lib.PnpError("signed_distance_2d: one-hot labels [B, H, W, ncls] expected, got shape %s" % (tuple(y.shape),))
+    B, H, W, ncls = y.shape
+    mask = class_mask(classes, ncls) if ncls <= 32 else 0          # (more than 8 classes: refused by the library, with its message)
+    phi = torch.empty_like(y)
+    ws = workspace(lib.pnp_signed_distance_2d_workspace_bytes(B, H, W, ncls, mask), y.device)      # row distances, read by the second launch
+    check(lib.pnp_signed_distance_2d(py, B, H, W, ncls, mask, _p(phi), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+          "pnp_signed_distance_2d")
+    return phi
+
+
+def boundary_loss(logits, phi, nsel, coef=1.0, want_grad=False):
+    """boundary loss (csrc/boundary.hip): mean over pixels and the nsel selected classes of softmax(logits) * phi ->
+    (value [1], not scaled by coef; coef * d value / d logits, or None without want_grad).  One streaming pass, stream-ordered,
+    bit-identical from run to run."""
+    lib = _lib.load()
+    pl, pq = _p(logits), _p(phi)
+    if phi.shape != logits.shape:
+        raise _lib.PnpError("boundary_loss: phi %s does not have the shape of the logits %s" % (tuple(phi.shape), tuple(logits.shape)))
+    ncls = logits.shape[-1]
+    P = logits.numel() // max(ncls, 1)
+    out = torch.empty(1, dtype=torch.float32, device=logits.device)
+    dl = torch.empty_like(logits) if want_grad else None
+    ws = workspace(lib.pnp_boundary_loss_workspace_bytes(P, ncls), logits.device)      # per-block partials, read by the second launch
+    check(lib.pnp_boundary_loss(pl, pq, P, ncls, int(nsel), float(coef), _p(dl), _p(out), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                _stream()), "pnp_boundary_loss")
+    return out, dl
+
+
 def filled(shape, value, device):
     t = torch.empty(shape, dtype=torch.float32, device=device)
     check(_lib.load().pnp_fill(_p(t), t.numel(), float(value), _stream()), "pnp_fill")

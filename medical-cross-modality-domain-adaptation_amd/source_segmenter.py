@@ -17,7 +17,7 @@ import torch
 
 from . import kernels as K
 from . import lib
-from .functional import SegLossFn, sync_now, wgrad_overlap
+from .functional import BoundaryLossFn, SegLossFn, fan_out, sync_now, wgrad_overlap
 from .layers import (DR_block, conv2d, conv_bn_relu2d, max_pool2d, pixel_wise_softmax_2, residual_block, weight_variable)
 from .lib import _dice_eval, _indicator_eval, _label_decomp
 from .ops import PS_conv2d
@@ -74,6 +74,7 @@ class Full_DRN(object):
         # outputs of the last forward (the tensors a TF user would fetch with sess.run)
         self.logits = self.predicter = self.compact_pred = self.compact_y = None
         self.cost = self.regularizer_loss = self.weighted_loss = self.dice_loss = None
+        self.bnd_value = None
         self.dice_eval = self.dice_eval_arr = None
         self.confusion_matrix = None
 
@@ -91,6 +92,18 @@ class Full_DRN(object):
         self.miu_dice = cost_kwargs.pop("miu_dice", None)
         self.miu_cross = cost_kwargs.pop("miu_cross", None)
         self.reg_coeff = cost_kwargs.pop("regularizer", 1e-4)
+        # opt-in boundary (distance-map) loss on the logits (not in the reference): 0 = the reference
+        self.bnd_weight = float(cost_kwargs.pop("bnd_weight", 0.0) or 0.0)
+        if not self.bnd_weight >= 0.0:
+            raise ValueError("cost_kwargs bnd_weight must be >= 0, got %r" % (self.bnd_weight,))
+        bc = cost_kwargs.pop("bnd_classes", None)
+        if bc is not None:
+            bc = tuple(bc)
+            try:
+                K.class_mask(bc, self.n_class)
+            except (TypeError, ValueError):
+                raise ValueError("cost_kwargs bnd_classes must be class indices in 0 ... %d, got %r" % (self.n_class - 1, bc))
+        self.bnd_classes = bc
 
     def _w(self, name):
         return self.store.vars[name].tensor
@@ -238,6 +251,9 @@ class Full_DRN(object):
             logits = self.forward(x, keep_prob, main_bn, adapt_bn)
             lv = self._get_cost(logits, y)
             self.cost, self.weighted_loss, self.dice_loss = lv[0], lv[1], lv[2]
+            if self.bnd_weight > 0:      # + bnd_weight * the boundary term: the value-only call
+                self.bnd_value = self._boundary_value(logits, y)
+                K.axpby(self.bnd_value, self.cost, self.bnd_weight, 1.0)
             self.predicter, self.compact_pred = K.softmax_argmax(logits.contiguous(), want_prob=True)
             self.compact_y, cm = lib.compact_and_confusion(y, self.compact_pred if want_confusion else None)
             self.dice_eval, self.dice_eval_arr = _dice_eval(self.compact_pred, y, self.n_class)
@@ -252,10 +268,27 @@ class Full_DRN(object):
             self._l2_table = self.store.chunk_table(lambda v: self.reg_coeff * v.l2_mult, np.float32)
         return K.l2_loss(self.store.arena, self._l2_table)
 
+    def _boundary_value(self, logits, y):
+        """the un-weighted boundary term [1] of these logits and labels, without a gradient"""
+        nsel = bin(K.class_mask(self.bnd_classes, self.n_class)).count("1")
+        return K.boundary_loss(logits.contiguous(), K.signed_distance_2d(y.contiguous(), self.bnd_classes), nsel)[0]
+
     def loss_and_grads(self, x, y, keep_prob, main_bn=True, adapt_bn=True, drop_seed=0):
         """fwd + bwd of cost (the L2 term's gradient is applied inside the optimiser kernel)."""
         self.store.zero_grad()
         logits = self.forward(x, keep_prob, main_bn, adapt_bn, drop_seed)
+        if self.bnd_weight > 0:
+            # + bnd_weight * boundary loss of the logits against the labels' distance maps: a second root of the same backward; its
+            # gradient and the region terms' meet in the logits' fan_out (pnp_add)
+            lg_seg, lg_bnd = fan_out(logits)
+            lv = self._get_cost(lg_seg, y)
+            bnd = BoundaryLossFn.apply(lg_bnd, y, self.bnd_classes, self.bnd_weight, 1.0 / self.world_size)
+            with wgrad_overlap():
+                torch.autograd.backward([lv, bnd], [self.store.unit_grad(3), self.store.unit_grad(1)])
+            self.bnd_value = bnd.detach()
+            self.weighted_loss, self.dice_loss = lv[1].detach(), lv[2].detach()
+            self.cost = K.axpby(self.bnd_value, lv[0].detach(), self.bnd_weight, 1.0)      # (in place: nothing else reads lv[0])
+            return self.cost
         lv = self._get_cost(logits, y)
         with wgrad_overlap():
             lv.backward(self.store.unit_grad(3))      # SegLossFn: element 0 is the root (cost); the upstream gradient is taken to be 1
@@ -350,8 +383,14 @@ class Trainer(object):
 
     def __init__(self, net, train_list, val_list, num_cls, batch_size, test_nii_list=None, test_label_list=None,
                  optimizer="momentum", opt_kwargs={}, num_epochs=100, checkpoint_space=500, lr_update_flag=False,
-                 reducer=None, shard=None):
+                 reducer=None, shard=None, bnd_ramp=None):
         self.net = net
+        # boundary term: bnd_ramp = N raises the weight over the first N epochs, epoch e trains with
+        # bnd_weight * min(1, (e + 1) / N) (the paper raises the weight over training); None: the configured weight throughout
+        self.bnd_ramp = None if not bnd_ramp else int(bnd_ramp)
+        if self.bnd_ramp is not None and self.bnd_ramp < 1:
+            raise ValueError("bnd_ramp must be a positive number of epochs, got %r" % (bnd_ramp,))
+        self.bnd_weight = getattr(net, "bnd_weight", 0.0)      # the configured (final) weight; net.bnd_weight is the current epoch's
         self.shard = shard              # (rank, world_size) under data parallelism: this rank's share of the file lists
         self.rank = shard[0] if shard else 0
         self.seed_offset = rank_seed(self.rank)
@@ -450,6 +489,8 @@ class Trainer(object):
         captured step's device block); the two warm-up steps are real updates.  Not under data parallelism."""
         if self.reducer is not None:
             raise RuntimeError("capture_step: not under data parallelism (the bucketed all-reduce runs on a side stream)")
+        if self.bnd_ramp is not None and self.bnd_weight > 0:
+            raise RuntimeError("capture_step: not with bnd_ramp (a recorded step holds the boundary term's coefficient by value)")
         if self.opt is None:
             self.opt = self._get_optimizer(100)
         if not isinstance(self.opt, AdamOptimizer):
@@ -512,6 +553,9 @@ class Trainer(object):
         pending = None
         try:
             for epoch in range(epochs):
+                if self.bnd_ramp is not None and self.bnd_weight > 0:
+                    self.net.bnd_weight = self.bnd_epoch_weight(epoch)
+                    logging.info("epoch %d: boundary loss weight %.6g" % (epoch, self.net.bnd_weight))
                 for step in range((epoch * training_iters), ((epoch + 1) * training_iters)):
                     start = time.time()
                     batch_x, batch_y, fid = feed_all.next()
@@ -544,12 +588,24 @@ class Trainer(object):
         barrier()
         return save_path
 
+    def bnd_epoch_weight(self, epoch):
+        """weight of the boundary term in epoch `epoch` (from 0): the configured one, raised linearly over the first bnd_ramp epochs"""
+        if self.bnd_ramp is None:
+            return self.bnd_weight
+        return self.bnd_weight * min(1.0, (epoch + 1) / float(self.bnd_ramp))
+
+    def _bnd_scalars(self):
+        """{"bnd": the un-weighted boundary term of the last evaluate()} while the term is on, {} otherwise"""
+        if not getattr(self.net, "bnd_weight", 0.0) > 0:
+            return {}
+        return {"bnd": float(self.net.bnd_value)}
+
     def output_minibatch_stats(self, step, batch_x, batch_y):
         """source_segmenter.py:525-539: logging-only forward (BN train mode, keep_prob 1: it DOES move the BN moving stats)"""
         self.net.evaluate(batch_x, batch_y, keep_prob=1.0, main_bn=True, adapt_bn=True)
         self.loss_dict["train"] = (step, float(self.net.cost), float(self.net.dice_eval))
         if getattr(self, "scalars", None) is not None:
-            self.scalars.write("train_eval", step=step, cost=self.loss_dict["train"][1], dice=self.loss_dict["train"][2])
+            self.scalars.write("train_eval", step=step, cost=self.loss_dict["train"][1], dice=self.loss_dict["train"][2], **self._bnd_scalars())
 
     def val_stats(self, step, batch_x, batch_y, detail=False):
         """source_segmenter.py:541-570"""
@@ -558,7 +614,7 @@ class Trainer(object):
             _indicator_eval(self.net.confusion_matrix, verbose=verbose)
         self.loss_dict["val"] = (step, float(self.net.cost), float(self.net.dice_eval))
         if getattr(self, "scalars", None) is not None:
-            self.scalars.write("val_eval", step=step, cost=self.loss_dict["val"][1], dice=self.loss_dict["val"][2])
+            self.scalars.write("val_eval", step=step, cost=self.loss_dict["val"][1], dice=self.loss_dict["val"][2], **self._bnd_scalars())
 
     # -- volume inference -------------------------------------------------------------------------------
     def _predict_batch(self, vol, slice_y):

@@ -4,7 +4,9 @@ them, --batch-size, --iters, --epochs, --output; --nii-train LIST --nii-val LIST
 (volume_source.py: one `image.nii[.gz] label.nii[.gz]` pair per line; --augment JSON / --no-augment; --sample-mm MM|PI,PJ,FRAME samples them on
 a millimetre grid; --prefilter auto|off|SX,SY,SZ low-passes them first; --axes 0,1,2 trains on slices of
 every listed orientation; --crop-body [N] crops every volume to its body, found without a label, --crop-margin N to its
-label bounding box).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
+label bounding box); --bnd-weight W adds W times the boundary (distance-map) loss of Kervadec et al. to the cost
+(default 0 = the reference), --bnd-ramp EPOCHS raises that weight linearly over the first EPOCHS epochs, --bnd-classes 1,3
+restricts it to the listed classes (default: every class but the background).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
 one process per GPU over RCCL, --batch-size slices PER RANK, file lists sharded by rank, rank 0 writes the checkpoint.
   python -m "medical-cross-modality-domain-adaptation_amd.train_segmenter" --synthetic 8 --batch-size 4 --iters 2 --epochs 1
 """
@@ -19,7 +21,11 @@ from .parallel import GradReducer, barrier, enable_sync_stats, init_distributed
 logging.basicConfig(level=logging.INFO)
 
 
-def main(argv=None):
+NUM_CLS = 5
+
+
+def parse_args(argv=None):
+    """the command line -> (parser, args); the flags of the boundary term are checked here, the volume flags by main()"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--batch-size", type=int, default=10)
@@ -44,7 +50,43 @@ def main(argv=None):
     add_sampling_flags(ap)
     from . import body
     body.add_crop_flags(ap)
+    ap.add_argument("--bnd-weight", type=float, default=0.0, help="weight of the boundary (distance-map) loss of the logits against the "
+                    "labels' signed distance maps, computed on the device every step (DESIGN.md §28); default 0 = the reference")
+    ap.add_argument("--bnd-ramp", type=int, default=None, metavar="EPOCHS", help="raise --bnd-weight linearly over the first EPOCHS epochs "
+                    "(epoch e trains with W * min(1, (e + 1) / EPOCHS)); default: W throughout")
+    ap.add_argument("--bnd-classes", default=None, metavar="C,C", help="classes of the boundary loss, e.g. 1,3; default: every class but "
+                    "the background")
     args = ap.parse_args(argv)
+    if not args.bnd_weight >= 0.0:
+        ap.error("--bnd-weight must be >= 0, got %r" % args.bnd_weight)
+    if args.bnd_ramp is not None and args.bnd_ramp < 1:
+        ap.error("--bnd-ramp must be a positive number of epochs, got %r" % args.bnd_ramp)
+    if (args.bnd_ramp is not None or args.bnd_classes is not None) and not args.bnd_weight > 0:
+        ap.error("--bnd-ramp and --bnd-classes go with --bnd-weight > 0")
+    if args.bnd_classes is not None:
+        try:
+            args.bnd_classes = tuple(int(c) for c in args.bnd_classes.split(","))
+        except ValueError:
+            ap.error("--bnd-classes takes class indices separated by commas, got %r" % args.bnd_classes)
+        if not args.bnd_classes or not all(0 <= c < NUM_CLS for c in args.bnd_classes):
+            ap.error("--bnd-classes must name classes in 0 ... %d, got %r" % (NUM_CLS - 1, args.bnd_classes))
+    return ap, args
+
+
+def cost_kwargs_from_args(args):
+    """the reference's cost dict (train_segmenter.py:60-66); the keys of the boundary term enter it only when --bnd-weight is > 0"""
+    ck = {"cross_flag": True, "miu_cross": 1.0, "dice_flag": True, "miu_dice": 1.0, "regularizer": 1e-4}
+    if args.bnd_weight > 0:
+        ck["bnd_weight"] = float(args.bnd_weight)
+        if args.bnd_classes is not None:
+            ck["bnd_classes"] = tuple(args.bnd_classes)
+    return ck
+
+
+def main(argv=None):
+    from .volume_source import augment_from_args, axes_from_args, prefilter_from_args, sample_mm_from_args, sampling_from_args
+    from . import body
+    ap, args = parse_args(argv)
     crop = body.crop_from_args(ap, args, have_lists=bool(args.nii_train))          # DESIGN.md §24
     sample_mm = sample_mm_from_args(ap, args)
     prefilter = prefilter_from_args(ap, args)
@@ -67,12 +109,12 @@ def main(argv=None):
 
     train_fid, val_fid = "./lists/mr_train_list", "./lists/mr_val_list"
     output_path = args.output
-    num_cls = 5
+    num_cls = NUM_CLS
     batch_size = args.batch_size
     training_iters, epochs = args.iters, args.epochs
     checkpoint_space = 1500
     optimizer = 'adam'
-    cost_kwargs = {"cross_flag": True, "miu_cross": 1.0, "dice_flag": True, "miu_dice": 1.0, "regularizer": 1e-4}
+    cost_kwargs = cost_kwargs_from_args(args)
     opt_kwargs = {"learning_rate": 1e-3}
     rank, local, world = init_distributed()
     if args.sync_stats:
@@ -106,7 +148,8 @@ def main(argv=None):
     print("Network has been built!")
     trainer = drn.Trainer(net, train_list=train_list, val_list=val_list, num_cls=num_cls, batch_size=batch_size, opt_kwargs=opt_kwargs,
                           checkpoint_space=checkpoint_space, optimizer=optimizer, lr_update_flag=False,
-                          reducer=GradReducer(net.store) if world > 1 else None, shard=(rank, world) if world > 1 else None)
+                          reducer=GradReducer(net.store) if world > 1 else None, shard=(rank, world) if world > 1 else None,
+                          **({"bnd_ramp": args.bnd_ramp} if args.bnd_weight > 0 and args.bnd_ramp else {}))
     print("Now start training...")
     trainer.train(output_path=output_path, training_iters=training_iters, epochs=epochs, restore=args.restore, restored_path=output_path)
     return trainer
