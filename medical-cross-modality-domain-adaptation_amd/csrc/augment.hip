@@ -18,6 +18,7 @@
 #include <math.h>
 #include <type_traits>
 
+#include "block_sum.h"
 #include "pnp_common.h"
 
 namespace {
@@ -80,33 +81,6 @@ __global__ void __launch_bounds__(64) pre_pick_kernel(const unsigned int* __rest
     st->k = k;
 }
 
-// fixed-order sum of a partial list by one block: thread t adds entries t, t + 256, ... then a tree over the 256 threads
-__device__ __forceinline__ double block_sum_of_list(const double* __restrict__ p, int np, double* sh) {
-    double a = 0.0;
-    for (int i = threadIdx.x; i < np; i += kThreads) a += p[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int h = kThreads / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ double block_tree(double a, double* sh) {
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int h = kThreads / 2; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) sh[threadIdx.x] += sh[threadIdx.x + h];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
 __global__ void __launch_bounds__(kThreads) pre_sum_kernel(const float* __restrict__ v, long long n, const SelState* __restrict__ st,
                                                            double* __restrict__ psum, float* __restrict__ pmin) {
     __shared__ double sh[kThreads];
@@ -121,7 +95,7 @@ __global__ void __launch_bounds__(kThreads) pre_sum_kernel(const float* __restri
         m = fminf(m, x);
     }
     shm[threadIdx.x] = m;
-    const double s = block_tree(a, sh);
+    const double s = block_tree<kThreads>(a, sh);
     for (int h = kThreads / 2; h > 0; h >>= 1) {
         if ((int)threadIdx.x < h) shm[threadIdx.x] = fminf(shm[threadIdx.x], shm[threadIdx.x + h]);
         __syncthreads();
@@ -136,14 +110,14 @@ __global__ void __launch_bounds__(kThreads) pre_dev_kernel(const float* __restri
                                                            const double* __restrict__ psum, double* __restrict__ pdev) {
     __shared__ double sh[kThreads];
     const float clip = float_of(st->prefix);
-    const double mean = block_sum_of_list(psum, gridDim.x, sh) / (double)n;
+    const double mean = block_sum_of_list<kThreads>(psum, gridDim.x, sh) / (double)n;
     const long long gs = (long long)gridDim.x * kThreads;
     double a = 0.0;
     for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += gs) {
         const double d = (double)fminf(v[i], clip) - mean;
         a = fma(d, d, a);
     }
-    const double s = block_tree(a, sh);
+    const double s = block_tree<kThreads>(a, sh);
     if (threadIdx.x == 0) pdev[blockIdx.x] = s;
 }
 
@@ -157,8 +131,8 @@ __global__ void __launch_bounds__(kThreads) pre_normalize_kernel(const float* v,
     __shared__ double sh[kThreads];
     __shared__ float shm[kThreads];
     const float clip = float_of(st->prefix);
-    const double mean = block_sum_of_list(psum, gridDim.x, sh) / (double)n;
-    const double std_ = sqrt(block_sum_of_list(pdev, gridDim.x, sh) / (double)n);
+    const double mean = block_sum_of_list<kThreads>(psum, gridDim.x, sh) / (double)n;
+    const double std_ = sqrt(block_sum_of_list<kThreads>(pdev, gridDim.x, sh) / (double)n);
     const double inv_std = std_ > 0.0 ? 1.0 / std_ : 0.0;          // std == 0: every output is 0
     if (blockIdx.x == 0) {
         float m = INFINITY;

@@ -14,7 +14,7 @@
 // read per row k serves the eight), over the rows that hold a pixel of the kind it looks for; one sqrtf at the end.  A block writes every
 // class of its pixels, so the partial lines of the per-class stores meet in one L2.
 // No atomics, no host read, fixed order: stream-ordered, capturable, bit-identical from run to run.
-#include "pnp_common.h"
+#include "pixel_loss.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,7 +23,6 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int MAXC = 8;
 constexpr int MAX_EXTENT = 1024;
 constexpr int MAX_WORDS = MAX_EXTENT / 64;
 constexpr int ROW_NONE = 0x7FFF;          // row distance where the row holds no pixel of the opposite membership
@@ -239,124 +238,29 @@ __global__ void __launch_bounds__(NT) sdist_col_kernel(const int16_t* __restrict
     }
 }
 
-// ---- loss pass (built like softmax_entropy_kernel of entropy.hip) --------------------------------------------------------------------
-constexpr int PIX_PER_THREAD = 8;
-constexpr int MAX_BLOCKS = 2048;
+// ---- loss pass: a term of the per-pixel skeleton (pixel_loss.h) ------------------------------------------------------------------------
+// one pixel: z[0..C), q = x[0][0..C) (phi) -> s = sum_k p_k q_k (returned); g[0..C) = gk * p (q - s) when GRAD
+struct BoundaryTerm {
+    static constexpr int NEXTRA = 1;
 
-inline int loss_blocks(long long P) {
-    long long b = (P + (long long)NT * PIX_PER_THREAD - 1) / ((long long)NT * PIX_PER_THREAD);
-    if (b > MAX_BLOCKS) b = MAX_BLOCKS;
-    if (b < 1) b = 1;
-    return (int)b;
-}
-
-// one pixel: z[0..C), q[0..C) (phi) -> s = sum_k p_k q_k (returned); g[0..C) = gk * p (q - s) when GRAD (g may alias z)
-template <int C, bool GRAD>
-__device__ __forceinline__ float boundary_pixel(const float* z, const float* q, int ncls, float gk, float* g) {
-    float m = z[0];
+    template <int C, bool GRAD>
+    static __device__ __forceinline__ float pixel(const float* z, const float* const* x, int ncls, float gk, float* g) {
+        const float* q = x[0];
+        float e[C], m;
+        const float inv = 1.0f / pixel_loss::softmax_exp<C>(z, ncls, e, m);
+        float s = 0.f;
 #pragma unroll
-    for (int j = 1; j < C; ++j)
-        if (j < ncls) m = fmaxf(m, z[j]);
-    float e[C], sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-        e[j] = j < ncls ? expf(z[j] - m) : 0.f;
-        sum += e[j];
-    }
-    const float inv = 1.0f / sum;
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-        e[j] *= inv;
-        s = fmaf(e[j], j < ncls ? q[j] : 0.f, s);
-    }
-    if (GRAD) {
-#pragma unroll
-        for (int j = 0; j < C; ++j) g[j] = gk * e[j] * ((j < ncls ? q[j] : 0.f) - s);
-    }
-    return s;
-}
-
-// VEC5: ncls == 5 and 16-byte aligned bases — four pixels are five float4 loads of each input (and five stores) per thread; the P % 4
-// pixels behind the last whole group take the scalar loop, which is the whole kernel otherwise (any 1 <= ncls <= MAXC, any alignment).
-template <bool VEC5, bool GRAD>
-__global__ void __launch_bounds__(NT) boundary_loss_kernel(const float* __restrict__ logits, const float* __restrict__ phi,
-                                                           float* __restrict__ dlogits, float* __restrict__ part, long long P, int ncls,
-                                                           float gk) {
-    __shared__ float lds[4];
-    float acc = 0.f;
-    const long long gs = (long long)gridDim.x * NT;
-    const long long t0 = (long long)blockIdx.x * NT + threadIdx.x;
-    long long first = 0;
-    if (VEC5) {
-        const long long ngrp = P >> 2;
-        const float4* __restrict__ in = reinterpret_cast<const float4*>(logits);
-        const float4* __restrict__ inq = reinterpret_cast<const float4*>(phi);
-        float4* __restrict__ out = reinterpret_cast<float4*>(dlogits);
-        for (long long g = t0; g < ngrp; g += gs) {
-            float f[20], q[20];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const float4 v = in[g * 5 + k];
-                f[4 * k] = v.x, f[4 * k + 1] = v.y, f[4 * k + 2] = v.z, f[4 * k + 3] = v.w;
-                const float4 u = inq[g * 5 + k];
-                q[4 * k] = u.x, q[4 * k + 1] = u.y, q[4 * k + 2] = u.z, q[4 * k + 3] = u.w;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc += boundary_pixel<5, GRAD>(f + 5 * r, q + 5 * r, 5, gk, f + 5 * r);
-            if (GRAD) {
-#pragma unroll
-                for (int k = 0; k < 5; ++k) out[g * 5 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
-            }
+        for (int j = 0; j < C; ++j) {
+            e[j] *= inv;
+            s = fmaf(e[j], j < ncls ? q[j] : 0.f, s);
         }
-        first = ngrp << 2;
-    }
-    for (long long i = first + t0; i < P; i += gs) {
-        float z[MAXC], q[MAXC];
-#pragma unroll
-        for (int j = 0; j < MAXC; ++j) {
-            z[j] = j < ncls ? logits[i * ncls + j] : 0.f;
-            q[j] = j < ncls ? phi[i * ncls + j] : 0.f;
-        }
-        acc += boundary_pixel<MAXC, GRAD>(z, q, ncls, gk, z);
         if (GRAD) {
 #pragma unroll
-            for (int j = 0; j < MAXC; ++j)
-                if (j < ncls) dlogits[i * ncls + j] = z[j];
+            for (int j = 0; j < C; ++j) g[j] = gk * e[j] * ((j < ncls ? q[j] : 0.f) - s);
         }
+        return s;
     }
-    // block sum in a fixed order: shuffle tree per wave, then the four waves
-    float x = acc;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-}
-
-// one block: thread t adds partials t, t + NT, ... in double, then a fixed tree over the block -> out[0] = sum * scale
-__global__ void __launch_bounds__(NT) boundary_loss_final_kernel(const float* __restrict__ part, int nblk, double scale,
-                                                                 float* __restrict__ out) {
-    __shared__ double red[NT];
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += NT) a += (double)part[b];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)(red[0] * scale);
-}
-
-template <bool VEC5>
-void launch_loss(const float* logits, const float* phi, float* dlogits, float* part, long long P, int ncls, float gk, int nblk,
-                 hipStream_t st) {
-    if (dlogits)
-        hipLaunchKernelGGL((boundary_loss_kernel<VEC5, true>), dim3(nblk), dim3(NT), 0, st, logits, phi, dlogits, part, P, ncls, gk);
-    else
-        hipLaunchKernelGGL((boundary_loss_kernel<VEC5, false>), dim3(nblk), dim3(NT), 0, st, logits, phi, dlogits, part, P, ncls, gk);
-}
+};
 
 // the served domain of the transform; 0 with the message set otherwise
 bool sdist_domain(int32_t B, int32_t H, int32_t W, int32_t ncls, uint32_t class_mask) {
@@ -424,7 +328,7 @@ int pnp_signed_distance_2d(const float* onehot, int32_t B, int32_t H, int32_t W,
 
 size_t pnp_boundary_loss_workspace_bytes(int64_t P, int32_t ncls) {
     (void)ncls;
-    return (size_t)loss_blocks(P) * sizeof(float);
+    return pixel_loss::workspace_bytes(P);
 }
 
 int pnp_boundary_loss(const float* logits, const float* phi, int64_t P, int32_t ncls, int32_t nsel, float coef, float* dlogits, float* out,
@@ -434,21 +338,11 @@ int pnp_boundary_loss(const float* logits, const float* phi, int64_t P, int32_t 
     PNP_REQUIRE(nsel >= 0 && nsel <= ncls, "pnp_boundary_loss: nsel = %d selected classes of ncls = %d", (int)nsel, (int)ncls);
     PNP_REQUIRE(workspace_bytes >= pnp_boundary_loss_workspace_bytes(P, ncls), "pnp_boundary_loss: workspace too small (%zu < %zu bytes)",
                 workspace_bytes, pnp_boundary_loss_workspace_bytes(P, ncls));
-    hipStream_t st = (hipStream_t)stream;
-    const int nblk = loss_blocks(P);
-    float* part = (float*)workspace;
     // 1 / (P nsel); no selected class: value and gradient are 0
     const double scale = nsel > 0 ? 1.0 / ((double)P * (double)nsel) : 0.0;
     const float gk = (float)((double)coef * scale);
-    const bool vec5 = ncls == 5 && P >= 4 && ((uintptr_t)logits & 15) == 0 && ((uintptr_t)phi & 15) == 0 && ((uintptr_t)dlogits & 15) == 0;
-    if (vec5)
-        launch_loss<true>(logits, phi, dlogits, part, (long long)P, ncls, gk, nblk, st);
-    else
-        launch_loss<false>(logits, phi, dlogits, part, (long long)P, ncls, gk, nblk, st);
-    PNP_CHECK_LAUNCH("boundary_loss_kernel");
-    hipLaunchKernelGGL(boundary_loss_final_kernel, dim3(1), dim3(NT), 0, st, (const float*)part, nblk, scale, out);
-    PNP_CHECK_LAUNCH("boundary_loss_final_kernel");
-    return PNP_OK;
+    return pixel_loss::run<BoundaryTerm>("pnp_boundary_loss", logits, {{phi}}, (long long)P, ncls, scale, gk, dlogits, out, workspace,
+                                         (hipStream_t)stream);
 }
 
 }  // extern "C"

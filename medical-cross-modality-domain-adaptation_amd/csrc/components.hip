@@ -40,7 +40,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxExtent = 4096;
-constexpr int MAXC = 8;                    // loss_optim.hip's
 constexpr int kMaxKeep = 8;
 constexpr int T0 = 8, T1 = 8, T2 = 32;     // tile extents; T2 = half a wave, T1 * T2 = the workgroup
 constexpr int kTile = T0 * T1 * T2;

@@ -3,6 +3,7 @@
 // conv -> dropout -> BN(train) [-> + channel-zero-padded shortcut] -> leaky-ReLU with respect to its input-gradient pass.
 // Tensors are [P][C] fp32 with C contiguous; 16 B per lane where C % 4 == 0, one channel per lane otherwise.
 // Every reduction is two-level in a fixed order (no atomics): run-to-run bitwise deterministic.  Nothing here synchronises.
+#include "block_sum.h"
 #include "pnp_common.h"
 
 namespace {
@@ -60,13 +61,8 @@ __global__ void __launch_bounds__(NT) gp_norm_partial_kernel(const float* __rest
     } else {
         for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < (size_t)n; i += stride) acc = fma((double)gs_[i], (double)gs_[i], acc);
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = NT / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[(size_t)s * GP_BLOCKS + blockIdx.x] = red[0];
+    const double sum = block_tree<NT>(acc, red);
+    if (threadIdx.x == 0) part[(size_t)s * GP_BLOCKS + blockIdx.x] = sum;
 }
 
 // one workgroup: norms, per-sample adjoint scale, penalty = coef * mean_i (|g_i| - 1)^2
@@ -83,13 +79,8 @@ __global__ void __launch_bounds__(NT) gp_final_kernel(const double* __restrict__
         scale[s] = nrm > 0.0 ? (float)((double)coef * (double)gscale * 2.0 / (double)B * (nrm - 1.0) / nrm) : 0.0f;
         acc += (nrm - 1.0) * (nrm - 1.0);
     }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int w = NT / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) penalty[0] = (float)((double)coef * red[0] / (double)B);
+    const double sum = block_tree<NT>(acc, red);
+    if (threadIdx.x == 0) penalty[0] = (float)((double)coef * sum / (double)B);
 }
 
 // g <- scale_i * g in place (the penalty's adjoint with respect to the input gradient); grid (blocks per sample, B)

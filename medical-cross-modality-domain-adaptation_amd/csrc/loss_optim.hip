@@ -8,7 +8,6 @@
 namespace {
 
 constexpr int NT = 256;
-constexpr int MAXC = 8;
 
 // reduce NV per-thread floats over the block; result valid in thread 0's `v`
 template <int NV>

@@ -47,7 +47,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxExtent = 4096;
-constexpr int MAXC = 8;        // loss_optim.hip's
 
 // where a launch writes: the X x Y x nb box of voxel columns and frames z0 .. z0 + nb - 1
 struct Box {

@@ -9,6 +9,8 @@
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+constexpr int MAXC = 8;      // classes served by the kernels that hold a pixel's classes in registers or per-class LDS slots
+
 void pnp_set_error(const char* fmt, ...);
 
 #define PNP_CHECK_LAUNCH(name)                                                   \

@@ -586,7 +586,16 @@ class WganLossFn(Function):
         return grads[0], grads[1], grads[2], grads[3], None, None
 
 
-class EntropyLossFn(Function):
+class _SavedGradRoot(Function):
+    """a ROOT of backward whose forward has already written its gradient with respect to the first input (and saved it): backward hands
+    it on, with None for every other input"""
+
+    @staticmethod
+    def backward(ctx, dout):
+        return (ctx.saved_tensors[0],) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+class EntropyLossFn(_SavedGradRoot):
     """scalar = normalised mean entropy of softmax(logits) (kernels.softmax_entropy).  A ROOT of backward like WganLossFn:
     the upstream gradient is taken to be `gscale` (1/world_size under data parallelism) and `coef * gscale * dL/dlogits` is written by
     the forward's own pass over the logits; backward hands it on.  Run it together with the step's other root in ONE
@@ -598,12 +607,8 @@ class EntropyLossFn(Function):
         ctx.save_for_backward(dl)
         return value
 
-    @staticmethod
-    def backward(ctx, dout):
-        return ctx.saved_tensors[0], None, None
 
-
-class BoundaryLossFn(Function):
+class BoundaryLossFn(_SavedGradRoot):
     """scalar = boundary loss of softmax(logits) against the signed distance maps of the one-hot labels y over `classes` (None: every class
     but the background) — kernels.signed_distance_2d + kernels.boundary_loss; DESIGN.md §28.  A ROOT of backward exactly like
     EntropyLossFn: the forward computes the maps, the value and `coef * gscale * dL/dlogits`, backward hands the latter on.  Run it with
@@ -617,10 +622,6 @@ class BoundaryLossFn(Function):
         value, dl = K.boundary_loss(_contig(logits), phi, nsel, coef * gscale, want_grad=True)
         ctx.save_for_backward(dl)
         return value
-
-    @staticmethod
-    def backward(ctx, dout):
-        return ctx.saved_tensors[0], None, None, None, None
 
 
 # ---- arithmetic type of the convolution operands (BASELINE configs[4])----------------------------------------------------------

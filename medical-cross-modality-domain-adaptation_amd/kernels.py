@@ -1053,15 +1053,21 @@ def wgan_loss(ct_cls, mr_cls, ct_mask, mr_mask, coefs):
 def softmax_entropy(logits, coef=1.0, want_grad=False):
     """normalised mean entropy of softmax(logits [..., ncls]) (csrc/entropy.hip, DESIGN.md §27) -> (value [1], not scaled by coef;
     coef * d value / d logits, or None without want_grad).  One streaming pass, stream-ordered, bit-identical from run to run."""
+    return _pixel_loss("pnp_softmax_entropy", logits, (_p(logits),), (), coef, want_grad)
+
+
+def _pixel_loss(entry, logits, inputs, scalars, coef, want_grad):
+    """the common part of the per-pixel loss terms (csrc/pixel_loss.h): lib.`entry`(*inputs, P, ncls, *scalars, coef, dlogits, out,
+    workspace, bytes, stream), inputs = the pointers of the logits and of the term's extra inputs, with the workspace that
+    lib.`entry`_workspace_bytes(P, ncls) asks for -> (value [1], dlogits | None)"""
     lib = _lib.load()
-    pl = _p(logits)
     ncls = logits.shape[-1]
     P = logits.numel() // max(ncls, 1)
     out = torch.empty(1, dtype=torch.float32, device=logits.device)
     dl = torch.empty_like(logits) if want_grad else None
-    ws = workspace(lib.pnp_softmax_entropy_workspace_bytes(P, ncls), logits.device)      # per-block partials, read by the second launch
-    check(lib.pnp_softmax_entropy(pl, P, ncls, float(coef), _p(dl), _p(out), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
-          "pnp_softmax_entropy")
+    ws = workspace(getattr(lib, entry + "_workspace_bytes")(P, ncls), logits.device)      # per-block partials, read by the second launch
+    check(getattr(lib, entry)(*inputs, P, ncls, *scalars, float(coef), _p(dl), _p(out), ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()),
+          entry)
     return out, dl
 
 
@@ -1099,18 +1105,10 @@ def boundary_loss(logits, phi, nsel, coef=1.0, want_grad=False):
     """boundary loss (csrc/boundary.hip): mean over pixels and the nsel selected classes of softmax(logits) * phi ->
     (value [1], not scaled by coef; coef * d value / d logits, or None without want_grad).  One streaming pass, stream-ordered,
     bit-identical from run to run."""
-    lib = _lib.load()
-    pl, pq = _p(logits), _p(phi)
+    inputs = (_p(logits), _p(phi))
     if phi.shape != logits.shape:
         raise _lib.PnpError("boundary_loss: phi %s does not have the shape of the logits %s" % (tuple(phi.shape), tuple(logits.shape)))
-    ncls = logits.shape[-1]
-    P = logits.numel() // max(ncls, 1)
-    out = torch.empty(1, dtype=torch.float32, device=logits.device)
-    dl = torch.empty_like(logits) if want_grad else None
-    ws = workspace(lib.pnp_boundary_loss_workspace_bytes(P, ncls), logits.device)      # per-block partials, read by the second launch
-    check(lib.pnp_boundary_loss(pl, pq, P, ncls, int(nsel), float(coef), _p(dl), _p(out), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
-                                _stream()), "pnp_boundary_loss")
-    return out, dl
+    return _pixel_loss("pnp_boundary_loss", logits, inputs, (int(nsel),), coef, want_grad)
 
 
 def filled(shape, value, device):

@@ -12,26 +12,12 @@ import torch
 
 from boundary_ref import boundary_ref, onehot_of_masks, patterns, phi_ref
 from conftest import pkg
+from kernel_bars import _bar, _value_bar
 from oracle import nets
 from oracle import tf_ops as T
 from test_gpu_segmenter import COST, _blob_labels, _cos, _rel, he_scaled
 
 pytestmark = pytest.mark.gpu
-
-
-def _bar(got, ref, what, tol=1e-5):
-    """the bar of the project's kernel tests (test_gpu_entropy._bar): within tol of max|ref|"""
-    got = torch.as_tensor(got).detach().cpu().double()
-    ref = torch.as_tensor(ref).double()
-    err = float((got - ref).abs().max())
-    scale = float(ref.abs().max())
-    print("%s: max err %.3e of max|ref| %.3e (%.2e)" % (what, err, scale, err / (scale + 1e-300)))
-    assert err <= tol * scale + 1e-30, what
-
-
-def _value_bar(got, ref, what):
-    print("%s: value %.9g, float64 %.9g (rel %.2e)" % (what, float(got), ref, abs(float(got) - ref) / (abs(ref) + 1e-300)))
-    assert abs(float(got) - ref) <= 1e-5 * abs(ref), what
 
 
 def _onehot(lab, C):

@@ -1,6 +1,7 @@
-// Timing experiment behind DESIGN.md §27: launch shapes of the entropy pass at P = 16*256*256, C = 5 — the shipped direct float4 kernel at
-// several grid sizes against a variant that stages 1 024-pixel tiles through LDS (coalesced 16-byte loads and stores).  Not part of the
-// library.  Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../include -o entropy_variants entropy_variants.hip
+// Timing experiment behind DESIGN.md §27: launch shapes of the entropy pass at P = 16*256*256, C = 5 — the shipped direct float4 kernel
+// (pixel_loss::stream_kernel<EntropyTerm, true, .> of csrc/pixel_loss.h) at several grid sizes against a variant that stages 1 024-pixel
+// tiles through LDS (coalesced 16-byte loads and stores) around the same EntropyTerm::pixel.  Not part of the library.
+// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../include -o entropy_variants entropy_variants.hip
 #include <hip/hip_runtime.h>
 #include <cstdarg>
 #include <cstdio>
@@ -11,6 +12,8 @@ void pnp_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprin
 #include "../../medical-cross-modality-domain-adaptation_amd/csrc/entropy.hip"
 
 namespace {
+constexpr int NT = pixel_loss::NT;
+
 template <bool GRAD>
 __global__ void __launch_bounds__(NT) ent_lds_kernel(const float* __restrict__ logits, float* __restrict__ dlogits, float* __restrict__ part,
                                                      long long ntile, float gk) {
@@ -31,7 +34,7 @@ __global__ void __launch_bounds__(NT) ent_lds_kernel(const float* __restrict__ l
             f[4 * k] = v.x, f[4 * k + 1] = v.y, f[4 * k + 2] = v.z, f[4 * k + 3] = v.w;
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc += entropy_pixel<5, GRAD>(f + 5 * r, 5, gk, f + 5 * r);
+        for (int r = 0; r < 4; ++r) acc += EntropyTerm::pixel<5, GRAD>(f + 5 * r, nullptr, 5, gk, f + 5 * r);
         if (GRAD) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) tile[threadIdx.x * 5 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
@@ -78,8 +81,13 @@ int main() {
         for (int grad = 1; grad >= 0; --grad) {
             auto launch = [&](int b) {
                 if (v.kind == 0) {
-                    if (grad) hipLaunchKernelGGL((softmax_entropy_kernel<true, true>), dim3(v.blocks), dim3(NT), 0, 0, z[b], g[b], part, P, C, gk);
-                    else hipLaunchKernelGGL((softmax_entropy_kernel<true, false>), dim3(v.blocks), dim3(NT), 0, 0, z[b], g[b], part, P, C, gk);
+                    const pixel_loss::Extra<0> none{};
+                    if (grad)
+                        hipLaunchKernelGGL((pixel_loss::stream_kernel<EntropyTerm, true, true>), dim3(v.blocks), dim3(NT), 0, 0, z[b], g[b], part, P,
+                                           C, gk, none);
+                    else
+                        hipLaunchKernelGGL((pixel_loss::stream_kernel<EntropyTerm, true, false>), dim3(v.blocks), dim3(NT), 0, 0, z[b], g[b], part, P,
+                                           C, gk, none);
                 } else {
                     if (grad) hipLaunchKernelGGL((ent_lds_kernel<true>), dim3(v.blocks), dim3(NT), 0, 0, z[b], g[b], part, ntile, gk);
                     else hipLaunchKernelGGL((ent_lds_kernel<false>), dim3(v.blocks), dim3(NT), 0, 0, z[b], g[b], part, ntile, gk);
