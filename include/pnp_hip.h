@@ -450,6 +450,26 @@ int pnp_signed_distance_2d(const float* onehot, int32_t B, int32_t H, int32_t W,
 size_t pnp_boundary_loss_workspace_bytes(int64_t P, int32_t ncls);
 int pnp_boundary_loss(const float* logits, const float* phi, int64_t P, int32_t ncls, int32_t nsel, float coef, float* dlogits, float* out,
                       void* workspace, size_t workspace_bytes, void* stream);
+/* Class-balanced pseudo-label self-training on unlabelled predictions (csrc/pseudo_label.hip; not in the reference).
+ * pnp_pseudo_label_loss: logits [P, ncls], fp32, 1 <= ncls <= 8, P < 2^31; thresholds [ncls] in DEVICE memory (read by the kernel, never
+ * by the host).  k_i = argmax_j logits_ij (lowest index on ties), s_i = sum_j exp(logits_ij - max), c_i = 1 / s_i; pixel i is selected
+ * iff bit k_i of class_mask is set and c_i >= thresholds[k_i].  out[0] = L = sum_selected log s_i / P (NOT scaled by coef), out[1] = the
+ * selected share of the pixels; counts[0..ncls) = pixels predicted as each class, counts[ncls..2 ncls) = pixels selected as each class;
+ * labels[i] = k_i | selected << 7; conf[i] = c_i; dlogits (nullable: value only, bit-identical) = coef * (p_ij - [j == k_i]) / P on the
+ * selected pixels, 0 elsewhere — fold 1/world_size into coef.  One streaming pass plus a one-block sum of its per-block partials in a
+ * fixed order; no float atomics, no host read, capturable.  ws: pnp_pseudo_label_loss_workspace_bytes(P, ncls).
+ * pnp_pseudo_label_update: for every class k with n_k >= 1 pixels (labels & 0x7f == k), q_k = the r-th largest conf among them,
+ * r = ceil(portion * n_k), EXACT (radix selection over the bit patterns, 4 rounds of 8 bits), then in place on the device
+ * thresholds[k] = fmaf(momentum, thresholds[k] - q_k, q_k)  (momentum == 1: untouched).  A class without pixels keeps its threshold bit
+ * for bit.  q_out (nullable) [ncls] = q_k, NaN for a class without pixels.  0 < portion <= 1, 0 <= momentum <= 1.  conf must be positive
+ * finite floats (what pnp_pseudo_label_loss writes).  ws: pnp_pseudo_label_update_workspace_bytes(P, ncls). */
+size_t pnp_pseudo_label_loss_workspace_bytes(int64_t P, int32_t ncls);
+int pnp_pseudo_label_loss(const float* logits, const float* thresholds, int64_t P, int32_t ncls, uint32_t class_mask, float coef,
+                          float* dlogits, uint8_t* labels, float* conf, float* out, int32_t* counts, void* workspace, size_t workspace_bytes,
+                          void* stream);
+size_t pnp_pseudo_label_update_workspace_bytes(int64_t P, int32_t ncls);
+int pnp_pseudo_label_update(const uint8_t* labels, const float* conf, int64_t P, int32_t ncls, double portion, float momentum,
+                            float* thresholds, float* q_out, void* workspace, size_t workspace_bytes, void* stream);
 /* p[0..n) = value  (constant gradient of a mean: coef / B) */
 int pnp_fill(float* p, size_t n, float value, void* stream);
 

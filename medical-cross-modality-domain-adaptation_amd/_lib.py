@@ -12,7 +12,7 @@ import os
 # "no ROCm-capable device is detected" (measured on the GPU box; tests/test_abi.py guards the order).
 import torch  # noqa: F401  (import order is the point)
 
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PNP_LIB") or os.path.join(_HERE, "libpnp_hip.so")   # PNP_LIB: timing-experiment builds (tools/)
@@ -160,6 +160,10 @@ PROTOTYPES = {
     "pnp_signed_distance_2d": (c_int, [_F, c_int32, c_int32, c_int32, c_int32, c_uint32, _F, c_void_p, c_size_t, c_void_p]),
     "pnp_boundary_loss_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "pnp_boundary_loss": (c_int, [_F, _F, c_int64, c_int32, c_int32, c_float, _F, _F, c_void_p, c_size_t, c_void_p]),
+    "pnp_pseudo_label_loss_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "pnp_pseudo_label_loss": (c_int, [_F, _F, c_int64, c_int32, c_uint32, c_float, _F, c_void_p, _F, _F, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "pnp_pseudo_label_update_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "pnp_pseudo_label_update": (c_int, [c_void_p, _F, c_int64, c_int32, c_double, c_float, _F, _F, c_void_p, c_size_t, c_void_p]),
     "pnp_wgan_loss": (c_int, [_F, _F, _F, _F, c_int32, c_float, c_float, c_float, c_float, _F, c_void_p]),
     "pnp_fill": (c_int, [_F, c_size_t, c_float, c_void_p]),
     "pnp_label_decomp": (c_int, [_F, _F, c_int64, c_int32, c_void_p]),

@@ -20,7 +20,7 @@ import torch
 
 from . import functional as Fn
 from . import kernels as K
-from .functional import Conv2dDropFn, CriticInputFn, CriticInputPsFn, EntropyLossFn, WganLossFn, fan_out, wgrad_overlap
+from .functional import Conv2dDropFn, CriticInputFn, CriticInputPsFn, EntropyLossFn, PseudoLabelLossFn, WganLossFn, fan_out, wgrad_overlap
 from .gradient_penalty import critic_gradient_penalty, critic_table
 from .layers import (DR_block, conv2d, conv_bn_relu2d, max_pool2d, residual_block, sharable_weight_variable, weight_variable)
 from .lib import _dice_eval, _label_decomp
@@ -62,6 +62,9 @@ class Full_DRN(object):
         self.dis_loss = self.ct_gen_loss = None
         self.ct_logits = self.mr_logits = None
         self.ent_value = None
+        self.pl_value = self.pl_share = self.pl_counts = self.pl_labels = None
+        if self.pl_weight > 0:      # the term's training state: on the device, read and rewritten by the kernels of the gen step
+            self.pl_threshold = torch.full((self.n_class,), self.pl_init, dtype=torch.float32, device=self.device)
 
     # ---- helpers ----------------------------------------------------------------------------------------------------
     def _names_of(self, tensors):
@@ -84,6 +87,23 @@ class Full_DRN(object):
         self.ent_weight = float(ck.pop("ent_weight", 0.0) or 0.0)
         if not self.ent_weight >= 0.0:
             raise ValueError("cost_kwargs ent_weight must be >= 0, got %r" % (self.ent_weight,))
+        # opt-in class-balanced pseudo-label self-training on the CT predictions in the gen step (not in the reference)
+        self.pl_weight = float(ck.pop("pl_weight", 0.0) or 0.0)
+        self.pl_portion = float(ck.pop("pl_portion", 0.5))
+        self.pl_momentum = float(ck.pop("pl_momentum", 0.9))
+        self.pl_init = float(ck.pop("pl_init", 0.9))
+        pc = ck.pop("pl_classes", None)
+        self.pl_classes = None if pc is None else tuple(int(c) for c in pc)
+        if not self.pl_weight >= 0.0:
+            raise ValueError("cost_kwargs pl_weight must be >= 0, got %r" % (self.pl_weight,))
+        if not 0.0 < self.pl_portion <= 1.0:
+            raise ValueError("cost_kwargs pl_portion must be in (0, 1], got %r" % (self.pl_portion,))
+        if not 0.0 <= self.pl_momentum <= 1.0:
+            raise ValueError("cost_kwargs pl_momentum must be in [0, 1], got %r" % (self.pl_momentum,))
+        if not 0.0 <= self.pl_init < float("inf"):
+            raise ValueError("cost_kwargs pl_init must be a finite value >= 0, got %r" % (self.pl_init,))
+        if self.pl_classes is not None:
+            K.class_mask(self.pl_classes, self.n_class)      # ValueError for a class that is not one of 0 ... n_class - 1
 
     def _fc(self, x, w):
         """tf.matmul(tf.reshape(x, [-1, D]), w) (adversarial.py:395-397, 438-440) as a 1x1 'convolution' on the MFMA kernel"""
@@ -255,7 +275,7 @@ class Full_DRN(object):
 
     # ---- the graph of adversarial.py:82-119, executed eagerly ---------------------------------------------------------------
     def _graph(self, mr, ct, keep_prob, mr_front_bn, joint_bn, ct_front_bn, record=False, segmenter_no_grad=False, drop_seed=0, critics=True, critic_keep=None,
-               entropy=False):
+               entropy=False, pseudo=False):
         """mr / ct: [B,256,256,3] (either may be None: pruned branch).  Returns dict of critic logits and segmenter logits."""
         st = self.store
         ckw = {} if critic_keep is None else {"keep_prob": critic_keep}     # None: the builders' own default (0.75, adversarial.py:320,402)
@@ -287,6 +307,8 @@ class Full_DRN(object):
                         lg_c = lg
                         if entropy and br == "ct":      # a third consumer of the CT logits: the entropy term (its edge comes first)
                             out["ct_entropy_in"], lg_c = fan_out(lg)
+                        if pseudo and br == "ct":       # and one for the pseudo-label term
+                            out["ct_pseudo_in"], lg_c = fan_out(lg_c)
                         lg_cls, lg_mask = fan_out(lg_c)          # the logits feed both critics
                         feats[br] = (c9, b8, b7, lg_mask)
                         out[br + "_cls"] = self.create_classifier(z[br + "_c4"], z[br + "_c6"], b7, c9, lg_cls, feature_base=self.feature_base,
@@ -382,23 +404,35 @@ class Full_DRN(object):
         self._activate("adapt")
         self.store.zero_grad()
         o = self._graph(None, ct, keep_prob, mr_front_bn=False, joint_bn=False, ct_front_bn=True, drop_seed=drop_seed,
-                        entropy=self.ent_weight > 0)
+                        entropy=self.ent_weight > 0, pseudo=self.pl_weight > 0)
         lam, mu = self.lambda_mask_loss, self.miu_gen
         use_mask = lam != 0.0
         loss = WganLossFn.apply(o["ct_cls"], None, o["ct_mask"] if use_mask else None, None, (-mu, 0.0, -lam * mu, 0.0), 1.0 / self.world_size)
-        if self.ent_weight > 0:
-            # + ent_weight * normalised mean entropy of the CT predictions: a second root of the same backward; its gradient and the
-            # critics' meet in the logits' fan_out (pnp_add)
+        # the opt-in terms on the CT predictions are further roots of the same backward; their gradients and the critics' meet in the
+        # logits' fan_out (pnp_add).  (weight, value) of each, in the order they are added to the loss
+        roots, extra = [loss], []
+        self.ent_value = self.pl_value = self.pl_share = self.pl_counts = self.pl_labels = None
+        if self.ent_weight > 0:       # + ent_weight * normalised mean entropy of the CT predictions
             ent = EntropyLossFn.apply(o["ct_entropy_in"], self.ent_weight, 1.0 / self.world_size)
-            with wgrad_overlap():
-                torch.autograd.backward([loss, ent], [self.store.unit_grad(1), self.store.unit_grad(1)])
+            roots.append(ent)
             self.ent_value = ent.detach()
-            self.ct_gen_loss = K.axpby(self.ent_value, loss.detach(), self.ent_weight, 1.0)      # (in place: nothing else reads `loss`)
-        else:
-            with wgrad_overlap():
+            extra.append((self.ent_weight, self.ent_value))
+        if self.pl_weight > 0:        # + pl_weight * the pseudo-label term under the thresholds the steps before this one left
+            pl, share, counts, labels, conf = PseudoLabelLossFn.apply(o["ct_pseudo_in"], self.pl_threshold, self.pl_classes, self.pl_weight,
+                                                                      1.0 / self.world_size)
+            roots.append(pl)
+            self.pl_value, self.pl_share, self.pl_counts, self.pl_labels = pl.detach(), share, counts, labels
+            extra.append((self.pl_weight, self.pl_value))
+        with wgrad_overlap():
+            if extra:
+                torch.autograd.backward(roots, [self.store.unit_grad(1)] * len(roots))
+            else:
                 loss.backward(self.store.unit_grad(1))
-            self.ent_value = None
-            self.ct_gen_loss = loss.detach()
+        self.ct_gen_loss = loss.detach()
+        for w, v in extra:
+            K.axpby(v, self.ct_gen_loss, w, 1.0)      # (in place: nothing else reads `loss`)
+        if self.pl_weight > 0:        # the thresholds of the NEXT step: per-class quantiles of this batch's confidences, in place
+            K.pseudo_label_update(labels, conf, self.pl_threshold, self.pl_portion, self.pl_momentum)
         self.ct_logits = o["ct_logits"]
         self.critic_scores = {k: o[k].detach() for k in ("ct_cls", "ct_mask") if o.get(k) is not None}
         return self.ct_gen_loss
@@ -492,6 +526,10 @@ def _host(t):
 
 def _ent_weight(net):
     return getattr(net, "ent_weight", 0.0)
+
+
+def _pl_weight(net):
+    return getattr(net, "pl_weight", 0.0)
 
 
 def _gp_weight(net):
@@ -606,6 +644,8 @@ class Trainer(object):
         self.net.save(ck)
         d, g = self.dis_optimizer.state_dict(), self.gen_optimizer.state_dict()
         slots = {k: v for src in (d, g) for k, v in src.items() if k != "lr"}       # the two var_lists are disjoint (cls* / adapt*)
+        if _pl_weight(self.net) > 0:      # the pseudo-label thresholds are training state like the slots (rank 0's under data parallelism)
+            slots["pl_threshold"] = self.net.pl_threshold.detach().cpu().numpy()
         atomic_savez(os.path.join(output_path, "optimizer.npz"), kind="rmsprop", dis_lr=d["lr"], gen_lr=g["lr"],
                      global_step=np.int64(self.global_step), **slots)
         return ck
@@ -625,6 +665,9 @@ class Trainer(object):
             dd, dm = self.dis_optimizer.load_state_dict(dict(sd, lr=sd["dis_lr"]), slots=not clear_rms, lr=not lr_update)
             gd, gm = self.gen_optimizer.load_state_dict(dict(sd, lr=sd["gen_lr"]), slots=not clear_rms, lr=not lr_update)
             self.global_step = int(z["global_step"])
+            if _pl_weight(self.net) > 0 and "pl_threshold" in z.files and z["pl_threshold"].shape == tuple(self.net.pl_threshold.shape):
+                # (in place: a captured gen step holds the tensor's address; a checkpoint without them starts from pl_init)
+                self.net.pl_threshold.copy_(torch.from_numpy(z["pl_threshold"].astype(np.float32)))
         if not clear_rms:
             if not (dd or gd):
                 raise RuntimeError("restore with clear_rms=False asked for the RMSProp slots, but %s holds none for this graph" % f)
@@ -788,6 +831,10 @@ class Trainer(object):
         if monitor:      # the label-free proxy of target quality: labelled and unlabelled CT sources alike
             gp["ct_entropy"] = _host(self.net.ct_entropy_eval)
             logging.info("step %d %s batch: ct_entropy %.4f" % (step, "validation" if detail else "training", gp["ct_entropy"]))
+        if _pl_weight(self.net) > 0:      # the last gen step's term and selected share (null before the first one), the thresholds as they stand
+            gp.update(pl=_host(self.net.pl_value), pl_share=_host(self.net.pl_share), pl_threshold=self.net.pl_threshold.tolist())
+            logging.info("step %d pseudo-label term %s, selected share %s, thresholds %s" % (
+                step, gp["pl"], gp["pl_share"], " ".join("%.4f" % t for t in gp["pl_threshold"])))
         if getattr(self, "scalars", None) is not None:      # evaluate() has just synchronised: the last losses cost nothing to read here
             self.scalars.write("val_eval" if detail else "train_eval", step=step, ct_dice=ct_d, mr_dice=mr_d,
                                dis_loss=_host(getattr(self.net, "dis_loss", None)), gen_loss=_host(getattr(self.net, "ct_gen_loss", None)), **gp)

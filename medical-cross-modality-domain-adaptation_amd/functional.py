@@ -608,6 +608,24 @@ class EntropyLossFn(_SavedGradRoot):
         return value
 
 
+class PseudoLabelLossFn(_SavedGradRoot):
+    """scalar = class-balanced pseudo-label term of softmax(logits) under the device thresholds [ncls] over `classes` (None: every class)
+    — kernels.pseudo_label_loss; DESIGN.md §29.  A ROOT of backward exactly like EntropyLossFn: the forward's pass over the logits writes
+    `coef * gscale * dL/dlogits`, backward hands it on.  -> (value [1], share [1], counts [2, ncls], labels, conf); only the value
+    takes part in backward, the others are what kernels.pseudo_label_update and the log read."""
+
+    @staticmethod
+    def forward(ctx, logits, thresholds, classes, coef, gscale):
+        value, share, counts, labels, conf, dl = K.pseudo_label_loss(_contig(logits), thresholds, classes, coef * gscale, want_grad=True)
+        ctx.save_for_backward(dl)
+        ctx.mark_non_differentiable(share, counts, labels, conf)
+        return value, share, counts, labels, conf
+
+    @staticmethod
+    def backward(ctx, dout, *unused):
+        return (ctx.saved_tensors[0],) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
 class BoundaryLossFn(_SavedGradRoot):
     """scalar = boundary loss of softmax(logits) against the signed distance maps of the one-hot labels y over `classes` (None: every class
     but the background) — kernels.signed_distance_2d + kernels.boundary_loss; DESIGN.md §28.  A ROOT of backward exactly like

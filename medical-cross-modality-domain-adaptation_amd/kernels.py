@@ -1111,6 +1111,50 @@ def boundary_loss(logits, phi, nsel, coef=1.0, want_grad=False):
     return _pixel_loss("pnp_boundary_loss", logits, inputs, (int(nsel),), coef, want_grad)
 
 
+def pseudo_label_loss(logits, thresholds, classes=None, coef=1.0, want_grad=False):
+    """class-balanced pseudo-label term of softmax(logits [..., ncls]) against its own arg-max where it is confident (csrc/pseudo_label.hip,
+    DESIGN.md §29).  thresholds: float32 device tensor [ncls], read by the kernel.  classes: iterable of class indices the term is
+    restricted to, default EVERY class, the background included.  -> (value [1] = sum over selected pixels of -log p_argmax / P, not
+    scaled by coef; share [1] of the pixels selected; counts int32 [2, ncls]: pixels predicted as / selected as each class; labels uint8
+    [...] = class | selected << 7; conf float32 [...] = softmax of the arg-max class; coef * d value / d logits, or None without
+    want_grad).  value and share are views of one [2] tensor.  One streaming pass, stream-ordered, bit-identical from run to run."""
+    lib = _lib.load()
+    pl, pt = _p(logits), _p(thresholds)
+    ncls = logits.shape[-1]
+    P = logits.numel() // max(ncls, 1)
+    if thresholds.numel() != ncls:
+        raise _lib.PnpError("pseudo_label_loss: %d thresholds for %d classes" % (thresholds.numel(), ncls))
+    mask = 0 if ncls > 32 else ((1 << ncls) - 1 if classes is None else class_mask(classes, ncls))      # (> 8 classes: the library refuses)
+    dev = logits.device
+    out = torch.empty(2, dtype=torch.float32, device=dev)
+    counts = torch.empty((2, ncls), dtype=torch.int32, device=dev)
+    labels = torch.empty(logits.shape[:-1], dtype=torch.uint8, device=dev)
+    conf = torch.empty(logits.shape[:-1], dtype=torch.float32, device=dev)
+    dl = torch.empty_like(logits) if want_grad else None
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    ws = workspace(lib.pnp_pseudo_label_loss_workspace_bytes(P, ncls), dev)      # per-block partials, read by the second launch
+    check(lib.pnp_pseudo_label_loss(pl, pt, P, ncls, mask, float(coef), _p(dl), vp(labels), _p(conf), _p(out), vp(counts), vp(ws), ws.numel(),
+                                    _stream()), "pnp_pseudo_label_loss")
+    return out[0:1], out[1:2], counts, labels, conf, dl
+
+
+def pseudo_label_update(labels, conf, thresholds, portion, momentum):
+    """thresholds[k] <- q_k + momentum * (thresholds[k] - q_k) IN PLACE on the device, q_k = the ceil(portion * n_k)-th largest conf among
+    the n_k pixels whose class byte (labels & 0x7f) is k — exact, by radix selection (csrc/pseudo_label.hip).  A class
+    without pixels keeps its threshold bit for bit.  -> q float32 [ncls], NaN for a class without pixels.  Stream-ordered, no host read."""
+    lib = _lib.load()
+    pc, pt = _p(conf), _p(thresholds)
+    if not labels.is_cuda or labels.dtype != torch.uint8 or not labels.is_contiguous() or labels.numel() != conf.numel():
+        raise _lib.PnpError("pseudo_label_update: labels must be a contiguous CUDA uint8 tensor with one byte per entry of conf")
+    ncls, P = thresholds.numel(), conf.numel()
+    q = torch.empty(ncls, dtype=torch.float32, device=conf.device)
+    vp = lambda t: ctypes.c_void_p(t.data_ptr())
+    ws = workspace(lib.pnp_pseudo_label_update_workspace_bytes(P, ncls), conf.device)      # histograms and selection state of the rounds
+    check(lib.pnp_pseudo_label_update(vp(labels), pc, P, ncls, float(portion), float(momentum), pt, _p(q), vp(ws), ws.numel(), _stream()),
+          "pnp_pseudo_label_update")
+    return q
+
+
 def filled(shape, value, device):
     t = torch.empty(shape, dtype=torch.float32, device=device)
     check(_lib.load().pnp_fill(_p(t), t.numel(), float(value), _stream()), "pnp_fill")

@@ -7,7 +7,10 @@ Extra flags: --synthetic N, --batch-size, --iters, --epochs, --output, --baselin
 volume_source.py; the two CT lists may name images alone — unlabelled target scans; --crop-body [N] / --crop-margin N crop
 every volume of both domains to its body / label box; --augment JSON / --no-augment; --axes 0,1,2: slices of every listed orientation, one value for MR and CT), --gp-weight L (opt-in WGAN-GP penalty of the critics instead of the +-0.03 weight clip; gradient_penalty.py; default 0 = the reference),
 --ent-weight W (opt-in entropy minimisation on the CT predictions in the gen step: gen loss + W * normalised mean entropy, DESIGN.md §27;
-default 0 = the reference), --monitor-entropy (log ct_entropy, the label-free monitor, with every Dice report; implied by --ent-weight > 0).
+default 0 = the reference), --monitor-entropy (log ct_entropy, the label-free monitor, with every Dice report; implied by --ent-weight > 0),
+--pl-weight W --pl-portion R --pl-momentum B --pl-init T --pl-classes C,C (opt-in class-balanced pseudo-label self-training on the CT
+predictions in the gen step, DESIGN.md §29: gen loss + W * cross-entropy against the arg-max on the pixels whose confidence reaches their
+class's threshold; the thresholds follow each batch's per-class R-quantile with momentum B from T; default W = 0 = the reference).
 """
 import argparse
 import datetime
@@ -78,6 +81,16 @@ def parse_args(phase, argv=None):
                     "generator loss (entropy minimisation on the unlabelled target, DESIGN.md §27); default 0 = the reference")
     ap.add_argument("--monitor-entropy", action="store_true", help="log ct_entropy (normalised mean entropy of the CT batch, BN in "
                     "inference mode) next to the Dice monitor and write it to the scalar log; implied by --ent-weight > 0")
+    ap.add_argument("--pl-weight", type=float, default=0.0, help="weight of the class-balanced pseudo-label term of the CT predictions in "
+                    "the generator loss (self-training on the unlabelled target, DESIGN.md §29); default 0 = the reference")
+    ap.add_argument("--pl-portion", type=float, default=0.5, help="portion of each predicted class's pixels, taken from the most confident "
+                    "down, that a batch's threshold admits; in (0, 1], default 0.5")
+    ap.add_argument("--pl-momentum", type=float, default=0.9, help="momentum of the thresholds: tau <- q + B (tau - q) per gen step; in "
+                    "[0, 1], default 0.9")
+    ap.add_argument("--pl-init", type=float, default=0.9, help="starting threshold of every class (a checkpoint that holds thresholds "
+                    "replaces it); default 0.9")
+    ap.add_argument("--pl-classes", default=None, metavar="C,C", help="restrict the pseudo-label term to these classes (default: every "
+                    "class, the background included)")
     for flag in NII_FLAGS:
         ap.add_argument("--" + flag.replace("_", "-"), default=None, metavar="LIST", help="NIfTI list file (one `image.nii[.gz] "
                         "label.nii[.gz]` pair per line, volume_source.py); the four --*-nii-* flags go together")
@@ -114,6 +127,19 @@ def parse_args(phase, argv=None):
         ap.error("--gp-weight must be >= 0, got %r" % args.gp_weight)
     if not args.ent_weight >= 0.0:
         ap.error("--ent-weight must be >= 0, got %r" % args.ent_weight)
+    if not args.pl_weight >= 0.0:
+        ap.error("--pl-weight must be >= 0, got %r" % args.pl_weight)
+    if not 0.0 < args.pl_portion <= 1.0:
+        ap.error("--pl-portion must be in (0, 1], got %r" % args.pl_portion)
+    if not 0.0 <= args.pl_momentum <= 1.0:
+        ap.error("--pl-momentum must be in [0, 1], got %r" % args.pl_momentum)
+    if not 0.0 <= args.pl_init < float("inf"):
+        ap.error("--pl-init must be a finite value >= 0, got %r" % args.pl_init)
+    if args.pl_classes is not None:
+        try:
+            args.pl_classes = tuple(int(c) for c in args.pl_classes.split(","))
+        except ValueError:
+            ap.error("--pl-classes takes class indices separated by commas, got %r" % args.pl_classes)
     if args.gp_weight > 0 and args.dtype != "f32":
         ap.error("--gp-weight > 0 runs fp32 convolutions only: the gradient penalty is not implemented for --dtype %s" % args.dtype)
     if args.gp_weight > 0 and args.sync_stats:
@@ -123,12 +149,18 @@ def parse_args(phase, argv=None):
 
 
 def configure_args(args):
-    """configure(args.phase) plus the flags that change the cost: gp_weight and ent_weight enter cost_kwargs only when they are > 0"""
+    """configure(args.phase) plus the flags that change the cost: gp_weight, ent_weight and the pl_* keys enter cost_kwargs only when
+    their weight is > 0"""
     ck, nc, tc = configure(args.phase)
     if args.gp_weight > 0:
         ck["gp_weight"] = float(args.gp_weight)
     if args.ent_weight > 0:
         ck["ent_weight"] = float(args.ent_weight)
+    if args.pl_weight > 0:
+        ck.update(pl_weight=float(args.pl_weight), pl_portion=float(args.pl_portion), pl_momentum=float(args.pl_momentum),
+                  pl_init=float(args.pl_init))
+        if args.pl_classes is not None:
+            ck["pl_classes"] = args.pl_classes
     if args.monitor_entropy:
         tc["monitor_entropy"] = True
     return ck, nc, tc
