@@ -240,11 +240,9 @@ __global__ void __launch_bounds__(NT) sdist_col_kernel(const int16_t* __restrict
 
 // ---- loss pass: a term of the per-pixel skeleton (pixel_loss.h) ------------------------------------------------------------------------
 // one pixel: z[0..C), q = x[0][0..C) (phi) -> s = sum_k p_k q_k (returned); g[0..C) = gk * p (q - s) when GRAD
-struct BoundaryTerm {
-    static constexpr int NEXTRA = 1;
-
+struct BoundaryTerm : pixel_loss::Plain<1> {
     template <int C, bool GRAD>
-    static __device__ __forceinline__ float pixel(const float* z, const float* const* x, int ncls, float gk, float* g) {
+    static __device__ __forceinline__ float pixel(const float* z, const float* const* x, int ncls, float gk, float* g, Lane<C>&, uint32_t&, float&) {
         const float* q = x[0];
         float e[C], m;
         const float inv = 1.0f / pixel_loss::softmax_exp<C>(z, ncls, e, m);

@@ -12,11 +12,9 @@
 namespace {
 
 // one pixel: z[0..C) -> H (returned); g[0..C) = -gk * p (log p + H) when GRAD
-struct EntropyTerm {
-    static constexpr int NEXTRA = 0;
-
+struct EntropyTerm : pixel_loss::Plain<0> {
     template <int C, bool GRAD>
-    static __device__ __forceinline__ float pixel(const float* z, const float* const*, int ncls, float gk, float* g) {
+    static __device__ __forceinline__ float pixel(const float* z, const float* const*, int ncls, float gk, float* g, Lane<C>&, uint32_t&, float&) {
         float e[C], m;
         const float s = pixel_loss::softmax_exp<C>(z, ncls, e, m);
         const float ls = logf(s), inv = 1.0f / s;

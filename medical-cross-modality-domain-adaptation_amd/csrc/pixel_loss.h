@@ -6,11 +6,18 @@
 //
 // A term is a struct with
 //   static constexpr int NEXTRA                       how many extra [P][ncls] float inputs a pixel reads (0: the logits alone)
-//   template <int C, bool GRAD> static __device__ float pixel(const float* z, const float* const* x, int ncls, float gk, float* g)
+//   struct Args : Extra<NEXTRA>                       what the kernel gets by value: the extra inputs and whatever else the term reads
+//   template <int C> struct Lane                      per-thread state, built once from (args, ncls) before the loops; block_end(args,
+//                                                     ncls) is called once per block, by every thread, behind the float block sum
+//   static constexpr bool SIDE                        the pixel also gives one byte and one float, stored to args.labels[P] (uint8_t) and
+//                                                     args.conf[P] (as one uint32_t and one float4 per group on the vector path)
+//   template <int C, bool GRAD> static __device__ float pixel(const float* z, const float* const* x, int ncls, float gk, float* g,
+//                                                             Lane<C>& lane, uint32_t& lab, float& conf)
 //       z[0..C) the logits (entries >= ncls are 0), x[k][0..C) extra input k -> the pixel's contribution; g[0..C) = gk * its gradient
-//       when GRAD (g may alias z; entries >= ncls are not stored)
+//       when GRAD (g may alias z; entries >= ncls are not stored); lab (< 256) and conf are read only when SIDE
 // and a host entry point that checks its arguments, computes scale (out[0] = scale * sum of contributions, in double) and
-// gk = (float)(coef * scale), and calls pixel_loss::run<TERM>.
+// gk = (float)(coef * scale), and calls pixel_loss::run<TERM>, or run_stream<TERM> and a second launch of its own.  Plain<NEXTRA> is the
+// base of a term that has neither state nor side outputs: it supplies everything but pixel, and every option is absent at compile time.
 #pragma once
 #include "block_sum.h"
 #include "pnp_common.h"
@@ -54,31 +61,47 @@ struct Extra {
     const float* p[N > 0 ? N : 1];
 };
 
-// VEC5: ncls == 5 and 16-byte aligned bases — four pixels are 80 bytes = five float4 loads of each input (and five stores) per thread;
-// the P % 4 pixels behind the last whole group take the scalar loop, which is the whole kernel otherwise (any 1 <= ncls <= MAXC, any
-// alignment).
+// a term of N extra inputs without per-thread state and without side outputs
+template <int N>
+struct Plain {
+    static constexpr int NEXTRA = N;
+    static constexpr bool SIDE = false;
+    using Args = Extra<N>;
+    template <int C>
+    struct Lane {
+        __device__ Lane(const Args&, int) {}
+        __device__ void block_end(const Args&, int) {}
+    };
+};
+
+// VEC5: ncls == 5 and every base aligned for its vector type — four pixels are 80 bytes = five float4 loads of each input (and five
+// stores) per thread; the P % 4 pixels behind the last whole group take the scalar loop, which is the whole kernel otherwise (any
+// 1 <= ncls <= MAXC, any alignment).  C, the length of a pixel's register arrays, is one value per instance: the tail of a VEC5 instance
+// runs at 5 as well (entries past ncls only ever add +0.f, so the bits are those of MAXC), and a term's Lane<C> serves both loops.
 template <typename TERM, bool VEC5, bool GRAD>
 __global__ void __launch_bounds__(NT) stream_kernel(const float* __restrict__ logits, float* __restrict__ dlogits, float* __restrict__ part,
-                                                    long long P, int ncls, float gk, const Extra<TERM::NEXTRA> extra) {
-    constexpr int NX = TERM::NEXTRA, NQ = NX > 0 ? NX : 1;
+                                                    long long P, int ncls, float gk, const typename TERM::Args args) {
+    constexpr int C = VEC5 ? 5 : MAXC, NX = TERM::NEXTRA, NQ = NX > 0 ? NX : 1;
     __shared__ float lds[4];
+    typename TERM::template Lane<C> lane(args, ncls);
     float acc = 0.f;
     const long long gs = (long long)gridDim.x * NT;
     const long long t0 = (long long)blockIdx.x * NT + threadIdx.x;
     long long first = 0;
-    if (VEC5) {
+    if constexpr (VEC5) {
         const long long ngrp = P >> 2;
         const float4* __restrict__ in = reinterpret_cast<const float4*>(logits);
         float4* __restrict__ out = reinterpret_cast<float4*>(dlogits);
         for (long long g = t0; g < ngrp; g += gs) {
-            float f[20], q[NQ][20];
+            float f[20], q[NQ][20], c[4];
+            uint32_t lab[4];
 #pragma unroll
             for (int k = 0; k < 5; ++k) {
                 const float4 v = in[g * 5 + k];
                 f[4 * k] = v.x, f[4 * k + 1] = v.y, f[4 * k + 2] = v.z, f[4 * k + 3] = v.w;
 #pragma unroll
                 for (int n = 0; n < NX; ++n) {
-                    const float4 u = reinterpret_cast<const float4*>(extra.p[n])[g * 5 + k];
+                    const float4 u = reinterpret_cast<const float4*>(args.p[n])[g * 5 + k];
                     q[n][4 * k] = u.x, q[n][4 * k + 1] = u.y, q[n][4 * k + 2] = u.z, q[n][4 * k + 3] = u.w;
                 }
             }
@@ -87,31 +110,40 @@ __global__ void __launch_bounds__(NT) stream_kernel(const float* __restrict__ lo
                 const float* x[NQ] = {};      // (null, not the unread q, without extras: that pointer cost <Entropy, true, true> 2 VGPRs)
 #pragma unroll
                 for (int n = 0; n < NX; ++n) x[n] = q[n] + 5 * r;
-                acc += TERM::template pixel<5, GRAD>(f + 5 * r, x, 5, gk, f + 5 * r);
+                acc += TERM::template pixel<5, GRAD>(f + 5 * r, x, 5, gk, f + 5 * r, lane, lab[r], c[r]);
             }
             if (GRAD) {
 #pragma unroll
                 for (int k = 0; k < 5; ++k) out[g * 5 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
             }
+            if constexpr (TERM::SIDE) {
+                reinterpret_cast<uint32_t*>(args.labels)[g] = lab[0] | lab[1] << 8 | lab[2] << 16 | lab[3] << 24;
+                reinterpret_cast<float4*>(args.conf)[g] = make_float4(c[0], c[1], c[2], c[3]);
+            }
         }
         first = ngrp << 2;
     }
     for (long long i = first + t0; i < P; i += gs) {
-        float z[MAXC], q[NQ][MAXC];
+        float z[C], q[NQ][C], c;
+        uint32_t lab;
         const float* x[NQ] = {};
 #pragma unroll
-        for (int j = 0; j < MAXC; ++j) {
+        for (int j = 0; j < C; ++j) {
             z[j] = j < ncls ? logits[i * ncls + j] : 0.f;
 #pragma unroll
-            for (int n = 0; n < NX; ++n) q[n][j] = j < ncls ? extra.p[n][i * ncls + j] : 0.f;
+            for (int n = 0; n < NX; ++n) q[n][j] = j < ncls ? args.p[n][i * ncls + j] : 0.f;
         }
 #pragma unroll
         for (int n = 0; n < NX; ++n) x[n] = q[n];
-        acc += TERM::template pixel<MAXC, GRAD>(z, x, ncls, gk, z);
+        acc += TERM::template pixel<C, GRAD>(z, x, ncls, gk, z, lane, lab, c);
         if (GRAD) {
 #pragma unroll
-            for (int j = 0; j < MAXC; ++j)
+            for (int j = 0; j < C; ++j)
                 if (j < ncls) dlogits[i * ncls + j] = z[j];
+        }
+        if constexpr (TERM::SIDE) {
+            args.labels[i] = (uint8_t)lab;
+            args.conf[i] = c;
         }
     }
     // block sum in a fixed order: shuffle tree per wave, then the four waves pairwise
@@ -121,6 +153,7 @@ __global__ void __launch_bounds__(NT) stream_kernel(const float* __restrict__ lo
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+    lane.block_end(args, ncls);
 }
 
 // one block: the partials in a fixed order in double -> out[0] = sum * scale.  (static on purpose: a kernel defined in a header needs
@@ -132,12 +165,12 @@ static __global__ void __launch_bounds__(NT) final_kernel(const float* __restric
 }
 
 template <typename TERM, bool VEC5>
-void launch_stream(const float* logits, const Extra<TERM::NEXTRA>& extra, float* dlogits, float* part, long long P, int ncls, float gk,
+void launch_stream(const float* logits, const typename TERM::Args& args, float* dlogits, float* part, long long P, int ncls, float gk,
                    int nblk, hipStream_t st) {
     if (dlogits)
-        hipLaunchKernelGGL((stream_kernel<TERM, VEC5, true>), dim3(nblk), dim3(NT), 0, st, logits, dlogits, part, P, ncls, gk, extra);
+        hipLaunchKernelGGL((stream_kernel<TERM, VEC5, true>), dim3(nblk), dim3(NT), 0, st, logits, dlogits, part, P, ncls, gk, args);
     else
-        hipLaunchKernelGGL((stream_kernel<TERM, VEC5, false>), dim3(nblk), dim3(NT), 0, st, logits, dlogits, part, P, ncls, gk, extra);
+        hipLaunchKernelGGL((stream_kernel<TERM, VEC5, false>), dim3(nblk), dim3(NT), 0, st, logits, dlogits, part, P, ncls, gk, args);
 }
 
 // PNP_CHECK_LAUNCH with the entry point in front: the kernels are shared, `who` says which term failed
@@ -147,21 +180,33 @@ inline bool launch_failed(const char* who, const char* kernel) {
     return e != hipSuccess;
 }
 
-// what every term's entry point (`who`) does behind its argument checks: the two launches.  extra: the term's NEXTRA inputs; dlogits may
-// be null (value only); workspace: workspace_bytes(P) bytes
+// the first launch of a term's entry point (`who`): blocks(P) workgroups of the instance that the operands allow.  args: the term's
+// extra inputs and whatever else it reads; dlogits may be null (value only); part: one float per workgroup
 template <typename TERM>
-int run(const char* who, const float* logits, const Extra<TERM::NEXTRA>& extra, long long P, int ncls, double scale, float gk,
-        float* dlogits, float* out, void* workspace, hipStream_t st) {
+int run_stream(const char* who, const float* logits, const typename TERM::Args& args, long long P, int ncls, float gk, float* dlogits,
+               float* part, hipStream_t st) {
     const int nblk = blocks(P);
-    float* part = (float*)workspace;
     uintptr_t bases = (uintptr_t)logits | (uintptr_t)dlogits;      // VEC5 needs every base it reads or writes 16-byte aligned
-    for (int n = 0; n < TERM::NEXTRA; ++n) bases |= (uintptr_t)extra.p[n];
-    if (ncls == 5 && P >= 4 && (bases & 15) == 0)
-        launch_stream<TERM, true>(logits, extra, dlogits, part, P, ncls, gk, nblk, st);
+    for (int n = 0; n < TERM::NEXTRA; ++n) bases |= (uintptr_t)args.p[n];
+    bool vec5 = ncls == 5 && P >= 4;
+    if constexpr (TERM::SIDE) {                                    // (four confidences are one float4, four label bytes one uint32_t)
+        bases |= (uintptr_t)args.conf;
+        vec5 = vec5 && ((uintptr_t)args.labels & 3) == 0;
+    }
+    if (vec5 && (bases & 15) == 0)
+        launch_stream<TERM, true>(logits, args, dlogits, part, P, ncls, gk, nblk, st);
     else
-        launch_stream<TERM, false>(logits, extra, dlogits, part, P, ncls, gk, nblk, st);
-    if (launch_failed(who, "pixel_loss::stream_kernel")) return PNP_ELAUNCH;
-    hipLaunchKernelGGL(final_kernel, dim3(1), dim3(NT), 0, st, (const float*)part, nblk, scale, out);
+        launch_stream<TERM, false>(logits, args, dlogits, part, P, ncls, gk, nblk, st);
+    return launch_failed(who, "pixel_loss::stream_kernel") ? PNP_ELAUNCH : PNP_OK;
+}
+
+// what the entry point of a term with one output does behind its argument checks: the two launches.  workspace: workspace_bytes(P) bytes
+template <typename TERM>
+int run(const char* who, const float* logits, const typename TERM::Args& args, long long P, int ncls, double scale, float gk,
+        float* dlogits, float* out, void* workspace, hipStream_t st) {
+    float* part = (float*)workspace;
+    if (const int rc = run_stream<TERM>(who, logits, args, P, ncls, gk, dlogits, part, st)) return rc;
+    hipLaunchKernelGGL(final_kernel, dim3(1), dim3(NT), 0, st, (const float*)part, blocks(P), scale, out);
     return launch_failed(who, "pixel_loss::final_kernel") ? PNP_ELAUNCH : PNP_OK;
 }
 

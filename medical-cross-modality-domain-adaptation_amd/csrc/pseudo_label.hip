@@ -5,10 +5,12 @@
 //   exponential is exactly 1).  Pixel i is SELECTED iff class k_i is in the class mask and c_i >= tau[k_i].
 //   L = (1/P) sum_selected log s_i  (= -log p_{i,k_i}, from the log-softmax),  dL/dz_ij = (p_ij - [j == k_i]) / P, 0 when not selected
 //
-//   loss     stream   one pass in the manner of pixel_loss::stream_kernel (five float4 per four pixels at ncls == 5, a scalar loop
-//                     otherwise): gradient, class | selected byte, confidence, per-block partial of the loss sum, per-block integer
-//                     partials of the pixels predicted as / selected as every class
-//            final    one block adds the loss partials in a fixed order (block_sum.h), one block per counter adds its integer partials
+//   loss     stream   pixel_loss::stream_kernel<PseudoLabelTerm, ., .>, the streaming pass of the per-pixel skeleton (pixel_loss.h): gradient
+//                     and per-block partial of the loss sum as for every term; the class | selected byte and the confidence are the
+//                     skeleton's side outputs; thresholds and counters are the term's per-thread state, whose block_end writes the
+//                     per-block integer partials of the pixels predicted as / selected as every class
+//            final    the term's own second launch: one block adds the loss partials in a fixed order (block_sum.h), one block per
+//                     counter adds its integer partials
 //   update   init     zero the 4 x [ncls][256] histograms and the per-class selection state
 //            hist x 4 per block: LDS histograms of the round's 8-bit digit of the confidence's bit pattern (a positive float orders as
 //                     its unsigned integer), one per class, over the pixels whose key shares their class's prefix; integer atomics of
@@ -30,112 +32,74 @@ using pixel_loss::NT;
 
 // ---- the loss ------------------------------------------------------------------------------------------------------------------------
 
-// one pixel: z[0..C) -> log s when selected, else 0; lab = k | selected << 7, conf = 1 / s; g[0..C) = gk (p - onehot(k)) or 0 when GRAD
-// (g may alias z); cnt[j] / cnt[C + j] count the pixels predicted as / selected as class j
-template <int C, bool GRAD>
-__device__ __forceinline__ float pl_pixel(const float* z, int ncls, const float* tau, uint32_t cmask, float gk, float* g, uint32_t& lab,
-                                          float& conf, int* cnt) {
-    float e[C], m;
-    const float s = pixel_loss::softmax_exp<C>(z, ncls, e, m);
-    int k = 0;
-#pragma unroll
-    for (int j = C - 1; j > 0; --j)
-        if (j < ncls && z[j] == m) k = j;
-    if (z[0] == m) k = 0;
-    conf = 1.0f / s;
-    bool sel = false;      // conf >= tau[k] without indexing tau by k: the thresholds stay in registers
-#pragma unroll
-    for (int j = 0; j < C; ++j) sel |= (j == k) & (conf >= tau[j]);
-    sel &= (cmask >> k) & 1u;
-    lab = (uint32_t)k | (sel ? 0x80u : 0u);
-#pragma unroll
-    for (int j = 0; j < C; ++j) {
-        cnt[j] += (j == k);
-        cnt[C + j] += (sel && j == k);
-    }
-    if (GRAD) {
-#pragma unroll
-        for (int j = 0; j < C; ++j) g[j] = sel ? gk * (e[j] * conf - (j == k ? 1.f : 0.f)) : 0.f;
-    }
-    return sel ? logf(s) : 0.f;
-}
+// the term of the per-pixel skeleton (pixel_loss.h), with all three of its options: thresholds and counters per thread, a class byte and
+// a confidence per pixel, integer partials per block
+struct PseudoLabelTerm {
+    static constexpr int NEXTRA = 0;
+    static constexpr bool SIDE = true;
+    struct Args : pixel_loss::Extra<0> {
+        const float* thresholds;      // [ncls], device memory
+        uint8_t* labels;              // [P]
+        float* conf;                  // [P]
+        int* part_cnt;                // [2 ncls][gridDim.x]: every counter's partials are one contiguous list
+        uint32_t cmask;
+    };
 
-// VEC5: ncls == 5, every base aligned for its vector type (logits, dlogits, conf: 16 bytes; labels: 4)
-template <bool VEC5, bool GRAD>
-__global__ void __launch_bounds__(NT) pl_stream_kernel(const float* __restrict__ logits, const float* __restrict__ thresholds,
-                                                       float* __restrict__ dlogits, uint8_t* __restrict__ labels, float* __restrict__ conf,
-                                                       float* __restrict__ part, int* __restrict__ part_cnt, long long P, int ncls,
-                                                       uint32_t cmask, float gk) {
-    constexpr int C = VEC5 ? 5 : MAXC;
-    __shared__ float lds[4];
-    __shared__ int lcnt[2 * MAXC];
-    if (threadIdx.x < 2 * MAXC) lcnt[threadIdx.x] = 0;
-    float tau[C];
+    // tau: the thresholds, in registers; cnt[j]: the pixels this thread saw predicted as class j in the low half, selected as class j in
+    // the high half (P < 2^31 over 2 048 x 256 threads at the cap: at most 4 096 pixels a thread, so neither half overflows)
+    template <int C>
+    struct Lane {
+        float tau[C];
+        uint32_t cnt[C] = {};
+        uint32_t cmask;
+        __device__ __forceinline__ Lane(const Args& a, int ncls) : cmask(a.cmask) {
 #pragma unroll
-    for (int j = 0; j < C; ++j) tau[j] = j < ncls ? thresholds[j] : 0.f;
-    int cnt[2 * C] = {};
-    float acc = 0.f;
-    const long long gs = (long long)gridDim.x * NT;
-    const long long t0 = (long long)blockIdx.x * NT + threadIdx.x;
-    long long first = 0;
-    if (VEC5) {
-        const long long ngrp = P >> 2;
-        const float4* __restrict__ in = reinterpret_cast<const float4*>(logits);
-        float4* __restrict__ out = reinterpret_cast<float4*>(dlogits);
-        for (long long g = t0; g < ngrp; g += gs) {
-            float f[20], c[4];
-            uint32_t lab[4];
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const float4 v = in[g * 5 + k];
-                f[4 * k] = v.x, f[4 * k + 1] = v.y, f[4 * k + 2] = v.z, f[4 * k + 3] = v.w;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc += pl_pixel<5, GRAD>(f + 5 * r, 5, tau, cmask, gk, f + 5 * r, lab[r], c[r], cnt);
-            if (GRAD) {
-#pragma unroll
-                for (int k = 0; k < 5; ++k) out[g * 5 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
-            }
-            reinterpret_cast<uint32_t*>(labels)[g] = lab[0] | lab[1] << 8 | lab[2] << 16 | lab[3] << 24;
-            reinterpret_cast<float4*>(conf)[g] = make_float4(c[0], c[1], c[2], c[3]);
+            for (int j = 0; j < C; ++j) tau[j] = j < ncls ? a.thresholds[j] : 0.f;
         }
-        first = ngrp << 2;
-    }
-    for (long long i = first + t0; i < P; i += gs) {
-        float z[C], c;
-        uint32_t lab;
+        // the block's counts: a shuffle tree per wave, the four wave sums through LDS.  Integers: any order gives the same number
+        __device__ __forceinline__ void block_end(const Args& a, int ncls) {
+            __shared__ int wcnt[4][2 * MAXC];
 #pragma unroll
-        for (int j = 0; j < C; ++j) z[j] = j < ncls ? logits[i * ncls + j] : 0.f;
-        acc += pl_pixel<C, GRAD>(z, ncls, tau, cmask, gk, z, lab, c, cnt);
+            for (int j = 0; j < 2 * C; ++j) {
+                int v = j < C ? cnt[j] & 0xffffu : cnt[j - C] >> 16;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+                if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6][j < C ? j : MAXC + j - C] = v;
+            }
+            __syncthreads();
+            if ((int)threadIdx.x < 2 * ncls) {
+                const int j = threadIdx.x, l = j < ncls ? j : MAXC + j - ncls;
+                a.part_cnt[(long long)j * gridDim.x + blockIdx.x] = (wcnt[0][l] + wcnt[1][l]) + (wcnt[2][l] + wcnt[3][l]);
+            }
+        }
+    };
+
+    // one pixel: z[0..C) -> log s when selected, else 0; lab = k | selected << 7, conf = 1 / s; g[0..C) = gk (p - onehot(k)) or 0 when GRAD
+    template <int C, bool GRAD>
+    static __device__ __forceinline__ float pixel(const float* z, const float* const*, int ncls, float gk, float* g, Lane<C>& lane, uint32_t& lab,
+                                                  float& conf) {
+        float e[C], m;
+        const float s = pixel_loss::softmax_exp<C>(z, ncls, e, m);
+        int k = 0;
+#pragma unroll
+        for (int j = C - 1; j > 0; --j)
+            if (j < ncls && z[j] == m) k = j;
+        if (z[0] == m) k = 0;
+        conf = 1.0f / s;
+        bool sel = false;      // conf >= tau[k] without indexing tau by k: the thresholds stay in registers
+#pragma unroll
+        for (int j = 0; j < C; ++j) sel |= (j == k) & (conf >= lane.tau[j]);
+        sel &= (lane.cmask >> k) & 1u;
+        lab = (uint32_t)k | (sel ? 0x80u : 0u);
+#pragma unroll
+        for (int j = 0; j < C; ++j) lane.cnt[j] += j == k ? (sel ? 0x10001u : 1u) : 0u;
         if (GRAD) {
 #pragma unroll
-            for (int j = 0; j < C; ++j)
-                if (j < ncls) dlogits[i * ncls + j] = z[j];
+            for (int j = 0; j < C; ++j) g[j] = sel ? gk * (e[j] * conf - (j == k ? 1.f : 0.f)) : 0.f;
         }
-        labels[i] = (uint8_t)lab;
-        conf[i] = c;
+        return sel ? logf(s) : 0.f;
     }
-    __syncthreads();      // lcnt is zero
-    // block sums: the loss in the fixed order of pixel_loss::stream_kernel; the counts are integers, any order gives the same number
-    float s = acc;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-#pragma unroll
-    for (int j = 0; j < 2 * C; ++j) {
-        int v = cnt[j];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if ((threadIdx.x & 63) == 0 && v) atomicAdd(&lcnt[(j < C ? 0 : MAXC) + (j < C ? j : j - C)], v);
-    }
-    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-    // part_cnt [2 ncls][gridDim.x]: every counter's partials are one contiguous list
-    if ((int)threadIdx.x < 2 * ncls) {
-        const int j = threadIdx.x;
-        part_cnt[(long long)j * gridDim.x + blockIdx.x] = lcnt[j < ncls ? j : MAXC + j - ncls];
-    }
-}
+};
 
 // 1 + 2 ncls blocks, so that no list waits for another: block 1 + j adds counter j's partials -> counts[j] (counts[0..ncls) = n_k,
 // counts[ncls..2 ncls) = m_k); block 0 adds the loss partials through the fixed-order tree in double -> out[0] = L, and all the selected
@@ -176,17 +140,6 @@ LossLayout loss_layout(long long P, int ncls) {
     L.cnt = nblk * sizeof(float);
     L.total = L.cnt + nblk * 2 * (size_t)(ncls > 0 ? ncls : 0) * sizeof(int);
     return L;
-}
-
-template <bool VEC5>
-void launch_pl_stream(const float* logits, const float* thresholds, float* dlogits, uint8_t* labels, float* conf, float* part, int* part_cnt,
-                      long long P, int ncls, uint32_t cmask, float gk, int nblk, hipStream_t st) {
-    if (dlogits)
-        hipLaunchKernelGGL((pl_stream_kernel<VEC5, true>), dim3(nblk), dim3(NT), 0, st, logits, thresholds, dlogits, labels, conf, part,
-                           part_cnt, P, ncls, cmask, gk);
-    else
-        hipLaunchKernelGGL((pl_stream_kernel<VEC5, false>), dim3(nblk), dim3(NT), 0, st, logits, thresholds, dlogits, labels, conf, part,
-                           part_cnt, P, ncls, cmask, gk);
 }
 
 // ---- the threshold update --------------------------------------------------------------------------------------------------------------
@@ -323,12 +276,8 @@ int pnp_pseudo_label_loss(const float* logits, const float* thresholds, int64_t 
     float* part = (float*)((char*)workspace + L.part);
     int* part_cnt = (int*)((char*)workspace + L.cnt);
     const float gk = (float)((double)coef / (double)P);
-    const uintptr_t b16 = (uintptr_t)logits | (uintptr_t)dlogits | (uintptr_t)conf;
-    if (ncls == 5 && P >= 4 && (b16 & 15) == 0 && ((uintptr_t)labels & 3) == 0)
-        launch_pl_stream<true>(logits, thresholds, dlogits, labels, conf, part, part_cnt, (long long)P, ncls, class_mask, gk, nblk, st);
-    else
-        launch_pl_stream<false>(logits, thresholds, dlogits, labels, conf, part, part_cnt, (long long)P, ncls, class_mask, gk, nblk, st);
-    if (pixel_loss::launch_failed(who, "pl_stream_kernel")) return PNP_ELAUNCH;
+    const PseudoLabelTerm::Args args{{}, thresholds, labels, conf, part_cnt, class_mask};
+    if (const int rc = pixel_loss::run_stream<PseudoLabelTerm>(who, logits, args, (long long)P, ncls, gk, dlogits, part, st)) return rc;
     hipLaunchKernelGGL(pl_final_kernel, dim3(1 + 2 * ncls), dim3(NT), 0, st, (const float*)part, (const int*)part_cnt, nblk, (int)ncls, 1.0 / (double)P,
                        out, counts);
     return pixel_loss::launch_failed(who, "pl_final_kernel") ? PNP_ELAUNCH : PNP_OK;

@@ -588,10 +588,10 @@ class WganLossFn(Function):
 
 class _SavedGradRoot(Function):
     """a ROOT of backward whose forward has already written its gradient with respect to the first input (and saved it): backward hands
-    it on, with None for every other input"""
+    it on, with None for every other input (whatever the forward returns besides the value: their gradients are not read)"""
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, *douts):
         return (ctx.saved_tensors[0],) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
@@ -620,10 +620,6 @@ class PseudoLabelLossFn(_SavedGradRoot):
         ctx.save_for_backward(dl)
         ctx.mark_non_differentiable(share, counts, labels, conf)
         return value, share, counts, labels, conf
-
-    @staticmethod
-    def backward(ctx, dout, *unused):
-        return (ctx.saved_tensors[0],) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
 class BoundaryLossFn(_SavedGradRoot):

@@ -1,10 +1,11 @@
 """Cost of the opt-in pseudo-label term of the generator step, after tools/bench_entropy.py: the joint step (one dis step and
 one gen step) of --phase train-gan at B = 16 on one GPU with pl_weight = 0 (the reference's step) against pl_weight > 0, alternating the
 two nets round by round so that the spread of one configuration is visible next to the difference between the two; the loss launch pair
-alone on logits [16 * 256 * 256, 5] next to pnp_softmax_entropy with a gradient on the same logits in the same process (the pseudo-label
-pass writes 5 more bytes per pixel: the class byte and the confidence); and the threshold update alone, all nine launches.  Kernel times
-are device times: `--reps` calls recorded into one hipGraph and replayed between two events, once on one buffer set (it stays in the
-Infinity Cache) and once rotating over sets larger than it together (HBM).  Prints one JSON object (and writes it to --out)."""
+alone on logits [--pixels, 5] (default 16 * 256 * 256) next to pnp_softmax_entropy with a gradient on the same logits in the same process
+(the pseudo-label pass writes 5 more bytes per pixel: the class byte and the confidence); and the threshold update alone, all nine
+launches.  Kernel times are device times: `--reps` calls recorded into one hipGraph and replayed between two events, once on one buffer
+set (it stays in the Infinity Cache) and once rotating over sets larger than it together (HBM).  Prints one JSON object (and writes it
+to --out)."""
 import argparse
 import json
 import os
@@ -45,10 +46,10 @@ def time_steps(tr, mr, ct, steps, seed0):
     return e0.elapsed_time(e1) / steps
 
 
-def kernel_bench(dev, reps):
-    P, C = 16 * 256 * 256, 5
+def kernel_bench(dev, reps, P):
+    C = 5
     nbytes = P * C * 4
-    nrot = 8                        # 8 x (21 MB logits + 21 MB gradient + 5 MB maps) = 376 MB: past the 256 MiB Infinity Cache
+    nrot = 8                        # at the default P: 8 x (21 MB logits + 21 MB gradient + 5 MB maps) = 376 MB: past the 256 MiB Infinity Cache
     gen = torch.Generator(device=dev).manual_seed(0)
     zs = [torch.randn((P, C), device=dev, generator=gen) * 3.0 for _ in range(nrot)]
     tau = torch.tensor([0.9, 0.8, 0.85, 0.7, 0.75], device=dev)
@@ -90,6 +91,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--pl-weight", type=float, default=0.01)
     ap.add_argument("--reps", type=int, default=64, help="calls per recorded graph of the kernel measurement")
+    ap.add_argument("--pixels", type=int, default=16 * 256 * 256, help="P of the kernel measurement (2048 * 2048: the grid cap of the loss)")
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -117,7 +119,7 @@ def main():
         res["peak_mem_gb"] = torch.cuda.max_memory_allocated() / 1e9
         del trs, tr, net
         torch.cuda.empty_cache()
-    res["kernels"] = kernel_bench(dev, a.reps)
+    res["kernels"] = kernel_bench(dev, a.reps, a.pixels)
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:

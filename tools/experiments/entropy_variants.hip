@@ -21,7 +21,9 @@ __global__ void __launch_bounds__(NT) ent_lds_kernel(const float* __restrict__ l
     __shared__ float lds[4];
     const float4* __restrict__ in = reinterpret_cast<const float4*>(logits);
     float4* __restrict__ out = reinterpret_cast<float4*>(dlogits);
-    float acc = 0.f;
+    float acc = 0.f, conf;      // (the term has no per-thread state and no side outputs: lane, lab and conf are the signature's only)
+    uint32_t lab;
+    EntropyTerm::Lane<5> lane({}, 5);
     for (long long t = blockIdx.x; t < ntile; t += gridDim.x) {
         const long long base = t * (5 * NT);
 #pragma unroll
@@ -34,7 +36,7 @@ __global__ void __launch_bounds__(NT) ent_lds_kernel(const float* __restrict__ l
             f[4 * k] = v.x, f[4 * k + 1] = v.y, f[4 * k + 2] = v.z, f[4 * k + 3] = v.w;
         }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc += EntropyTerm::pixel<5, GRAD>(f + 5 * r, nullptr, 5, gk, f + 5 * r);
+        for (int r = 0; r < 4; ++r) acc += EntropyTerm::pixel<5, GRAD>(f + 5 * r, nullptr, 5, gk, f + 5 * r, lane, lab, conf);
         if (GRAD) {
 #pragma unroll
             for (int k = 0; k < 5; ++k) tile[threadIdx.x * 5 + k] = make_float4(f[4 * k], f[4 * k + 1], f[4 * k + 2], f[4 * k + 3]);
@@ -81,7 +83,7 @@ int main() {
         for (int grad = 1; grad >= 0; --grad) {
             auto launch = [&](int b) {
                 if (v.kind == 0) {
-                    const pixel_loss::Extra<0> none{};
+                    const EntropyTerm::Args none{};
                     if (grad)
                         hipLaunchKernelGGL((pixel_loss::stream_kernel<EntropyTerm, true, true>), dim3(v.blocks), dim3(NT), 0, 0, z[b], g[b], part, P,
                                            C, gk, none);
