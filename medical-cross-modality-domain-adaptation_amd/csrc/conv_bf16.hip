@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_taps_bf16_kernel(ConvArgs a)
 
 // ===================================== filter gradient ============================================
 // dW[m' = (tap, c)][k] = sum_p x[p shifted by tap][c] * dy[p][k]; a.x = x, a.w = dy ([P][K]); reduction over output pixels p, split over
-// workgroups (grid.x = tiles * nsplit, partials summed by conv_igemm.hip's splitk_reduce_kernel).  Both operands are pixel-major in
+// workgroups (grid.x = tiles * nsplit, partials summed by split_sum.h's serial_kernel<Plain>).  Both operands are pixel-major in
 // memory, so both tiles are transposed on the way into LDS.
 template <int BM, int BN, int WM, int WN>
 __global__ void __launch_bounds__(NTHREADS, 2) conv_wgrad_bf16_kernel(ConvArgs a) {

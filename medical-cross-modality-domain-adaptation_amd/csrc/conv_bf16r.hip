@@ -249,7 +249,7 @@ __global__ void __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 2 : (NBUF * (BM 
 // bytes apart, so the 16-byte chunk index is XOR-ed with 4 * (row & 3) (4 * ((row >> 1) & 1) for 128-byte rows): the 4 rows x 4 chunks
 // a half-wave reads then cover the 256-byte bank row exactly once.
 // a.x = x (bf16), a.w = dy (bf16, [P][K]); reduction split over workgroups in chunks of 64 pixels (grid.x = tiles * nsplit; partials
-// summed by conv_igemm.hip's splitk_reduce_kernel).  A tile holds ONE tap (C % BM == 0), OW and OH*OW are powers of two.
+// summed by split_sum.h's serial_kernel<Plain>).  A tile holds ONE tap (C % BM == 0), OW and OH*OW are powers of two.
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 // (inline asm, not __builtin_amdgcn_ds_read_tr16_b64_v4i16: behind an LDS-DMA in flight hipcc fences the builtin with s_waitcnt vmcnt(0))
 __device__ __forceinline__ s16x4 lds_tr16_asm(unsigned lds_byte_addr) {

@@ -1,6 +1,7 @@
 // conv_common.h — what the convolution translation units share: the kernel argument block, tile / XCD mapping, accumulators and the
-// buffer-descriptor loads (conv_igemm.hip: fp32 MFMA + vector-ALU kernels, the plan of every pass — plan_fwd / plan_dgrad / plan_wgrad, the
-// one place that combines the predicates declared below — and the entry points; conv_bf16.hip: bf16-operand MFMA kernels).
+// buffer-descriptor loads (conv_igemm.hip: fp32 MFMA kernels, the plan of every pass — plan_fwd / plan_dgrad / plan_wgrad, the one place
+// that combines the predicates declared below — and the entry points; conv_valu.hip: the vector-ALU kernels of the K <= 16 layers;
+// conv_bf16.hip: bf16-operand MFMA kernels; split_sum.h: the sums over reduction-split partials).
 #pragma once
 #include "pnp_common.h"
 
@@ -370,12 +371,21 @@ struct DgradPhase {
 int plan_phases(const pnp_conv_geom* g, DgradPhase* ph);
 pnp_conv_geom phase_geom(const pnp_conv_geom* g, const DgradPhase& p);
 // 3x3 stride-1 convolutions with exactly 16 output channels and 16 / 32 input channels on the 16x16x4 MFMA (conv_small.hip): forward,
-// data gradient (kind 1; honours res_add) and filter gradient (per-workgroup partials [n16_wgrad_blocks][9*C][16] -> splitk_reduce_many)
+// data gradient (kind 1; honours res_add) and filter gradient (per-workgroup partials [n16_wgrad_blocks][9*C][16] -> split_sum's sliced_kernel<1>)
 bool n16_geom_ok(const pnp_conv_geom* g);
 bool n16_wgrad_ok(const pnp_conv_geom* g);       // superset: filter gradients of 16/32 -> 32/64 channel layers too
 int launch_n16_fwd(const ConvArgs& a, int kind, hipStream_t st);
 int n16_wgrad_blocks(const pnp_conv_geom* g);
 int launch_n16_wgrad(const ConvArgs& a, float* part, hipStream_t st);
+// convolutions with K <= 16 filters on the vector ALUs (conv_valu.hip).  narrow_fwd_ok: a stride-1 zero-padded layer the forward kernel
+// takes (route NARROW; launch_narrow: x, w, y and geometry of the forward, or of a data gradient expressed as one; dropout from `a`).
+// wgd_ok: the filter gradient (route WGD): per-workgroup partials [wgd_blocks][R*S*C*K] in wgd_workspace_bytes(g) -> split_sum's sliced_kernel<1>
+bool narrow_fwd_ok(const pnp_conv_geom* g);
+int launch_narrow(const float* x, const float* w, float* y, const pnp_conv_geom* g, const ConvArgs& a, hipStream_t st);
+bool wgd_ok(const pnp_conv_geom* g);
+size_t wgd_workspace_bytes(const pnp_conv_geom* g);
+int wgd_blocks(const pnp_conv_geom* g);
+int launch_wgd(const float* x, const float* dy, float* part, const pnp_conv_geom* g, const ConvArgs& a, hipStream_t st);
 // Winograd F(2x2, 3x3) route of the wide stride-1 3x3 convolutions, forward and data gradient (conv_wino.hip).  eligible: the geometry can
 // run it; chosen: eligible and the policy takes it (PNP_WINOGRAD = 0 never / 1 where the cost model says it pays / 2 wherever eligible).
 // launch_wino runs Winograd and nothing else, with the whole epilogue of ConvArgs (dropout, residual add, statistics partials, fused inference BN); its statistics

@@ -17,14 +17,16 @@
 //   conv_taps_kernel        zero/VALID padding, C % 32 == 0, filter shapes 1x1..3x3 / 5x5, any stride (forward, stride-1 data gradient,
 //                           stride-phase sub-filters): taps unrolled, scalar offsets; optional fused inference-BN epilogue
 //   conv_fwd_kernel         everything else on the matrix cores (any C, in-kernel SYMMETRIC mirror, filters smaller than the stride)
-//   conv_wgrad_kernel       filter gradient; reduction over pixels split across workgroups + splitk_reduce_kernel
-//   conv_fwd_narrow_kernel  K <= 16 outputs at stride 1 on the vector ALUs (LDS patch, filters through the scalar cache, v_pk_fma_f32)
-//   wgrad_direct(4)_kernel  filter gradient for K <= 16 on the vector ALUs (dy through the scalar cache) + splitk_reduce_many_kernel
-//   flip_transpose(_phase)_kernel, splitk_reduce(_scatter/_drop)_kernel, sympad_fwd/bwd_kernel, bn_fold_kernel, naive_conv_kernel
-// Host planners: choose_tile / choose_split (dispatch-round filling), plan_phases (strided data gradients), wgrad_plan_split, wgd_plan,
-// narrow_fwd_ok answer "can / should this family take the layer", like the route files' predicates (conv_common.h).  plan_fwd / plan_dgrad /
+//   conv_wgrad_kernel       filter gradient; reduction over pixels split across workgroups + split_sum.h's serial_kernel<Plain>
+//   flip_transpose(_phase)_kernel, sympad_fwd/bwd_kernel, bn_fold_kernel, naive_conv_kernel
+// The partial sums of every split reduction are split_sum.h's (serial_kernel<Plain / Drop / Scatter>, sliced_kernel<1>); the vector-ALU
+// kernels of the K <= 16 layers (routes NARROW, WGD) live in conv_valu.hip.
+// Host planners: choose_tile / choose_split (dispatch-round filling), plan_phases (strided data gradients), wgrad_plan_split, ring_tile
+// answer "can / should this family take the layer", like the route files' predicates (conv_common.h).  plan_fwd / plan_dgrad /
 // plan_wgrad alone COMBINE them: one cascade per pass, read by the workspace / partial-row / route queries (pnp_conv2d_*_workspace_bytes,
 // pnp_conv2d_fwd_stats*_parts, pnp_conv2d_wino_chosen, pnp_conv2d_route; tests/test_abi.py) and by the entry points, which switch on the route.
+// The plan also fixes the reduction split and the workspace layout (dgrad_ws): the launchers receive the planned split count and only fit
+// it to the bytes the caller brought (fit_split); none of them calls choose_split / wgrad_plan_split.
 //
 // LDS layouts (dwords):
 //   fwd  A tile  [BM][36]     row = output pixel, 32 k's contiguous (+4 pad). A fragments are read with
@@ -36,6 +38,7 @@
 //   wgrad A tile [32][BM+4]   row = pixel (reduction index), m' contiguous; ds_read_b32 like B.
 #include "conv_common.h"
 #include "conv_mma.h"
+#include "split_sum.h"
 
 using namespace pnpconv;
 
@@ -1153,351 +1156,6 @@ __global__ void __launch_bounds__(NTHREADS, (BN <= 64 ? PNP_WGRAD_NARROW_WAVES :
     wgrad_epilogue<TM, TN>(a, acc, a.y + (size_t)z * a.split_stride, mm0, n0, wm0, wn0, lane);
 }
 
-__global__ void splitk_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, size_t n, int nsplit,
-                                     size_t stride, int accumulate) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t gs = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += gs) {
-        float s = 0.f;
-        for (int z = 0; z < nsplit; ++z) s += part[(size_t)z * stride + i];
-        out[i] = accumulate ? out[i] + s : s;
-    }
-}
-// The same sum for MANY partials of a SMALL gradient (cls1's 64->64 @256^2 filter gradient at N = 32: 300+ partials of 36 864 values —
-// one thread per value walking all of them serially ran at 0.3 TB/s, 247 us; r06 trace), in two deterministic levels and 16 bytes per lane:
-// level 1 (blockIdx.y = group g): the partials [g zg, (g + 1) zg) summed in order into the group's FIRST partial (in place: that row is read
-// by this thread only); level 2: the group rows summed in order into out.  n % 4 == 0, 16-byte aligned.
-__global__ void __launch_bounds__(256) splitk_reduce_group_kernel(float* __restrict__ part, size_t n4, int nsplit, size_t stride, int zg) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n4) return;
-    const int z0 = blockIdx.y * zg, z1 = min(z0 + zg, nsplit);
-    f32x4 s = *reinterpret_cast<const f32x4*>(part + (size_t)z0 * stride + i * 4);
-    for (int z = z0 + 1; z < z1; ++z) s += *reinterpret_cast<const f32x4*>(part + (size_t)z * stride + i * 4);
-    *reinterpret_cast<f32x4*>(part + (size_t)z0 * stride + i * 4) = s;
-}
-static int launch_splitk_reduce(float* ws, float* out, size_t n, int nsplit, int accumulate, hipStream_t st) {
-    // OFF by default: the filter gradients run on the side stream next to the data gradients, so the 0.2 ms per step this saves in kernel
-    // time does not show in the step (within-run A/B: 269.65 vs 270.65 slices/s), and it changes the summation ORDER of every split
-    // direct filter gradient — one more realisation of the chaotic fp32-vs-fp32 comparison of tests/test_gpu_adversarial.py for nothing
-    static const int two_level = getenv("PNP_SPLITK_TWO_LEVEL") ? atoi(getenv("PNP_SPLITK_TWO_LEVEL")) : 0;
-    int nz = nsplit;
-    size_t stride = n;
-    if (two_level && nsplit >= 32 && (n % 4) == 0 && ((uintptr_t)ws % 16) == 0 && n / 4 * (size_t)nsplit >= (size_t)1 << 18) {
-        const int zg = 16, ng = pnp_cdiv(nsplit, zg);
-        hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3((unsigned)pnp_cdiv((long long)(n / 4), 256), (unsigned)ng), dim3(256), 0, st, ws, n / 4, nsplit, n, zg);
-        PNP_CHECK_LAUNCH("splitk_reduce_group_kernel");
-        nz = ng;
-        stride = n * zg;
-    }
-    int nb = pnp_cdiv((long long)n, 256);
-    if (nb > 4096) nb = 4096;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, (const float*)ws, out, n, nz, stride, accumulate);
-    PNP_CHECK_LAUNCH("splitk_reduce_kernel");
-    return PNP_OK;
-}
-
-// ===================================== direct forward conv for narrow outputs ============================================
-// K <= 16 output channels at stride 1 (the 40->5 logits conv and g1's 16->16 convs at 256^2, and their data gradients when the INPUT
-// is that narrow): an MFMA tile is half to 5/6 empty in N (40->5 measured 15 TF/s, bound by the matrix pipe doing mostly zeros).  A thread owns one output pixel and its K accumulators.  The workgroup's input patch
-// ((8 + (R-1)dil) x (32 + (S-1)dil) pixels x C channels) is staged once in LDS with a pixel stride of C+4 floats when C/4 is even (an odd
-// number of 16-byte slots per pixel: the 64 lanes of a ds_read_b128 spread over all banks); the filter values are uniform over the
-// wave and come through the scalar cache (constant address space), so the inner loop is v_pk_fma_f32 acc, x, s[w].
-struct NarrowArgs {
-    const float* x;
-    const float* w;
-    float* y;
-    int N, H, W, C, K, R, S, OH, OW, dil, pad_t, pad_l;
-    int PH, PW, CP;                 // patch extent (pixels) and padded pixel stride (floats)
-    int do_drop;
-    float drop_keep;
-    uint32_t drop_thresh, drop_key;
-    unsigned x_bytes;
-    const pnp_step_params* sp;
-    uint32_t drop_sid;
-};
-
-template <int KK, bool EXACT>
-__global__ void __launch_bounds__(256) conv_fwd_narrow_kernel(NarrowArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float xs[];
-    const int t = threadIdx.x;
-    const int tx = t & 31, ty = t >> 5;
-    const int ow0 = blockIdx.x * 32, oh0 = blockIdx.y * 8, n = blockIdx.z;
-    const int K = EXACT ? KK : a.K;
-    const int C4 = a.C >> 2;
-    // ---- stage the patch (zero outside the image) --------------------------------------------------------------------
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, a.x_bytes);
-    const int nvec = a.PH * a.PW * C4;
-    for (int i = t; i < nvec; i += 256) {
-        const int pix = i / C4, c4 = i - pix * C4;
-        const int pr = pix / a.PW, pc = pix - pr * a.PW;
-        const int ih = oh0 - a.pad_t + pr, iw = ow0 - a.pad_l + pc;
-        const bool ok = ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
-        const f32x4 v = bload4(rx, ok ? (unsigned)((((n * a.H + ih) * a.W + iw) * a.C + 4 * c4) * 4) : OOB);
-        *reinterpret_cast<f32x4*>(xs + pix * a.CP + 4 * c4) = v;
-    }
-    __syncthreads();
-    // ---- accumulate ---------------------------------------------------------------------------------------------------
-    pnp_cfloat* wc = (pnp_cfloat*)(uintptr_t)a.w;
-    constexpr int UNR = KK <= 8 ? 2 : 1;        // 4*KK filter values per channel quad live in SGPRs
-    float acc[KK];
-#pragma unroll
-    for (int k = 0; k < KK; ++k) acc[k] = 0.f;
-    for (int r = 0; r < a.R; ++r)
-        for (int sx = 0; sx < a.S; ++sx) {
-            const float* xp = xs + ((ty + r * a.dil) * a.PW + tx + sx * a.dil) * a.CP;
-            const int wbase = (r * a.S + sx) * a.C * K;
-#pragma unroll UNR
-            for (int c4 = 0; c4 < C4; ++c4) {
-                const f32x4 xv = *reinterpret_cast<const f32x4*>(xp + 4 * c4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int k = 0; k < KK; ++k)
-                        if (k < K) acc[k] = fmaf(xv[e], wc[wbase + (4 * c4 + e) * K + k], acc[k]);
-            }
-        }
-    const int oh = oh0 + ty, ow = ow0 + tx;
-    if (oh < a.OH && ow < a.OW) {
-        const size_t m = ((size_t)n * a.OH + oh) * a.OW + ow;
-#pragma unroll
-        for (int k = 0; k < KK; ++k)
-            if (k < K) {
-                const size_t idx = m * K + k;
-                float v = acc[k];
-                if (a.do_drop) v = pnp_drop_keep((uint32_t)idx, pnp_eff_drop_key(a.drop_key, a.sp, a.drop_sid), a.drop_thresh) ? v / a.drop_keep : 0.f;
-                a.y[idx] = v;
-            }
-    }
-}
-
-// ===================================== direct filter gradient for narrow outputs ============================================
-// K <= 16 output channels (g1's 16-channel convs, the 40->5 logits conv, the mask critic's first conv): an MFMA tile is at most half
-// full in N and the reduction (all pixels) is long, so this one runs on the vector ALUs.  A thread owns PPT (tap, channel) pairs x K
-// accumulators, walks the pixels of its workgroup's slab, reads ONE x value per pair and pixel plus the pixel's K dy values (the
-// same address for a whole pixel group: a broadcast load) and issues PPT*K FMAs.  Workgroups with few pairs split their slab over G
-// pixel groups and combine through LDS.  Partials [nblk][R*S*C*K] are summed by splitk_reduce_kernel (fixed order: deterministic).
-struct WgdArgs {
-    const float* x;
-    const float* dy;
-    float* part;
-    int N, H, W, C, K, R, S, OH, OW, stride, dil, pad_t, pad_l;
-    int P;             // N*OH*OW
-    int npairs;        // R*S*C
-    int G;             // pixel groups per workgroup (1 when a thread owns several pairs)
-    int ppb;           // pixels per workgroup
-    unsigned x_bytes, dy_bytes;
-};
-
-
-// UNI (one pixel group): the pixel index is uniform over the workgroup, so the K dy values come through the SCALAR cache into SGPRs
-// (v_fmac with an SGPR operand) instead of 64 lanes x 16 B of vector-memory traffic per wave and pixel for 64 useful bytes — the
-// texture-address unit, not the FMAs, bounded the first version (16->16: 0.54 ms).
-template <int KK, int PPT, bool EXACT, bool UNI>
-__global__ void __launch_bounds__(256) wgrad_direct_kernel(WgdArgs a) {
-    extern __shared__ float red[];      // [G][npairs*K], only when G > 1
-    const int t = threadIdx.x;
-    if (UNI && PPT == 1 && (t & ~63) >= a.npairs) return;      // whole wave without a pair (no barrier on this path)
-    const int g = (PPT == 1 && !UNI) ? t / a.npairs : 0;
-    const int j0 = (PPT == 1) ? t - g * a.npairs : t;
-    const bool active = g < a.G;
-    const int K = EXACT ? KK : a.K;
-    int coff[PPT], dh[PPT], dw[PPT];
-    bool pv[PPT];
-#pragma unroll
-    for (int q = 0; q < PPT; ++q) {
-        const int j = j0 + q * 256;
-        pv[q] = active && j < a.npairs;
-        const int jj = pv[q] ? j : 0;
-        const int tap = jj / a.C;
-        coff[q] = jj - tap * a.C;
-        const int r = tap / a.S;
-        dh[q] = r * a.dil - a.pad_t;
-        dw[q] = (tap - r * a.S) * a.dil - a.pad_l;
-    }
-    float acc[PPT][KK];
-#pragma unroll
-    for (int q = 0; q < PPT; ++q)
-#pragma unroll
-        for (int k = 0; k < KK; ++k) acc[q][k] = 0.f;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, a.x_bytes);
-    const __amdgpu_buffer_rsrc_t rd = make_rsrc(a.dy, a.dy_bytes);
-    const int p0 = blockIdx.x * a.ppb;
-    const int p1 = (p0 + a.ppb < a.P) ? p0 + a.ppb : a.P;
-    int p = UNI ? p0 : p0 + g;
-    pnp_cfloat* dyc = (pnp_cfloat*)(uintptr_t)a.dy;
-    const int OHW = a.OH * a.OW;
-    int n = p / OHW;
-    int rem = p - n * OHW;
-    int oh = rem / a.OW;
-    int ow = rem - oh * a.OW;
-    // U pixels per trip: all their loads are issued before the first FMA (one pixel per trip is bound by the global-load latency:
-    // 16->16 ran at 0.58 ms that way)
-    constexpr int U = 4;
-    for (; p < p1; p += U * a.G) {
-        float dv[U][KK], xv[U][PPT];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int pu = p + u * a.G;
-            const bool pin = pu < p1;
-            if constexpr (UNI) {
-                const size_t base = (size_t)(pin ? pu : p) * K;      // uniform; a pixel past the slab re-reads a valid row (its x is 0)
-#pragma unroll
-                for (int k = 0; k < KK; ++k) dv[u][k] = (k < K) ? dyc[base + k] : 0.f;
-            } else if constexpr (EXACT && (KK % 4) == 0) {
-#pragma unroll
-                for (int k4 = 0; k4 < KK / 4; ++k4) {
-                    const f32x4 v = bload4(rd, pin ? (unsigned)((pu * KK + 4 * k4) * 4) : OOB);
-                    dv[u][4 * k4] = v[0]; dv[u][4 * k4 + 1] = v[1]; dv[u][4 * k4 + 2] = v[2]; dv[u][4 * k4 + 3] = v[3];
-                }
-            } else {
-#pragma unroll
-                for (int k = 0; k < KK; ++k) dv[u][k] = (pin && k < K) ? bload1(rd, (unsigned)((pu * K + k) * 4)) : 0.f;
-            }
-            const int vh = oh * a.stride, vw = ow * a.stride;
-#pragma unroll
-            for (int q = 0; q < PPT; ++q) {
-                const int ih = vh + dh[q], iw = vw + dw[q];
-                const bool ok = pin & pv[q] & ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
-                xv[u][q] = bload1(rx, ok ? (unsigned)((((n * a.H + ih) * a.W + iw) * a.C + coff[q]) * 4) : OOB);
-            }
-            ow += a.G;
-            while (ow >= a.OW) {
-                ow -= a.OW;
-                if (++oh == a.OH) { oh = 0; ++n; }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int q = 0; q < PPT; ++q)
-#pragma unroll
-                for (int k = 0; k < KK; ++k) acc[q][k] = fmaf(xv[u][q], dv[u][k], acc[q][k]);
-    }
-    const int nout = a.npairs * K;
-    float* outp = a.part + (size_t)blockIdx.x * nout;
-    if (a.G > 1) {          // PPT == 1
-        if (active) {
-#pragma unroll
-            for (int k = 0; k < KK; ++k)
-                if (k < K) red[g * nout + j0 * K + k] = acc[0][k];
-        }
-        __syncthreads();
-        for (int e = t; e < nout; e += 256) {
-            float sum = 0.f;
-            for (int gg = 0; gg < a.G; ++gg) sum += red[gg * nout + e];
-            outp[e] = sum;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < PPT; ++q) {
-            if (pv[q]) {
-                const int j = j0 + q * 256;
-#pragma unroll
-                for (int k = 0; k < KK; ++k)
-                    if (k < K) outp[j * K + k] = acc[q][k];
-            }
-        }
-    }
-}
-
-// Same for C % 4 == 0 and many pairs (the 40->5 logits conv: 1000 pairs): a thread owns QPT quads of 4 consecutive channels of one
-// tap and fetches each with ONE 16-byte load — with one dword per pair the 4 loads per lane and pixel kept the texture-address unit
-// busy for the whole 0.41 ms of the kernel.  One pixel group (uniform pixel): dy through the scalar cache.
-template <int KK, int QPT, bool EXACT>
-__global__ void __launch_bounds__(256) wgrad_direct4_kernel(WgdArgs a) {
-    const int t = threadIdx.x;
-    const int nquads = a.npairs >> 2;
-    const int K = EXACT ? KK : a.K;
-    int coff[QPT], dh[QPT], dw[QPT];
-    bool pv[QPT];
-#pragma unroll
-    for (int q = 0; q < QPT; ++q) {
-        const int i = t + q * 256;
-        pv[q] = i < nquads;
-        const int j = pv[q] ? 4 * i : 0;
-        const int tap = j / a.C;
-        coff[q] = j - tap * a.C;
-        const int r = tap / a.S;
-        dh[q] = r * a.dil - a.pad_t;
-        dw[q] = (tap - r * a.S) * a.dil - a.pad_l;
-    }
-    float acc[QPT][4][KK];
-#pragma unroll
-    for (int q = 0; q < QPT; ++q)
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-            for (int k = 0; k < KK; ++k) acc[q][e][k] = 0.f;
-    const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, a.x_bytes);
-    pnp_cfloat* dyc = (pnp_cfloat*)(uintptr_t)a.dy;
-    const int p0 = blockIdx.x * a.ppb;
-    const int p1 = (p0 + a.ppb < a.P) ? p0 + a.ppb : a.P;
-    const int OHW = a.OH * a.OW;
-    int n = p0 / OHW;
-    int rem = p0 - n * OHW;
-    int oh = rem / a.OW;
-    int ow = rem - oh * a.OW;
-    constexpr int U = 4;
-    for (int p = p0; p < p1; p += U) {
-        float dv[U][KK];
-        f32x4 xv[U][QPT];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int pu = p + u;
-            const bool pin = pu < p1;
-            const size_t base = (size_t)(pin ? pu : p) * K;
-#pragma unroll
-            for (int k = 0; k < KK; ++k) dv[u][k] = (k < K) ? dyc[base + k] : 0.f;
-            const int vh = oh * a.stride, vw = ow * a.stride;
-#pragma unroll
-            for (int q = 0; q < QPT; ++q) {
-                const int ih = vh + dh[q], iw = vw + dw[q];
-                const bool ok = pin & pv[q] & ((unsigned)ih < (unsigned)a.H) & ((unsigned)iw < (unsigned)a.W);
-                xv[u][q] = bload4(rx, ok ? (unsigned)((((n * a.H + ih) * a.W + iw) * a.C + coff[q]) * 4) : OOB);
-            }
-            if (++ow == a.OW) {
-                ow = 0;
-                if (++oh == a.OH) { oh = 0; ++n; }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int q = 0; q < QPT; ++q)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-#pragma unroll
-                    for (int k = 0; k < KK; ++k) acc[q][e][k] = fmaf(xv[u][q][e], dv[u][k], acc[q][e][k]);
-    }
-    float* outp = a.part + (size_t)blockIdx.x * a.npairs * K;
-#pragma unroll
-    for (int q = 0; q < QPT; ++q) {
-        if (pv[q]) {
-            const int j = 4 * (t + q * 256);
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-#pragma unroll
-                for (int k = 0; k < KK; ++k)
-                    if (k < K) outp[(j + e) * K + k] = acc[q][e][k];
-        }
-    }
-}
-
-// forward conv with a split reduction: sum the partials, then the dropout of the fused conv->dropout (same element-index hash as the
-// un-split epilogue)
-__global__ void splitk_reduce_drop_kernel(const float* __restrict__ part, float* __restrict__ out, size_t n, int nsplit, size_t stride,
-                                          uint32_t drop_key, uint32_t drop_thresh, float drop_keep, const pnp_step_params* sp,
-                                          uint32_t drop_sid) {
-    drop_key = pnp_eff_drop_key(drop_key, sp, drop_sid);
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t gs = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += gs) {
-        float s = 0.f;
-        for (int z = 0; z < nsplit; ++z) s += part[(size_t)z * stride + i];
-        out[i] = pnp_drop_keep((uint32_t)i, drop_key, drop_thresh) ? s / drop_keep : 0.f;
-    }
-}
-
 // inference-mode batch norm as one multiply-add per channel: scale = gamma * rsqrt(var + eps), shift = beta - mean * scale
 __global__ void bn_fold_kernel(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
                                const float* __restrict__ var, float* __restrict__ scale, float* __restrict__ shift, int C, float eps) {
@@ -1506,38 +1164,6 @@ __global__ void bn_fold_kernel(const float* __restrict__ gamma, const float* __r
     const float sc = gamma[c] * (1.0f / sqrtf(var[c] + eps));
     scale[c] = sc;
     shift[c] = beta[c] - mean[c] * sc;
-}
-
-// many partials (one per workgroup of wgrad_direct_kernel), few outputs: 64 outputs x 16 slices of the partial list per workgroup
-__global__ void __launch_bounds__(1024) splitk_reduce_many_kernel(const float* __restrict__ part, float* __restrict__ out, int n,
-                                                                  int nsplit, int accumulate) {
-    __shared__ float red[16][64];
-    const int l = threadIdx.x & 63, sl = threadIdx.x >> 6;
-    const int e = blockIdx.x * 64 + l;
-    float s = 0.f;
-    if (e < n)
-        for (int z = sl; z < nsplit; z += 16) s += part[(size_t)z * n + e];
-    red[sl][l] = s;
-    __syncthreads();
-    if (sl == 0 && e < n) {
-        float tot = 0.f;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) tot += red[j][l];
-        out[e] = accumulate ? out[e] + tot : tot;
-    }
-}
-
-// split partials of one stride-phase ([nsplit][M][K] row-major) -> summed and scattered to the phase's pixels of dx
-__global__ void splitk_reduce_scatter_kernel(const float* __restrict__ part, ConvArgs a, int nsplit, size_t stride) {
-    const size_t n = (size_t)a.M * a.K;
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t gs = (size_t)gridDim.x * blockDim.x;
-    for (; i < n; i += gs) {
-        float s = 0.f;
-        for (int z = 0; z < nsplit; ++z) s += part[(size_t)z * stride + i];
-        const int m = (int)(i / a.K);
-        a.y[out_row(a, m, true) + (i - (size_t)m * a.K)] = s;
-    }
 }
 
 // every stride-phase sub-filter of w [R][S][C][K] in one launch: tap (r, s) belongs to phase (pa, pb) = (r % st, s % st) and lands,
@@ -1727,7 +1353,8 @@ int choose_tile(long long M, int K) {
 }
 // Split of the reduction (data gradients only — they have a workspace for the partials): 512 workgroup slots per dispatch round
 // (2 per CU).  Fewer workgroups than slots, or a nearly empty last round (g10's dgrad: 580 workgroups = 1.13 rounds, i.e. the time of
-// 2), waste the chip; shorter, more numerous workgroups fill it.  Partials are summed by splitk_reduce_kernel (deterministic).
+// 2), waste the chip; shorter, more numerous workgroups fill it.  Partials are summed by split_sum.h's serial_kernel (deterministic).
+// Called by the planners only (fwd_split, dgrad_ws): a launcher is handed the count.
 int choose_split(long long M, int K, int Kred, int tile) {
     static const int off = getenv("PNP_CONV_NOSPLIT") ? 1 : 0;
     if (off) return 1;
@@ -1752,6 +1379,20 @@ int choose_split(long long M, int K, int Kred, int tile) {
     if (nsplit > cap) nsplit = cap;
     if (nsplit > nch / 8) nsplit = nch / 8;
     return nsplit < 1 ? 1 : nsplit;
+}
+
+// What a launcher does with a planned split: `want` splits of `units` reduction units (32-deep chunks; whole channel groups on the taps
+// kernels) are cut down to the partials of `floats` values that fit the bytes the caller brought (a single partial is no split), then
+// re-normalised so that no split is empty.
+struct SplitFit { int nsplit, per; };
+SplitFit fit_split(int units, int want, size_t floats, size_t ws_bytes) {
+    if (want > 1 && ws_bytes < (size_t)want * floats * sizeof(float)) {
+        want = (int)(ws_bytes / (floats * sizeof(float)));
+        if (want < 2) want = 1;
+    }
+    if (want < 1) want = 1;
+    const int per = pnp_cdiv(units, want);
+    return {pnp_cdiv(units, per), per};
 }
 
 #ifndef PNP_TAPS3_DEFAULT
@@ -1805,25 +1446,22 @@ bool launch_taps(const ConvArgs& a, dim3 grid, hipStream_t st) {
     return false;
 }
 
+// want: the plan's reduction split (1: none); split_ws / split_bytes: the room for its partials
 template <int BM, int BN, int WM, int WN, int KIND, bool VECB>
-int launch_fwd_tile(ConvArgs& a, float* split_ws, int nsplit, hipStream_t st) {
+int launch_fwd_tile(ConvArgs& a, float* split_ws, size_t split_bytes, int want, hipStream_t st) {
     a.nblk_m = pnp_cdiv(a.M, BM);
     a.nblk_n = pnp_cdiv(a.K, BN);
     const int nch = pnp_cdiv(a.Kred, BK);
-    if (!split_ws) nsplit = 1;
+    const size_t nout = (size_t)a.M * a.K;
+    if (!split_ws) want = 1;
     // tap-unrolled fast path: instantiated filter shape, zero padding, C % 32 == 0, K % 4 == 0, both tensors < 2 GiB
     static const int env_notaps = getenv("PNP_CONV_NOTAPS") ? 1 : 0;
     const bool taps = !env_notaps && VECB && KIND != 2 && a.pad_mode == PNP_PAD_ZERO && taps_shape(KIND, a.R, a.S) &&
                       (a.C % 32) == 0 && a.x_bytes < 0x80000000u && a.w_bytes < 0x80000000u;
-    if (taps) {
-        const int ncc = a.C / BK;                                    // split in whole channel groups (R*S stages each)
-        const int cc_per = pnp_cdiv(ncc, nsplit);
-        nsplit = pnp_cdiv(ncc, cc_per);
-        a.chunks_per_split = cc_per * a.R * a.S;
-    } else {
-        a.chunks_per_split = pnp_cdiv(nch, nsplit);
-        nsplit = pnp_cdiv(nch, a.chunks_per_split);
-    }
+    // taps: split in whole channel groups (R*S stages each)
+    const SplitFit fit = fit_split(taps ? a.C / BK : nch, want, nout, split_bytes);
+    const int nsplit = fit.nsplit;
+    a.chunks_per_split = taps ? fit.per * a.R * a.S : fit.per;
     a.nsplit = nsplit;
     a.split_stride = (long long)a.M * a.K;
     float* final_out = a.y;
@@ -1852,32 +1490,26 @@ int launch_fwd_tile(ConvArgs& a, float* split_ws, int nsplit, hipStream_t st) {
     }
     PNP_CHECK_LAUNCH("conv_fwd_kernel");
     if (nsplit > 1) {
-        const size_t nout = (size_t)a.M * a.K;
-        int nb = pnp_cdiv((long long)nout, 256);
-        if (nb > 4096) nb = 4096;
-        if (drop_in_reduce) {
-            hipLaunchKernelGGL(splitk_reduce_drop_kernel, dim3(nb), dim3(256), 0, st, (const float*)split_ws, final_out, nout, nsplit, nout,
-                               a.drop_key, a.drop_thresh, a.drop_keep, a.sp, a.drop_sid);
-        } else if (a.o_s != 0) {
-            ConvArgs ar = a;
-            ar.y = final_out;
-            hipLaunchKernelGGL(splitk_reduce_scatter_kernel, dim3(nb), dim3(256), 0, st, (const float*)split_ws, ar, nsplit, nout);
-        } else {
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(nb), dim3(256), 0, st, (const float*)split_ws, final_out, nout, nsplit, nout, 0);
+        if (drop_in_reduce)
+            return split_sum::launch_serial(split_ws, nout, nsplit, nout, split_sum::Drop{final_out, a.drop_key, a.drop_thresh, a.drop_keep, a.sp, a.drop_sid}, st);
+        if (a.o_s != 0) {
+            split_sum::Scatter sc{a};
+            sc.a.y = final_out;
+            return split_sum::launch_serial(split_ws, nout, nsplit, nout, sc, st);
         }
-        PNP_CHECK_LAUNCH("splitk_reduce_kernel");
+        return split_sum::launch_serial(split_ws, nout, nsplit, nout, split_sum::Plain{final_out, 0}, st);
     }
     return PNP_OK;
 }
 
+// nsplit: the reduction split the plan chose for this launch (1: none), split_ws / split_bytes the room for its partials
 template <int KIND>
-int launch_fwd(ConvArgs& a, hipStream_t st, float* split_ws = nullptr) {
+int launch_fwd(ConvArgs& a, hipStream_t st, float* split_ws = nullptr, size_t split_bytes = 0, int nsplit = 1) {
     const int tile = choose_tile(a.M, a.K);
-    const int nsplit = split_ws ? choose_split(a.M, a.K, a.Kred, tile) : 1;
-    if (tile == 3) return launch_fwd_tile<128, 32, 4, 1, KIND, false>(a, split_ws, nsplit, st);
-    if (tile == 0) return launch_fwd_tile<128, 128, 2, 2, KIND, true>(a, split_ws, nsplit, st);
-    if (tile == 1) return launch_fwd_tile<128, 64, 2, 2, KIND, true>(a, split_ws, nsplit, st);
-    return launch_fwd_tile<128, 32, 4, 1, KIND, true>(a, split_ws, nsplit, st);
+    if (tile == 3) return launch_fwd_tile<128, 32, 4, 1, KIND, false>(a, split_ws, split_bytes, nsplit, st);
+    if (tile == 0) return launch_fwd_tile<128, 128, 2, 2, KIND, true>(a, split_ws, split_bytes, nsplit, st);
+    if (tile == 1) return launch_fwd_tile<128, 64, 2, 2, KIND, true>(a, split_ws, split_bytes, nsplit, st);
+    return launch_fwd_tile<128, 32, 4, 1, KIND, true>(a, split_ws, split_bytes, nsplit, st);
 }
 
 // wgrad reduction split: enough workgroups for >= 1 dispatch round (512 slots), as few nearly-empty last rounds as possible
@@ -1906,20 +1538,30 @@ int wgrad_ring_depth() {
     return d < 1 ? 1 : (d > 3 ? 3 : d);
 }
 
+// the ring kernel's tile by filter count: 128 x {128, 64, 32}, the narrow one with scalar dy loads where K % 4 != 0
+struct RingTile { int bm, bn, wm, wn; bool vecb; };
+RingTile ring_tile(int K) {
+    if ((K & 3) != 0) return {128, 32, 4, 1, false};
+    if (K > 64) return {128, 128, 2, 2, true};
+    if (K > 32) return {128, 64, 2, 2, true};
+    return {128, 32, 4, 1, true};
+}
+// ... and the reduction split planned for it
+int ring_split(const pnp_conv_geom* g) {
+    const RingTile t = ring_tile(g->K);
+    return wgrad_plan_split(pnp_cdiv(g->R * g->S * g->C, t.bm) * pnp_cdiv(g->K, t.bn), pnp_cdiv((long long)g->N * g->OH * g->OW, BK));
+}
+
+// want: ring_split(g); the launch takes as many of those splits as the workspace holds
 template <int BM, int BN, int WM, int WN, bool VECB>
-int launch_wgrad_tile(ConvArgs& a, float* dw, float* ws, size_t ws_bytes, hipStream_t st) {
+int launch_wgrad_tile(ConvArgs& a, float* dw, float* ws, size_t ws_bytes, int want, hipStream_t st) {
     a.nblk_m = pnp_cdiv(a.Kred, BM);
     a.nblk_n = pnp_cdiv(a.K, BN);
     const int nblk = a.nblk_m * a.nblk_n;
-    const int nchunks = pnp_cdiv(a.M, BK);
-    int nsplit = wgrad_plan_split(nblk, nchunks);
     const size_t nout = (size_t)a.Kred * a.K;
-    if (nsplit > 1 && ws_bytes < nsplit * nout * sizeof(float)) {
-        nsplit = (int)(ws_bytes / (nout * sizeof(float)));
-        if (nsplit < 2) nsplit = 1;
-    }
-    a.chunks_per_split = pnp_cdiv(nchunks, nsplit);
-    nsplit = pnp_cdiv(nchunks, a.chunks_per_split);
+    const SplitFit fit = fit_split(pnp_cdiv(a.M, BK), want, nout, ws_bytes);
+    const int nsplit = fit.nsplit;
+    a.chunks_per_split = fit.per;
     a.nsplit = nsplit;
     a.split_stride = (long long)nout;
     a.y = (nsplit > 1) ? ws : dw;
@@ -1965,99 +1607,7 @@ int launch_wgrad_tile(ConvArgs& a, float* dw, float* ws, size_t ws_bytes, hipStr
         else hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, WM, WN, 2, VECB>), grid, dim3(NTHREADS), 0, st, a);
     }
     PNP_CHECK_LAUNCH("conv_wgrad_kernel");
-    if (nsplit > 1) return launch_splitk_reduce(ws, dw, (size_t)nout, nsplit, accumulate, st);
-    return PNP_OK;
-}
-
-// ---- direct forward for K <= 8 (conv_fwd_narrow_kernel): applicability + launch -------------------------------------------------
-bool narrow_fwd_ok(const pnp_conv_geom* g, NarrowArgs* na) {
-    static const int off = getenv("PNP_CONV_NONARROW") ? 1 : 0;
-    if (off || g->K > 16 || g->stride != 1 || g->pad_mode != PNP_PAD_ZERO || (g->C & 3) != 0 || g->C < 8) return false;
-    if ((long long)g->N * g->OH * g->OW < 8192) return false;
-    // launch_narrow puts the images on the grid's z extent.  hipGetDeviceProperties on an MI355X (ROCm 7.2) reports maxGridSize =
-    // (2147483647, 65536, 65536), and hipDeviceAttributeMaxGridDimZ 65536: a launch past that is outside what HIP promises, so such a
-    // batch of tiny maps runs on the implicit GEMM.  The figure is a constant here because the route query must answer on hosts without
-    // a device.  n16_geom_ok (conv_small.hip) stops one short, at the 65535 of the CUDA-style limit it was written against; both are safe,
-    // and (65536, 1, 1, 16 -> 16) is the row of tests/test_gpu_igemm_domain.py that runs this kernel at the bound.
-    if (g->N > 65536) return false;
-    // 9..16 outputs: the MFMA tile is half full, the vector ALUs only win while the work per pixel is small (16->16 3x3: 0.154 -> 0.130 ms;
-    // 32->16 3x3, twice the work: 0.062 -> 0.071)
-    if (g->K > 8 && (long long)g->R * g->S * g->C * g->K > 2304) return false;
-    const int PH = 8 + (g->R - 1) * g->dil, PW = 32 + (g->S - 1) * g->dil;
-    const int CP = ((g->C >> 2) & 1) ? g->C : g->C + 4;
-    if ((size_t)PH * PW * CP * sizeof(float) > 150 * 1024) return false;
-    if (na) { na->PH = PH; na->PW = PW; na->CP = CP; }
-    return true;
-}
-
-template <int KK, bool EXACT>
-int launch_narrow_inst(const NarrowArgs& na, dim3 grid, size_t lds, hipStream_t st) {
-    PNP_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_fwd_narrow_kernel<KK, EXACT>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess,
-                "conv_fwd_narrow_kernel: cannot reserve %zu bytes of LDS", lds);
-    const double npx = (double)na.N * na.OH * na.OW, red = (double)na.R * na.S * na.C;
-    PnpProfScope ps(PNP_PROF_CONV_DIRECT, st, 2.0 * npx * red * na.K, 4.0 * ((double)na.N * na.H * na.W * na.C + npx * na.K + red * na.K),
-                    "conv_fwd_narrow_kernel<%d, %s>", KK, EXACT ? "true" : "false");
-    hipLaunchKernelGGL((conv_fwd_narrow_kernel<KK, EXACT>), grid, dim3(256), lds, st, na);
-    PNP_CHECK_LAUNCH("conv_fwd_narrow_kernel");
-    return PNP_OK;
-}
-
-// x, w, y and geometry of a stride-1 zero-padded conv with K <= 16 (forward, or a data gradient expressed as one); dropout from `a`
-int launch_narrow(const float* x, const float* w, float* y, const pnp_conv_geom* g, const ConvArgs& a, hipStream_t st) {
-    NarrowArgs na{};
-    narrow_fwd_ok(g, &na);
-    na.x = x; na.w = w; na.y = y;
-    na.N = g->N; na.H = g->H; na.W = g->W; na.C = g->C; na.K = g->K; na.R = g->R; na.S = g->S; na.OH = g->OH; na.OW = g->OW;
-    na.dil = g->dil; na.pad_t = g->pad_t; na.pad_l = g->pad_l;
-    na.do_drop = a.do_drop; na.drop_keep = a.drop_keep; na.drop_thresh = a.drop_thresh; na.drop_key = a.drop_key;
-    na.sp = a.sp; na.drop_sid = a.drop_sid;
-    na.x_bytes = a.x_bytes;
-    const size_t lds = (size_t)na.PH * na.PW * na.CP * sizeof(float);
-    dim3 grid((unsigned)pnp_cdiv(g->OW, 32), (unsigned)pnp_cdiv(g->OH, 8), (unsigned)g->N);
-    if (g->K == 5) return launch_narrow_inst<5, true>(na, grid, lds, st);
-    if (g->K == 16) return launch_narrow_inst<16, true>(na, grid, lds, st);
-    if (g->K <= 8) return launch_narrow_inst<8, false>(na, grid, lds, st);
-    return launch_narrow_inst<16, false>(na, grid, lds, st);
-}
-
-// ---- direct (vector-ALU) filter gradient for K <= 16: plan shared by the workspace query and the launch -------------------------
-struct WgdPlan { int use, nblk, ppb, G, ppt; size_t ws_bytes; };
-
-WgdPlan wgd_plan(const pnp_conv_geom* g) {
-    static const int off = getenv("PNP_CONV_NODIRECT") ? 1 : 0;
-    WgdPlan pl{};
-    const long long P = (long long)g->N * g->OH * g->OW;
-    const int npairs = g->R * g->S * g->C;
-    if (off || g->K > 16 || g->pad_mode != PNP_PAD_ZERO || npairs > 1024 || P < 8192) return pl;
-    pl.use = 1;
-    pl.ppt = npairs <= 256 ? 1 : pnp_cdiv(npairs, 256);
-    pl.G = pl.ppt == 1 ? 256 / npairs : 1;
-    if (pl.G > 16) pl.G = 16;
-    long long nblk = P / 128;
-    if (nblk > 2048) nblk = 2048;
-    pl.ppb = (int)pnp_cdiv(P, nblk);
-    pl.nblk = (int)pnp_cdiv(P, pl.ppb);
-    pl.ws_bytes = (size_t)pl.nblk * npairs * g->K * sizeof(float);
-    return pl;
-}
-
-template <int KK, bool EXACT>
-int launch_wgd(const WgdArgs& a, const WgdPlan& pl, hipStream_t st) {
-    const size_t lds = pl.G > 1 ? (size_t)pl.G * a.npairs * a.K * sizeof(float) : 0;
-    dim3 grid((unsigned)pl.nblk), blk(256);
-    const int nquads = a.npairs / 4;
-    PnpProfScope ps(PNP_PROF_CONV_DIRECT, st, 2.0 * (double)a.P * a.npairs * a.K,
-                    4.0 * ((double)a.N * a.H * a.W * a.C + (double)a.P * a.K + (double)a.npairs * a.K), "wgrad_direct_kernel<%d> (all variants)", KK);
-    if ((a.C % 4) == 0 && nquads >= 128 && nquads <= 512 && KK <= 8) {      // quads: one 16-byte x load per 4 pairs
-        if (nquads <= 256) hipLaunchKernelGGL((wgrad_direct4_kernel<KK, 1, EXACT>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((wgrad_direct4_kernel<KK, 2, EXACT>), grid, blk, 0, st, a);
-    } else if (pl.ppt == 1 && pl.G > 1) hipLaunchKernelGGL((wgrad_direct_kernel<KK, 1, EXACT, false>), grid, blk, lds, st, a);
-    else if (pl.ppt == 1) hipLaunchKernelGGL((wgrad_direct_kernel<KK, 1, EXACT, true>), grid, blk, lds, st, a);
-    else if (pl.ppt == 2) hipLaunchKernelGGL((wgrad_direct_kernel<KK, 2, EXACT, true>), grid, blk, lds, st, a);
-    else if (pl.ppt == 3) hipLaunchKernelGGL((wgrad_direct_kernel<KK, 3, EXACT, true>), grid, blk, lds, st, a);
-    else hipLaunchKernelGGL((wgrad_direct_kernel<KK, 4, EXACT, true>), grid, blk, lds, st, a);
-    PNP_CHECK_LAUNCH("wgrad_direct_kernel");
+    if (nsplit > 1) return split_sum::launch_serial(ws, nout, nsplit, nout, split_sum::Plain{dw, accumulate}, st);
     return PNP_OK;
 }
 
@@ -2172,16 +1722,26 @@ int launch_phase_group(const float* dy, const float* wt, float* outp, const pnp_
 
 // ---- one plan per pass ---------------------------------------------------------------------------------------------------------
 // plan_fwd / plan_dgrad / plan_wgrad are the ONLY code that combines the families' predicates (n16_geom_ok, narrow_fwd_ok, wino_tile,
-// x3d_chosen, x3s_chosen, x3n_chosen, plan_phases, x3w_chosen, n16_wgrad_ok, wgd_plan, choose_tile / choose_split, wgrad_plan_split): each states the
+// x3d_chosen, x3s_chosen, x3n_chosen, plan_phases, x3w_chosen, n16_wgrad_ok, wgd_ok, choose_tile / choose_split, ring_split): each states the
 // precedence of its pass once, top to bottom.  The workspace / partial-row / route queries read the plan, and the entry points take the
 // first candidate whose workspace the caller brought and switch on its route.
+// Workspace of the fp32 data-gradient kernels, in bytes: [flipped / transposed filters R*S*K*C, 256-aligned at 0][padded dx for SYMMETRIC,
+// 256-aligned at filt][reduction-split partials at filt + padded], and the split each launch takes: nsplit[i] for stride phase i on route
+// PHASES (parts holds the largest phase's partials), nsplit[0] otherwise.
+struct DgradWs {
+    size_t filt, padded, parts, total;
+    int nsplit[16];
+};
+
 struct ConvPlan {
-    struct Cand { int route; size_t need; } cand[5];   // PNP_ROUTE_*, in order of preference; need: workspace bytes the launch asks for
+    // PNP_ROUTE_*, in order of preference; need: workspace bytes the launch asks for; nsplit: its reduction split (forward IGEMM)
+    struct Cand { int route; size_t need; int nsplit; } cand[5];
     int ncand;
     size_t ws_bytes;      // what the pass's *_workspace_bytes query reports
     int stats_parts;      // partial rows of the statistics epilogue on cand[0]; 0 = none
     int tile;             // the Winograd planner's tile (0 / 2 / 4): it sizes the workspace ALSO where X3D takes the launch
-    void add(int route, size_t need) { cand[ncand].route = route; cand[ncand].need = need; ++ncand; }
+    DgradWs dws;          // data gradient off the Winograd planner's layers
+    void add(int route, size_t need, int nsplit = 1) { cand[ncand].route = route; cand[ncand].need = need; cand[ncand].nsplit = nsplit; ++ncand; }
     const Cand& pick(const void* ws, size_t ws_bytes) const {
         int i = 0;
         while (i + 1 < ncand && cand[i].need > 0 && !(ws && ws_bytes >= cand[i].need)) ++i;
@@ -2219,7 +1779,7 @@ static ConvPlan plan_fwd(const pnp_conv_geom* g, unsigned ep) {
         if (ws) p.add(PNP_ROUTE_X3N, x3n_filter_bytes(0));
     };
     if (n16_geom_ok(g)) p.add(PNP_ROUTE_N16, 0);
-    else if (!bn && narrow_fwd_ok(g, nullptr)) {                                // (no fused BN in the vector-ALU kernel)
+    else if (!bn && narrow_fwd_ok(g)) {                                // (no fused BN in the vector-ALU kernel)
         if (x3n) add_x3n();
         p.add(PNP_ROUTE_NARROW, 0);
     }
@@ -2236,7 +1796,7 @@ static ConvPlan plan_fwd(const pnp_conv_geom* g, unsigned ep) {
             const size_t x3 = x3d ? x3d_filter_bytes(g->C, g->K) : (x3s_chosen(g, 0) ? x3s_filter_bytes(g) : 0);      // the split filter image
             if (x3 > split) p.ws_bytes = x3;
             if (x3 && ws && !bn) p.add(x3d ? PNP_ROUTE_X3D : PNP_ROUTE_X3S, x3);
-            else if (split && ws && !stats && !bn) p.add(PNP_ROUTE_IGEMM, split);      // need > 0: the reduction-split launch
+            else if (split && ws && !stats && !bn) p.add(PNP_ROUTE_IGEMM, split, ns);  // need > 0: the reduction-split launch
         }
         p.add(PNP_ROUTE_IGEMM, 0);     // un-split (same result up to fp32 rounding): what runs when the workspace is missing
     }
@@ -2268,8 +1828,30 @@ static pnp_conv_geom dgrad_as_conv(const pnp_conv_geom* g) {
     return d;
 }
 
+// g: the forward geometry, d = dgrad_as_conv(g), ph[nph] = plan_phases(g).  The one place that sizes and lays out the fp32 kernels'
+// workspace and splits their reductions (GEMM M = the pixels of dx, or of one phase; N = C; reduction over taps x K).
+static DgradWs dgrad_ws(const pnp_conv_geom* g, const pnp_conv_geom& d, const DgradPhase* ph, int nph) {
+    DgradWs w{};
+    const size_t outb = (size_t)d.N * d.OH * d.OW * d.K * sizeof(float);
+    w.filt = ((size_t)g->R * g->S * g->C * g->K * sizeof(float) + 255) & ~(size_t)255;
+    w.padded = g->pad_mode == PNP_PAD_SYMMETRIC ? (outb + 255) & ~(size_t)255 : 0;
+    if (nph > 0) {       // strided, one stride-phase at a time: the largest phase's partials
+        for (int i = 0; i < nph; ++i) {
+            const long long Mp = (long long)g->N * ph[i].I * ph[i].J;
+            w.nsplit[i] = Mp == 0 ? 1 : choose_split(Mp, g->C, ph[i].T * ph[i].U * g->K, choose_tile(Mp, g->C));
+            const size_t b = w.nsplit[i] > 1 ? (size_t)w.nsplit[i] * Mp * g->C * sizeof(float) : 0;
+            if (b > w.parts) w.parts = b;
+        }
+    } else {
+        const long long Md = (long long)(outb / sizeof(float)) / g->C;
+        w.nsplit[0] = choose_split(Md, g->C, g->R * g->S * g->K, choose_tile(Md, g->C));
+        if (w.nsplit[0] > 1) w.parts = (size_t)w.nsplit[0] * outb;
+    }
+    w.total = w.filt + w.padded + w.parts;
+    return w;
+}
+
 // One candidate: pnp_conv2d_dgrad* refuses a workspace smaller than ws_bytes.
-// Workspace of the fp32 kernels: [flipped / transposed filters R*S*K*C] [+ padded dx for SYMMETRIC] [+ reduction-split partials]
 static ConvPlan plan_dgrad(const pnp_conv_geom* g) {
     ConvPlan p{};
     const bool sym = g->pad_mode == PNP_PAD_SYMMETRIC;
@@ -2281,30 +1863,18 @@ static ConvPlan plan_dgrad(const pnp_conv_geom* g) {
         p.add(x3d_chosen(&d) ? PNP_ROUTE_X3D : PNP_ROUTE_WINO, p.ws_bytes);
         return p;
     }
-    size_t b = ((size_t)g->R * g->S * g->C * g->K * sizeof(float) + 255) & ~(size_t)255;
-    const size_t outb = (size_t)d.N * d.OH * d.OW * d.K * sizeof(float);
-    if (sym) b += (outb + 255) & ~(size_t)255;
     int route;
     size_t x3 = 0;       // split filter image of the direct split-bf16 kernels
     DgradPhase ph[16];
     const int nph = plan_phases(g, ph);
-    if (nph > 0) {       // strided, one stride-phase at a time: the largest phase's partials (GEMM M = the phase's pixels, N = C, reduction T*U*K)
-        size_t mx = 0;
-        for (int i = 0; i < nph; ++i) {
-            const long long Mp = (long long)g->N * ph[i].I * ph[i].J;
-            if (Mp == 0) continue;
-            const int ns = choose_split(Mp, g->C, ph[i].T * ph[i].U * g->K, choose_tile(Mp, g->C));
-            if (ns > 1 && (size_t)ns * Mp * g->C * sizeof(float) > mx) mx = (size_t)ns * Mp * g->C * sizeof(float);
-        }
-        b += mx;
+    p.dws = dgrad_ws(g, d, ph, nph);
+    const size_t b = p.dws.total;
+    if (nph > 0) {       // strided, one stride-phase at a time
         route = x3s_chosen(g, 1) ? PNP_ROUTE_X3S : PNP_ROUTE_PHASES;       // X3S: every phase in one launch
         if (route == PNP_ROUTE_X3S) x3 = x3s_filter_bytes(g);
     } else {
-        const long long Md = (long long)(outb / sizeof(float)) / g->C;
-        const int ns = choose_split(Md, g->C, g->R * g->S * g->K, choose_tile(Md, g->C));
-        if (ns > 1) b += (size_t)ns * outb;
         if (!sym && n16_geom_ok(&d)) route = PNP_ROUTE_N16;                            // 16 INPUT channels: a 16-output conv of dy
-        else if (g->stride == 1 && narrow_fwd_ok(&d, nullptr)) route = PNP_ROUTE_NARROW;    // few INPUT channels: a narrow-output conv of dy
+        else if (g->stride == 1 && narrow_fwd_ok(&d)) route = PNP_ROUTE_NARROW;        // few INPUT channels: a narrow-output conv of dy
         else if (plain && x3d_chosen(&d)) route = PNP_ROUTE_X3D;
         else if (plain && x3n_chosen(g, 1)) route = PNP_ROUTE_X3N;                     // the logits layer's (conv_x3_narrow.hip)
         else route = PNP_ROUTE_IGEMM;                                                  // (stride > 1 without phases: dy zero-upsampled)
@@ -2323,20 +1893,17 @@ static ConvPlan plan_wgrad(const pnp_conv_geom* g) {
     if (p.tile) p.add(PNP_ROUTE_WINO_WGRAD, wino_wgrad_workspace_bytes(g));             // conv_wino.hip
     if (x3w_chosen(g)) p.add(PNP_ROUTE_X3W, x3w_workspace_bytes(g));                    // conv_x3_wgrad.hip
     const size_t nout = (size_t)g->R * g->S * g->C * g->K;
-    const WgdPlan pl = wgd_plan(g);
+    const bool wgd = wgd_ok(g);
+    const int nsplit = ring_split(g);
     if (p.ncand) p.ws_bytes = p.cand[0].need;
     else if (n16_wgrad_ok(g)) p.ws_bytes = (size_t)n16_wgrad_blocks(g) * nout * sizeof(float);
     else {               // the larger of the vector-ALU kernel's slabs and the ring kernel's split partials
-        const long long P = (long long)g->N * g->OH * g->OW;
-        const int bn = ((g->K & 3) != 0 || g->K <= 32) ? 32 : (g->K > 64 ? 128 : 64);
-        const int nblk = pnp_cdiv((long long)g->R * g->S * g->C, 128) * pnp_cdiv(g->K, bn);
-        const int nsplit = wgrad_plan_split(nblk, pnp_cdiv(P, BK));
         const size_t mfma_ws = nsplit <= 1 ? 0 : (size_t)nsplit * nout * sizeof(float);
-        p.ws_bytes = (pl.use && pl.ws_bytes > mfma_ws) ? pl.ws_bytes : mfma_ws;
+        p.ws_bytes = (wgd && wgd_workspace_bytes(g) > mfma_ws) ? wgd_workspace_bytes(g) : mfma_ws;
     }
     if (n16_wgrad_ok(g)) p.add(PNP_ROUTE_N16_WGRAD, p.ws_bytes);
-    if (pl.use) p.add(PNP_ROUTE_WGD, pl.ws_bytes);
-    p.add(PNP_ROUTE_RING, 0);
+    if (wgd) p.add(PNP_ROUTE_WGD, wgd_workspace_bytes(g));
+    p.add(PNP_ROUTE_RING, 0, nsplit);
     return p;
 }
 
@@ -2358,7 +1925,7 @@ static int launch_fwd_cand(const ConvPlan::Cand& c, ConvArgs& a, const pnp_conv_
     case PNP_ROUTE_X3D: return launch_x3_direct(a, 0, false, ws, ws_bytes, st);
     case PNP_ROUTE_X3S: return launch_x3_strided(a, g, 0, ws, ws_bytes, st);
     case PNP_ROUTE_X3N: return launch_x3_narrow(a, 0, ws, ws_bytes, st);
-    default: return launch_fwd<0>(a, st, c.need ? (float*)ws : nullptr);
+    default: return launch_fwd<0>(a, st, c.need ? (float*)ws : nullptr, ws_bytes, c.nsplit);
     }
 }
 
@@ -2508,12 +2075,12 @@ static int dgrad_impl(const float* dy, const float* w, float* dx, const pnp_conv
         return route == PNP_ROUTE_WINO ? launch_wino(a, 1, true, workspace, workspace_bytes, st)
                                        : launch_x3_direct(a, 1, true, workspace, workspace_bytes, st);
     }
-    // the fp32 kernels: [flipped filters][padded dx for SYMMETRIC][reduction-split partials, where the caller brought room for them]
+    // the fp32 kernels: [flipped filters][padded dx for SYMMETRIC][reduction-split partials of the launches the plan splits]
+    const DgradWs& dws = p.dws;
     float* wt = (float*)workspace;
-    const size_t woff = ((size_t)g->R * g->S * g->C * g->K * sizeof(float) + 255) & ~(size_t)255;
-    float* out = sym ? (float*)((char*)workspace + woff) : dx;
-    const size_t poff = woff + (sym ? ((size_t)d.N * d.OH * d.OW * d.K * sizeof(float) + 255) & ~(size_t)255 : 0);
-    float* split_ws = (workspace_bytes > poff) ? (float*)((char*)workspace + poff) : nullptr;
+    float* out = sym ? (float*)((char*)workspace + dws.filt) : dx;
+    float* parts = (float*)((char*)workspace + dws.filt + dws.padded);
+    auto split_ws = [&](int ns) { return ns > 1 ? parts : nullptr; };
     const dim3 tg((unsigned)pnp_cdiv(g->K, 32), (unsigned)pnp_cdiv(g->C, 32), (unsigned)(g->R * g->S));
     if (route == PNP_ROUTE_PHASES) {
         DgradPhase ph[16];
@@ -2529,7 +2096,7 @@ static int dgrad_impl(const float* dy, const float* w, float* dx, const pnp_conv
                 const pnp_conv_geom dp = phase_geom(g, q);
                 ConvArgs a = make_args(dy, wt + q.wt_off, out, &dp);
                 a.o_s = g->stride; a.o_H = d.OH; a.o_W = d.OW; a.o_h0 = q.h0; a.o_w0 = q.w0;
-                if (int e = launch_fwd<1>(a, st, split_ws)) return e;
+                if (int e = launch_fwd<1>(a, st, split_ws(dws.nsplit[i]), dws.parts, dws.nsplit[i])) return e;
             }
         }
     } else {
@@ -2549,7 +2116,8 @@ static int dgrad_impl(const float* dy, const float* w, float* dx, const pnp_conv
                 a.res_add = residual;
                 residual = nullptr;
             }
-            if (int e = (g->stride > 1 ? launch_fwd<2>(a, st, split_ws) : launch_fwd<1>(a, st, split_ws))) return e;
+            const int ns = dws.nsplit[0];
+            if (int e = (g->stride > 1 ? launch_fwd<2>(a, st, split_ws(ns), dws.parts, ns) : launch_fwd<1>(a, st, split_ws(ns), dws.parts, ns))) return e;
         }
     }
     if (sym) {
@@ -2580,41 +2148,28 @@ static int wgrad_impl(const float* x, const float* dy, float* dw, const pnp_conv
     float* ws = (float*)workspace;
     if (!ws) workspace_bytes = 0;
     const size_t nout = (size_t)a.Kred * a.K;
-    int nparts = 0;          // per-workgroup partials in ws, summed by splitk_reduce_many_kernel
-    switch (plan_wgrad(g).pick(workspace, workspace_bytes).route) {
+    int nparts = 0;          // per-workgroup partials in ws, summed by split_sum::sliced_kernel<1>
+    const ConvPlan::Cand c = plan_wgrad(g).pick(workspace, workspace_bytes);
+    switch (c.route) {
     case PNP_ROUTE_WINO_WGRAD: return launch_wino_wgrad(a, dw, accumulate, workspace, workspace_bytes, st);
     case PNP_ROUTE_X3W: return launch_x3_wgrad(x, dy, dw, g, accumulate, workspace, workspace_bytes, st);
     case PNP_ROUTE_N16_WGRAD:
         if (int e = launch_n16_wgrad(a, ws, st)) return e;
         nparts = n16_wgrad_blocks(g);
         break;
-    case PNP_ROUTE_WGD: {
-        const WgdPlan pl = wgd_plan(g);
-        WgdArgs d{};
-        d.x = x; d.dy = dy; d.part = ws;
-        d.N = g->N; d.H = g->H; d.W = g->W; d.C = g->C; d.K = g->K; d.R = g->R; d.S = g->S; d.OH = g->OH; d.OW = g->OW;
-        d.stride = g->stride; d.dil = g->dil; d.pad_t = g->pad_t; d.pad_l = g->pad_l;
-        d.P = a.M; d.npairs = a.Kred; d.G = pl.G; d.ppb = pl.ppb;
-        d.x_bytes = a.x_bytes; d.dy_bytes = a.w_bytes;
-        int e;
-        if (g->K == 16) e = launch_wgd<16, true>(d, pl, st);
-        else if (g->K == 5) e = launch_wgd<5, true>(d, pl, st);
-        else if (g->K <= 8) e = launch_wgd<8, false>(d, pl, st);
-        else e = launch_wgd<16, false>(d, pl, st);
-        if (e) return e;
-        nparts = pl.nblk;
+    case PNP_ROUTE_WGD:
+        if (int e = launch_wgd(x, dy, ws, g, a, st)) return e;
+        nparts = wgd_blocks(g);
         break;
+    default: {               // the ring kernel, with as many of the planned reduction splits as the workspace holds
+        const RingTile t = ring_tile(a.K);
+        if (!t.vecb) return launch_wgrad_tile<128, 32, 4, 1, false>(a, dw, ws, workspace_bytes, c.nsplit, st);
+        if (t.bn == 128) return launch_wgrad_tile<128, 128, 2, 2, true>(a, dw, ws, workspace_bytes, c.nsplit, st);
+        if (t.bn == 64) return launch_wgrad_tile<128, 64, 2, 2, true>(a, dw, ws, workspace_bytes, c.nsplit, st);
+        return launch_wgrad_tile<128, 32, 4, 1, true>(a, dw, ws, workspace_bytes, c.nsplit, st);
     }
-    default:                 // the ring kernel, with as many reduction splits as the workspace holds
-        if ((a.K & 3) != 0) return launch_wgrad_tile<128, 32, 4, 1, false>(a, dw, ws, workspace_bytes, st);
-        if (a.K > 64) return launch_wgrad_tile<128, 128, 2, 2, true>(a, dw, ws, workspace_bytes, st);
-        if (a.K > 32) return launch_wgrad_tile<128, 64, 2, 2, true>(a, dw, ws, workspace_bytes, st);
-        return launch_wgrad_tile<128, 32, 4, 1, true>(a, dw, ws, workspace_bytes, st);
     }
-    hipLaunchKernelGGL(splitk_reduce_many_kernel, dim3((unsigned)pnp_cdiv((long long)nout, 64)), dim3(1024), 0, st,
-                       (const float*)ws, dw, (int)nout, nparts, accumulate);
-    PNP_CHECK_LAUNCH("splitk_reduce_many_kernel");
-    return PNP_OK;
+    return split_sum::launch_sliced<1>(ws, dw, (int)nout, nparts, accumulate, st);
 }
 
 int pnp_conv2d_wgrad(const float* x, const float* dy, float* dw, const pnp_conv_geom* g, void* workspace,
@@ -2669,8 +2224,8 @@ int pnp_conv2d_wgrad_bf16r(const void* xh, const void* dyh, float* dw, int32_t a
     if (int e = check_geom(g, "pnp_conv2d_wgrad_bf16r")) return e;
     PNP_REQUIRE(xh && dyh && dw, "pnp_conv2d_wgrad_bf16r: null pointer");
     int bm, bn;
-    int nsplit = wgrad_bf16r_plan(g, &bm, &bn);
-    PNP_REQUIRE(nsplit >= 1, "pnp_conv2d_wgrad_bf16r: geometry not served (pnp_conv2d_bf16r_served(g, 2))");
+    const int want = wgrad_bf16r_plan(g, &bm, &bn);
+    PNP_REQUIRE(want >= 1, "pnp_conv2d_wgrad_bf16r: geometry not served (pnp_conv2d_bf16r_served(g, 2))");
     ConvArgs a = make_args((const float*)xh, (const float*)dyh, dw, g);
     a.dtype = PNP_DTYPE_BF16;
     a.x_bytes = (unsigned)((size_t)g->N * g->H * g->W * g->C * 2);
@@ -2680,13 +2235,9 @@ int pnp_conv2d_wgrad_bf16r(const void* xh, const void* dyh, float* dw, int32_t a
     const size_t nout = (size_t)a.Kred * a.K;
     float* ws = (float*)workspace;
     if (!ws) workspace_bytes = 0;
-    if (nsplit > 1 && workspace_bytes < nsplit * nout * sizeof(float)) {
-        nsplit = (int)(workspace_bytes / (nout * sizeof(float)));
-        if (nsplit < 2) nsplit = 1;
-    }
-    const int nchunks = pnp_cdiv(a.M, kWgradBf16rChunk);
-    a.chunks_per_split = pnp_cdiv(nchunks, nsplit);
-    nsplit = pnp_cdiv(nchunks, a.chunks_per_split);
+    const SplitFit fit = fit_split(pnp_cdiv(a.M, kWgradBf16rChunk), want, nout, workspace_bytes);
+    const int nsplit = fit.nsplit;
+    a.chunks_per_split = fit.per;
     a.nsplit = nsplit;
     a.split_stride = (long long)nout;
     a.y = (nsplit > 1) ? ws : dw;
@@ -2695,7 +2246,7 @@ int pnp_conv2d_wgrad_bf16r(const void* xh, const void* dyh, float* dw, int32_t a
     dim3 grid((unsigned)(a.nblk_m * a.nblk_n * nsplit));
     PNP_REQUIRE(launch_wgrad_bf16r(a, wgrad_bf16r_tile(g), grid, st), "conv_wgrad_bf16r_kernel: no instance");
     PNP_CHECK_LAUNCH("conv_wgrad_bf16r_kernel");
-    if (nsplit > 1) return launch_splitk_reduce(ws, dw, (size_t)nout, nsplit, (int)accumulate, st);
+    if (nsplit > 1) return split_sum::launch_serial(ws, nout, nsplit, nout, split_sum::Plain{dw, (int)accumulate}, st);
     return PNP_OK;
 }
 

@@ -14,7 +14,7 @@
 //                           fused inference BN + shortcut + leaky-ReLU, residual add).
 //   wgrad_n16_kernel<C>     filter gradient: dW[(tap, c)][k] = sum_p x[p + tap][c] * dy[p][k] with M = 16 channels of one tap, N = 16
 //                           filters, K = 4 pixels per MFMA; x from the same LDS patch, dy straight from memory (64 lanes = 4 pixels x 16
-//                           filters = 256 contiguous bytes); per-workgroup partials are summed by splitk_reduce_many_kernel (fixed order).
+//                           filters = 256 contiguous bytes); per-workgroup partials are summed by split_sum.h's sliced_kernel<1> (fixed order).
 #include "conv_common.h"
 
 using namespace pnpconv;

@@ -23,12 +23,13 @@
 //     input channels there are only two such blocks: the waves pair up on one block and take two of the four k-slabs each (two partial
 //     sums per workgroup).
 //   * persistent workgroups (at most one per CU) over a STATIC contiguous share of the tiles; each writes its partial [9 C 64] once, and
-//     x3w_reduce_kernel sums the partials in a fixed order (two deterministic levels: 16 interleaved chains per value, then the 16 in order)
+//     split_sum.h's sliced_kernel<4> sums the partials in a fixed order (two deterministic levels: 16 interleaved chains per value, then the 16 in order)
 //     and adds into dW for the accumulating entry point.  No atomics: two runs are bit-identical.
 // Entry: plan_wgrad (conv_igemm.hip) asks x3w_chosen() after the Winograd filter-gradient planner and before the fp32-pipe ring kernel;
 // x3w_workspace_bytes() is what wgrad_ws() reports for the layers the predicate takes.  PNP_X3_WGRAD / pnp_conv2d_x3_wgrad(): 0 off, 1 on,
 // under PNP_X3_DIRECT's mode (0 there: off; 1: layers with >= 256 tiles; 2: wherever the shapes allow).
 #include "conv_x3_common.h"
+#include "split_sum.h"
 
 using namespace pnpconv;
 
@@ -264,24 +265,6 @@ __global__ void __launch_bounds__(512, 1) conv_x3_wgrad_kernel(X3wArgs a) {
         }
 }
 
-// dW (+)= the partials summed in a fixed order: thread (column c of 16 float4, slice s of 16) adds the partials s, s + 16, ... in order, the 16
-// slice sums are added in order through LDS.  n4 % 16 == 0.
-__global__ void __launch_bounds__(256) x3w_reduce_kernel(const float* __restrict__ part, float* __restrict__ out, int n4, int nparts, int accumulate) {
-    __shared__ f32x4 sh[16][16];
-    const int c = threadIdx.x & 15, s = threadIdx.x >> 4;
-    const int col = blockIdx.x * 16 + c;
-    f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    for (int z = s; z < nparts; z += 16) v += *reinterpret_cast<const f32x4*>(part + ((size_t)z * n4 + col) * 4);
-    sh[s][c] = v;
-    __syncthreads();
-    if (s == 0) {
-#pragma unroll
-        for (int z = 1; z < 16; ++z) v += sh[z][c];
-        f32x4* o = reinterpret_cast<f32x4*>(out) + col;
-        *o = accumulate ? *o + v : v;
-    }
-}
-
 ModeSwitch x3w_switch{"PNP_X3_WGRAD", 1, 1, true};
 
 int x3w_grid(const pnp_conv_geom* g) {
@@ -334,10 +317,9 @@ int launch_x3_wgrad(const float* x, const float* dy, float* dw, const pnp_conv_g
         else hipLaunchKernelGGL((conv_x3_wgrad_kernel<2>), grid, dim3(512), 0, st, a);
         PNP_CHECK_LAUNCH("conv_x3_wgrad_kernel");
     }
-    PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)nparts * nout + (accumulate ? 2.0 : 1.0) * nout), "x3w_reduce_kernel");
-    hipLaunchKernelGGL(x3w_reduce_kernel, dim3((unsigned)(nout / 64)), dim3(256), 0, st, (const float*)ws, dw, nout / 4, nparts, accumulate);
-    PNP_CHECK_LAUNCH("x3w_reduce_kernel");
-    return PNP_OK;
+    // dW (+)= the partials in a fixed order, 16 bytes per lane (nout % 64 == 0, the workspace and dW 16-byte aligned)
+    PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)nparts * nout + (accumulate ? 2.0 : 1.0) * nout), "%s", split_sum::Lane<4>::label);
+    return split_sum::launch_sliced<4>((const float*)ws, dw, nout, nparts, accumulate, st);
 }
 
 }  // namespace pnpconv

@@ -338,7 +338,7 @@ def bf16_expected(case, kind):
 
 
 STAGED = H.FWD + H.STRIDED + H.WGRAD
-# forward cases the GPU file also runs with dropout: the reduction-split taps launch leaves dropout to splitk_reduce_drop_kernel
+# forward cases the GPU file also runs with dropout: the reduction-split taps launch leaves dropout to split_sum::serial_kernel<Drop>
 STAGED_DROPOUT = [c for c in H.DROPOUT if bf16_plan(c, 0, drop=True)["bf16"]]
 
 
@@ -362,7 +362,7 @@ REQUIRED = (
     + sorted({re.sub(r"^conv_taps3?_kernel<", "conv_taps_bf16_kernel<", s) for s in H.REQUIRED if s.startswith("conv_taps")})
     + ["conv_wgrad_bf16_kernel<128, 128, 2, 2>", "conv_wgrad_bf16_kernel<128, 64, 2, 2>", "conv_wgrad_bf16_kernel<128, 32, 4, 1>"]
     + ["staged taps split", "staged taps unsplit", "staged wgrad split", "staged wgrad unsplit",
-       "staged splitk_reduce_kernel", "staged splitk_reduce_drop_kernel", "staged splitk_reduce_scatter_kernel"]
+       "staged split_sum::serial_kernel<Plain>", "staged split_sum::serial_kernel<Drop>", "staged split_sum::serial_kernel<Scatter>"]
 )
 
 

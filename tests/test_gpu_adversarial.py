@@ -216,7 +216,7 @@ def test_joint_step_B16_vs_float32_oracle(dev):
         # arithmetic (tests/test_gpu_teacher_forced_adv.py, B = 16: HIP min cosine 0.999955 = distance 9.5e-3, float32 CPU oracle 0.99996
         # = 8.9e-3): sum 1.84e-2, with 50 % head-room 2.76e-2 = cosine 0.9996.  It had been 0.9998 — the value measured in round 5 —
         # and the measurement sits ON it: 0.99980261 / 0.99979480 with the split direct filter gradients summed in one / two levels
-        # (PNP_SPLITK_TWO_LEVEL: a change of summation order in kernels that are each exact to 1e-6).  A band that a re-ordered sum
+        # (a since-removed experiment: a change of summation order in kernels that are each exact to 1e-6).  A band that a re-ordered sum
         # crosses is noise, not a parity statement; the parity statement for this path is the float64 adjudication, whose bars
         # (1.5 x the oracle's distance, cosine 0.9999) are unchanged.  The median bar (2e-2 = 1.5 x (7e-3 + 6e-3)) is unchanged too.
         lim_cos, lim_med = (0.9999, 1e-2) if tag == "dis" else (0.9996, 2e-2)

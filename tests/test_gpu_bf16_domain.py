@@ -393,7 +393,7 @@ def test_staged_domain(fp32, dev, case):
 
 @pytest.mark.parametrize("case", BH.STAGED_DROPOUT, ids=H.case_id)
 def test_staged_dropout_is_exact_on_exact_operands(fp32, dev, case):
-    """keep_prob = 0.5 on a bf16 taps forward: in the kernel's epilogue, and in splitk_reduce_drop_kernel where the forward splits"""
+    """keep_prob = 0.5 on a bf16 taps forward: in the kernel's epilogue, and in split_sum::serial_kernel<Drop> where the forward splits"""
     K = fp32
     x, w, _, _, _ = G._operands(case, True)
     g = BH.lib_geom(K, case)

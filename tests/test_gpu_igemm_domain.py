@@ -5,7 +5,7 @@ a GPU; here every pass of every row asserts WHICH SYMBOLS RAN against that resta
 fails), and the file ends with a test that the asserted variants cover test_igemm_domain_host.REQUIRED.
 
 What is OBSERVED and what is only RESTATED: the profiler records the convolution kernels' symbols, and those are compared.  It does not
-record the summing kernels (splitk_reduce_kernel, _drop_, _scatter_: they open no profiler scope), the number of reduction splits a launch
+record the summing kernels (split_sum::serial_kernel<Plain / Drop / Scatter>: they open no profiler scope), the number of reduction splits a launch
 took, or which instance of the wgrad_direct family ran ("wgrad_direct_kernel<KK> (all variants)").  The tags for those — the reducers,
 "ring split", "phases one at a time", the WGD variants, tpw > 1 — enter ASSERTED from the restatement alone, and check A is by design
 independent of the split count.  The split count itself is observed where the partials lie at the start of the workspace (the forward
@@ -251,7 +251,7 @@ def test_filter_gradient_domain(fp32, dev, case):
 
 @pytest.mark.parametrize("case", H.DROPOUT, ids=H.case_id)
 def test_dropout_epilogue_is_exact_on_exact_operands(fp32, dev, case):
-    """keep_prob = 0.5: y = conv x mask x 2, bit for bit — in the kernel's epilogue, and in splitk_reduce_drop_kernel where the forward
+    """keep_prob = 0.5: y = conv x mask x 2, bit for bit — in the kernel's epilogue, and in split_sum::serial_kernel<Drop> where the forward
     splits its reduction"""
     K = fp32
     x, w, dy, _, _ = _operands(case, True)

@@ -25,7 +25,7 @@ CASES = [
     (3, 48, 64, 64, "normal"),          # 27 tiles: an odd number of tiles per workgroup share
     (1, 64, 64, 64, "wide"),            # magnitudes 1e-6 .. 1e3, 75 % exact zeros
 ]
-NEW, NEW_SUM = "conv_x3_wgrad_kernel<%d>", "x3w_reduce_kernel"
+NEW, NEW_SUM = "conv_x3_wgrad_kernel<%d>", "split_sum::sliced_kernel<4>"
 
 
 def _rel(a, b):
@@ -110,6 +110,38 @@ def test_wgrad_split_bf16_accumulates_and_is_deterministic(dev, route):
         assert err_new <= _bar(err_old), (err_new, err_old)
         assert torch.equal(dw, K.conv2d_wgrad(x, dy, g)), "two launches differ"
         assert torch.equal(acc1, K.conv2d_wgrad(x, dy, g, into=pre.clone())), "two accumulating launches differ"
+
+
+# (N, OH, OW, C) -> partials: one per 16 x 16 tile, two where C = 32.  The sum (split_sum::sliced_kernel<4>) gives slice s the partials
+# s, s + 16, ...: fewer partials than slices (3, 6), one and two past a full round of 16 (17, 34).  CASES above reach 16, 27, 32, 64, 128.
+FEW_PARTS = [((1, 16, 48, 64), 3), ((1, 16, 48, 32), 6), ((17, 16, 16, 64), 17), ((17, 16, 16, 32), 34)]
+
+
+@pytest.mark.parametrize("shape,parts", FEW_PARTS, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_wgrad_split_bf16_part_counts_off_the_slice_count(dev, route, shape, parts):
+    K, L = route, pkg("_lib")
+    N, H, W, C = shape
+    rng = np.random.default_rng(N + W + C)
+    x, dy = _operands(rng, (N, H, W, C), "normal"), _operands(rng, (N, H, W, 64), "normal")
+    pre = torch.from_numpy(rng.standard_normal((3, 3, C, 64)).astype(np.float32) * 50.0).to(dev)
+    g = K.conv_geom(x.shape, (3, 3, C, 64), 1, 1, "SAME")
+    xd, dyd = torch.from_numpy(x).to(dev), torch.from_numpy(dy).to(dev)
+    wg = torch.zeros((3, 3, C, 64), dtype=torch.float64, requires_grad=True)
+    T.conv2d(torch.from_numpy(x).double(), wg, 1, 1, "SAME").backward(torch.from_numpy(dy).double())
+    K.x3_direct(2)
+    K.x3_wgrad(0)
+    dw0, acc0 = K.conv2d_wgrad(xd, dyd, g), K.conv2d_wgrad(xd, dyd, g, into=pre.clone())
+    K.x3_wgrad(1)
+    assert int(L.load().pnp_conv2d_wgrad_workspace_bytes(ctypes.byref(g))) == parts * 9 * C * 64 * 4
+    dw1, names = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g), L.PROF_CONV_WGRAD)
+    assert names == sorted([NEW % (C // 32), NEW_SUM]), names
+    acc1, names_a = _ran(L, lambda: K.conv2d_wgrad(xd, dyd, g, into=pre.clone()), L.PROF_CONV_WGRAD)
+    assert names_a == names, names_a
+    ref_acc = pre.cpu().double() + wg.grad
+    errs = (_rel(dw1, wg.grad), _rel(dw0, wg.grad), _rel(acc1, ref_acc), _rel(acc0, ref_acc))
+    print("x3 wgrad %s, %d partials: split-bf16 %.2e (fp32 route %.2e), accumulating %.2e (%.2e) of max|ref|" % ((shape, parts) + errs))
+    assert errs[0] <= _bar(errs[1]) and errs[2] <= _bar(errs[3]), errs
+    assert torch.equal(acc1, pre + dw1), "accumulate differs from pre-fill + gradient"
 
 
 def test_wgrad_split_bf16_planner(dev, route):

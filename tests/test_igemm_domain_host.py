@@ -10,8 +10,9 @@ count of the workspace query); `plan(case, kind)` gives the details (the splits 
 for what the profiler does not name).  Here it is held to pnp_conv2d_route and the three workspace queries of the built library for every
 row and every pass; the GPU file holds the symbols that RAN to it.
 
-wgrad_direct4_kernel<KK, 2, ...> (launch_wgd: nquads > 256) needs more than 1024 (tap, channel) pairs, which wgd_plan refuses (npairs >
-1024 -> use = 0): it is unreachable through any entry point, see test_direct4_two_quads_per_thread_is_unreachable."""
+wgrad_direct4_kernel<KK, 2, ...> (two quads per thread: nquads > 256) would need more than 1024 (tap, channel) pairs, which wgd_plan refuses
+(npairs > 1024 -> use = 0): no entry point could reach it and the instance is gone, see test_direct4_two_quads_per_thread_is_unreachable.
+The vector-ALU family (NARROW, WGD) lives in csrc/conv_valu.hip, the summing kernels in csrc/split_sum.h."""
 import ctypes
 import math
 
@@ -92,7 +93,7 @@ STRIDED = [
     (2, 17, 19, 32, 32, 5, 5, 2, 1, "SAME"),         # stride 2, 5x5: sub-filters 3x3, 3x2, 2x3, 2x2 in one launch
     (2, 10, 10, 20, 24, 3, 3, 2, 1, "SAME"),         # K % 32 != 0: one phase at a time on conv_fwd_kernel (mode 1: 24 channels of dy), no split
     (2, 12, 14, 16, 64, 5, 5, 2, 1, "SAME"),         # C < 32: one phase at a time on the taps kernels 3x3 (2 splits + scatter), 3x2, 2x3, 2x2
-    (2, 16, 16, 16, 272, 5, 5, 2, 1, "SAME"),        # one phase at a time, split 9 + splitk_reduce_scatter_kernel (split phases are its only reach)
+    (2, 16, 16, 16, 272, 5, 5, 2, 1, "SAME"),        # one phase at a time, split 9 + split_sum::serial_kernel<Scatter> (split phases are its only reach)
     (2, 12, 12, 16, 64, 6, 6, 3, 1, "SAME"),         # stride 3, 6x6: every sub-filter 2x2; one at a time
     (8, 130, 130, 32, 32, 3, 3, 2, 1, "SAME"),       # more than 512 phase tiles: one at a time, taps 2x2, 2x1, 1x2, 1x1 un-split
     (2, 16, 16, 64, 32, 3, 3, 2, 1, "SYMMETRIC"),    # SYMMETRIC strided: phases over the mirror-padded image, then sympad_bwd
@@ -137,6 +138,7 @@ WGRAD = [
     (2, 64, 64, 100, 12, 3, 3, 1, 1, "SAME"),        # 900 pairs, K = 12 > 8: ppt = 4 <16, 4, false, true>
     (2, 64, 64, 5, 7, 3, 3, 1, 1, "SAME"),           # 45 pairs, 5 groups, K = 7: <8, 1, false, false>, C % 4 != 0
     (2, 128, 128, 5, 16, 3, 3, 2, 1, "SAME"),        # stride 2 (the mask critic's first layer): <16, 1, true, false>
+    (1, 80, 104, 8, 5, 3, 3, 1, 1, "SAME"),          # WGD, 65 = 4 x 16 + 1 partials of 360 = 5 x 64 + 40 values: sliced_kernel<1> with ragged slices AND a ragged last workgroup
 ]
 
 # anchors too large for the GPU file's float64 oracle: routes and counts only
@@ -270,7 +272,7 @@ def igemm_launch(M, K, C, R, S, zero, kind, split, drop=False, scatter=False):
         sym = "conv_fwd_kernel<%s, %d, %d, %s>" % (TILE_ARGS[tile], kmode, kind, "true" if vecb else "false")
     reducer = None
     if ns > 1:
-        reducer = "splitk_reduce_drop_kernel" if drop else ("splitk_reduce_scatter_kernel" if scatter else "splitk_reduce_kernel")
+        reducer = "split_sum::serial_kernel<Drop>" if drop else ("split_sum::serial_kernel<Scatter>" if scatter else "split_sum::serial_kernel<Plain>")
     return dict(sym=sym, ns=ns, per=per, total=total, reducer=reducer, taps=taps, tile=tile)
 
 
@@ -438,7 +440,7 @@ def ring_launch(g, ws_bytes):
         sym = "conv_wgrad_ring_kernel<%s, %d>" % (TILE_ARGS[tile], 12 if g.C % 128 == 0 else 2)
     else:
         sym = "conv_wgrad_kernel<%s, %d, %s>" % (TILE_ARGS[tile], 3 if lin else (1 if g.C % 4 == 0 else 2), "true" if vecb else "false")
-    return dict(sym=sym, ns=ns, per=per, total=total, planned=planned, reducer="splitk_reduce_kernel" if ns > 1 else None)
+    return dict(sym=sym, ns=ns, per=per, total=total, planned=planned, reducer="split_sum::serial_kernel<Plain>" if ns > 1 else None)
 
 
 def plan(case, kind, drop=False):
@@ -609,14 +611,16 @@ def test_restated_planner_anchors(fp32_routes):
     assert cdiv(136 * 136, 128) * cdiv(512, 128) == 580 and L["tile"] == 0 and fp32_expected(c, 1)[2] == 2 and L["ns"] == 2
     c = (2, 16, 16, 16, 272, 5, 5, 2, 1, "SAME")
     p = _p(c, 1)
-    assert p["route"] == PHASES and p["nsplit"] == 9 and "splitk_reduce_scatter_kernel" in p["tags"] and "phases one at a time" in p["tags"]
-    scat = [s for s in (STRIDED + FWD + WGRAD) if "splitk_reduce_scatter_kernel" in plan(s, 1)["tags"]]      # only split phases reach it
+    assert p["route"] == PHASES and p["nsplit"] == 9 and "split_sum::serial_kernel<Scatter>" in p["tags"] and "phases one at a time" in p["tags"]
+    scat = [s for s in (STRIDED + FWD + WGRAD) if "split_sum::serial_kernel<Scatter>" in plan(s, 1)["tags"]]      # only split phases reach it
     assert c in scat and all("phases one at a time" in plan(s, 1)["tags"] for s in scat)
     g = geom_of((4, 176, 176, 32, 64, 3, 3, 1, 1, "SAME"))
     assert cdiv(g.OW, 32) * cdiv(g.OH, 8) * g.N == 528 and fp32_expected((4, 176, 176, 32, 64, 3, 3, 1, 1, "SAME"), 2)[::2] == (N16_WGRAD, 455)
     assert fp32_expected((5, 256, 256, 16, 16, 3, 3, 1, 1, "SAME"), 2)[::2] == (N16_WGRAD, 1024)
     c = (2, 64, 64, 116, 8, 3, 3, 1, 1, "SAME")
     assert 9 * 116 == 1044 and fp32_expected(c, 2)[::2] == (RING, 32)
+    c = (1, 80, 104, 8, 5, 3, 3, 1, 1, "SAME")          # sliced_kernel<1>: 65 partials = 4 per slice + 1, 360 values = 5 workgroups of 64 + 40
+    assert fp32_expected(c, 2)[::2] == (WGD, 65) and 9 * 8 * 5 == 360 and _p(c, 2)["wgd"]["ws_bytes"] == _p(c, 2)["ws_bytes"] == 65 * 360 * 4
     assert fp32_expected((1, 64, 8, 64, 32, 3, 3, 1, 1, "SAME"), 2) == (RING, ["conv_wgrad_ring_kernel<128, 32, 4, 1, 2>"], 2)
     assert fp32_expected((1, 30, 12, 64, 32, 3, 3, 1, 1, "SAME"), 2)[:2] == (RING, ["conv_wgrad_kernel<128, 32, 4, 1, 1, true>"])
     # ragged last splits: ns * per != total
@@ -647,7 +651,7 @@ REQUIRED = [
     "conv_fwd_kernel<128, 32, 4, 1, 1, 0, true>", "conv_fwd_kernel<128, 32, 4, 1, 2, 0, true>", "conv_fwd_kernel<128, 32, 4, 1, 2, 0, false>",
     "conv_fwd_kernel<128, 32, 4, 1, 0, 0, false>", "conv_fwd_kernel<128, 32, 4, 1, 4, 0, false>", "conv_fwd_kernel<128, 32, 4, 1, 1, 0, false>",
     "conv_fwd_kernel<128, 32, 4, 1, 0, 2, true>", "conv_fwd_kernel<128, 32, 4, 1, 1, 2, true>",
-    "splitk_reduce_kernel", "splitk_reduce_drop_kernel", "splitk_reduce_scatter_kernel", "phases one at a time",
+    "split_sum::serial_kernel<Plain>", "split_sum::serial_kernel<Drop>", "split_sum::serial_kernel<Scatter>", "phases one at a time",
     "conv_n16_kernel<16, 0>", "conv_n16_kernel<16, 1>", "conv_n16_kernel<32, 0>", "conv_n16_kernel<32, 1>", "conv_c3n16_kernel<3, 0>",
     "conv_c3n16_kernel<3, 1>", "n16 tpw>1",
     "conv_fwd_narrow_kernel<5, true>", "conv_fwd_narrow_kernel<16, true>", "conv_fwd_narrow_kernel<8, false>", "conv_fwd_narrow_kernel<16, false>",
@@ -700,8 +704,9 @@ def test_epilogue_rows_are_unsplit_and_on_their_tile_class(fp32_routes):
 
 
 def test_direct4_two_quads_per_thread_is_unreachable():
-    """launch_wgd picks wgrad_direct4_kernel<KK, 2, ...> for nquads = R S C / 4 in 257..512, i.e. more than 1024 pairs, and wgd_plan returns
-    use = 0 for npairs > 1024 — the instance is compiled and never launched.  The largest quad count wgd_plan lets through is 256."""
+    """wgrad_direct4_kernel<KK, 2, ...> served nquads = R S C / 4 in 257..512, i.e. more than 1024 pairs, and wgd_plan returns use = 0 for
+    npairs > 1024 — so the instance is gone from the library (csrc/conv_valu.hip keeps <KK, 1, ...> alone).  The largest quad count wgd_plan
+    lets through is 256."""
     for C in range(4, 1200, 4):
         for (R, S) in ((1, 1), (2, 2), (3, 3), (5, 5)):
             g = geom_of((2, 64, 64, C, 8, R, S, 1, 1, "SAME"))
