@@ -9,10 +9,6 @@ namespace pnpconv {
 
 constexpr int BK = 32;
 constexpr int NTHREADS = 256;
-#ifndef PNP_CONV_ABLATE
-#define PNP_CONV_ABLATE 0
-#endif
-constexpr int kAblate = PNP_CONV_ABLATE;
 
 struct ConvArgs {
     const float* x;

@@ -27,6 +27,8 @@
 // pnp_conv2d_fwd_stats*_parts, pnp_conv2d_wino_chosen, pnp_conv2d_route; tests/test_abi.py) and by the entry points, which switch on the route.
 // The plan also fixes the reduction split and the workspace layout (dgrad_ws): the launchers receive the planned split count and only fit
 // it to the bytes the caller brought (fit_split); none of them calls choose_split / wgrad_plan_split.
+// Shared pieces: conv_mma.h holds Frag and the stage schedule — PNP_MMA_STAGE is the whole stage of conv_taps_kernel, conv_wgrad_kernel,
+// conv_wgrad_ring_kernel and conv_wino.hip's two GEMMs; conv_common.h the argument block, tile mapping, loads and epilogues.
 //
 // LDS layouts (dwords):
 //   fwd  A tile  [BM][36]     row = output pixel, 32 k's contiguous (+4 pad). A fragments are read with
@@ -91,20 +93,6 @@ struct BLoader {
                 for (int e = 0; e < 4; ++e) reg[i][e] = bload1(rb, (rok && n + e < ncols) ? base + 4u * e : OOB);
             }
         }
-    }
-    // Scalar-offset variant (wgrad, dy < 2 GiB): the thread's byte offset inside a 32-row stage never changes, the stage itself is a
-    // scalar offset; rows past the end of the matrix are past the buffer -> 0 from the hardware.  No VALU per stage.
-    unsigned boff[NP];
-    __device__ __forceinline__ void init_s(int ncols, int n0) {
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-            boff[i] = (n0 + 4 * bcol < ncols) ? (unsigned)(((brow + RP * i) * ncols + n0 + 4 * bcol) * 4) : 0x80000000u;
-    }
-    __device__ __forceinline__ void load_s(__amdgpu_buffer_rsrc_t rb, int k0, int ncols) {
-        const int soff = k0 * ncols * 4;
-#pragma unroll
-        for (int i = 0; i < NP; ++i)
-            reg[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rb, boff[i], soff, 0));
     }
     __device__ __forceinline__ void store(float* lds) const {
 #pragma unroll
@@ -324,32 +312,6 @@ struct WgradALoader {
     }
 };
 
-// Split accumulation (narrow tiles): a wave with TM*TN <= 2 accumulator tiles rotates through only two dependent MFMA chains; with a
-// second accumulator set for the odd k of every 8-group it rotates through four, like the 2x2 tile (summed once in front of the epilogue).
-#ifndef PNP_SPLIT_ACC
-#define PNP_SPLIT_ACC 0
-#endif
-template <int TM, int TN, bool A_MMAJOR, int LDA, int LDB>
-__device__ __forceinline__ void frag_mma2(const Frag<TM, TN, A_MMAJOR, LDA, LDB>& f, Acc<TM, TN>& acc0, Acc<TM, TN>& acc1) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) {
-                if (j & 1) acc1.v[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tm][j], f.b[j][tn], acc1.v[tm][tn], 0, 0, 0);
-                else acc0.v[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tm][j], f.b[j][tn], acc0.v[tm][tn], 0, 0, 0);
-            }
-}
-template <int TM, int TN>
-__device__ __forceinline__ void acc_add(Acc<TM, TN>& a, const Acc<TM, TN>& b) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) a.v[i][j][e] += b.v[i][j][e];
-}
 // ================================ forward / dgrad kernel ========================================
 // KIND 0 = forward, 1 = data gradient of a stride-1 convolution, 2 = data gradient of a strided convolution (input = dy
 // zero-upsampled by `ups`).  0 and 1 run the same code; the distinct symbol lets rocprof separate forward from backward
@@ -421,9 +383,8 @@ __device__ __forceinline__ void conv_fwd_body(ConvArgs a, const int blk) {
     // Main loop — ONE basic block per stage (no branches: the prefetch past the last stage reads out of range = zeros
     // and lands in the LDS buffer nobody reads).  Per stage and wave: 64 MFMAs in 4 slices of 16; under slice q the
     // ds_reads of slice q+1 are in flight; the next stage's global loads are issued under slice 0 and written to the
-    // other LDS buffer under slice 3; only the 6 reads of the next stage's slice 0 are exposed after the barrier.
-    // PNP_CONV_ABLATE (compile-time, timing experiments only — results are wrong when set):
-    //   1 = no global loads after the first stage, 2 = no MFMAs, 4 = no LDS stores, 8 = no barrier
+    // other LDS buffer under slice 3; only the 6 reads of the next stage's slice 0 are exposed after the barrier.  (Not PNP_MMA_STAGE:
+    // here the stores follow ALL MFMAs of slice 3, a different schedule.)
     for (int c = 0; c < nchunks; ++c) {
         const int cur = c & 1;
         const float* As = lds + cur * ASZ;
@@ -433,11 +394,9 @@ __device__ __forceinline__ void conv_fwd_body(ConvArgs a, const int blk) {
         const int k0 = stage_k0(c_begin + c + 1);
         // ---- slice 0
         f1.load(As, Bs, 1, wm0, wn0, lane);
-        if constexpr (!(kAblate & 1)) {
-            la.load(a, rx, k0);
-            lb.load(rw, k0, a.Kred, a.K, n0);
-        }
-        if constexpr (!(kAblate & 2)) f0.mma(acc);
+        la.load(a, rx, k0);
+        lb.load(rw, k0, a.Kred, a.K, n0);
+        f0.mma(acc);
         // interleave: the 6 ds_reads first, then per MFMA a handful of the address VALU/SALU and, when its address is
         // ready, one buffer_load — the ~130 address instructions of the next stage ride in the shadow of the 16 MFMAs
         // (64 cycles each) instead of in front of them.
@@ -452,24 +411,22 @@ __device__ __forceinline__ void conv_fwd_body(ConvArgs a, const int blk) {
         // ---- slice 1
         f0.load(As, Bs, 2, wm0, wn0, lane);
         PNP_SCHED_FENCE();
-        if constexpr (!(kAblate & 2)) f1.mma(acc);
+        f1.mma(acc);
         PNP_SCHED_FENCE();
         // ---- slice 2
         f1.load(As, Bs, 3, wm0, wn0, lane);
         PNP_SCHED_FENCE();
-        if constexpr (!(kAblate & 2)) f0.mma(acc);
+        f0.mma(acc);
         PNP_SCHED_FENCE();
         // ---- slice 3: MFMAs first, THEN the LDS stores of the next stage.  The stores need the global loads issued under slice 0;
         // measured load-to-use latency under this traffic is ~3000 cycles (ablation: load->LDS->barrier chain alone 2.3 us per
         // stage), so waiting for them before the slice-3 MFMAs (2100 cycles after issue) stalled the matrix pipe ~20 %.
-        if constexpr (!(kAblate & 2)) f1.mma(acc);
+        f1.mma(acc);
         PNP_SCHED_FENCE();
-        if constexpr (!(kAblate & 4)) {
-            la.store(An);
-            lb.store(Bn);
-        }
+        la.store(An);
+        lb.store(Bn);
         PNP_SCHED_FENCE();
-        if constexpr (!(kAblate & 8)) __syncthreads();
+        __syncthreads();
         f0.load(An, Bn, 0, wm0, wn0, lane);
     }
 
@@ -526,15 +483,10 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_dgrad_phases_kernel(GroupArg
 //   B:  voffset = constant per thread, soffset = (tap*C + channel-group*32) * K * 4   (scalar)
 // i.e. ~16 VALU per stage instead of ~130 (the general kernel re-derives tap, mirror/zero test and pixel offset per row per stage).
 
-// Waves per SIMD the register allocation must leave room for.  The 128x64 / 128x32 tiles take 54 / 46 KB of LDS — three workgroups fit a
-// CU's 160 KB — but at 175 VGPRs only two waves fit a SIMD; asking for three (<= 168 VGPRs) gives every SIMD a third wave to issue MFMAs
-// while the other two sit in the per-stage barrier / LDS-store part (a 128x64 stage carries half the MFMAs of a 128x128 one for the same
-// fixed part).  PNP_TAPS_NARROW_WAVES = 2 restores the round-2 allocation (A/B: tools/experiments/).
-#ifndef PNP_TAPS_NARROW_WAVES
-#define PNP_TAPS_NARROW_WAVES 2
-#endif
+// Two waves per SIMD: three for the 128x64 / 128x32 tiles (their LDS would fit three workgroups; <= 168 VGPRs) measured no gain
+// (tools/experiments/README.md, round 3 run 1).
 template <int BM, int BN, int WM, int WN, int KIND, int R, int S>
-__global__ void __launch_bounds__(NTHREADS, ((BN <= 64 && R * S <= 9) ? PNP_TAPS_NARROW_WAVES : 2)) conv_taps_kernel(ConvArgs a) {
+__global__ void __launch_bounds__(NTHREADS, 2) conv_taps_kernel(ConvArgs a) {
     constexpr int NTAP = R * S;
     static_assert(NTAP <= 32, "one validity bit per tap");
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
@@ -638,22 +590,7 @@ __global__ void __launch_bounds__(NTHREADS, ((BN <= 64 && R * S <= 9) ? PNP_TAPS
             const int ntap = (tap + 1 < NTAP) ? tap + 1 : 0;
             int ncc = (tap + 1 < NTAP) ? cc : cc + 1;
             ncc = (ncc < cc_end) ? ncc : cc;
-            // ---- slice 0 (same 4-slice register pipeline as conv_fwd_kernel)
-            f1.load(As, Bs, 1, wm0, wn0, lane);
-            gload(ncc, ntap);
-            f0.mma(acc);
-            __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-#pragma unroll
-            for (int i = 0; i < 4 * TM * TN; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x006, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-            PNP_SCHED_FENCE();
-            PNP_SLICE(f0.load(As, Bs, 2, wm0, wn0, lane), f1.mma(acc), 4 * TM * TN, (TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN))
-            PNP_SLICE2(f1.load(As, Bs, 3, wm0, wn0, lane), f0.mma(acc), lstore(An, Bn), 4 * TM * TN, (TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN))
-            PNP_LAST_SLICE(f1.mma(acc), lstore(An, Bn), 4 * TM * TN)
-            __syncthreads();
+            PNP_MMA_STAGE(4, 8, 4 * TM * TN, gload(ncc, ntap), lstore(An, Bn))
             PNP_TRACE_MARK(3 + sc);
             f0.load(An, Bn, 0, wm0, wn0, lane);
         }
@@ -755,11 +692,8 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_taps3_kernel(ConvArgs a) {
         for (int i = 0; i < NPB; ++i) *reinterpret_cast<f32x4*>(Bn + (brow + RPB * i) * LDB + 4 * bcol) = r.b[i];
     };
 
-    constexpr bool SPLIT = PNP_SPLIT_ACC != 0 && TM * TN <= 2;
-    Acc<TM, TN> acc, accb;
+    Acc<TM, TN> acc;
     acc.zero();
-    if constexpr (SPLIT) accb.zero();
-#define PNP_T3_MMA(F) do { if constexpr (SPLIT) frag_mma2(F, acc, accb); else F.mma(acc); } while (0)
 
     const int ncc_total = a.C / BK;
     const int cc_begin = z * (a.chunks_per_split / NTAP);
@@ -788,7 +722,6 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_taps3_kernel(ConvArgs a) {
     PNP_TRACE_MARK(2);
     int o_cur = 0, o_nxt = STG, o_st = 2 * STG;        // float offsets of the LDS stages holding s, s+1 and receiving s+2
     constexpr int NMF = 4 * TM * TN;
-    constexpr int NDS = (TM + 4 * TN + NMF - 1) / NMF;
     for (int cc0 = cc_begin; cc0 < cc_end; cc0 += CCU) {
 #pragma unroll
         for (int u = 0; u < CCU; ++u) {
@@ -805,7 +738,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_taps3_kernel(ConvArgs a) {
                 // ---- slice 0: fragments of slice 2, the global loads of stage s+3 into the ring slot stored LAST stage
                 fr[2].load(As, Bs, 2, wm0, wn0, lane);
                 gload(ring[par ^ 1], PNP_T3_CC(cc, tap, 3), PNP_T3_TAP(tap, 3));
-                PNP_T3_MMA(fr[0]);
+                fr[0].mma(acc);
                 __builtin_amdgcn_sched_group_barrier(0x100, TM + 4 * TN, 0);
 #pragma unroll
                 for (int i = 0; i < NMF; ++i) {
@@ -814,21 +747,13 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_taps3_kernel(ConvArgs a) {
                     __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                 }
                 PNP_SCHED_FENCE();
-                PNP_SLICE(fr[3].load(As, Bs, 3, wm0, wn0, lane), PNP_T3_MMA(fr[1]), NMF, NDS)
+                PNP_SLICE(fr[3].load(As, Bs, 3, wm0, wn0, lane), fr[1].mma(acc))
                 // ---- slices 2, 3: the NEXT stage's slices 0, 1 (visible since the previous barrier); the LDS stores of stage s+2 ride
                 // behind the last MFMAs; the barrier then has nothing to wait for but the slowest wave
-                PNP_SLICE(fr[0].load(An, Bn, 0, wm0, wn0, lane), PNP_T3_MMA(fr[2]), NMF, NDS)
+                PNP_SLICE(fr[0].load(An, Bn, 0, wm0, wn0, lane), fr[2].mma(acc))
                 fr[1].load(An, Bn, 1, wm0, wn0, lane);
                 PNP_SCHED_FENCE();
-                PNP_T3_MMA(fr[3]);
-                lstore(ring[par], Ast, Bst);
-                __builtin_amdgcn_sched_group_barrier(0x008, NMF / 2, 0);
-#pragma unroll
-                for (int i = 0; i < NMF / 2; ++i) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-                }
-                PNP_SCHED_FENCE();
+                PNP_LAST_SLICE(fr[3].mma(acc), lstore(ring[par], Ast, Bst), NMF)
                 __syncthreads();
                 ++tsc;
                 PNP_TRACE_MARK(2 + tsc);
@@ -841,8 +766,6 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_taps3_kernel(ConvArgs a) {
     }
 #undef PNP_T3_CC
 #undef PNP_T3_TAP
-#undef PNP_T3_MMA
-    if constexpr (SPLIT) acc_add(acc, accb);
 
     PNP_TRACE_MARK(3 + tsc);
     conv_epilogue<TM, TN>(a, acc, a.y + (size_t)z * a.split_stride, m0, n0, wm0, wn0, lane, mt * WM + wave / WN, z == 0);
@@ -877,8 +800,6 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_wgrad_kernel(ConvArgs a) {
     BLoader<BN, VECB> lb;
     la.init(t, mm0, a, z * a.chunks_per_split * BK);
     lb.init(t);
-    constexpr bool BS = (MODE == 3) && VECB;       // host: dy < 2 GiB on this path
-    if constexpr (BS) lb.init_s(a.K, n0);
 
     Acc<TM, TN> acc;
     acc.zero();
@@ -894,8 +815,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_wgrad_kernel(ConvArgs a) {
     if (nchunks > 0) {
         const int pend = (c_end * BK < P) ? c_end * BK : P;     // this split's pixel range ends here
         la.load(a, rx, c_begin * BK, pend);
-        if constexpr (BS) lb.load_s(rw, c_begin * BK, a.K);
-        else lb.load(rw, c_begin * BK, pend, a.K, n0);
+        lb.load(rw, c_begin * BK, pend, a.K, n0);
         la.store(lds);
         lb.store(lds + 2 * ASZ);
         __syncthreads();
@@ -908,24 +828,8 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_wgrad_kernel(ConvArgs a) {
             float* An = lds + (cur ^ 1) * ASZ;
             float* Bn = lds + 2 * ASZ + (cur ^ 1) * BSZ;
             const int p0 = (c_begin + c + 1) * BK;                 // >= pend on the last stage -> zeros
-            f1.load(As, Bs, 1, wm0, wn0, lane);
-            la.load(a, rx, p0, pend);
-            if constexpr (BS) lb.load_s(rw, p0, a.K);
-            else lb.load(rw, p0, pend, a.K, n0);
-            f0.mma(acc);
-            __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);      // slice-1 fragment reads first
-#pragma unroll
-            for (int i = 0; i < 4 * TM * TN; ++i) {                     // then address arithmetic + loads under the MFMAs
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x006, 12, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-            PNP_SCHED_FENCE();
-            PNP_SLICE(f0.load(As, Bs, 2, wm0, wn0, lane), f1.mma(acc), 4 * TM * TN, (4 * TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN))
-            PNP_SLICE2(f1.load(As, Bs, 3, wm0, wn0, lane), f0.mma(acc), (la.store(An), lb.store(Bn)), 4 * TM * TN, (4 * TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN))
-            // stores after the last MFMAs: gives the global loads a whole stage of latency cover (see conv_fwd_kernel)
-            PNP_LAST_SLICE(f1.mma(acc), (la.store(An), lb.store(Bn)), 4 * TM * TN)
-            __syncthreads();
+            // stores behind the last MFMAs: gives the global loads a whole stage of latency cover (see conv_fwd_kernel)
+            PNP_MMA_STAGE(12, 16, 4 * TM * TN, (la.load(a, rx, p0, pend), lb.load(rw, p0, pend, a.K, n0)), (la.store(An), lb.store(Bn)))
             f0.load(An, Bn, 0, wm0, wn0, lane);
         }
     }
@@ -934,31 +838,22 @@ __global__ void __launch_bounds__(NTHREADS, 2) conv_wgrad_kernel(ConvArgs a) {
 }
 
 // ---- filter gradient, linear pixel walk (any stride, zero padding, OW >= 32, C % 4 == 0, K % 4 == 0), with a register
-// ring of DEPTH global-load stages.  Unlike the forward kernel (whose A rows are re-read for 9 taps and whose filters sit in L2), every
+// ring of DEPTH = 2 global-load stages.  Unlike the forward kernel (whose A rows are re-read for 9 taps and whose filters sit in L2), every
 // stage of the filter gradient fetches pixels nobody has touched before — all (tap, channel, filter) tiles of a pixel range walk it in
 // step, so the first toucher misses to HBM and the others wait on the same miss: the load latency of EVERY stage is an HBM round trip,
 // longer than the one stage (~64 MFMAs per wave) of cover conv_wgrad_kernel gives it.  Here stage j + DEPTH is requested while stage j
-// is contracted; the ring is indexed with compile-time constants only (loop unrolled by DEPTH), the tail is peeled.
-// PNP_WGRAD_ABLATE (compile-time, timing experiments only — results are wrong when set): 1 = no global loads after the prologue,
-// 2 = x loads at a fixed address (no address arithmetic), 4 = no LDS stores, 8 = no barrier
-#ifndef PNP_WGRAD_ABLATE
-#define PNP_WGRAD_ABLATE 0
-#endif
-// UNI (opt-in, see launch_wgrad_tile): C % BM == 0, so a 128-row tile of the filter gradient holds ONE filter tap and the coordinates /
-// validity / offset of a loader row depend on the pixel only — they are wave-uniform and are carried in SGPRs by the scalar unit (a wave's
-// two half-waves load two consecutive pixels: two scalar rows per load, selected per lane).  The per-lane walk costs 1.45 VALU
-// instructions per MFMA (PMC), this form about 0.15.
-#ifndef PNP_WGRAD_UNIFORM_ROWS
-#define PNP_WGRAD_UNIFORM_ROWS 1      // round 3: measured +2 % (512->512: 0.613 -> 0.601 ms, g10 3.07 -> 2.98 ms); PNP_WGRAD_UNI=0 at run time: off
-#endif
-// (UNI is folded into the depth parameter — DEPTH_ = 10 + depth — so that the measured kernels keep their symbol names.)
-#ifndef PNP_WGRAD_NARROW_WAVES
-#define PNP_WGRAD_NARROW_WAVES 2
-#endif
+// is contracted; the ring is indexed with compile-time constants only (loop unrolled by DEPTH), the tail is peeled.  Depths 1 and 3
+// measured slower.
+// UNI (PNP_WGRAD_UNI, default on; see launch_wgrad_tile): C % BM == 0, so a 128-row tile of the filter gradient holds ONE filter tap and
+// the coordinates / validity / offset of a loader row depend on the pixel only — they are wave-uniform and are carried in SGPRs by the
+// scalar unit (a wave's two half-waves load two consecutive pixels: two scalar rows per load, selected per lane).  The per-lane walk costs
+// 1.45 VALU instructions per MFMA (PMC), this form about 0.15 (round 3: 512->512 0.613 -> 0.601 ms, g10 3.07 -> 2.98 ms).
+// (UNI is folded into the last template argument — DEPTH_ = 10 + depth — so that the measured kernels keep their symbol names.)
 template <int BM, int BN, int WM, int WN, int DEPTH_>
-__global__ void __launch_bounds__(NTHREADS, (BN <= 64 ? PNP_WGRAD_NARROW_WAVES : 2)) conv_wgrad_ring_kernel(ConvArgs a) {
+__global__ void __launch_bounds__(NTHREADS, 2) conv_wgrad_ring_kernel(ConvArgs a) {
+    static_assert(DEPTH_ == 2 || DEPTH_ == 12, "a ring of two stages, per-lane or uniform rows");
     constexpr bool UNI = DEPTH_ >= 10;
-    constexpr int DEPTH = UNI ? DEPTH_ - 10 : DEPTH_;
+    constexpr int DEPTH = 2;
     constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
     constexpr int LDA = BM + 4, LDB = BN + 4;
     constexpr int ASZ = BK * LDA, BSZ = BK * LDB;
@@ -1073,10 +968,6 @@ __global__ void __launch_bounds__(NTHREADS, (BN <= 64 ? PNP_WGRAD_NARROW_WAVES :
                 st.a[i] = bload4(rx, ((lane & 32) ? so[1] : so[0]) + lane_c);
                 continue;
             }
-            if constexpr (PNP_WGRAD_ABLATE & 2) {          // timing experiment: the loads without their address arithmetic
-                st.a[i] = bload4(rx, (unsigned)l_off[i] & 0xFFFFFu);
-                continue;
-            }
             const bool ok = mok & ((unsigned)l_ih[i] < (unsigned)a.H) & ((unsigned)l_iw[i] < (unsigned)a.W);
             st.a[i] = bload4(rx, ok ? (unsigned)l_off[i] : OOB);
             l_iw[i] += step_w;
@@ -1113,34 +1004,13 @@ __global__ void __launch_bounds__(NTHREADS, (BN <= 64 ? PNP_WGRAD_NARROW_WAVES :
         __syncthreads();
         Frag<TM, TN, false, LDA, LDB> f0, f1;
         f0.load(lds, lds + 2 * ASZ, 0, wm0, wn0, lane);
-        constexpr int NDS = (4 * TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN);
         auto stage = [&](int j, Stage& fetch_into, const Stage& store_from, bool fetch) {
             const int cur = j & 1;
             const float* As = lds + cur * ASZ;
             const float* Bs = lds + 2 * ASZ + cur * BSZ;
             float* An = lds + (cur ^ 1) * ASZ;
             float* Bn = lds + 2 * ASZ + (cur ^ 1) * BSZ;
-            f1.load(As, Bs, 1, wm0, wn0, lane);
-            if constexpr (!(PNP_WGRAD_ABLATE & 1)) {
-                if (fetch) gload(fetch_into);
-            }
-            f0.mma(acc);
-            __builtin_amdgcn_sched_group_barrier(0x100, 4 * TM + 4 * TN, 0);      // slice-1 fragment reads first
-#pragma unroll
-            for (int i = 0; i < 4 * TM * TN; ++i) {                                // then address arithmetic + loads under the MFMAs
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x006, 12, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-            PNP_SCHED_FENCE();
-            PNP_SLICE(f0.load(As, Bs, 2, wm0, wn0, lane), f1.mma(acc), 4 * TM * TN, NDS)
-            PNP_SLICE2(f1.load(As, Bs, 3, wm0, wn0, lane), f0.mma(acc), lstore(store_from, An, Bn), 4 * TM * TN, NDS)
-            if constexpr (PNP_WGRAD_ABLATE & 4) {
-                f1.mma(acc);
-            } else {
-                PNP_LAST_SLICE(f1.mma(acc), lstore(store_from, An, Bn), 4 * TM * TN)
-            }
-            if constexpr (!(PNP_WGRAD_ABLATE & 8)) __syncthreads();
+            PNP_MMA_STAGE(12, 4 * TM + 4 * TN, 4 * TM * TN, if (fetch) gload(fetch_into), lstore(store_from, An, Bn))
             f0.load(An, Bn, 0, wm0, wn0, lane);
         };
         const int nmain = (nchunks / DEPTH) * DEPTH;
@@ -1148,9 +1018,7 @@ __global__ void __launch_bounds__(NTHREADS, (BN <= 64 ? PNP_WGRAD_NARROW_WAVES :
 #pragma unroll
             for (int d = 0; d < DEPTH; ++d) stage(j0 + d, ring[d], ring[(d + 1) % DEPTH], true);
         }
-        static_assert(DEPTH >= 1 && DEPTH <= 3, "tail below is written for rings of up to three");
-        if (DEPTH >= 2 && nchunks - nmain >= 1) stage(nmain, ring[0], ring[1 % DEPTH], false);
-        if (DEPTH >= 3 && nchunks - nmain >= 2) stage(nmain + 1, ring[1 % DEPTH], ring[2 % DEPTH], false);
+        if (nchunks - nmain >= 1) stage(nmain, ring[0], ring[1], false);
     }
 
     wgrad_epilogue<TM, TN>(a, acc, a.y + (size_t)z * a.split_stride, mm0, n0, wm0, wn0, lane);
@@ -1395,9 +1263,6 @@ SplitFit fit_split(int units, int want, size_t floats, size_t ws_bytes) {
     return {pnp_cdiv(units, per), per};
 }
 
-#ifndef PNP_TAPS3_DEFAULT
-#define PNP_TAPS3_DEFAULT 1
-#endif
 // filter shapes the tap-unrolled kernel is instantiated for: forward 3x3 / 5x5; data gradient 3x3 and the stride-phase sub-filters
 constexpr bool taps_shape(int kind, int R, int S) {
     if (R == 3 && S == 3) return true;
@@ -1409,7 +1274,7 @@ constexpr bool taps_shape(int kind, int R, int S) {
 template <int BM, int BN, int WM, int WN, int KIND>
 bool launch_taps(const ConvArgs& a, dim3 grid, hipStream_t st) {
     // three-stage kernel (conv_taps3_kernel) for the narrow tiles: its channel-group loop runs in pairs for odd tap counts
-    static const int env_t3 = getenv("PNP_CONV_TAPS3") ? atoi(getenv("PNP_CONV_TAPS3")) : PNP_TAPS3_DEFAULT;
+    static const int env_t3 = getenv("PNP_CONV_TAPS3") ? atoi(getenv("PNP_CONV_TAPS3")) : 1;
     // conv_taps3_kernel contracts channel groups in PAIRS when the tap count is odd (CCU = 2): every reduction split must then hold an
     // even number of groups — nothing on the device checks it (a clamped, duplicated stage would be contracted past cc_end), so the
     // condition is stated here per split, not inferred from the planner (round-3 advisor finding)
@@ -1532,12 +1397,6 @@ int wgrad_plan_split(int nblk, int nchunks) {
     return best;
 }
 
-// global-load stages in flight in the linear filter-gradient kernel (conv_wgrad_ring_kernel); measured at B=16, see DESIGN.md §4.1
-int wgrad_ring_depth() {
-    static const int d = getenv("PNP_WGRAD_DEPTH") ? atoi(getenv("PNP_WGRAD_DEPTH")) : 2;
-    return d < 1 ? 1 : (d > 3 ? 3 : d);
-}
-
 // the ring kernel's tile by filter count: 128 x {128, 64, 32}, the narrow one with scalar dy loads where K % 4 != 0
 struct RingTile { int bm, bn, wm, wn; bool vecb; };
 RingTile ring_tile(int K) {
@@ -1578,32 +1437,23 @@ int launch_wgrad_tile(ConvArgs& a, float* dw, float* ws, size_t ws_bytes, int wa
     if (lin && VECB && a.dtype == PNP_DTYPE_BF16) {
         const bool launched = launch_wgrad_bf16(a, BN == 128 ? 0 : (BN == 64 ? 1 : 2), grid, st);
         PNP_REQUIRE(launched, "conv_wgrad_bf16_kernel: no instance for a %dx%d tile", BM, BN);
-    } else if (lin_any && VECB && wgrad_ring_depth() > 1) {
-        // linear pixel walk with DEPTH global-load stages in flight (PNP_WGRAD_DEPTH = 1: conv_wgrad_kernel MODE 3, one stage in flight)
-        const int depth = wgrad_ring_depth();
+    } else if (lin_any && VECB) {
+        // linear pixel walk with two global-load stages in flight; scalar loader rows where a tile holds one tap (PNP_WGRAD_UNI=0: off)
         static const int env_uni = getenv("PNP_WGRAD_UNI") ? atoi(getenv("PNP_WGRAD_UNI")) : 1;
-        const bool uni = PNP_WGRAD_UNIFORM_ROWS != 0 && BM == 128 && env_uni && depth == 2 && (a.C % BM) == 0;
+        const bool uni = env_uni && (a.C % BM) == 0;
         // (the symbol rocprofv3 prints: the scalar-row variant carries 10 + depth as its last template argument)
         PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, conv_flops(a), conv_bytes(a), "conv_wgrad_ring_kernel<%d, %d, %d, %d, %d>", BM, BN, WM, WN,
-                        uni ? 10 + depth : depth);
-        if constexpr (VECB) {
-            bool done = false;
-            if constexpr (PNP_WGRAD_UNIFORM_ROWS != 0 && BM == 128) {          // scalar loader rows where a tile holds one tap
-                if (uni) {
-                    hipLaunchKernelGGL((conv_wgrad_ring_kernel<BM, BN, WM, WN, 12>), grid, dim3(NTHREADS), 0, st, a);
-                    done = true;
-                }
-            }
-            if (done) {
-            } else if (depth == 2) hipLaunchKernelGGL((conv_wgrad_ring_kernel<BM, BN, WM, WN, 2>), grid, dim3(NTHREADS), 0, st, a);
-            else hipLaunchKernelGGL((conv_wgrad_ring_kernel<BM, BN, WM, WN, 3>), grid, dim3(NTHREADS), 0, st, a);
-        }
+                        uni ? 12 : 2);
+        if (uni) hipLaunchKernelGGL((conv_wgrad_ring_kernel<BM, BN, WM, WN, 12>), grid, dim3(NTHREADS), 0, st, a);
+        else hipLaunchKernelGGL((conv_wgrad_ring_kernel<BM, BN, WM, WN, 2>), grid, dim3(NTHREADS), 0, st, a);
     } else {
+        // scalar dy columns (K % 4 != 0) on the linear walk: MODE 3; VECB with the linear walk is the ring kernel's
         const int kmode = lin ? 3 : ((a.C % 4 == 0) ? 1 : 2);
         PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, conv_flops(a), conv_bytes(a), "conv_wgrad_kernel<%d, %d, %d, %d, %d, %s>", BM, BN, WM, WN,
                         kmode, VECB ? "true" : "false");
-        if (lin) hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, WM, WN, 3, VECB>), grid, dim3(NTHREADS), 0, st, a);
-        else if (a.C % 4 == 0) hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, WM, WN, 1, VECB>), grid, dim3(NTHREADS), 0, st, a);
+        if (lin) {
+            if constexpr (!VECB) hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, WM, WN, 3, false>), grid, dim3(NTHREADS), 0, st, a);
+        } else if (a.C % 4 == 0) hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, WM, WN, 1, VECB>), grid, dim3(NTHREADS), 0, st, a);
         else hipLaunchKernelGGL((conv_wgrad_kernel<BM, BN, WM, WN, 2, VECB>), grid, dim3(NTHREADS), 0, st, a);
     }
     PNP_CHECK_LAUNCH("conv_wgrad_kernel");

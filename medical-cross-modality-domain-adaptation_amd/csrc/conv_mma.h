@@ -1,5 +1,5 @@
 // conv_mma.h — the register-pipelined fragment set and the slice schedule macros of the fp32 MFMA main loops
-// (conv_igemm.hip: convolutions; conv_wino.hip: the batched GEMM of the Winograd path).  Moved here unchanged from conv_igemm.hip.
+// (conv_igemm.hip: convolutions; conv_wino.hip: the batched GEMM of the Winograd path).
 #pragma once
 #include "conv_common.h"
 
@@ -44,62 +44,53 @@ struct Frag {
 }  // namespace pnpconv
 
 #define PNP_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-// Schedule of slices 1..3 of a stage (two Frag sets: the fragment reads of the NEXT slice and the MFMAs of THIS slice are independent).
-// PNP_CONV_ILV selects where the next stage's LDS stores go (compile-time; measured A/B/A/B on the 512-channel layers at B=16):
-//   0  after the last slice's MFMAs (round 1)
-//   1  as 0, with the fragment reads of slices 2 / 3 interleaved behind single MFMAs instead of in front of them: no change
-//   2  behind the second half of the last slice's MFMAs: 512->512 forward +2.4 %, g10 forward +3.2 % / wgrad +4.6 %, segmenter step
-//      422 -> 434 slices/s, joint GAN step 147.4 -> 151.1 — the stores (and the vmcnt wait in front of them) left the exposed chain
-//      [last MFMA -> stores -> barrier -> first fragment reads -> first MFMA] that the co-resident workgroup has to cover
-//   3  behind the first half of the last slice;  4  behind the second half of slice 2 (loads are issued under slice 0)
-#ifndef PNP_CONV_ILV
-#define PNP_CONV_ILV 2
-#endif
-#define PNP_STORE_BEHIND(MMA, STORE, NMFMA, LEAD)                           \
-    MMA;                                                                    \
-    STORE;                                                                  \
-    if ((LEAD) > 0) __builtin_amdgcn_sched_group_barrier(0x008, (LEAD), 0); \
-    _Pragma("unroll") for (int i_ = 0; i_ < (NMFMA) / 2; ++i_) {            \
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                  \
-        __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                  \
-    }                                                                       \
-    PNP_SCHED_FENCE();
-// last slice (+ the next stage's LDS stores unless they already went behind slice 2)
-#define PNP_LAST_SLICE(MMA, STORE, NMFMA)                                   \
-    if constexpr (PNP_CONV_ILV == 2) {                                      \
-        PNP_STORE_BEHIND(MMA, STORE, NMFMA, (NMFMA) / 2)                    \
-    } else if constexpr (PNP_CONV_ILV == 3) {                               \
-        PNP_STORE_BEHIND(MMA, STORE, NMFMA, 0)                              \
-    } else if constexpr (PNP_CONV_ILV == 4) {                               \
-        MMA;                                                                \
-        PNP_SCHED_FENCE();                                                  \
-    } else {                                                                \
-        MMA;                                                                \
-        PNP_SCHED_FENCE();                                                  \
-        STORE;                                                              \
-        PNP_SCHED_FENCE();                                                  \
+// Slices 1..3 of a stage (two Frag sets: the fragment reads of the NEXT slice and the MFMAs of THIS slice are independent).  A slice is its
+// fragment reads, then its MFMAs; the next stage's LDS stores go behind the second half of the LAST slice's MFMAs.  Measured A/B/A/B on the
+// 512-channel layers at B=16 against stores after the last slice (round 1): 512->512 forward +2.4 %, g10 forward +3.2 % / wgrad +4.6 %,
+// segmenter step 422 -> 434 slices/s, joint GAN step 147.4 -> 151.1 — the stores (and the vmcnt wait in front of them) left the exposed
+// chain [last MFMA -> stores -> barrier -> first fragment reads -> first MFMA] that the co-resident workgroup has to cover.  Fragment reads
+// interleaved behind single MFMAs, stores behind the first half of the last slice or behind slice 2 were no better (tools/experiments/).
+#define PNP_SLICE(LOAD, MMA) \
+    {                        \
+        LOAD;                \
+        PNP_SCHED_FENCE();   \
+        MMA;                 \
+        PNP_SCHED_FENCE();   \
     }
-// slice 2 (variant 4 carries the stores here)
-#define PNP_SLICE2(LOAD, MMA, STORE, NMFMA, NDS)                            \
-    if constexpr (PNP_CONV_ILV == 4) {                                      \
-        LOAD;                                                               \
-        PNP_SCHED_FENCE();                                                  \
-        PNP_STORE_BEHIND(MMA, STORE, NMFMA, (NMFMA) / 2)                    \
-    } else {                                                                \
-        PNP_SLICE(LOAD, MMA, NMFMA, NDS)                                    \
+#define PNP_LAST_SLICE(MMA, STORE, NMFMA)                                \
+    {                                                                    \
+        MMA;                                                             \
+        STORE;                                                           \
+        __builtin_amdgcn_sched_group_barrier(0x008, (NMFMA) / 2, 0);     \
+        _Pragma("unroll") for (int i_ = 0; i_ < (NMFMA) / 2; ++i_) {     \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);           \
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);           \
+        }                                                                \
+        PNP_SCHED_FENCE();                                               \
     }
-#define PNP_SLICE(LOAD, MMA, NMFMA, NDS)                                   \
-    if constexpr (PNP_CONV_ILV == 1) {                                      \
-        LOAD;                                                               \
-        MMA;                                                                \
-        _Pragma("unroll") for (int i_ = 0; i_ < (NMFMA); ++i_) {            \
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);              \
-            __builtin_amdgcn_sched_group_barrier(0x100, (NDS), 0);          \
-        }                                                                   \
-        PNP_SCHED_FENCE();                                                  \
-    } else {                                                                \
-        LOAD;                                                               \
-        PNP_SCHED_FENCE();                                                  \
-        MMA;                                                                \
-        PNP_SCHED_FENCE();                                                  \
+// One whole stage of the two-buffer, four-slice pipeline, barrier included (conv_igemm.hip: conv_taps_kernel, conv_wgrad_kernel,
+// conv_wgrad_ring_kernel; conv_wino.hip: wino_gemm_kernel, wino_wgrad_gemm_kernel).  It names the caller's locals: Frag sets f0 / f1 (f0
+// holds slice 0 on entry), acc, this stage's LDS tiles As / Bs, wm0 / wn0 / lane.  FETCH issues the next stage's global loads, STORE writes
+// them to the other LDS buffer.  Slice 0 puts the slice-1 fragment reads first (NDS0 ds_reads), then per MFMA (NMFMA of them) NVALU
+// address VALU / SALU instructions and one buffer_load, so that the next stage's address arithmetic rides in the MFMAs' shadow.  The two
+// counts follow the kernel's fetch and A layout: NVALU is the address work per load — 4 for tap-unrolled or precomputed scalar-offset rows
+// (taps, wino_gemm), 6 for wino_wgrad_gemm's row test, 12 for the filter gradients' per-row pixel walk / divisions; NDS0 covers one
+// slice's fragments — TM + 4*TN <= 10 reads for an M-major A tile (8 passed), 4*TM + 4*TN <= 16 for a k-major one (16, or the ring
+// kernel's exact count).  conv_fwd_body keeps a stage of its own: its stores come after ALL MFMAs of the last slice, a different schedule.
+#define PNP_MMA_STAGE(NVALU, NDS0, NMFMA, FETCH, STORE)                               \
+    {                                                                                 \
+        f1.load(As, Bs, 1, wm0, wn0, lane);                                           \
+        FETCH;                                                                        \
+        f0.mma(acc);                                                                  \
+        __builtin_amdgcn_sched_group_barrier(0x100, (NDS0), 0);                       \
+        _Pragma("unroll") for (int i_ = 0; i_ < (NMFMA); ++i_) {                      \
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                        \
+            __builtin_amdgcn_sched_group_barrier(0x006, (NVALU), 0);                  \
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                        \
+        }                                                                             \
+        PNP_SCHED_FENCE();                                                            \
+        PNP_SLICE(f0.load(As, Bs, 2, wm0, wn0, lane), f1.mma(acc))                    \
+        PNP_SLICE(f1.load(As, Bs, 3, wm0, wn0, lane), f0.mma(acc))                    \
+        PNP_LAST_SLICE(f1.mma(acc), STORE, NMFMA)                                     \
+        __syncthreads();                                                              \
     }

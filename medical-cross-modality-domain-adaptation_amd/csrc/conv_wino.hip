@@ -451,25 +451,10 @@ __global__ void __launch_bounds__(NTHREADS, 2) wino_gemm_kernel(WinoGemmArgs g) 
             const int cn = lastst ? cc0_n : cc + 1;
             const int sa = cn * (BK * 4);
             const int sb = (cn * BK * g.K) * 4;
-            // ---- slice 0
-            f1.load(As, Bs, 1, wm0, wn0, lane);
-#pragma unroll
-            for (int i = 0; i < NR; ++i) areg[i] = bload4s(rx, lastst ? abase_n[i] : abase[i], sa);
-#pragma unroll
-            for (int i = 0; i < NPB; ++i) breg[i] = bload4s(rw, lastst ? boff_n[i] : boff[i], sb);
-            f0.mma(acc);
-            __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);
-#pragma unroll
-            for (int i = 0; i < 4 * TM * TN; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x006, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-            PNP_SCHED_FENCE();
-            PNP_SLICE(f0.load(As, Bs, 2, wm0, wn0, lane), f1.mma(acc), 4 * TM * TN, (TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN))
-            PNP_SLICE2(f1.load(As, Bs, 3, wm0, wn0, lane), f0.mma(acc), lstore(An, Bn), 4 * TM * TN, (TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN))
-            PNP_LAST_SLICE(f1.mma(acc), lstore(An, Bn), 4 * TM * TN)
-            __syncthreads();
+            PNP_MMA_STAGE(4, 8, 4 * TM * TN,
+                          _Pragma("unroll") for (int i = 0; i < NR; ++i) areg[i] = bload4s(rx, lastst ? abase_n[i] : abase[i], sa);
+                          _Pragma("unroll") for (int i = 0; i < NPB; ++i) breg[i] = bload4s(rw, lastst ? boff_n[i] : boff[i], sb),
+                          lstore(An, Bn))
             f0.load(An, Bn, 0, wm0, wn0, lane);
         }
         if (in_tail && tail_piece > 0) {
@@ -1000,21 +985,7 @@ __global__ void __launch_bounds__(NTHREADS, 2) wino_wgrad_gemm_kernel(WinoWgradG
             const float* Bs = lds + 2 * ASZ + cur * BSZ;
             float* An = lds + (cur ^ 1) * ASZ;
             float* Bn = lds + 2 * ASZ + (cur ^ 1) * BSZ;
-            f1.load(As, Bs, 1, wm0, wn0, lane);
-            gload(r_begin + (c + 1) * BK);
-            f0.mma(acc);
-            __builtin_amdgcn_sched_group_barrier(0x100, 16, 0);
-#pragma unroll
-            for (int i = 0; i < 4 * TM * TN; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x006, 6, 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-            PNP_SCHED_FENCE();
-            PNP_SLICE(f0.load(As, Bs, 2, wm0, wn0, lane), f1.mma(acc), 4 * TM * TN, (4 * TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN))
-            PNP_SLICE2(f1.load(As, Bs, 3, wm0, wn0, lane), f0.mma(acc), lstore(An, Bn), 4 * TM * TN, (4 * TM + 4 * TN + 4 * TM * TN - 1) / (4 * TM * TN))
-            PNP_LAST_SLICE(f1.mma(acc), lstore(An, Bn), 4 * TM * TN)
-            __syncthreads();
+            PNP_MMA_STAGE(6, 16, 4 * TM * TN, gload(r_begin + (c + 1) * BK), lstore(An, Bn))
             f0.load(An, Bn, 0, wm0, wn0, lane);
         }
     }

@@ -7,7 +7,8 @@ partial sums of csrc/split_sum.h, the vector-ALU route file csrc/conv_valu.hip).
 
 `dump` runs conv2d_fwd (with and without dropout 0.5), conv2d_dgrad (with and without residual) and conv2d_wgrad (with and without into=)
 over the FWD, STRIDED and WGRAD tables of tests/test_igemm_domain_host.py in fp32 and bf16 arithmetic, at the library's default switches and
-(filter gradient only) with the Winograd and split-bf16 routes off, which is where the fp32 routes of the tables run; the X3W part counts of
+(filter gradient only) with the Winograd and split-bf16 routes off, which is where the fp32 routes of the tables run; FWD and WGRAD once more
+with the Winograd route wherever eligible and its GEMMs in fp32 (wino_x3 0); the X3W part counts of
 tests/test_gpu_x3_wgrad.py (FEW_PARTS, x3_direct mode 2); and the bf16-resident filter gradient of one layer.  PNP_BF16R_WSPLIT is read once
 per process: `dump <file> bf16r` runs that layer alone, for one dump per forced split.  Inputs are seeded on the device; the file holds one
 SHA-256 per output array."""
@@ -82,6 +83,12 @@ def dump(path, only=None):
         for N, OH, OW, C in ((1, 16, 48, 64), (1, 16, 48, 32), (17, 16, 16, 64), (17, 16, 16, 32)):           # test_gpu_x3_wgrad.FEW_PARTS
             _layer(K, L, out, "X3W %dx%dx%dx%d" % (N, OH, OW, C), (N, OH, OW, C, 64, 3, 3, 1, 1, "SAME"), L.DTYPE_F32, dev, gen, passes=(2,))
         K.wino_mode(prev[0]); K.wino_wgrad_mode(prev[1]); K.x3_direct(prev[2]); K.x3_strided(prev[3]); K.x3_wgrad(prev[4])
+        # the Winograd route wherever eligible, its GEMMs on the fp32 matrix pipe (wino_gemm_kernel, wino_wgrad_gemm_kernel)
+        prev = (K.wino_x3(0), K.wino_mode(2), K.wino_wgrad_mode(2), K.x3_direct(0), K.x3_wgrad(0))
+        for table, cases in (("FWD", H.FWD), ("WGRAD", H.WGRAD)):
+            for case in cases:
+                _layer(K, L, out, "%s %s f32 wino-fp32" % (table, H.case_id(case)), case, L.DTYPE_F32, dev, gen)
+        K.wino_x3(prev[0]); K.wino_mode(prev[1]); K.wino_wgrad_mode(prev[2]); K.x3_direct(prev[3]); K.x3_wgrad(prev[4])
     json.dump(out, open(path, "w"), indent=0, sort_keys=True)
     print("%s: %d arrays, library %s" % (path, len(out), os.environ.get("PNP_LIB", "(the tree's)")))
 
