@@ -470,6 +470,17 @@ int pnp_pseudo_label_loss(const float* logits, const float* thresholds, int64_t 
 size_t pnp_pseudo_label_update_workspace_bytes(int64_t P, int32_t ncls);
 int pnp_pseudo_label_update(const uint8_t* labels, const float* conf, int64_t P, int32_t ncls, double portion, float momentum,
                             float* thresholds, float* q_out, void* workspace, size_t workspace_bytes, void* stream);
+/* Fourier domain adaptation (csrc/fda.hip; not in the reference; Yang & Soatto, CVPR 2020).
+ * src [B, H, W, C], tgt [Bt, H, W, C], fp32 NHWC in device memory; band, pair: HOST int32 arrays of length B (they travel in the kernel
+ * argument block).  Per sample i and channel c, S = DFT2(src[i, :, :, c]), T = DFT2(tgt[pair[i], :, :, c]), b = band[i]:
+ * out[i, :, :, c] = src[i, :, :, c] + Re IDFT2(D), D(u, v) = (|T| - |S|) S / |S| on |u| <= b, |v| <= b (|S| = 0: |T|), 0 elsewhere —
+ * the source keeps its phase and takes the target's amplitude on the band.  band[i] = -1: sample i is copied bit for bit.
+ * 1 <= B, Bt <= 256, 1 <= H, W <= 1024, 1 <= C <= 4, -1 <= band[i] <= (min(H, W) - 1) / 2, 0 <= pair[i] < Bt; out may be src itself
+ * (in place), no other overlap of out with src or tgt.  Separable truncated DFT, fp32 FMAs, no atomics: bit-identical from run to run.
+ * ws: pnp_fda_workspace_bytes(B, Bt, H, W, C, max over i of band[i]) (0, and ws may be NULL, when every band is -1). */
+size_t pnp_fda_workspace_bytes(int32_t B, int32_t Bt, int32_t H, int32_t W, int32_t C, int32_t max_band);
+int pnp_fda_amplitude_swap(const float* src, int32_t B, const float* tgt, int32_t Bt, int32_t H, int32_t W, int32_t C, const int32_t* band,
+                           const int32_t* pair, float* out, void* workspace, size_t workspace_bytes, void* stream);
 /* p[0..n) = value  (constant gradient of a mean: coef / B) */
 int pnp_fill(float* p, size_t n, float value, void* stream);
 

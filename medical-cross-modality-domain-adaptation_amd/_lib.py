@@ -164,6 +164,8 @@ PROTOTYPES = {
     "pnp_pseudo_label_loss": (c_int, [_F, _F, c_int64, c_int32, c_uint32, c_float, _F, c_void_p, _F, _F, c_void_p, c_void_p, c_size_t, c_void_p]),
     "pnp_pseudo_label_update_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "pnp_pseudo_label_update": (c_int, [c_void_p, _F, c_int64, c_int32, c_double, c_float, _F, _F, c_void_p, c_size_t, c_void_p]),
+    "pnp_fda_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "pnp_fda_amplitude_swap": (c_int, [_F, c_int32, _F, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, _F, c_void_p, c_size_t, c_void_p]),
     "pnp_wgan_loss": (c_int, [_F, _F, _F, _F, c_int32, c_float, c_float, c_float, c_float, _F, c_void_p]),
     "pnp_fill": (c_int, [_F, c_size_t, c_float, c_void_p]),
     "pnp_label_decomp": (c_int, [_F, _F, c_int64, c_int32, c_void_p]),

@@ -1155,6 +1155,36 @@ def pseudo_label_update(labels, conf, thresholds, portion, momentum):
     return q
 
 
+def fda_amplitude_swap(src, tgt, band, pair, out=None):
+    """Fourier domain adaptation (csrc/fda.hip): src [B, H, W, C] keeps the phase of every channel's 2-D spectrum and takes
+    the amplitude of tgt[pair[i]] ([Bt, H, W, C]) on the square |u|, |v| <= band[i] of low frequencies; band[i] = -1 leaves sample i as it
+    is, bit for bit.  band, pair: B host integers each (sequences, numpy arrays or CPU tensors), checked by the library.  out: None (a new
+    tensor), src itself (in place) or a tensor that overlaps neither input.  -> out.  Stream-ordered, bit-identical from run to run."""
+    import numpy as np
+    lib = _lib.load()
+    ps, pt = _p(src), _p(tgt)
+    if src.dim() != 4 or tgt.dim() != 4 or tuple(tgt.shape[1:]) != tuple(src.shape[1:]):
+        raise _lib.PnpError("fda_amplitude_swap: src [B, H, W, C] and tgt [Bt, H, W, C] of one image size, got %s and %s"
+                            % (tuple(src.shape), tuple(tgt.shape)))
+    B, H, W, C = src.shape
+    bd = np.ascontiguousarray(np.asarray(band, dtype=np.int64).reshape(-1))
+    pr = np.ascontiguousarray(np.asarray(pair, dtype=np.int64).reshape(-1))
+    if bd.shape != (B,) or pr.shape != (B,):
+        raise _lib.PnpError("fda_amplitude_swap: %d bands and %d pairs for %d samples" % (bd.size, pr.size, B))
+    if B and (np.abs(bd).max() >= 2 ** 31 or np.abs(pr).max() >= 2 ** 31):
+        raise _lib.PnpError("fda_amplitude_swap: band or pair out of the int32 range")
+    bd, pr = bd.astype(np.int32), pr.astype(np.int32)
+    y = torch.empty_like(src) if out is None else out
+    po = _p(y)
+    if tuple(y.shape) != tuple(src.shape):
+        raise _lib.PnpError("fda_amplitude_swap: out has shape %s, src %s" % (tuple(y.shape), tuple(src.shape)))
+    need = lib.pnp_fda_workspace_bytes(B, tgt.shape[0], H, W, C, int(bd.max()) if B else -1)
+    ws = workspace(need, src.device, slot="fda")
+    check(lib.pnp_fda_amplitude_swap(ps, B, pt, tgt.shape[0], H, W, C, bd.ctypes.data_as(ctypes.c_void_p), pr.ctypes.data_as(ctypes.c_void_p),
+                                     po, ctypes.c_void_p(ws.data_ptr()), ws.numel(), _stream()), "pnp_fda_amplitude_swap")
+    return y
+
+
 def filled(shape, value, device):
     t = torch.empty(shape, dtype=torch.float32, device=device)
     check(_lib.load().pnp_fill(_p(t), t.numel(), float(value), _stream()), "pnp_fill")

@@ -379,12 +379,15 @@ class Trainer(object):
     :param net: the network instance to train
     :param train_list / val_list: lists of .tfrecords files (one 256x256x3 slice each), or any object with a
            `next_batch(batch_size) -> np.ndarray [B,256,256,4]` method (image channels 0:3, label map in channel 3)
+    :param fda: None, or a callable on the training batch's images (fda.FdaStylizer) applied before each training step, outside a
+           recorded step; output_minibatch_stats sees its result, validation never does
     """
 
     def __init__(self, net, train_list, val_list, num_cls, batch_size, test_nii_list=None, test_label_list=None,
                  optimizer="momentum", opt_kwargs={}, num_epochs=100, checkpoint_space=500, lr_update_flag=False,
-                 reducer=None, shard=None, bnd_ramp=None):
+                 reducer=None, shard=None, bnd_ramp=None, fda=None):
         self.net = net
+        self.fda = fda                  # fda.FdaStylizer or None: stylises every training batch before its step (DESIGN.md §30)
         # boundary term (DESIGN.md §28): bnd_ramp = N raises the weight over the first N epochs, epoch e trains with
         # bnd_weight * min(1, (e + 1) / N) (the paper raises the weight over training); None: the configured weight throughout
         self.bnd_ramp = None if not bnd_ramp else int(bnd_ramp)
@@ -559,6 +562,8 @@ class Trainer(object):
                 for step in range((epoch * training_iters), ((epoch + 1) * training_iters)):
                     start = time.time()
                     batch_x, batch_y, fid = feed_all.next()
+                    if self.fda is not None:
+                        batch_x = self.fda(batch_x)
                     loss = self.train_step(batch_x, batch_y, dropout, step)
                     if pending is not None:
                         self._log_step(pending)

@@ -6,7 +6,8 @@ a millimetre grid; --prefilter auto|off|SX,SY,SZ low-passes them
 every listed orientation; --crop-body [N] crops every volume to its body, found without a label, --crop-margin N to its
 label bounding box); --bnd-weight W adds W times the boundary (distance-map) loss of Kervadec et al. to the cost
 (default 0 = the reference), --bnd-ramp EPOCHS raises that weight linearly over the first EPOCHS epochs, --bnd-classes 1,3
-restricts it to the listed classes (default: every class but the background).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
+restricts it to the listed classes (default: every class but the background); --fda-target LIST --fda-beta B|LO,HI --fda-prob P
+stylise every training batch with the low-frequency amplitude spectra of target slices (Fourier domain adaptation).  Launched under `python -m torch.distributed.run --nproc-per-node N` it trains data-parallel:
 one process per GPU over RCCL, --batch-size slices PER RANK, file lists sharded by rank, rank 0 writes the checkpoint.
   python -m "medical-cross-modality-domain-adaptation_amd.train_segmenter" --synthetic 8 --batch-size 4 --iters 2 --epochs 1
 """
@@ -50,6 +51,8 @@ def parse_args(argv=None):
     add_sampling_flags(ap)
     from . import body
     body.add_crop_flags(ap)
+    from .fda import add_fda_flags, fda_from_args
+    add_fda_flags(ap)
     ap.add_argument("--bnd-weight", type=float, default=0.0, help="weight of the boundary (distance-map) loss of the logits against the "
                     "labels' signed distance maps, computed on the device every step (DESIGN.md §28); default 0 = the reference")
     ap.add_argument("--bnd-ramp", type=int, default=None, metavar="EPOCHS", help="raise --bnd-weight linearly over the first EPOCHS epochs "
@@ -70,6 +73,7 @@ def parse_args(argv=None):
             ap.error("--bnd-classes takes class indices separated by commas, got %r" % args.bnd_classes)
         if not args.bnd_classes or not all(0 <= c < NUM_CLS for c in args.bnd_classes):
             ap.error("--bnd-classes must name classes in 0 ... %d, got %r" % (NUM_CLS - 1, args.bnd_classes))
+    fda_from_args(ap, args)
     return ap, args
 
 
@@ -144,14 +148,32 @@ def main(argv=None):
         if not train_list:
             raise SystemExit("no training list at %s (use --synthetic N)" % train_fid)
 
+    fda = None
+    if args.fda_target:          # the target list is sharded by rank like the training list
+        from .fda import FdaStylizer, nifti_target_source
+        shard = (rank, world) if world > 1 else None
+        if args.nii_train:
+            target = nifti_target_source(args.fda_target, device, batch_size, sample_mm=sample_mm, prefilter=prefilter, axes=axes, crop=crop,
+                                         shard=shard)
+        else:
+            target = _read_lists(args.fda_target)
+            if not target:
+                raise SystemExit("no target slice list at %s" % args.fda_target)
+        fda = FdaStylizer(target, beta=args.fda_beta, prob=args.fda_prob, shard=shard)
+
     net = drn.Full_DRN(channels=3, batch_size=batch_size, n_class=num_cls, cost_kwargs=cost_kwargs, device=device, world_size=world)
     print("Network has been built!")
     trainer = drn.Trainer(net, train_list=train_list, val_list=val_list, num_cls=num_cls, batch_size=batch_size, opt_kwargs=opt_kwargs,
                           checkpoint_space=checkpoint_space, optimizer=optimizer, lr_update_flag=False,
                           reducer=GradReducer(net.store) if world > 1 else None, shard=(rank, world) if world > 1 else None,
-                          **({"bnd_ramp": args.bnd_ramp} if args.bnd_weight > 0 and args.bnd_ramp else {}))
+                          **({"bnd_ramp": args.bnd_ramp} if args.bnd_weight > 0 and args.bnd_ramp else {}),
+                          **({"fda": fda} if fda is not None else {}))
     print("Now start training...")
-    trainer.train(output_path=output_path, training_iters=training_iters, epochs=epochs, restore=args.restore, restored_path=output_path)
+    try:
+        trainer.train(output_path=output_path, training_iters=training_iters, epochs=epochs, restore=args.restore, restored_path=output_path)
+    finally:
+        if fda is not None:
+            fda.close()
     return trainer
 
 
