@@ -11,7 +11,8 @@
 //   2 column analysis    F(u, v) = sum_h R(h, v) e^{-2 pi i u h / H},  u in [-b, b]
 //   3 column synthesis   G(h, v) = sum_u D(u, v) e^{+2 pi i u h / H}, D formed from the source's and the target's F with hypotf
 //   4 row synthesis      out(h, w) = src(h, w) + 1 / (H W) sum_v m_v Re(G(h, v) e^{+2 pi i v w / W}),  m_0 = 1, m_v>0 = 2
-// Twiddles: (k x) mod N is kept exactly in integers and indexes a table that each block fills with sincospif; no angle is accumulated.
+// Twiddles: (k x) mod N is kept exactly in integers and indexes a table that each block fills with sincospi in double, rounded to fp32;
+// no angle is accumulated.
 // Plain fp32 FMAs, no atomics, one fixed summation order: bit-identical from run to run.  band and pair travel in the argument block
 // (checked on the host, no copy, no host read); a target's band is the largest band of the samples paired with it.
 #include "pnp_common.h"
@@ -33,13 +34,14 @@ struct FdaArgs {
     uint8_t pair[MAX_BATCH];
 };
 
-// tw[k] = (cos, sin)(2 pi k / N), the angle taken in (-pi, pi]
+// tw[k] = (cos, sin)(2 pi k / N), the angle taken in (-pi, pi], evaluated in double and rounded once to fp32.  An fp32 argument 2 kk / N
+// is itself off by up to 2^-24 of its value; such a table nearly doubled the error of a phase-sensitive case.
 __device__ __forceinline__ void fill_twiddles(float2* tw, int N) {
     for (int k = threadIdx.x; k < N; k += NT) {
         const int kk = 2 * k <= N ? k : k - N;
-        float s, c;
-        sincospif((float)(2 * kk) / (float)N, &s, &c);
-        tw[k] = make_float2(c, s);
+        double s, c;
+        sincospi((double)(2 * kk) / (double)N, &s, &c);
+        tw[k] = make_float2((float)c, (float)s);
     }
 }
 
