@@ -382,13 +382,12 @@ bool wgd_ok(const pnp_conv_geom* g);
 size_t wgd_workspace_bytes(const pnp_conv_geom* g);
 int wgd_blocks(const pnp_conv_geom* g);
 int launch_wgd(const float* x, const float* dy, float* part, const pnp_conv_geom* g, const ConvArgs& a, hipStream_t st);
-// Winograd F(2x2, 3x3) route of the wide stride-1 3x3 convolutions, forward and data gradient (conv_wino.hip).  eligible: the geometry can
-// run it; chosen: eligible and the policy takes it (PNP_WINOGRAD = 0 never / 1 where the cost model says it pays / 2 wherever eligible).
+// Winograd F(2x2, 3x3) route of the wide stride-1 3x3 convolutions, forward and data gradient (conv_wino.hip; declarations below).  The
+// policy takes an eligible geometry under PNP_WINOGRAD = 0 never / 1 where the cost model says it pays / 2 wherever eligible.
 // launch_wino runs Winograd and nothing else, with the whole epilogue of ConvArgs (dropout, residual add, statistics partials, fused inference BN); its statistics
-// partial rows are the tile slabs of the output transform (wino_stats_parts), not the direct kernel's wave rows.
+// partial rows are the tile slabs of the output transform (WinoQuery::stats_parts), not the direct kernel's wave rows.
 // Round 5: the route has two output tiles, F(2x2, 3x3) and F(4x4, 3x3) (36 instead of 64 multiplications per 4x4 outputs; PNP_WINOGRAD_TILE /
-// pnp_conv2d_wino_tile: the largest the planner may pick).  wino_tile: 0 (direct kernels), 2 or 4 for the forward of this geometry.
-bool wino_eligible(const pnp_conv_geom* g);
+// pnp_conv2d_wino_tile: the largest the planner may pick).
 // conv_x3_direct.hip: direct split-bf16 3x3 convolutions of the narrow layers x3d_chosen() takes (the plan's route X3D, ahead of Winograd;
 // no fused inference BN)
 bool x3d_chosen(const pnp_conv_geom* g);
@@ -412,13 +411,17 @@ int launch_x3_wgrad(const float* x, const float* dy, float* dw, const pnp_conv_g
 bool x3n_chosen(const pnp_conv_geom* g, int kind);
 size_t x3n_filter_bytes(int kind);
 int launch_x3_narrow(const ConvArgs& a, int kind, void* ws, size_t ws_bytes, hipStream_t st);
-int wino_tile(const pnp_conv_geom* g);
-size_t wino_workspace_bytes(const pnp_conv_geom* g);
-int wino_stats_parts(const pnp_conv_geom* g);
+// what the route's plan of a pass (conv_wino.hip: plan_wino / plan_wino_wgrad — the same plan the launch reads) answers for a geometry:
+// tile 0 (direct kernels: no bytes, no parts), 2 or 4; the workspace the launch asks for; the statistics partial rows it leaves (forward)
+struct WinoQuery {
+    int tile;
+    size_t ws_bytes;
+    int stats_parts;
+};
+WinoQuery wino_query(const pnp_conv_geom* g);
 int launch_wino(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st);
 // the filter gradient on the same route (its own switch, PNP_WINOGRAD_WGRAD): a = make_args(x, dy, -, g) of the forward geometry
-int wino_wgrad_tile(const pnp_conv_geom* g);
-size_t wino_wgrad_workspace_bytes(const pnp_conv_geom* g);
+WinoQuery wino_wgrad_query(const pnp_conv_geom* g);
 int launch_wino_wgrad(const ConvArgs& a, float* dw, int accumulate, void* ws, size_t ws_bytes, hipStream_t st);
 // split-bf16 GEMMs of the route (conv_wino_x3.hip): M[pos] = V3[pos] x U3[pos]^T, V3 [npos][3][T][C] / U3 [npos][3][K][C] bf16 planes
 // (hi, mid, lo: their sum is the fp32 value), M [npos][T][K] fp32.  dims_ok: one buffer descriptor per operand and transform point.

@@ -1571,7 +1571,7 @@ int launch_phase_group(const float* dy, const float* wt, float* outp, const pnp_
 }  // namespace
 
 // ---- one plan per pass ---------------------------------------------------------------------------------------------------------
-// plan_fwd / plan_dgrad / plan_wgrad are the ONLY code that combines the families' predicates (n16_geom_ok, narrow_fwd_ok, wino_tile,
+// plan_fwd / plan_dgrad / plan_wgrad are the ONLY code that combines the families' predicates (n16_geom_ok, narrow_fwd_ok, wino_query,
 // x3d_chosen, x3s_chosen, x3n_chosen, plan_phases, x3w_chosen, n16_wgrad_ok, wgd_ok, choose_tile / choose_split, ring_split): each states the
 // precedence of its pass once, top to bottom.  The workspace / partial-row / route queries read the plan, and the entry points take the
 // first candidate whose workspace the caller brought and switch on its route.
@@ -1616,7 +1616,8 @@ enum { EP_WS = 1, EP_STATS = 2, EP_BN = 4 };
 static ConvPlan plan_fwd(const pnp_conv_geom* g, unsigned ep) {
     const bool ws = ep & EP_WS, stats = ep & EP_STATS, bn = ep & EP_BN;
     ConvPlan p{};
-    p.tile = wino_tile(g);
+    const WinoQuery wq = wino_query(g);          // conv_wino.hip: its plan of this layer, asked once
+    p.tile = wq.tile;
     const long long M = (long long)g->N * g->OH * g->OW;
     const int ns = fwd_split(g);
     const size_t split = ns > 1 ? (size_t)ns * M * g->K * sizeof(float) : 0;
@@ -1640,7 +1641,7 @@ static ConvPlan plan_fwd(const pnp_conv_geom* g, unsigned ep) {
         if (p.tile) {
             // the Winograd planner's layer: transformed filter + input + product (conv_wino.hip) — ALSO where the narrow layers then run on
             // the direct split-bf16 kernel, whose filter image is smaller
-            p.ws_bytes = wino_workspace_bytes(g);
+            p.ws_bytes = wq.ws_bytes;
             if (ws) p.add(x3d && !bn ? PNP_ROUTE_X3D : PNP_ROUTE_WINO, p.ws_bytes);
         } else {
             const size_t x3 = x3d ? x3d_filter_bytes(g->C, g->K) : (x3s_chosen(g, 0) ? x3s_filter_bytes(g) : 0);      // the split filter image
@@ -1656,7 +1657,7 @@ static ConvPlan plan_fwd(const pnp_conv_geom* g, unsigned ep) {
         // Winograd: the tile slabs of its output transform; the direct split-bf16 kernels: one partial per 64 output pixels
         const int tile = choose_tile(M, g->K);
         if (r == PNP_ROUTE_IGEMM) p.stats_parts = ns > 1 ? 0 : pnp_cdiv(M, 128) * ((tile == 0 || tile == 1) ? 2 : 4);
-        else if (r == PNP_ROUTE_WINO) p.stats_parts = wino_stats_parts(g);
+        else if (r == PNP_ROUTE_WINO) p.stats_parts = wq.stats_parts;
         else if (r == PNP_ROUTE_X3D || r == PNP_ROUTE_X3S) p.stats_parts = x3d_stats_parts(g);
     }
     return p;
@@ -1707,9 +1708,10 @@ static ConvPlan plan_dgrad(const pnp_conv_geom* g) {
     const bool sym = g->pad_mode == PNP_PAD_SYMMETRIC;
     const pnp_conv_geom d = dgrad_as_conv(g);
     const bool plain = g->stride == 1 && !sym && d.pad_t >= 0 && d.pad_l >= 0;      // a stride-1 zero-padded convolution of dy
-    p.tile = plain ? wino_tile(&d) : 0;
+    const WinoQuery wq = plain ? wino_query(&d) : WinoQuery{};
+    p.tile = wq.tile;
     if (p.tile) {        // the Winograd planner's layer, as in the forward (the filter transform / image flips and transposes on the way)
-        p.ws_bytes = wino_workspace_bytes(&d);
+        p.ws_bytes = wq.ws_bytes;
         p.add(x3d_chosen(&d) ? PNP_ROUTE_X3D : PNP_ROUTE_WINO, p.ws_bytes);
         return p;
     }
@@ -1739,8 +1741,9 @@ static ConvPlan plan_dgrad(const pnp_conv_geom* g) {
 // Every family against its own byte count, the 16x16x4-MFMA kernel against the query's; the ring kernel takes as many splits as fit.
 static ConvPlan plan_wgrad(const pnp_conv_geom* g) {
     ConvPlan p{};
-    p.tile = wino_wgrad_tile(g);
-    if (p.tile) p.add(PNP_ROUTE_WINO_WGRAD, wino_wgrad_workspace_bytes(g));             // conv_wino.hip
+    const WinoQuery wq = wino_wgrad_query(g);
+    p.tile = wq.tile;
+    if (p.tile) p.add(PNP_ROUTE_WINO_WGRAD, wq.ws_bytes);             // conv_wino.hip
     if (x3w_chosen(g)) p.add(PNP_ROUTE_X3W, x3w_workspace_bytes(g));                    // conv_x3_wgrad.hip
     const size_t nout = (size_t)g->R * g->S * g->C * g->K;
     const bool wgd = wgd_ok(g);

@@ -324,6 +324,7 @@ struct GemmPlan {
     int grid;                 // workgroups
     int P, F, R, s;           // per XCD: tiles, whole-round tiles, tail tiles, pieces per tail tile (s == 1: no split)
     size_t px_bytes;          // partial products of the pieces 1 .. s-1
+    bool whole;               // V and U of ALL points fit 31-bit byte offsets (WinoGemmArgs::whole; a persistent launch needs it)
 };
 
 template <int BM, int BN, int WM, int WN, int KIND>
@@ -1076,35 +1077,12 @@ int env_xcd_in() {
     static const int v = env_int("PNP_WINO_XCD_IN", 1);
     return v;
 }
-std::atomic<int> g_wino_wgrad_mode{-1};    // the filter gradient's own switch (PNP_WINOGRAD_WGRAD): 0 never / 1 planner / 2 wherever eligible
-int wino_wgrad_mode() {
-    int m = g_wino_wgrad_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = env_int("PNP_WINOGRAD_WGRAD", PNP_WINOGRAD_WGRAD_DEFAULT);
-        if (m < 0) m = 0;
-        g_wino_wgrad_mode.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
-std::atomic<int> g_wino_mode{-1};          // -1: not read yet (environment PNP_WINOGRAD, else the compiled-in default)
-int wino_mode() {
-    int m = g_wino_mode.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = env_int("PNP_WINOGRAD", PNP_WINOGRAD_DEFAULT);
-        if (m < 0) m = 0;
-        g_wino_mode.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
-std::atomic<int> g_wino_tile{-1};          // largest output tile the route may use (PNP_WINOGRAD_TILE): 2 = F(2x2, 3x3) only, 4 = F(4x4, 3x3) first
-int wino_tile_max() {
-    int m = g_wino_tile.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = env_int("PNP_WINOGRAD_TILE", PNP_WINOGRAD_TILE_DEFAULT) >= 4 ? 4 : 2;
-        g_wino_tile.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+// The route's run-time switches (conv_x3_common.h: ModeSwitch; an environment value is clamped into the range, a negative one reads as off):
+// the route (PNP_WINOGRAD) and the filter gradient's own switch (PNP_WINOGRAD_WGRAD): 0 never / 1 planner / 2 wherever eligible; the largest
+// output tile the route may use (PNP_WINOGRAD_TILE): 2 = F(2x2, 3x3) only, 4 = F(4x4, 3x3) first — whatever is stored below 4 reads as 2
+ModeSwitch wino_switch{"PNP_WINOGRAD", PNP_WINOGRAD_DEFAULT, 2, true}, wino_wgrad_switch{"PNP_WINOGRAD_WGRAD", PNP_WINOGRAD_WGRAD_DEFAULT, 2, true},
+    wino_tile_switch{"PNP_WINOGRAD_TILE", PNP_WINOGRAD_TILE_DEFAULT, 4, true};
+int wino_tile_max() { return wino_tile_switch.get() >= 4 ? 4 : 2; }
 
 // arithmetic of the route's forward / data-gradient GEMMs (PNP_WINOGRAD_X3 / pnp_conv2d_wino_x3): 0 = fp32 matrix pipe (wino_gemm_kernel);
 // 1 = split-bf16 operands on the bf16 matrix pipe with chunked accumulation (conv_wino_x3.hip) where it pays: reductions over >= 256
@@ -1114,19 +1092,10 @@ int wino_tile_max() {
 #ifndef PNP_WINOGRAD_X3_DEFAULT
 #define PNP_WINOGRAD_X3_DEFAULT 1
 #endif
-std::atomic<int> g_wino_x3{-1};
-int wino_x3_mode() {
-    int m = g_wino_x3.load(std::memory_order_relaxed);
-    if (m < 0) {
-        m = env_int("PNP_WINOGRAD_X3", PNP_WINOGRAD_X3_DEFAULT);
-        m = m < 0 ? 0 : (m > 2 ? 2 : m);
-        g_wino_x3.store(m, std::memory_order_relaxed);
-    }
-    return m;
-}
+ModeSwitch wino_x3_switch{"PNP_WINOGRAD_X3", PNP_WINOGRAD_X3_DEFAULT, 2, true};
 inline bool use_x3(int T, int C, int K) {
     static const int cmin = env_int("PNP_WINOGRAD_X3_CMIN", 256);
-    const int m = wino_x3_mode();
+    const int m = wino_x3_switch.get();
     return m != 0 && wino_x3_dims_ok(T, C, K) && (m >= 2 || C >= cmin);
 }
 
@@ -1201,42 +1170,40 @@ int wgrad_split(int T, int C, int K, int npos, int* chunks_per_split) {
     return pnp_cdiv(nchunks, *chunks_per_split);
 }
 
-WinoGeom make_wgeom(int N, int Hi, int Wi, int Ho, int Wo, int dil, int pad, int m) {
+// what the route reads of a layer: the fields that pnp_conv_geom (the queries) and ConvArgs (the launches) both carry
+struct WinoDims {
+    int dtype, R, S, stride, pad_mode, dil, pad_t, pad_l, H, W, OH, OW, N, C, K;
+    template <class G>
+    explicit WinoDims(const G& g) : dtype(g.dtype), R(g.R), S(g.S), stride(g.stride), pad_mode(g.pad_mode), dil(g.dil), pad_t(g.pad_t), pad_l(g.pad_l), H(g.H), W(g.W), OH(g.OH), OW(g.OW), N(g.N), C(g.C), K(g.K) {}
+    explicit WinoDims(const pnp_conv_geom* g) : WinoDims(*g) {}
+};
+
+WinoGeom make_wgeom(const WinoDims& d, int m) {
     WinoGeom g{};
-    g.N = N; g.Hi = Hi; g.Wi = Wi; g.Ho = Ho; g.Wo = Wo; g.dil = dil; g.ps = pad / dil; g.m = m;
-    g.Hsi = Hi / dil; g.Wsi = Wi / dil; g.Hso = Ho / dil; g.Wso = Wo / dil;
+    g.N = d.N; g.Hi = d.H; g.Wi = d.W; g.Ho = d.OH; g.Wo = d.OW; g.dil = d.dil; g.ps = d.pad_t / d.dil; g.m = m;
+    g.Hsi = d.H / d.dil; g.Wsi = d.W / d.dil; g.Hso = d.OH / d.dil; g.Wso = d.OW / d.dil;
     g.th = (g.Hso + m - 1) / m; g.tw = (g.Wso + m - 1) / m;
-    g.T = N * dil * dil * g.th * g.tw;
+    g.T = d.N * d.dil * d.dil * g.th * g.tw;
     return g;
 }
-WinoGeom make_wgeom(const pnp_conv_geom* g, int m) { return make_wgeom(g->N, g->H, g->W, g->OH, g->OW, g->dil, g->pad_t, m); }
 
 inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// tile slabs of the output transform (= BN statistics partial rows): ~1024 workgroups per channel slice
-void out_plan(int T, int K, int* tpb, int* nblk) {
-    const int K4 = K >> 2;
-    const int K4s = K4 < NT ? K4 : NT;
-    const int rpi = NT / K4s;
-    int iters = pnp_cdiv(T, (long long)rpi * 1024);
-    if (iters < 1) iters = 1;
-    *tpb = rpi * iters;
-    *nblk = pnp_cdiv(T, *tpb);
+// can F(m x m, 3x3) run this stride-1 3x3 geometry at all
+bool eligible_dims(const WinoDims& d, int m) {
+    if (d.dtype != PNP_DTYPE_F32 || d.R != 3 || d.S != 3 || d.stride != 1 || d.pad_mode != PNP_PAD_ZERO) return false;
+    // padding 0 (VALID on a mirror-padded image: g10), dil (SAME) or 2 dil (the data gradient of a VALID convolution), same on both axes
+    if (d.dil < 1 || d.dil > 2 || d.pad_t != d.pad_l || (d.pad_t % d.dil) != 0 || d.pad_t > 2 * d.dil) return false;
+    if (d.OH != d.H + 2 * d.pad_t - 2 * d.dil || d.OW != d.W + 2 * d.pad_l - 2 * d.dil) return false;
+    if ((d.H % d.dil) != 0 || (d.W % d.dil) != 0 || (d.OH % d.dil) != 0 || (d.OW % d.dil) != 0) return false;
+    if ((d.C % 32) != 0 || (d.K % 4) != 0 || d.K < 32) return false;       // (K <= 16: vector-ALU kernels)
+    const WinoGeom w = make_wgeom(d, m);
+    const long long lim = 1ll << 29;        // 2 GiB per transform-point plane: 32-bit buffer offsets with the OOB2 sentinel
+    return (long long)w.T * d.C < lim && (long long)w.T * d.K < lim && (long long)d.C * d.K < lim;
 }
 
-// can F(m x m, 3x3) run this stride-1 3x3 geometry at all
-bool eligible_dims(int dtype, int R, int S, int stride, int pad_mode, int dil, int pad_t, int pad_l, int H, int W, int OH, int OW, int N, int C, int K,
-                   int m) {
-    if (dtype != PNP_DTYPE_F32 || R != 3 || S != 3 || stride != 1 || pad_mode != PNP_PAD_ZERO) return false;
-    // padding 0 (VALID on a mirror-padded image: g10), dil (SAME) or 2 dil (the data gradient of a VALID convolution), same on both axes
-    if (dil < 1 || dil > 2 || pad_t != pad_l || (pad_t % dil) != 0 || pad_t > 2 * dil) return false;
-    if (OH != H + 2 * pad_t - 2 * dil || OW != W + 2 * pad_l - 2 * dil) return false;
-    if ((H % dil) != 0 || (W % dil) != 0 || (OH % dil) != 0 || (OW % dil) != 0) return false;
-    if ((C % 32) != 0 || (K % 4) != 0 || K < 32) return false;       // (K <= 16: vector-ALU kernels)
-    const WinoGeom w = make_wgeom(N, H, W, OH, OW, dil, pad_t, m);
-    const long long lim = 1ll << 29;        // 2 GiB per transform-point plane: 32-bit buffer offsets with the OOB2 sentinel
-    return (long long)w.T * C < lim && (long long)w.T * K < lim && (long long)C * K < lim;
-}
+// filter-tile width of the route's GEMMs: 64 filters take a 128 x 64 tile (a 128-wide one would be half empty)
+inline int gemm_bn(int K) { return K <= 64 ? 64 : 128; }
 
 // The planner: which output tile (0 = the direct kernels, 2, 4) a layer gets.  wgrad: the filter gradient's own thresholds.
 // The transforms move ~(2 + 2 P^2/M^2) 4 (C + K) bytes per output pixel through HBM that the direct kernel does not (P = M + 2: V and M are
@@ -1244,10 +1211,10 @@ bool eligible_dims(int dtype, int R, int S, int stride, int pad_mode, int dil, i
 // C K / (C + K).  F(2x2), measured at B = 16 (profiles/r04_conv_layers_wino_B16.txt): 512->512 0.546 -> 0.336 ms, 256->256 0.156 -> 0.121,
 // 128->256 0.083 -> 0.078 (C K / (C + K) = 85: break-even), 128->128 0.047 -> 0.050; filter gradient (two transforms in front of the
 // contraction): break-even 120.  F(4x4) moves 0.66x the bytes and saves 1.35x the flops: break-even ~ 0.5x F(2x2)'s (profiles/r05_*).
-int plan_tile(int dtype, int R, int S, int stride, int pad_mode, int dil, int pad_t, int pad_l, int H, int W, int OH, int OW, int N, int C, int K,
-              bool wgrad) {
-    const int mode = wgrad ? wino_wgrad_mode() : wino_mode();
-    if (mode <= 0 || wino_mode() <= 0) return 0;              // PNP_WINOGRAD=0 switches the whole route off
+int plan_tile(const WinoDims& d, bool wgrad) {
+    const int C = d.C, K = d.K;
+    const int mode = wgrad ? wino_wgrad_switch.get() : wino_switch.get();
+    if (mode <= 0 || wino_switch.get() <= 0) return 0;              // PNP_WINOGRAD=0 switches the whole route off
     static const double thr2 = env_dbl("PNP_WINOGRAD_MIN", 85.0), thr2w = env_dbl("PNP_WINOGRAD_WGRAD_MIN", 120.0);
     static const double thr4 = env_dbl("PNP_WINOGRAD4_MIN", 60.0), thr4w = env_dbl("PNP_WINOGRAD4_WGRAD_MIN", 60.0);
     static const int tmin2 = env_int("PNP_WINOGRAD_TMIN", 512), tmin4 = env_int("PNP_WINOGRAD4_TMIN", 128);
@@ -1255,17 +1222,17 @@ int plan_tile(int dtype, int R, int S, int stride, int pad_mode, int dil, int pa
     static const double thr4lo = env_dbl("PNP_WINOGRAD4_LOW", 32.0);
     const double ck = (double)C * K / ((double)C + K);
     for (int m = wino_tile_max(); m >= 2; m -= 2) {
-        if (!eligible_dims(dtype, R, S, stride, pad_mode, dil, pad_t, pad_l, H, W, OH, OW, N, C, K, m)) continue;
+        if (!eligible_dims(d, m)) continue;
         // F(4x4)'s rounding error grows with the reduction length (the GEMMs accumulate in the transform domain, where the output transform's
         // 8 x 8 coefficients meet cancelling sums): 512-channel reductions 3e-6..8e-6 of max|ref|, group_10's data gradient (2 560 channels)
         // 1.7e-5 (teacher-forced, profiles/r05_pytest_gpu.log) — too close to the 2e-5 adoption bar: reductions over > 1 024 channels stay
         // on F(2x2) (1e-6), at 1.80 instead of 1.39 ms for that one launch per generator step
-        // (the split-bf16 GEMM accumulates in 96-channel chunks: 1.7e-6 at 2 560 channels — no cap)
-        const WinoGeom w = make_wgeom(N, H, W, OH, OW, dil, pad_t, m);
+        // (the split-bf16 GEMM accumulates in 64-channel chunks: 1.7e-6 at 2 560 channels — no cap)
+        const WinoGeom w = make_wgeom(d, m);
         if (m == 4 && !wgrad && C > c4max && !use_x3(w.T, C, K)) continue;
         if (mode >= 2) return m;
         if (w.T < (m == 4 ? tmin4 : tmin2)) continue;
-        const long long nwg = (long long)(m + 2) * (m + 2) * pnp_cdiv(w.T, 128) * pnp_cdiv(K, K <= 64 ? 64 : 128);
+        const long long nwg = (long long)(m + 2) * (m + 2) * pnp_cdiv(w.T, 128) * pnp_cdiv(K, gemm_bn(K));
         const double thr = m == 4 ? (wgrad ? thr4w : thr4) : (wgrad ? thr2w : thr2);
         if (ck < thr) {
             // F(4x4) below its break-even, measured at B = 16 with the 128 x 64 GEMM tile (profiles/r05_wino_thresholds.txt, part 3):
@@ -1285,23 +1252,10 @@ int plan_tile(int dtype, int R, int S, int stride, int pad_mode, int dil, int pa
     }
     return 0;
 }
-int plan_tile(const pnp_conv_geom* g, bool wgrad) {
-    if (!g) return 0;
-    return plan_tile(g->dtype, g->R, g->S, g->stride, g->pad_mode, g->dil, g->pad_t, g->pad_l, g->H, g->W, g->OH, g->OW, g->N, g->C, g->K, wgrad);
-}
-int plan_tile(const ConvArgs& a, bool wgrad) {
-    return plan_tile(a.dtype, a.R, a.S, a.stride, a.pad_mode, a.dil, a.pad_t, a.pad_l, a.H, a.W, a.OH, a.OW, a.N, a.C, a.K, wgrad);
-}
 
 }  // namespace
 
 namespace pnpconv {
-
-bool wino_eligible(const pnp_conv_geom* g) {
-    return g && eligible_dims(g->dtype, g->R, g->S, g->stride, g->pad_mode, g->dil, g->pad_t, g->pad_l, g->H, g->W, g->OH, g->OW, g->N, g->C, g->K, 2);
-}
-
-int wino_tile(const pnp_conv_geom* g) { return plan_tile(g, false); }
 
 // One plan per GEMM launch of forward / data gradient, shared by the workspace query, the launch and the output transform.
 // Persistent (grid = 512 = 2 workgroups per CU, 64 per XCD) when there are more tiles than slots and every transform point fits 31-bit
@@ -1309,21 +1263,21 @@ int wino_tile(const pnp_conv_geom* g) { return plan_tile(g, false); }
 // run one tile more than the rest (512->512 at B = 16: P = 144 = 2 rounds + 16, i.e. a makespan of 3 tiles for 2.25 tiles of work per
 // workgroup); cutting each tail tile into s pieces of the reduction (s R <= 64, >= 2 stages per piece) hands every workgroup 1 / s of a tile
 // instead.  Pieces 1 .. s-1 leave their partial products in Px, summed by the output transform in a fixed order.
-static GemmPlan gemm_plan(int T, int C, int K, int NP, bool xcd) {
+// x3: the split-bf16 GEMM (conv_wino_x3.hip) sizes its own persistent grid and has no tail split: s = 1, no Px.
+static GemmPlan gemm_plan(int T, int C, int K, int NP, int bn, bool x3, bool xcd) {
     // (the tail split is OFF by default: measured within one run, round 5: tools/experiments/README.md — the GEMMs gain 4-16 % (512->512 163 ->
     // 156 us, 256->256 59.7 -> 49.9, 256->512 data gradient 106.5 -> 88.4) but the output transform pays for finding and summing the pieces
     // (512->512 20.0 -> 26.0 us, g10 95 -> 113): joint step 248.6 -> 249.5 slices/s, inside the noise.  Kept, parity-tested, as the measured
     // answer to "balance the 2.25 tiles per workgroup": a lone workgroup on a CU already runs its extra tile at nearly twice the speed)
     static const int persist = env_int("PNP_WINO_PERSIST", 1), split_on = env_int("PNP_WINO_TAILSPLIT", 0);
     GemmPlan p{};
-    const int bn = K <= 64 ? 64 : 128;
     const long long ntiles = (long long)NP * pnp_cdiv(T, 128) * pnp_cdiv(K, bn);
-    const bool whole = (double)NP * T * C * 4.0 < 2147483648.0 && (double)NP * C * K * 4.0 < 2147483648.0;
+    p.whole = (double)NP * T * C * 4.0 < 2147483648.0 && (double)NP * C * K * 4.0 < 2147483648.0;
     p.grid = (int)ntiles;
     p.P = (int)ntiles; p.F = (int)ntiles; p.R = 0; p.s = 1; p.px_bytes = 0;
-    if (!(persist && whole && ntiles > 512)) return p;
+    if (!(persist && p.whole && ntiles > 512)) return p;
     p.grid = 512;
-    if (!(xcd && split_on) || (ntiles % 8) != 0) return p;
+    if (!(xcd && split_on) || x3 || (ntiles % 8) != 0) return p;
     const int P = (int)(ntiles / 8), F = (P / 64) * 64, R = P - F, ncc = C / BK;
     p.P = P; p.F = F; p.R = R;
     if (R == 0) return p;
@@ -1336,46 +1290,71 @@ static GemmPlan gemm_plan(int T, int C, int K, int NP, bool xcd) {
     return p;
 }
 
-static size_t fwd_ws_bytes(const WinoGeom& w, int C, int K) {
-    const size_t np = (size_t)(w.m + 2) * (w.m + 2);
-    if (use_x3(w.T, C, K)) return al256(np * C * K * 6) + al256(np * w.T * C * 6) + al256(np * w.T * K * 4);
-    return al256(np * C * K * 4) + al256(np * w.T * C * 4) + al256(np * w.T * K * 4) + gemm_plan(w.T, C, K, (int)np, true).px_bytes;
+// The plan of one forward / data gradient on the route: the only code that picks the tile and the GEMM's arithmetic, plans the GEMM launch and
+// the output transform's slabs, and sizes and lays out the workspace [U | V | M | Px].  The query and the launch both read it.
+struct WinoPlan {
+    int m;                    // output tile edge; 0: the planner does not route the layer
+    WinoGeom g;
+    bool x3;                  // GEMM on split-bf16 operands (conv_wino_x3.hip), else wino_gemm_kernel
+    size_t eb;                // bytes per transformed operand value (U, V): 6 (three bf16 planes) / 4
+    int bn;                   // filter-tile width of the GEMM
+    bool xcd;                 // the GEMM deals its tiles to the XCDs in contiguous ranges (the tail split needs it)
+    GemmPlan gemm;
+    int gn;                   // PNP_WINO_GN: filter-tile group width of the route's GEMM (< 0: the convolutions' PNP_CONV_GN, ConvArgs::gn)
+    size_t off_v, off_m, off_px, total;        // (U at 0)
+    int tiles_per_block, slabs;                // output transform: tiles per workgroup; tile slabs = BN statistics partial rows
+};
+static WinoPlan plan_wino(const WinoDims& d, bool xcd) {
+    static const int gn = env_int("PNP_WINO_GN", -1);
+    WinoPlan p{};
+    p.m = plan_tile(d, false);
+    if (!p.m) return p;
+    p.g = make_wgeom(d, p.m);
+    const int T = p.g.T, np = (p.m + 2) * (p.m + 2);
+    p.x3 = use_x3(T, d.C, d.K);
+    p.eb = p.x3 ? 6 : 4;
+    p.bn = gemm_bn(d.K);
+    p.xcd = xcd;
+    p.gemm = gemm_plan(T, d.C, d.K, np, p.bn, p.x3, xcd);
+    p.gn = gn;
+    p.off_v = al256((size_t)np * d.C * d.K * p.eb);
+    p.off_m = p.off_v + al256((size_t)np * T * d.C * p.eb);
+    p.off_px = p.off_m + al256((size_t)np * T * d.K * 4);
+    p.total = p.off_px + p.gemm.px_bytes;
+    // ~1024 workgroups of the output transform per channel slice
+    const int K4 = d.K >> 2, rpi = NT / (K4 < NT ? K4 : NT);
+    int iters = pnp_cdiv(T, (long long)rpi * 1024);
+    if (iters < 1) iters = 1;
+    p.tiles_per_block = rpi * iters;
+    p.slabs = pnp_cdiv(T, p.tiles_per_block);
+    return p;
 }
 
-size_t wino_workspace_bytes(const pnp_conv_geom* g) {
-    const int m = plan_tile(g, false);
-    return fwd_ws_bytes(make_wgeom(g, m ? m : 2), g->C, g->K);
-}
-
-int wino_stats_parts(const pnp_conv_geom* g) {
-    const int m = plan_tile(g, false);
-    const WinoGeom w = make_wgeom(g, m ? m : 2);
-    int tpb, nblk;
-    out_plan(w.T, g->K, &tpb, &nblk);
-    return nblk;
+// tile 0: the route does not take the layer (no bytes, no parts).  Px is sized as if the launch dealt whole ranges to the XCDs, whatever
+// ConvArgs::xcd_swizzle will say: an upper bound of what any launch of this geometry asks for.
+WinoQuery wino_query(const pnp_conv_geom* g) {
+    const WinoPlan p = plan_wino(WinoDims(g), true);
+    return {p.m, p.total, p.slabs};
 }
 
 template <int M>
-static int launch_wino_m(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st) {
+static int launch_wino_m(const ConvArgs& a, const WinoPlan& p, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st) {
     constexpr int NP = (M + 2) * (M + 2);
-    const WinoGeom w = make_wgeom(a.N, a.H, a.W, a.OH, a.OW, a.dil, a.pad_t, M);
-    const bool x3 = use_x3(w.T, a.C, a.K);
-    const size_t eb = x3 ? 6 : 4;          // bytes per transformed operand value
-    const size_t ub = al256((size_t)NP * a.C * a.K * eb), vb = al256((size_t)NP * w.T * a.C * eb), mb = al256((size_t)NP * w.T * a.K * 4);
-    static const int xcd_mode = env_int("PNP_WINO_XCD", 2);
-    const bool xcd = a.xcd_swizzle && xcd_mode;
-    GemmPlan plan = gemm_plan(w.T, a.C, a.K, NP, xcd);
-    if (x3) { plan.s = 1; plan.px_bytes = 0; }
-    if (!ws || ws_bytes < ub + vb + mb + plan.px_bytes) {
-        pnp_set_error("launch_wino: workspace too small (%zu < %zu)", ws_bytes, ub + vb + mb + plan.px_bytes);
+    const WinoGeom& w = p.g;
+    const bool x3 = p.x3, xcd = p.xcd;
+    const size_t eb = p.eb;
+    const GemmPlan& plan = p.gemm;
+    if (!ws || ws_bytes < p.total) {
+        pnp_set_error("launch_wino: workspace too small (%zu < %zu)", ws_bytes, p.total);
         return PNP_EWORKSPACE;
     }
     PNP_REQUIRE(a.y_h == nullptr && a.o_s == 0 && a.ups == 1, "launch_wino: unsupported epilogue");
     bool run_filter;
     float* U = filter_slot(a.w, flip_transpose ? 1 : 0, M, a.C, a.K, x3 ? 1 : 0, (size_t)NP * a.C * a.K * eb, (float*)ws, st, &run_filter);
-    float* V = (float*)((char*)ws + ub);
-    float* Mm = (float*)((char*)ws + ub + vb);
-    float* Px = (float*)((char*)ws + ub + vb + mb);
+    float* V = (float*)((char*)ws + p.off_v);
+    float* Mm = (float*)((char*)ws + p.off_m);
+    float* Px = (float*)((char*)ws + p.off_px);
+    const int gn = p.gn >= 0 ? p.gn : a.gn;
     const int cls = prof_class(kind);
     if (run_filter) {
         dim3 grid((unsigned)pnp_cdiv(a.K, 32), (unsigned)pnp_cdiv(a.C, 32));
@@ -1399,19 +1378,17 @@ static int launch_wino_m(const ConvArgs& a, int kind, bool flip_transpose, void*
         PNP_CHECK_LAUNCH("wino_in_kernel");
     }
     if (x3) {
-        static const int wino_gn3 = env_int("PNP_WINO_GN", -1);
-        const int rc = launch_wino_gemm_x3((const unsigned short*)V, (const unsigned short*)U, Mm, w.T, a.C, a.K, NP, (M == 4 ? 2 : 0) + (kind != 0), wino_gn3 >= 0 ? wino_gn3 : a.gn,
-                                           xcd ? 1 : 0, 1, a.C / 32, st);
+        const int rc = launch_wino_gemm_x3((const unsigned short*)V, (const unsigned short*)U, Mm, w.T, a.C, a.K, NP, (M == 4 ? 2 : 0) + (kind != 0), gn, xcd ? 1 : 0, 1,
+                                           a.C / 32, st);
         if (rc != PNP_OK) return rc;
     } else {
         WinoGemmArgs ga{};
         ga.V = V; ga.U = U; ga.Mm = Mm; ga.T = w.T; ga.C = a.C; ga.K = a.K;
-        const bool narrow = a.K <= 64;                 // 64 filters: a 128 x 64 tile (a 128-wide one would be half empty)
-        ga.nblk_m = pnp_cdiv(w.T, 128); ga.nblk_n = pnp_cdiv(a.K, narrow ? 64 : 128);
-        static const int wino_gn = env_int("PNP_WINO_GN", -1);          // filter-tile group width of the route's GEMM (< 0: the convolutions' PNP_CONV_GN)
-        ga.gn = wino_gn >= 0 ? wino_gn : a.gn; ga.xcd_swizzle = xcd ? 2 : 0;
+        const bool narrow = p.bn == 64;
+        ga.nblk_m = pnp_cdiv(w.T, 128); ga.nblk_n = pnp_cdiv(a.K, p.bn);
+        ga.gn = gn; ga.xcd_swizzle = xcd ? 2 : 0;
         ga.npos = NP;
-        ga.whole = ((double)NP * w.T * a.C * 4.0 < 2147483648.0 && (double)NP * a.C * a.K * 4.0 < 2147483648.0) ? 1 : 0;
+        ga.whole = plan.whole ? 1 : 0;
         ga.tail_F = plan.F; ga.tail_R = plan.R; ga.tail_s = plan.s; ga.Px = Px;
         dim3 grid((unsigned)plan.grid);
         const double fl = 2.0 * NP * (double)w.T * a.C * a.K;
@@ -1427,17 +1404,14 @@ static int launch_wino_m(const ConvArgs& a, int kind, bool flip_transpose, void*
     }
     {
         WinoOutArgs oa{};
-        oa.Mm = Mm; oa.y = a.y; oa.g = w; oa.K = a.K;
-        int nblk;
-        out_plan(w.T, a.K, &oa.tiles_per_block, &nblk);
+        oa.Mm = Mm; oa.y = a.y; oa.g = w; oa.K = a.K; oa.tiles_per_block = p.tiles_per_block;
         oa.do_drop = a.do_drop; oa.drop_thresh = a.drop_thresh; oa.drop_key = a.drop_key; oa.drop_keep = a.drop_keep;
         oa.sp = a.sp; oa.drop_sid = a.drop_sid;
         oa.res_add = a.res_add; oa.stat_ws = a.stat_ws; oa.stat_shift = a.stat_shift;
         oa.ep_scale = a.ep_scale; oa.ep_shift = a.ep_shift; oa.ep_res = a.ep_res; oa.ep_cs = a.ep_cs; oa.ep_alpha = a.ep_alpha;
-        oa.Px = Px; oa.tail_P = plan.P; oa.tail_F = plan.F; oa.tail_R = plan.R; oa.tail_s = plan.s; oa.tail_bn = a.K <= 64 ? 64 : 128;
-        static const int wino_gn_o = env_int("PNP_WINO_GN", -1);
-        oa.nblk_m = pnp_cdiv(w.T, 128); oa.nblk_n = pnp_cdiv(a.K, oa.tail_bn); oa.gn = wino_gn_o >= 0 ? wino_gn_o : a.gn;
-        dim3 grid((unsigned)nblk, (unsigned)pnp_cdiv(a.K / 4, NT));
+        oa.Px = Px; oa.tail_P = plan.P; oa.tail_F = plan.F; oa.tail_R = plan.R; oa.tail_s = plan.s; oa.tail_bn = p.bn;
+        oa.nblk_m = pnp_cdiv(w.T, 128); oa.nblk_n = pnp_cdiv(a.K, p.bn); oa.gn = gn;
+        dim3 grid((unsigned)p.slabs, (unsigned)pnp_cdiv(a.K / 4, NT));
         PnpProfScope ps(cls, st, 0.0, 4.0 * ((double)NP * w.T * a.K + (double)a.M * a.K), "wino_out_kernel<%d>", M);
         if (oa.tail_s > 1) hipLaunchKernelGGL((wino_out_kernel<M, true>), grid, dim3(NT), 0, st, oa);
         else hipLaunchKernelGGL((wino_out_kernel<M, false>), grid, dim3(NT), 0, st, oa);
@@ -1447,25 +1421,25 @@ static int launch_wino_m(const ConvArgs& a, int kind, bool flip_transpose, void*
 }
 
 // a: the convolution's arguments as make_args built them (kind 1: of the data gradient AS a convolution of dy: a.C = the forward's K,
-// a.K = its C) with every epilogue field honoured; flip_transpose: a.w is the FORWARD filter [3][3][a.K][a.C].  The tile is planned here
-// from the same fields the workspace / parts queries see (one decision per call).  Winograd and nothing else: the narrow layers that run as
+// a.K = its C) with every epilogue field honoured; flip_transpose: a.w is the FORWARD filter [3][3][a.K][a.C].  The launch is planned here
+// from the same fields, by the same plan_wino, as the query's answer (one decision per call).  Winograd and nothing else: the narrow layers that run as
 // direct split-bf16 convolutions instead are another route of the plan (conv_igemm.hip: plan_fwd / plan_dgrad)
 int launch_wino(const ConvArgs& a, int kind, bool flip_transpose, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int m = plan_tile(a, false);
-    PNP_REQUIRE(m == 2 || m == 4, "launch_wino: the planner does not route this layer (policy changed between the query and the launch?)");
-    return m == 4 ? launch_wino_m<4>(a, kind, flip_transpose, ws, ws_bytes, st) : launch_wino_m<2>(a, kind, flip_transpose, ws, ws_bytes, st);
+    static const int xcd_mode = env_int("PNP_WINO_XCD", 2);
+    const WinoPlan p = plan_wino(WinoDims(a), a.xcd_swizzle && xcd_mode);
+    PNP_REQUIRE(p.m == 2 || p.m == 4, "launch_wino: the planner does not route this layer (policy changed between the query and the launch?)");
+    return p.m == 4 ? launch_wino_m<4>(a, p, kind, flip_transpose, ws, ws_bytes, st) : launch_wino_m<2>(a, p, kind, flip_transpose, ws, ws_bytes, st);
 }
 
-int wino_wgrad_tile(const pnp_conv_geom* g) { return plan_tile(g, true); }
-
 // the filter gradient's GEMMs on the split-bf16 kernel (PNP_WINOGRAD_X3 on, PNP_WINOGRAD_X3_WGRAD != 0).  Mode 1: where measured to pay at
-// B = 16 (profiles/r06_x3_wgrad_layers_B16.txt) — reductions over 256 .. 2 048 tiles, i.e. the 32^2 maps: 512->512 0.239 -> 0.200 ms, g10
-// 0.94 -> 0.71, 256->256 0.089 -> 0.074; on the large maps the two TRANSPOSING transforms (6 bytes per value, through LDS) cost more than
-// the GEMM gains: cls3 256->256 @64^2 (4 096 tiles) 0.255 -> 0.267, cls2 128->128 @128^2 (16 384 tiles) 0.36 -> 0.48.  Mode 2: everywhere.
+// B = 16 — reductions over 256 .. 2 048 tiles, i.e. the 32^2 maps: 512->512 0.239 -> 0.200 ms, g10 0.94 -> 0.71, 256->256 0.089 -> 0.074; on
+// the large maps the two TRANSPOSING transforms (6 bytes per value, through LDS) cost more than the GEMM gains: cls3 256->256 @64^2 (4 096
+// tiles) 0.255 -> 0.267, cls2 128->128 @128^2 (16 384 tiles) 0.36 -> 0.48.  Mode 2: everywhere.  (The table these figures were read from
+// was not kept; profiles/r06_x3_layers_B16.txt is the kept run of the same three passes, X3 = 0 / 1 / 2: 512->512 0.242 -> 0.189 ms.)
 inline int x3_tp(int T) { return (T + 63) & ~63; }
 inline bool use_x3_wgrad(int T, int C, int K) {
     static const int on = env_int("PNP_WINOGRAD_X3_WGRAD", 1), tmin = env_int("PNP_WINOGRAD_X3_WGRAD_TMIN", 256), tmax = env_int("PNP_WINOGRAD_X3_WGRAD_TMAX", 2048);
-    const int m = wino_x3_mode();
+    const int m = wino_x3_switch.get();
     if (!on || m == 0 || !wino_x3_dims_ok(C, x3_tp(T), K) || !wino_x3_dims_ok(K, x3_tp(T), C)) return false;
     return m >= 2 || (T >= tmin && T <= tmax);
 }
@@ -1473,7 +1447,7 @@ inline bool use_x3_wgrad(int T, int C, int K) {
 // fill + epilogue); every split writes npos C K floats that the 6x6 -> 3x3 kernel reads back.  Returns the splits; *sps = stages per split (even)
 int wgrad_split_x3(int T, int C, int K, int npos, int* sps) {
     const int nchunks = x3_tp(T) / 64;
-    const long long tiles = (long long)pnp_cdiv(C, 128) * pnp_cdiv(K, K <= 64 ? 64 : 128) * npos;
+    const long long tiles = (long long)pnp_cdiv(C, 128) * pnp_cdiv(K, gemm_bn(K)) * npos;
     int best = 1;
     double best_cost = 1e30;
     for (int ns = 1; ns <= 32 && ns <= nchunks; ++ns) {
@@ -1489,40 +1463,53 @@ int wgrad_split_x3(int T, int C, int K, int npos, int* sps) {
     return pnp_cdiv(nchunks, cps);
 }
 
-static size_t wgrad_ws_bytes(const WinoGeom& w, int C, int K) {
-    const int np = (w.m + 2) * (w.m + 2);
-    if (use_x3_wgrad(w.T, C, K)) {
-        int sps;
-        const int ns = wgrad_split_x3(w.T, C, K, np, &sps);
-        const size_t tp = (size_t)x3_tp(w.T);
-        return al256((size_t)np * tp * C * 6) + al256((size_t)np * tp * K * 6) + al256((size_t)ns * np * C * K * 4);
-    }
-    int cps;
-    const int ns = wgrad_split(w.T, C, K, np, &cps);
-    return al256((size_t)np * w.T * C * 4) + al256((size_t)np * w.T * K * 4) + al256((size_t)ns * np * C * K * 4);
+// The plan of one filter gradient on the route: the only code that picks its arithmetic, splits its reduction and sizes and lays out its
+// workspace [V | Y | S].  The query and the launch both read it.
+struct WinoWgradPlan {
+    int m;                    // output tile edge; 0: the planner does not route the layer
+    WinoGeom g;
+    bool x3;                  // GEMMs on split-bf16 operands (wino_in_t / wino_dy_t kernels -> conv_wino_x3.hip), else wino_wgrad_gemm_kernel
+    int ns, per_split;        // reduction splits and the length of one: 32-tile chunks (fp32) / 32-tile stages (x3: even)
+    int tp;                   // tile rows of V and Y: T, for x3 padded to a multiple of 64 (zero-filled)
+    size_t off_y, off_s, total;
+    bool splitsum;            // few (channel, filter) vectors, many splits: wino_splitsum_kernel sums the splits at full width first
+};
+static WinoWgradPlan plan_wino_wgrad(const WinoDims& d) {
+    WinoWgradPlan p{};
+    p.m = plan_tile(d, true);
+    if (!p.m) return p;
+    p.g = make_wgeom(d, p.m);
+    const int np = (p.m + 2) * (p.m + 2), T = p.g.T;
+    p.x3 = use_x3_wgrad(T, d.C, d.K);
+    p.ns = p.x3 ? wgrad_split_x3(T, d.C, d.K, np, &p.per_split) : wgrad_split(T, d.C, d.K, np, &p.per_split);
+    p.tp = p.x3 ? x3_tp(T) : T;
+    const size_t eb = p.x3 ? 6 : 4;          // bytes per transformed operand value
+    p.off_y = al256((size_t)np * p.tp * d.C * eb);
+    p.off_s = p.off_y + al256((size_t)np * p.tp * d.K * eb);
+    p.total = p.off_s + al256((size_t)p.ns * np * d.C * d.K * 4);
+    p.splitsum = p.ns > 2 && (size_t)d.C * (d.K / 4) < (size_t)NT * 512;
+    return p;
 }
 
-size_t wino_wgrad_workspace_bytes(const pnp_conv_geom* g) {
-    const int m = plan_tile(g, true);
-    return wgrad_ws_bytes(make_wgeom(g, m ? m : 2), g->C, g->K);
+WinoQuery wino_wgrad_query(const pnp_conv_geom* g) {
+    const WinoWgradPlan p = plan_wino_wgrad(WinoDims(g));
+    return {p.m, p.total, 0};
 }
 
 template <int M>
-static int launch_wino_wgrad_m(const ConvArgs& a, float* dw, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
+static int launch_wino_wgrad_m(const ConvArgs& a, const WinoWgradPlan& p, float* dw, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
     constexpr int NP = (M + 2) * (M + 2);
-    const WinoGeom w = make_wgeom(a.N, a.H, a.W, a.OH, a.OW, a.dil, a.pad_t, M);
-    if (use_x3_wgrad(w.T, a.C, a.K)) {
-        int sps;
-        const int ns = wgrad_split_x3(w.T, a.C, a.K, NP, &sps);
-        const int tp = x3_tp(w.T), ntb = tp / 32;
-        const size_t vb = al256((size_t)NP * tp * a.C * 6), yb = al256((size_t)NP * tp * a.K * 6), sb = al256((size_t)ns * NP * a.C * a.K * 4);
-        if (!ws || ws_bytes < vb + yb + sb) {
-            pnp_set_error("launch_wino_wgrad: workspace too small (%zu < %zu)", ws_bytes, vb + yb + sb);
-            return PNP_EWORKSPACE;
-        }
+    const WinoGeom& w = p.g;
+    const int ns = p.ns;
+    if (!ws || ws_bytes < p.total) {
+        pnp_set_error("launch_wino_wgrad: workspace too small (%zu < %zu)", ws_bytes, p.total);
+        return PNP_EWORKSPACE;
+    }
+    float* S = (float*)((char*)ws + p.off_s);
+    if (p.x3) {
+        const int tp = p.tp, ntb = tp / 32;
         __bf16* V3 = (__bf16*)ws;
-        __bf16* Y3 = (__bf16*)((char*)ws + vb);
-        float* S = (float*)((char*)ws + vb + yb);
+        __bf16* Y3 = (__bf16*)((char*)ws + p.off_y);
         {
             WinoTArgs ta{};
             ta.src = a.x; ta.out = V3; ta.g = w; ta.rows = a.C; ta.src_bytes = a.x_bytes; ta.ntb = ntb;
@@ -1537,115 +1524,82 @@ static int launch_wino_wgrad_m(const ConvArgs& a, float* dw, int accumulate, voi
             hipLaunchKernelGGL(wino_dy_t_kernel<M>, dim3((unsigned)ntb, (unsigned)pnp_cdiv(a.K, 32)), dim3(NT), 0, st, ta);
             PNP_CHECK_LAUNCH("wino_dy_t_kernel");
         }
-        const int rc = launch_wino_gemm_x3((const unsigned short*)V3, (const unsigned short*)Y3, S, a.C, tp, a.K, NP, M == 4 ? 5 : 4, 0, a.xcd_swizzle ? 1 : 0, ns, sps, st);
+        const int rc = launch_wino_gemm_x3((const unsigned short*)V3, (const unsigned short*)Y3, S, a.C, tp, a.K, NP, M == 4 ? 5 : 4, 0, a.xcd_swizzle ? 1 : 0, ns, p.per_split, st);
         if (rc != PNP_OK) return rc;
-        int ns_out = ns;
-        if (ns > 2 && (size_t)a.C * (a.K / 4) < (size_t)NT * 512) {
-            const size_t nv = (size_t)NP * a.C * (a.K / 4);
-            PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)ns + 1.0) * NP * a.C * a.K, "wino_splitsum_kernel");
-            hipLaunchKernelGGL(wino_splitsum_kernel, dim3((unsigned)((nv + NT - 1) / NT)), dim3(NT), 0, st, S, nv, ns);
-            PNP_CHECK_LAUNCH("wino_splitsum_kernel");
-            ns_out = 1;
+    } else {
+        float* V = (float*)ws;
+        float* Y = (float*)((char*)ws + p.off_y);
+        {
+            WinoInArgs ia{};
+            ia.x = a.x; ia.V = V; ia.g = w; ia.C = a.C; ia.x_bytes = a.x_bytes; ia.xcd = a.xcd_swizzle ? env_xcd_in() : 0;
+            long long nb = (long long)(((size_t)w.T * (a.C / 4) + NT - 1) / NT);
+            if (nb > 65536) nb = 65536;
+            PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)a.N * a.H * a.W * a.C + (double)NP * w.T * a.C), "wino_in_kernel<%d, false>", M);
+            hipLaunchKernelGGL((wino_in_kernel<M, false>), dim3((unsigned)nb), dim3(NT), 0, st, ia);
+            PNP_CHECK_LAUNCH("wino_in_kernel");
         }
-        const size_t nvec = (size_t)a.C * (a.K / 4);
-        PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)ns_out * NP + 9.0 * (1 + (accumulate != 0))) * a.C * a.K, "wino_wgrad_out_kernel<%d>", M);
-        hipLaunchKernelGGL(wino_wgrad_out_kernel<M>, dim3((unsigned)((nvec + NT - 1) / NT)), dim3(NT), 0, st, (const float*)S, dw, a.C, a.K, ns_out, accumulate);
-        PNP_CHECK_LAUNCH("wino_wgrad_out_kernel");
-        return PNP_OK;
+        {
+            WinoDyArgs da{};
+            da.dy = a.w; da.Y = Y; da.g = w; da.K = a.K;
+            long long nb = (long long)(((size_t)w.T * (a.K / 4) + NT - 1) / NT);
+            if (nb > 65536) nb = 65536;
+            PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)a.M * a.K + (double)NP * w.T * a.K), "wino_dy_kernel<%d>", M);
+            hipLaunchKernelGGL(wino_dy_kernel<M>, dim3((unsigned)nb), dim3(NT), 0, st, da);
+            PNP_CHECK_LAUNCH("wino_dy_kernel");
+        }
+        {
+            WinoWgradGemmArgs ga{};
+            ga.V = V; ga.Y = Y; ga.S = S; ga.T = w.T; ga.C = a.C; ga.K = a.K;
+            ga.nblk_m = pnp_cdiv(a.C, 128); ga.nblk_n = pnp_cdiv(a.K, 128);
+            ga.nsplit = ns; ga.chunks_per_split = p.per_split; ga.xcd_swizzle = a.xcd_swizzle; ga.npos = NP;
+            dim3 grid((unsigned)(ga.nblk_m * ga.nblk_n * NP * ns));
+            const double fl = 2.0 * NP * (double)w.T * a.C * a.K;
+            const double by = 4.0 * NP * ((double)w.T * a.C + (double)w.T * a.K + (double)ns * a.C * a.K);
+            PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, fl, by, "wino_wgrad_gemm_kernel<128, 128, 2, 2, %d>", M);
+            hipLaunchKernelGGL((wino_wgrad_gemm_kernel<128, 128, 2, 2, M>), grid, dim3(NTHREADS), 0, st, ga);
+            PNP_CHECK_LAUNCH("wino_wgrad_gemm_kernel");
+        }
     }
-    int cps;
-    const int ns = wgrad_split(w.T, a.C, a.K, NP, &cps);
-    const size_t vb = al256((size_t)NP * w.T * a.C * 4), yb = al256((size_t)NP * w.T * a.K * 4), sb = al256((size_t)ns * NP * a.C * a.K * 4);
-    if (!ws || ws_bytes < vb + yb + sb) {
-        pnp_set_error("launch_wino_wgrad: workspace too small (%zu < %zu)", ws_bytes, vb + yb + sb);
-        return PNP_EWORKSPACE;
-    }
-    float* V = (float*)ws;
-    float* Y = (float*)((char*)ws + vb);
-    float* S = (float*)((char*)ws + vb + yb);
-    {
-        WinoInArgs ia{};
-        ia.x = a.x; ia.V = V; ia.g = w; ia.C = a.C; ia.x_bytes = a.x_bytes; ia.xcd = a.xcd_swizzle ? env_xcd_in() : 0;
-        long long nb = (long long)(((size_t)w.T * (a.C / 4) + NT - 1) / NT);
-        if (nb > 65536) nb = 65536;
-        PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)a.N * a.H * a.W * a.C + (double)NP * w.T * a.C), "wino_in_kernel<%d, false>", M);
-        hipLaunchKernelGGL((wino_in_kernel<M, false>), dim3((unsigned)nb), dim3(NT), 0, st, ia);
-        PNP_CHECK_LAUNCH("wino_in_kernel");
-    }
-    {
-        WinoDyArgs da{};
-        da.dy = a.w; da.Y = Y; da.g = w; da.K = a.K;
-        long long nb = (long long)(((size_t)w.T * (a.K / 4) + NT - 1) / NT);
-        if (nb > 65536) nb = 65536;
-        PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)a.M * a.K + (double)NP * w.T * a.K), "wino_dy_kernel<%d>", M);
-        hipLaunchKernelGGL(wino_dy_kernel<M>, dim3((unsigned)nb), dim3(NT), 0, st, da);
-        PNP_CHECK_LAUNCH("wino_dy_kernel");
-    }
-    {
-        WinoWgradGemmArgs ga{};
-        ga.V = V; ga.Y = Y; ga.S = S; ga.T = w.T; ga.C = a.C; ga.K = a.K;
-        ga.nblk_m = pnp_cdiv(a.C, 128); ga.nblk_n = pnp_cdiv(a.K, 128);
-        ga.nsplit = ns; ga.chunks_per_split = cps; ga.xcd_swizzle = a.xcd_swizzle; ga.npos = NP;
-        dim3 grid((unsigned)(ga.nblk_m * ga.nblk_n * NP * ns));
-        const double fl = 2.0 * NP * (double)w.T * a.C * a.K;
-        const double by = 4.0 * NP * ((double)w.T * a.C + (double)w.T * a.K + (double)ns * a.C * a.K);
-        PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, fl, by, "wino_wgrad_gemm_kernel<128, 128, 2, 2, %d>", M);
-        hipLaunchKernelGGL((wino_wgrad_gemm_kernel<128, 128, 2, 2, M>), grid, dim3(NTHREADS), 0, st, ga);
-        PNP_CHECK_LAUNCH("wino_wgrad_gemm_kernel");
-    }
+    // S[z][pos][C][K] -> dW, whichever arithmetic produced it
     int ns_out = ns;
-    if (ns > 2 && (size_t)a.C * (a.K / 4) < (size_t)NT * 512) {       // few (channel, filter) vectors, many splits: sum the splits at full width first
+    if (p.splitsum) {
         const size_t nv = (size_t)NP * a.C * (a.K / 4);
         PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)ns + 1.0) * NP * a.C * a.K, "wino_splitsum_kernel");
         hipLaunchKernelGGL(wino_splitsum_kernel, dim3((unsigned)((nv + NT - 1) / NT)), dim3(NT), 0, st, S, nv, ns);
         PNP_CHECK_LAUNCH("wino_splitsum_kernel");
         ns_out = 1;
     }
-    {
-        const size_t nvec = (size_t)a.C * (a.K / 4);
-        PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)ns_out * NP + 9.0 * (1 + (accumulate != 0))) * a.C * a.K, "wino_wgrad_out_kernel<%d>", M);
-        hipLaunchKernelGGL(wino_wgrad_out_kernel<M>, dim3((unsigned)((nvec + NT - 1) / NT)), dim3(NT), 0, st, (const float*)S, dw, a.C, a.K, ns_out, accumulate);
-        PNP_CHECK_LAUNCH("wino_wgrad_out_kernel");
-    }
+    const size_t nvec = (size_t)a.C * (a.K / 4);
+    PnpProfScope ps(PNP_PROF_CONV_WGRAD, st, 0.0, 4.0 * ((double)ns_out * NP + 9.0 * (1 + (accumulate != 0))) * a.C * a.K, "wino_wgrad_out_kernel<%d>", M);
+    hipLaunchKernelGGL(wino_wgrad_out_kernel<M>, dim3((unsigned)((nvec + NT - 1) / NT)), dim3(NT), 0, st, (const float*)S, dw, a.C, a.K, ns_out, accumulate);
+    PNP_CHECK_LAUNCH("wino_wgrad_out_kernel");
     return PNP_OK;
 }
 
 // a: make_args(x, dy, dw, g) of the FORWARD geometry (a.x = x, a.w = dy, a.y unused); dw [3][3][C][K]
 int launch_wino_wgrad(const ConvArgs& a, float* dw, int accumulate, void* ws, size_t ws_bytes, hipStream_t st) {
-    const int m = plan_tile(a, true);
-    PNP_REQUIRE(m == 2 || m == 4, "launch_wino_wgrad: the planner does not route this layer (policy changed between the query and the launch?)");
-    return m == 4 ? launch_wino_wgrad_m<4>(a, dw, accumulate, ws, ws_bytes, st) : launch_wino_wgrad_m<2>(a, dw, accumulate, ws, ws_bytes, st);
+    const WinoWgradPlan p = plan_wino_wgrad(WinoDims(a));
+    PNP_REQUIRE(p.m == 2 || p.m == 4, "launch_wino_wgrad: the planner does not route this layer (policy changed between the query and the launch?)");
+    return p.m == 4 ? launch_wino_wgrad_m<4>(a, p, dw, accumulate, ws, ws_bytes, st) : launch_wino_wgrad_m<2>(a, p, dw, accumulate, ws, ws_bytes, st);
 }
 
 }  // namespace pnpconv
 
 // route policy at run time (tests, A/B measurements): mode 0 never / 1 where the cost model says it pays / 2 wherever the geometry
 // allows; mode < 0 only reads.  Returns the previous mode.  The workspace / parts queries follow the mode in force when they are called.
-extern "C" int32_t pnp_conv2d_wino_wgrad_mode(int32_t mode) {
-    const int prev = wino_wgrad_mode();
-    if (mode >= 0) g_wino_wgrad_mode.store(mode > 2 ? 2 : mode, std::memory_order_relaxed);
-    return prev;
-}
-extern "C" int32_t pnp_conv2d_wino_mode(int32_t mode) {
-    const int prev = wino_mode();
-    if (mode >= 0) g_wino_mode.store(mode > 2 ? 2 : mode, std::memory_order_relaxed);
-    return prev;
-}
+extern "C" int32_t pnp_conv2d_wino_wgrad_mode(int32_t mode) { return wino_wgrad_switch.set(mode); }
+extern "C" int32_t pnp_conv2d_wino_mode(int32_t mode) { return wino_switch.set(mode); }
 // largest output tile of the route: 2 = F(2x2, 3x3) only, 4 = F(4x4, 3x3) wherever the planner takes it (else F(2x2), else the direct
 // kernels); tile < 2 only reads.  Returns the previous value.
 extern "C" int32_t pnp_conv2d_wino_tile(int32_t tile) {
     const int prev = wino_tile_max();
-    if (tile >= 2) g_wino_tile.store(tile >= 4 ? 4 : 2, std::memory_order_relaxed);
+    if (tile >= 2) wino_tile_switch.set(tile >= 4 ? 4 : 2);
     return prev;
 }
-
-// arithmetic of the route's forward / data-gradient GEMMs: 0 = fp32 MFMA (wino_gemm_kernel), 1 = split-bf16 operands with chunked
-// accumulation (wino_gemm_x3_kernel); mode < 0 only reads.  Returns the previous mode.  Workspace queries follow the mode in force.
-extern "C" int32_t pnp_conv2d_wino_x3(int32_t mode) {
-    const int prev = wino_x3_mode();
-    if (mode >= 0) g_wino_x3.store(mode > 2 ? 2 : mode, std::memory_order_relaxed);
-    return prev;
-}
+// arithmetic of the route's forward / data-gradient GEMMs: 0 = fp32 MFMA (wino_gemm_kernel), 1 / 2 = split-bf16 operands with chunked
+// accumulation (wino_gemm_x3_kernel) where it pays / wherever the shapes allow; mode < 0 only reads.  Returns the previous mode.  Workspace
+// queries follow the mode in force.
+extern "C" int32_t pnp_conv2d_wino_x3(int32_t mode) { return wino_x3_switch.set(mode); }
 
 // ---- transformed-filter cache: the caller's side -----------------------------------------------------------------------------------------
 // bytes of one (filter, pass) entry that serves either output tile: 36 C K floats; 0: this filter shape never takes the route

@@ -10,7 +10,7 @@
 // X3 = true), this file contracts them.  Roof: 2.5 PF / 6 = 417 TF/s fp32-equivalent (2.65x the fp32 MFMA peak).
 //
 // Accuracy is BETTER than the fp32 pipe's, not merely equal: the route's error is the fp32 accumulation chain over the channels in the
-// transform domain (tools/wino_f43_study.py: 6.7e-7 with an fp64 GEMM, 4e-6 with fp32), so the kernel accumulates in CHUNKS of 96 channels:
+// transform domain (tools/wino_f43_study.py: 6.7e-7 with an fp64 GEMM, 4e-6 with fp32), so the kernel accumulates in CHUNKS of 64 channels:
 // the MFMA accumulator of a chunk is added into a second register set (`total`) and restarted from zero.  tools/wino_bf16x3_study.py ->
 // profiles/r06_wino_bf16x3_tolerance.txt: 512->512 6.1e-6 (fp32 chain) -> 1.1e-6..1.6e-6; 2 560-channel reduction 1.7e-5 -> 1.7e-6.
 //

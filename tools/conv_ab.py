@@ -8,7 +8,9 @@ partial sums of csrc/split_sum.h, the vector-ALU route file csrc/conv_valu.hip).
 `dump` runs conv2d_fwd (with and without dropout 0.5), conv2d_dgrad (with and without residual) and conv2d_wgrad (with and without into=)
 over the FWD, STRIDED and WGRAD tables of tests/test_igemm_domain_host.py in fp32 and bf16 arithmetic, at the library's default switches and
 (filter gradient only) with the Winograd and split-bf16 routes off, which is where the fp32 routes of the tables run; FWD and WGRAD once more
-with the Winograd route wherever eligible and its GEMMs in fp32 (wino_x3 0); the X3W part counts of
+with the Winograd route wherever eligible and its GEMMs in fp32 (wino_x3 0) and again on split-bf16 operands (wino_x3 2); the SHAPES,
+SPLITS and WIDE tables of tests/test_wino_domain_host.py in that file's four arithmetics (tile 2 / 4 x wino_x3 0 / 2), at every pass the
+route's planner takes, the forward also through conv2d_fwd_stats (output and partial rows) and conv2d_fwd_bn; the X3W part counts of
 tests/test_gpu_x3_wgrad.py (FEW_PARTS, x3_direct mode 2); and the bf16-resident filter gradient of one layer.  PNP_BF16R_WSPLIT is read once
 per process: `dump <file> bf16r` runs that layer alone, for one dump per forced split.  Inputs are seeded on the device; the file holds one
 SHA-256 per output array."""
@@ -51,6 +53,21 @@ def _layer(K, L, out, tag, case, dt, dev, gen, passes=(0, 1, 2)):
         out[tag + " dw into"] = _sha(K.conv2d_wgrad(x, dy, g, into=pre.clone()))
 
 
+def _wino_row(K, L, out, tag, case, dev, gen):
+    """a (N, H, W, C, K, dil, padding) row of tests/test_wino_domain_host.py at every pass the route's planner takes: the six arrays of
+    _layer, and for the forward the statistics entry point (output and partial rows) and the fused inference BN"""
+    N, H, W, C, Kf, dil, padding = case
+    g = K.conv_geom((N, H, W, C), (3, 3, C, Kf), 1, dil, padding)
+    _layer(K, L, out, tag, (N, H, W, C, Kf, 3, 3, 1, dil, padding), L.DTYPE_F32, dev, gen, passes=[k for k in (0, 1, 2) if K.wino_chosen(g, k)])
+    if K.wino_chosen(g, 0):
+        x, w = _rand(gen, (N, H, W, C), dev), _rand(gen, (3, 3, C, Kf), dev, 0.05)
+        shift, scale, sc = _rand(gen, (Kf,), dev, 0.1), _rand(gen, (Kf,), dev), _rand(gen, (N, g.OH, g.OW, Kf), dev)
+        y, (parts, nparts) = K.conv2d_fwd_stats(x, w, g, shift, keep_prob=0.5, seed=11, stream_id=3)
+        out[tag + " stats y"] = _sha(y)
+        out[tag + " stats parts %d" % nparts] = _sha(parts.view(torch.uint8).flatten()[:nparts * 2 * Kf * 4])
+        out[tag + " bn y"] = _sha(K.conv2d_fwd_bn(x, w, g, (scale, shift), shortcut=sc))
+
+
 def _bf16r(K, L, out, dev, gen):
     N, H, W, C, Kf, R, S, st, dil, padding = BF16R_CASE
     g = K.conv_geom((N, H, W, C), (R, S, C, Kf), st, dil, padding, dtype=L.DTYPE_BF16)
@@ -88,6 +105,21 @@ def dump(path, only=None):
         for table, cases in (("FWD", H.FWD), ("WGRAD", H.WGRAD)):
             for case in cases:
                 _layer(K, L, out, "%s %s f32 wino-fp32" % (table, H.case_id(case)), case, L.DTYPE_F32, dev, gen)
+        # ... and on split-bf16 operands wherever the shapes allow (the persistent wino_gemm_x3_kernel grid, wino_splitsum_kernel, the filter
+        # gradient's tiles padded to 64)
+        K.wino_x3(2)
+        for table, cases in (("FWD", H.FWD), ("WGRAD", H.WGRAD)):
+            for case in cases:
+                _layer(K, L, out, "%s %s f32 wino-x3" % (table, H.case_id(case)), case, L.DTYPE_F32, dev, gen)
+        # every instance of the route's own kernels: the tables of tests/test_wino_domain_host.py in its four arithmetics
+        import test_wino_domain_host as Wd
+        prev_t = K.wino_tile(-1)
+        for (tile, x3), an in zip(Wd.ARITH, Wd.ARITH_IDS):
+            K.wino_tile(tile); K.wino_x3(2 if x3 else 0)
+            for table, cases in (("SHAPES", Wd.SHAPES), ("SPLITS", Wd.SPLITS), ("WIDE", Wd.WIDE)):
+                for case in cases:
+                    _wino_row(K, L, out, "WINO %s %s %s" % (an, table, Wd.case_id(case)), case, dev, gen)
+        K.wino_tile(prev_t)
         K.wino_x3(prev[0]); K.wino_mode(prev[1]); K.wino_wgrad_mode(prev[2]); K.x3_direct(prev[3]); K.x3_wgrad(prev[4])
     json.dump(out, open(path, "w"), indent=0, sort_keys=True)
     print("%s: %d arrays, library %s" % (path, len(out), os.environ.get("PNP_LIB", "(the tree's)")))
