@@ -3,8 +3,6 @@
 // Reference call sites: layers.py:95-100 (batch_norm), 145-189 (residual_block / DR_block tails),
 // 102-103 (max_pool2d), ops.py:3-27 (PS), adversarial.py:325-335 (critic input), layers.py:25,74,93 (dropout).
 // All tensors are [P][C] fp32 with C contiguous; every kernel moves 16 B per lane where C % 4 == 0.
-#include <atomic>
-#include <mutex>
 #include "pnp_common.h"
 
 namespace {
@@ -58,26 +56,62 @@ struct ColArgs {
     int C;
     int rows_per_block;
     float eps, alpha;
-    // one-launch combine (round 5): tick != null -> the LAST workgroup of every slab of COLRED_SLAB partial rows sums its slab (double,
-    // fixed order), and the last of those sums the slabs and writes the results — no colreduce_compact / colreduce_final launch.
-    // tick: nslab slab counters + 1 top counter, zero on entry and left zero (self-resetting)
-    unsigned* tick;
-    int nslab;
-    float* o0;           // KIND0: mean ; KIND1: dbeta
-    float* o1;           // KIND0: var  ; KIND1: dgamma
-    float* acc0;         // KIND1: += (gradient arena slots), nullable
-    float* acc1;
-    float* mm;           // KIND0: moving mean / variance update, nullable
-    float* mv;
-    float decay;
 };
 
 constexpr int COLRED_SLAB = 128;
 
+// The arithmetic every BN kernel shares, written once: the vector kernels call it per lane of a channel quad, the scalar kernels per element,
+// so "the same expressions in the same order" (tests/test_gpu_elementwise_domain.py holds the two forms to the same bits) is one text.
+// The pre-activation value.  The fused multiply-add is explicit: the backward kernels recompute this value bit for bit when they are not
+// handed `out`.
+__device__ __forceinline__ float bn_pre(float x, float m, float gsc, float b) { return fmaf(x - m, gsc, b); }
+
+// g through a leaky ReLU whose deciding value (the activation's output, or its input: they have the same sign) is o
+__device__ __forceinline__ float leaky_gate(float g, float o, float alpha) { return o > 0.f ? g : g * alpha; }
+
+// Per-channel coefficients of channels c .. c + 3 (quad) or of channel c alone, in lane 0 (!quad): 1 / sqrt(var + eps) — a square root and
+// a correctly rounded division, formed once per thread where the thread owns its channels — gamma times it, and for the backward the two
+// sums over the rows behind them.  bn_coef gives m and rs and leaves the rest zero: a kernel adds what it reads (bn_coef_scale, b = ldc(beta),
+// bn_coef_sums) under its own conditions, since gamma, beta and the sums may each be absent.
+struct BnCoef {
+    f32x4 m, rs, gsc, b, dgp, dbp;       // mean, 1 / sqrt(var + eps), gamma * rs, beta, dgamma * invP, dbeta * invP
+};
+__device__ __forceinline__ f32x4 ldc(const float* p, int c, bool quad) { return quad ? ld4(p + c) : f32x4{p[c], 0.f, 0.f, 0.f}; }
+__device__ __forceinline__ BnCoef bn_coef(const float* mean, const float* var, float eps, int c, bool quad) {
+    BnCoef k{};
+    k.m = ldc(mean, c, quad);
+    const f32x4 v = ldc(var, c, quad);
+#pragma unroll
+    for (int e = 0; e < (quad ? 4 : 1); ++e) k.rs[e] = 1.0f / sqrtf(v[e] + eps);
+    return k;
+}
+__device__ __forceinline__ void bn_coef_scale(BnCoef& k, const float* gamma, int c, bool quad) {
+    const f32x4 ga = ldc(gamma, c, quad);
+#pragma unroll
+    for (int e = 0; e < (quad ? 4 : 1); ++e) k.gsc[e] = ga[e] * k.rs[e];
+}
+__device__ __forceinline__ void bn_coef_sums(BnCoef& k, const float* dgamma, const float* dbeta, float invP, int c, bool quad) {
+    const f32x4 dg = ldc(dgamma, c, quad), db = ldc(dbeta, c, quad);
+#pragma unroll
+    for (int e = 0; e < (quad ? 4 : 1); ++e) {
+        k.dgp[e] = dg[e] * invP;
+        k.dbp[e] = db[e] * invP;
+    }
+}
+
+// The gradient behind the fused activation (alpha < 0: none): its sign is read from `out` (o) where the caller has it, otherwise it is that
+// of the pre-activation value exactly as bn_apply_kernel formed it, recomputed from x.
+__device__ __forceinline__ float bn_gated(float g, bool has_out, float o, float x, const BnCoef& k, int e, float alpha) {
+    if (alpha < 0.f) return g;
+    return leaky_gate(g, has_out ? o : bn_pre(x, k.m[e], k.gsc[e], k.b[e]), alpha);
+}
+
+// the normalised input: what dgamma sums against the gated gradient, and what the training-mode dx subtracts
+__device__ __forceinline__ float bn_xhat(float x, const BnCoef& k, int e) { return (x - k.m[e]) * k.rs[e]; }
+
 template <int KIND>
 __global__ void __launch_bounds__(NT) colreduce_kernel(ColArgs a) {
     __shared__ float red[NT * 8];
-    __shared__ int s_last;
     const int C4 = a.C >> 2;
     const int rpi = NT / C4;                 // rows per iteration (C4 <= 256 guaranteed by the host)
     const int t = threadIdx.x;
@@ -89,19 +123,14 @@ __global__ void __launch_bounds__(NT) colreduce_kernel(ColArgs a) {
     f32x4 s0 = {0, 0, 0, 0}, s1 = {0, 0, 0, 0};
     if (active) {
         const int c = cg * 4;
-        f32x4 m, rs, gsc = {0, 0, 0, 0}, bet = {0, 0, 0, 0};
+        BnCoef k{};
         if constexpr (KIND == 0) {
-            m = ld4(a.x + c);   // shift
+            k.m = ld4(a.x + c);   // shift
         } else {
-            m = ld4(a.mean + c);
-            f32x4 v = ld4(a.var + c);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) rs[e] = 1.0f / sqrtf(v[e] + a.eps);
+            k = bn_coef(a.mean, a.var, a.eps, c, true);
             if (!a.out && a.alpha >= 0.f) {
-                const f32x4 ga = ld4(a.gamma + c);
-                bet = ld4(a.beta + c);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) gsc[e] = ga[e] * rs[e];
+                bn_coef_scale(k, a.gamma, c, true);
+                k.b = ld4(a.beta + c);
             }
         }
         for (long long r = r0 + rsub; r < r1; r += rpi) {
@@ -110,27 +139,18 @@ __global__ void __launch_bounds__(NT) colreduce_kernel(ColArgs a) {
             if constexpr (KIND == 0) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float d = xv[e] - m[e];
+                    float d = xv[e] - k.m[e];
                     s0[e] += d;
                     s1[e] = fmaf(d, d, s1[e]);
                 }
             } else {
-                f32x4 g = ld4(a.dout + off);
-                if (a.alpha >= 0.f) {
-                    if (a.out) {
-                        f32x4 o = ld4(a.out + off);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) g[e] = o[e] > 0.f ? g[e] : g[e] * a.alpha;
-                    } else {        // the pre-activation value exactly as bn_apply_kernel formed it
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) g[e] = fmaf(xv[e] - m[e], gsc[e], bet[e]) > 0.f ? g[e] : g[e] * a.alpha;
-                    }
-                }
+                f32x4 g = ld4(a.dout + off), o = {0, 0, 0, 0};
+                if (a.alpha >= 0.f && a.out) o = ld4(a.out + off);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    float xh = (xv[e] - m[e]) * rs[e];
+                    g[e] = bn_gated(g[e], a.out, o[e], xv[e], k, e, a.alpha);
                     s0[e] += g[e];
-                    s1[e] = fmaf(g[e], xh, s1[e]);
+                    s1[e] = fmaf(g[e], bn_xhat(xv[e], k, e), s1[e]);
                 }
             }
         }
@@ -156,113 +176,6 @@ __global__ void __launch_bounds__(NT) colreduce_kernel(ColArgs a) {
         st4(w0, a0);
         st4(w1, a1);
     }
-    if (!a.tick) return;
-    // ---- one-launch combine.  Release: the partial row is visible device-wide before the ticket is taken; acquire: the last taker sees
-    // every row of its slab.  Summation orders are fixed (rows of a slab by (row lane, stride), slabs in order): deterministic whichever
-    // workgroup happens to be last.
-    const int nblk = (int)gridDim.x;
-    const int slab = blockIdx.x / COLRED_SLAB;
-    const int b0 = slab * COLRED_SLAB;
-    const int b1 = (b0 + COLRED_SLAB < nblk) ? b0 + COLRED_SLAB : nblk;
-    __threadfence();
-    __syncthreads();
-    if (t == 0) s_last = (atomicAdd(&a.tick[slab], 1u) == (unsigned)(b1 - b0 - 1));
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    double* dred = reinterpret_cast<double*>(red);          // NT x 4 doubles (the float scratch, reused): two passes, q0 then q1
-    double d0[4] = {0, 0, 0, 0}, d1[4] = {0, 0, 0, 0};
-    if (active) {
-        for (int b = b0 + rsub; b < b1; b += rpi) {
-            const f32x4 v0 = ld4(a.ws + ((size_t)b * 2 + 0) * a.C + cg * 4), v1 = ld4(a.ws + ((size_t)b * 2 + 1) * a.C + cg * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                d0[e] += (double)v0[e];
-                d1[e] += (double)v1[e];
-            }
-        }
-    }
-    double t0[4] = {0, 0, 0, 0}, t1[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        __syncthreads();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) dred[t * 4 + e] = q == 0 ? d0[e] : d1[e];
-        __syncthreads();
-        if (t < C4) {
-            for (int j = 0; j < rpi; ++j)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) (q == 0 ? t0 : t1)[e] += dred[(j * C4 + t) * 4 + e];
-        }
-    }
-    // the slab's sum as a (high, low) pair of floats over its own first two rows (colreduce_compact_kernel's layout): only this workgroup
-    // reads or writes them from here on (a slab of one row keeps the high part only: its low part is exactly zero)
-    if (t < C4) {
-        f32x4 h0, h1, l0, l1;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            h0[e] = (float)t0[e];
-            h1[e] = (float)t1[e];
-            l0[e] = (fabsf(h0[e]) <= 3.4e38f) ? (float)(t0[e] - (double)h0[e]) : 0.f;
-            l1[e] = (fabsf(h1[e]) <= 3.4e38f) ? (float)(t1[e] - (double)h1[e]) : 0.f;
-        }
-        st4(a.ws + ((size_t)b0 * 2 + 0) * a.C + t * 4, h0);
-        st4(a.ws + ((size_t)b0 * 2 + 1) * a.C + t * 4, h1);
-        if (b1 - b0 > 1) {
-            st4(a.ws + ((size_t)(b0 + 1) * 2 + 0) * a.C + t * 4, l0);
-            st4(a.ws + ((size_t)(b0 + 1) * 2 + 1) * a.C + t * 4, l1);
-        }
-    }
-    __threadfence();
-    __syncthreads();
-    if (t == 0) {
-        a.tick[slab] = 0u;                                   // every workgroup of the slab has taken its ticket: re-arm
-        s_last = (atomicAdd(&a.tick[a.nslab], 1u) == (unsigned)(a.nslab - 1));
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __threadfence();
-    if (t == 0) a.tick[a.nslab] = 0u;
-    if (t >= C4) return;
-    double f0[4] = {0, 0, 0, 0}, f1[4] = {0, 0, 0, 0};
-    for (int sl = 0; sl < a.nslab; ++sl) {
-        const int r0s = sl * COLRED_SLAB;
-        const int nrow = (r0s + 1 < nblk) ? 2 : 1;
-        for (int j = 0; j < nrow; ++j) {
-            const f32x4 v0 = ld4(a.ws + ((size_t)(r0s + j) * 2 + 0) * a.C + t * 4), v1 = ld4(a.ws + ((size_t)(r0s + j) * 2 + 1) * a.C + t * 4);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                f0[e] += (double)v0[e];
-                f1[e] += (double)v1[e];
-            }
-        }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int c = t * 4 + e;
-        if constexpr (KIND == 0) {
-            const double inv = 1.0 / (double)a.P;
-            const double md = f0[e] * inv;
-            double var = f1[e] * inv - md * md;
-            if (var < 0.0) var = 0.0;
-            const float meanf = (float)((double)a.x[c] + md), varf = (float)var;
-            a.o0[c] = meanf;
-            a.o1[c] = varf;
-            if (a.mm) {
-                const float one_minus = 1.0f - a.decay;
-                const float bessel = a.P > 1 ? (float)((double)a.P / (double)(a.P - 1)) : 1.0f;
-                a.mm[c] -= (a.mm[c] - meanf) * one_minus;
-                a.mv[c] -= (a.mv[c] - varf * bessel) * one_minus;
-            }
-        } else {
-            a.o0[c] = (float)f0[e];
-            a.o1[c] = (float)f1[e];
-            if (a.acc0) {
-                a.acc0[c] += (float)f0[e];
-                a.acc1[c] += (float)f1[e];
-            }
-        }
-    }
 }
 
 // scalar fallback for C % 4 != 0 or C > 1024: one thread per channel per block-slab.  The thread walks ALL rows of its slab (P below 64 rows, 64 or more otherwise) in
@@ -276,80 +189,45 @@ __global__ void colreduce_scalar_kernel(ColArgs a) {
     long long r1 = r0 + a.rows_per_block;
     if (r1 > a.P) r1 = a.P;
     double s0 = 0.0, s1 = 0.0;
-    float m, rs = 0.f;
-    if constexpr (KIND == 0) m = a.x[c];
-    else { m = a.mean[c]; rs = 1.0f / sqrtf(a.var[c] + a.eps); }
+    BnCoef k{};
+    if constexpr (KIND == 0) {
+        k.m[0] = a.x[c];
+    } else {
+        k = bn_coef(a.mean, a.var, a.eps, c, false);
+        if (!a.out && a.alpha >= 0.f) {
+            bn_coef_scale(k, a.gamma, c, false);
+            k.b[0] = a.beta[c];
+        }
+    }
     for (long long r = r0; r < r1; ++r) {
         const size_t off = (size_t)r * a.C + c;
         float xv = a.x[off];
         if constexpr (KIND == 0) {
-            const float d = xv - m;
+            const float d = xv - k.m[0];
             s0 += (double)d;
             s1 += (double)d * (double)d;
         } else {
-            float g = a.dout[off];
-            if (a.alpha >= 0.f) {
-                const float o = a.out ? a.out[off] : fmaf(xv - m, a.gamma[c] * rs, a.beta[c]);
-                g = o > 0.f ? g : g * a.alpha;
-            }
+            const float g = bn_gated(a.dout[off], a.out, (a.alpha >= 0.f && a.out) ? a.out[off] : 0.f, xv, k, 0, a.alpha);
             s0 += (double)g;
-            s1 += (double)g * (double)((xv - m) * rs);
+            s1 += (double)g * (double)bn_xhat(xv, k, 0);
         }
     }
     a.ws[((size_t)blockIdx.x * 2 + 0) * a.C + c] = (float)s0;
     a.ws[((size_t)blockIdx.x * 2 + 1) * a.C + c] = (float)s1;
 }
 
-// Long partial lists (the convolution epilogue leaves one partial per 64 output rows: 16 384 of them for a 64-channel layer at 256^2,
-// which the C/32 = 2 workgroups of the final kernel walked alone: 240 us) are first compacted IN PLACE by (C/32) x nslab workgroups:
-// slab s = partials [s*SLAB, (s+1)*SLAB) (the last slab takes the remainder) is summed in double and written back over its own first two
-// partials as a (high, low) pair of floats, which together carry the double sum to 48 bits.  Only this workgroup ever reads those two
-// rows of its 32 channels, so there is no race; the summation order is fixed => deterministic.  The partial list is consumed.
-__global__ void __launch_bounds__(1024) colreduce_compact_kernel(float* __restrict__ ws, int nblk, int nslab, int C) {
-    __shared__ double red[2][32][33];
+// The sum of a list of partials by one workgroup of 1024 threads = 32 channels x 32 slices of the list: entries b0 .. b1 - 1 of channel c,
+// slice sl taking every 32nd, in double; then the 32 slices in order.  Fixed summation order => deterministic.  slab > 0: the list was
+// compacted; entry b is partial (b >> 1) * slab + (b & 1).  `mine` for the threads (slice 0 of a channel below C) that hold the sums.
+struct SlabSum {
+    double s0, s1;
+    bool mine;
+};
+__device__ __forceinline__ SlabSum slab_sum(double (&red)[2][32][33], const float* ws, int b0, int b1, int slab, int C, int c) {
     const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    const int s = blockIdx.y;
-    const int b0 = s * COLRED_SLAB;
-    const int b1 = (s == nslab - 1) ? nblk : b0 + COLRED_SLAB;
     double s0 = 0.0, s1 = 0.0;
     if (c < C) {
         for (int b = b0 + sl; b < b1; b += 32) {
-            s0 += (double)ws[((size_t)b * 2 + 0) * C + c];
-            s1 += (double)ws[((size_t)b * 2 + 1) * C + c];
-        }
-    }
-    red[0][sl][cl] = s0;
-    red[1][sl][cl] = s1;
-    __syncthreads();
-    if (sl != 0 || c >= C) return;
-    s0 = 0.0;
-    s1 = 0.0;
-    for (int j = 0; j < 32; ++j) {
-        s0 += red[0][j][cl];
-        s1 += red[1][j][cl];
-    }
-    const float h0 = (float)s0, h1 = (float)s1;
-    ws[((size_t)b0 * 2 + 0) * C + c] = h0;
-    ws[((size_t)b0 * 2 + 1) * C + c] = h1;
-    // (an overflowed sum stays +-inf like in the single-launch combine: inf - inf would turn it into NaN)
-    ws[((size_t)(b0 + 1) * 2 + 0) * C + c] = (fabsf(h0) <= 3.4e38f) ? (float)(s0 - (double)h0) : 0.f;
-    ws[((size_t)(b0 + 1) * 2 + 1) * C + c] = (fabsf(h1) <= 3.4e38f) ? (float)(s1 - (double)h1) : 0.f;
-}
-
-// final combine over blocks in double. KIND 0 -> mean,var ; KIND 1 -> dbeta (o0), dgamma (o1)
-// slab > 0: the list was compacted; entry b is partial (b >> 1) * slab + (b & 1)
-template <int KIND>
-__global__ void __launch_bounds__(1024) colreduce_final_kernel(const float* __restrict__ ws, const float* __restrict__ x0,
-                                                               float* o0, float* o1, int nblk, int C, long long P, float* mm, float* mv,
-                                                               float decay, int slab, float* acc0, float* acc1) {
-    // 1024 threads = 32 channels x 32 slices of the block list; fixed summation order => deterministic
-    __shared__ double red[2][32][33];
-    const int cl = threadIdx.x & 31, sl = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    double s0 = 0.0, s1 = 0.0;
-    if (c < C) {
-        for (int b = sl; b < nblk; b += 32) {
             const int row = slab > 0 ? (b >> 1) * slab + (b & 1) : b;
             s0 += (double)ws[((size_t)row * 2 + 0) * C + c];
             s1 += (double)ws[((size_t)row * 2 + 1) * C + c];
@@ -358,13 +236,55 @@ __global__ void __launch_bounds__(1024) colreduce_final_kernel(const float* __re
     red[0][sl][cl] = s0;
     red[1][sl][cl] = s1;
     __syncthreads();
-    if (sl != 0 || c >= C) return;
+    if (sl != 0 || c >= C) return {0.0, 0.0, false};
     s0 = 0.0;
     s1 = 0.0;
     for (int j = 0; j < 32; ++j) {
         s0 += red[0][j][cl];
         s1 += red[1][j][cl];
     }
+    return {s0, s1, true};
+}
+
+// what the float hi = (float)s leaves of a double sum s, as a float: (hi, low) carry s to 48 bits.  An overflowed sum stays +-inf with a
+// zero low part: inf - inf would turn it into NaN
+__device__ __forceinline__ float low_part(double s, float hi) { return (fabsf(hi) <= 3.4e38f) ? (float)(s - (double)hi) : 0.f; }
+
+// Long partial lists (the convolution epilogue leaves one partial per 64 output rows: 16 384 of them for a 64-channel layer at 256^2,
+// which the C/32 = 2 workgroups of the final kernel walked alone: 240 us) are first compacted IN PLACE by (C/32) x nslab workgroups:
+// slab s = partials [s*SLAB, (s+1)*SLAB) (the last slab takes the remainder) is summed in double and written back over its own first two
+// partials as a (high, low) pair of floats, which together carry the double sum to 48 bits.  Only this workgroup ever reads those two
+// rows of its 32 channels, so there is no race; the summation order is fixed => deterministic.  The partial list is consumed.
+__global__ void __launch_bounds__(1024) colreduce_compact_kernel(float* __restrict__ ws, int nblk, int nslab, int C) {
+    __shared__ double red[2][32][33];
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+    const int s = blockIdx.y;
+    const int b0 = s * COLRED_SLAB;
+    const int b1 = (s == nslab - 1) ? nblk : b0 + COLRED_SLAB;
+    const SlabSum t = slab_sum(red, ws, b0, b1, 0, C, c);
+    if (!t.mine) return;
+    const float h0 = (float)t.s0, h1 = (float)t.s1;
+    ws[((size_t)b0 * 2 + 0) * C + c] = h0;
+    ws[((size_t)b0 * 2 + 1) * C + c] = h1;
+    ws[((size_t)(b0 + 1) * 2 + 0) * C + c] = low_part(t.s0, h0);
+    ws[((size_t)(b0 + 1) * 2 + 1) * C + c] = low_part(t.s1, h1);
+}
+
+// tf.contrib.layers.batch_norm(updates_collections=None): the moving averages move with every training-mode forward (the variance that
+// goes in is the unbiased one)
+__device__ __forceinline__ float bn_bessel(long long P) { return P > 1 ? (float)((double)P / (double)(P - 1)) : 1.0f; }
+__device__ __forceinline__ void bn_move(float* avg, float v, float one_minus_decay) { *avg -= (*avg - v) * one_minus_decay; }
+
+// final combine over blocks in double. KIND 0 -> mean,var ; KIND 1 -> dbeta (o0), dgamma (o1)
+template <int KIND>
+__global__ void __launch_bounds__(1024) colreduce_final_kernel(const float* __restrict__ ws, const float* __restrict__ x0,
+                                                               float* o0, float* o1, int nblk, int C, long long P, float* mm, float* mv,
+                                                               float decay, int slab, float* acc0, float* acc1) {
+    __shared__ double red[2][32][33];
+    const int c = blockIdx.x * 32 + (threadIdx.x & 31);
+    const SlabSum t = slab_sum(red, ws, 0, nblk, slab, C, c);
+    if (!t.mine) return;
+    const double s0 = t.s0, s1 = t.s1;
     if constexpr (KIND == 0) {
         const double inv = 1.0 / (double)P;
         const double md = s0 * inv;                 // mean of (x - shift)
@@ -373,11 +293,10 @@ __global__ void __launch_bounds__(1024) colreduce_final_kernel(const float* __re
         const float meanf = (float)((double)x0[c] + md), varf = (float)var;
         o0[c] = meanf;
         o1[c] = varf;
-        if (mm) {       // tf.contrib.layers.batch_norm(updates_collections=None): the moving averages move with every training-mode forward
-            const float one_minus = 1.0f - decay;
-            const float bessel = P > 1 ? (float)((double)P / (double)(P - 1)) : 1.0f;
-            mm[c] -= (mm[c] - meanf) * one_minus;
-            mv[c] -= (mv[c] - varf * bessel) * one_minus;
+        if (mm) {
+            const float one_minus = 1.0f - decay, bessel = bn_bessel(P);
+            bn_move(mm + c, meanf, one_minus);
+            bn_move(mv + c, varf * bessel, one_minus);
         }
     } else {
         o0[c] = (float)s0;
@@ -393,9 +312,8 @@ __global__ void __launch_bounds__(1024) colreduce_final_kernel(const float* __re
 template <int KIND>
 int launch_colreduce_final(float* ws, const float* x0, float* o0, float* o1, int nblk, int C, long long P, float* mm, float* mv, float decay,
                            hipStream_t st, const char* who, float* acc0 = nullptr, float* acc1 = nullptr) {
-    static const int two_stage = getenv("PNP_BN_FINAL_1STAGE") ? 0 : 1;
     int slab = 0, n = nblk;
-    if (two_stage && nblk >= 4 * COLRED_SLAB) {
+    if (nblk >= 4 * COLRED_SLAB) {
         const int nslab = nblk / COLRED_SLAB;
         hipLaunchKernelGGL(colreduce_compact_kernel, dim3(pnp_cdiv(C, 32), nslab), dim3(1024), 0, st, ws, nblk, nslab, C);
         PNP_CHECK_LAUNCH(who);
@@ -408,7 +326,7 @@ int launch_colreduce_final(float* ws, const float* x0, float* o0, float* o1, int
     return PNP_OK;
 }
 
-int colreduce_plan(long long P, int C, int* nblk, int* rpb) {
+int colreduce_plan(long long P, int* nblk, int* rpb) {
     // ~2048 blocks max, at least 64 rows per block
     static const int cap = getenv("PNP_BN_NBLK") ? atoi(getenv("PNP_BN_NBLK")) : 2048;
     long long b = (P + 63) / 64;
@@ -418,59 +336,18 @@ int colreduce_plan(long long P, int C, int* nblk, int* rpb) {
     b = (P + r - 1) / r;
     *nblk = (int)b;
     *rpb = (int)r;
-    (void)C;
     return 0;
 }
 
-// Ticket counters of the one-launch combine: a library-owned, zero-initialised device buffer of TICKET_SLOTS x TICKET_STRIDE counters,
-// handed out round-robin (a slot is busy for the lifetime of ONE launch and re-arms itself: two launches share a slot only if
-// TICKET_SLOTS launches are in flight at once).  Allocated at the first un-captured use (hipMalloc is not legal inside a stream
-// capture: a recording that comes first falls back to the separate combine launches).
-// OFF by default (PNP_BN_ONE_LAUNCH=1 switches it on): measured within one run on the joint step (round 5: tools/experiments/README.md), 242.4 ->
-// 208.3 slices/s — colreduce_kernel<1> 32 -> 141 us per launch: the device-scope release / acquire every workgroup needs around its
-// ticket (buffer_wbl2 + buffer_inv sc1 on a part whose 8 L2s are only coherent through them) costs far more than the two ~8 us combine
-// launches it removes.  Kept as the measured answer to VERDICT r4 #5c; parity-tested (tests/test_gpu_elementwise.py).
-constexpr int TICKET_SLOTS = 512, TICKET_STRIDE = 32;
-unsigned* ticket_slot(hipStream_t st, int nslab) {
-    static const int on = getenv("PNP_BN_ONE_LAUNCH") ? atoi(getenv("PNP_BN_ONE_LAUNCH")) : 0;
-    if (!on || nslab + 1 > TICKET_STRIDE) return nullptr;
-    // one buffer per DEVICE (a process that drives several GPUs must not hand device 0's tickets to a launch on device 1)
-    constexpr int MAXDEV = 16;
-    static std::atomic<unsigned*> bufs[MAXDEV];
-    static std::atomic<unsigned> seq{0};
-    static std::mutex mx;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    std::atomic<unsigned*>& buf = bufs[dev];
-    unsigned* b = buf.load(std::memory_order_acquire);
-    if (!b) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-        std::lock_guard<std::mutex> lk(mx);
-        b = buf.load(std::memory_order_acquire);
-        if (!b) {
-            if (hipMalloc((void**)&b, sizeof(unsigned) * TICKET_SLOTS * TICKET_STRIDE) != hipSuccess ||
-                hipMemset(b, 0, sizeof(unsigned) * TICKET_SLOTS * TICKET_STRIDE) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
-                (void)hipGetLastError();
-                return nullptr;
-            }
-            buf.store(b, std::memory_order_release);
-        }
-    }
-    return b + (size_t)(seq.fetch_add(1, std::memory_order_relaxed) % TICKET_SLOTS) * TICKET_STRIDE;
-}
-
+// A column reduction is the reduction launch (one partial row per workgroup) and then the final combine of launch_colreduce_final: one
+// launch, or two for a list of >= 4 slabs.  Combining inside the reduction launch (the last workgroup to take a ticket sums the list) was
+// built, measured and removed: the device-scope release / acquire around every workgroup's ticket cost far more than the two ~8 us launches
+// it saved (242.4 -> 208.3 slices/s: profiles/r05_bn_one_launch_ab.txt, tools/experiments/README.md row 5).
 template <int KIND>
 int run_colreduce(ColArgs a, float* o0, float* o1, void* ws, size_t ws_bytes, hipStream_t st, const char* who, float* mm = nullptr,
                   float* mv = nullptr, float decay = 0.f, float* acc0 = nullptr, float* acc1 = nullptr) {
     int nblk, rpb;
-    colreduce_plan(a.P, a.C, &nblk, &rpb);
+    colreduce_plan(a.P, &nblk, &rpb);
     const size_t need = (size_t)nblk * 2 * a.C * sizeof(float);
     if (ws_bytes < need || !ws) {
         pnp_set_error("%s: workspace too small (%zu < %zu)", who, ws_bytes, need);
@@ -478,18 +355,8 @@ int run_colreduce(ColArgs a, float* o0, float* o1, void* ws, size_t ws_bytes, hi
     }
     a.ws = (float*)ws;
     a.rows_per_block = rpb;
-    if ((a.C & 3) == 0 && a.C <= 1024) {
-        a.nslab = pnp_cdiv(nblk, COLRED_SLAB);
-        a.tick = ticket_slot(st, a.nslab);
-        a.o0 = o0; a.o1 = o1; a.acc0 = acc0; a.acc1 = acc1; a.mm = mm; a.mv = mv; a.decay = decay;
-        hipLaunchKernelGGL(colreduce_kernel<KIND>, dim3(nblk), dim3(NT), 0, st, a);
-        if (a.tick) {
-            PNP_CHECK_LAUNCH(who);
-            return PNP_OK;
-        }
-    } else {
-        hipLaunchKernelGGL(colreduce_scalar_kernel<KIND>, dim3(nblk, pnp_cdiv(a.C, 64)), dim3(64), 0, st, a);
-    }
+    if ((a.C & 3) == 0 && a.C <= 1024) hipLaunchKernelGGL(colreduce_kernel<KIND>, dim3(nblk), dim3(NT), 0, st, a);
+    else hipLaunchKernelGGL(colreduce_scalar_kernel<KIND>, dim3(nblk, pnp_cdiv(a.C, 64)), dim3(64), 0, st, a);
     PNP_CHECK_LAUNCH(who);
     return launch_colreduce_final<KIND>((float*)ws, a.x, o0, o1, nblk, a.C, a.P, mm, mv, decay, st, who, acc0, acc1);
 }
@@ -498,10 +365,9 @@ __global__ void bn_update_moving_kernel(float* mm, float* mv, const float* mean,
                                         float decay) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float one_minus = 1.0f - decay;
-    const float bessel = P > 1 ? (float)((double)P / (double)(P - 1)) : 1.0f;
-    mm[c] -= (mm[c] - mean[c]) * one_minus;
-    mv[c] -= (mv[c] - var[c] * bessel) * one_minus;
+    const float one_minus = 1.0f - decay, bessel = bn_bessel(P);
+    bn_move(mm + c, mean[c], one_minus);
+    bn_move(mv + c, var[c] * bessel, one_minus);
 }
 
 struct BnApplyArgs {
@@ -516,7 +382,15 @@ struct BnApplyArgs {
 // VEC: a thread owns ONE channel quad and walks rows (block = rpi rows x C4s quads, blockIdx.y = slice of 256 quads): the per-channel
 // coefficients — 1 / sqrt(var + eps) is a square root and a correctly rounded division — are formed once per thread, and no index needs a
 // 64-bit division (round 6: the element-at-a-time form re-did both for every vector and ran VALU-bound at 1.8-2.4 TB/s on the critics'
-// 537 MB maps).  Same expressions in the same order: bit-identical results.
+// 537 MB maps).  Both forms run bn_apply_elem on every element and differ only in how they walk memory: bit-identical results.
+// one element of the forward: BN, + the shortcut's element s where the channel has one, leaky ReLU (alpha < 0: none)
+__device__ __forceinline__ float bn_apply_elem(float x, const BnCoef& k, int e, bool has_s, float s, float alpha) {
+    float r = bn_pre(x, k.m[e], k.gsc[e], k.b[e]);
+    if (has_s) r += s;
+    if (alpha >= 0.f) r = leaky_gate(r, r, alpha);
+    return r;
+}
+
 template <bool VEC>
 __global__ void __launch_bounds__(NT) bn_apply_kernel(BnApplyArgs a) {
     const int cpad = (a.C - a.Cs) / 2;
@@ -528,10 +402,9 @@ __global__ void __launch_bounds__(NT) bn_apply_kernel(BnApplyArgs a) {
         const int cg = threadIdx.x % C4s, rsub = threadIdx.x / C4s;
         if (rsub >= rpi) return;
         const int c = (kq0 + cg) * 4;
-        const f32x4 m = ld4(a.mean + c), v = ld4(a.var + c), g = ld4(a.gamma + c), b = ld4(a.beta + c);
-        f32x4 gsc;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) gsc[e] = g[e] * (1.0f / sqrtf(v[e] + a.eps));
+        BnCoef k = bn_coef(a.mean, a.var, a.eps, c, true);
+        bn_coef_scale(k, a.gamma, c, true);
+        k.b = ld4(a.beta + c);
         const int cs = c - cpad;
         const bool has_s = a.shortcut && cs >= 0 && cs < a.Cs;
         // a workgroup streams ONE contiguous slab of rows (like colreduce_kernel, which reads the same tensors at 6 TB/s; strided passes of
@@ -541,19 +414,10 @@ __global__ void __launch_bounds__(NT) bn_apply_kernel(BnApplyArgs a) {
         for (long long row = (long long)blockIdx.x * per + rsub; row < rend; row += rpi) {
             const size_t i = (size_t)row * C4 + kq0 + cg;
             const f32x4 xv = ld4(a.x + i * 4);
-            f32x4 r;
+            f32x4 r, sv = {0, 0, 0, 0};
+            if (has_s) sv = ld4(a.shortcut + (size_t)row * a.Cs + cs);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) r[e] = fmaf(xv[e] - m[e], gsc[e], b[e]);    // (explicit: the backward kernels recompute this value
-            // bit for bit when they are not handed `out`)
-            if (has_s) {
-                const f32x4 sv = ld4(a.shortcut + (size_t)row * a.Cs + cs);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) r[e] += sv[e];
-            }
-            if (a.alpha >= 0.f) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) r[e] = r[e] > 0.f ? r[e] : r[e] * a.alpha;
-            }
+            for (int e = 0; e < 4; ++e) r[e] = bn_apply_elem(xv[e], k, e, has_s, sv[e], a.alpha);
             st4(a.y + i * 4, r);
             if (a.yh) st4h(a.yh + i * 4, r);
         }
@@ -564,12 +428,12 @@ __global__ void __launch_bounds__(NT) bn_apply_kernel(BnApplyArgs a) {
         for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < nvec; i += gs) {
             const size_t row = i / CV;
             const int c = (int)(i - row * CV);
-            float r = fmaf(a.x[i] - a.mean[c], a.gamma[c] * (1.0f / sqrtf(a.var[c] + a.eps)), a.beta[c]);
-            if (a.shortcut) {
-                const int cs = c - cpad;
-                if (cs >= 0 && cs < a.Cs) r += a.shortcut[row * a.Cs + cs];
-            }
-            if (a.alpha >= 0.f) r = r > 0.f ? r : r * a.alpha;
+            BnCoef k = bn_coef(a.mean, a.var, a.eps, c, false);
+            bn_coef_scale(k, a.gamma, c, false);
+            k.b[0] = a.beta[c];
+            const int cs = c - cpad;
+            const bool has_s = a.shortcut && cs >= 0 && cs < a.Cs;
+            const float r = bn_apply_elem(a.x[i], k, 0, has_s, has_s ? a.shortcut[row * a.Cs + cs] : 0.f, a.alpha);
             a.y[i] = r;
             if (a.yh) a.yh[i] = (__bf16)r;
         }
@@ -592,16 +456,28 @@ struct BnBwdArgs {
     __bf16* dxh;     // bf16 copy of dx (operand of the bf16-resident data / filter gradient kernels); null: none
 };
 
-// (VEC: the thread-owns-a-channel-quad mapping of bn_apply_kernel; same expressions in the same order as the element-at-a-time form.
-// Which products are fused into an FMA is written out and not left to the compiler: it fused g - dbeta * invP in the scalar form, where the
-// vector form holds the rounded product in a register, and the two forms differed in the last bit of a training-mode dx:
-// tests/test_gpu_elementwise_domain.py)
+// One element of dx from g, the gradient behind the activation (bn_gated: what the shortcut receives); idx is the element's flat index (the
+// dropout mask's).
+// Which products are fused into an FMA is written out and not left to the compiler: it once fused g - dbeta * invP in the scalar kernel,
+// where the vector kernel held the rounded product in a register, and the two differed in the last bit of a training-mode dx
+// (tests/test_gpu_elementwise_domain.py).
+__device__ __forceinline__ float bn_bwd_elem(const BnBwdArgs& a, const BnCoef& k, int e, float x, float g, uint32_t idx, uint32_t dkey) {
+#pragma clang fp contract(off)
+    float r = a.training ? k.gsc[e] * fmaf(-bn_xhat(x, k, e), k.dgp[e], g - k.dbp[e]) : k.gsc[e] * g;
+    if (a.do_drop) r = pnp_drop_keep(idx, dkey, a.drop_thresh) ? r / a.drop_keep : 0.f;
+    return r;
+}
+
+// VEC: the thread-owns-a-channel-quad mapping of bn_apply_kernel.  This branch keeps its own staged text (gate, store, dx, dropout, each
+// over the quad): the same expressions in the same order as bn_gated + bn_bwd_elem, which the scalar branch calls.  Built on the helpers it
+// gave the same bits but lost packed multiplies and ran 44 -> 47-49 us per launch in the joint step (profiles/bn_once_ab.txt).
 template <bool VEC>
 __global__ void __launch_bounds__(NT) bn_bwd_apply_kernel(BnBwdArgs a) {
 #pragma clang fp contract(off)
     const int cpad = (a.C - a.Cs) / 2;
     const float invP = (float)(1.0 / (double)a.P_norm);
     const uint32_t dkey = a.do_drop ? pnp_eff_drop_key(a.drop_key, a.sp, a.drop_sid) : 0u;
+    const bool resign = a.alpha >= 0.f && !a.out;
     if constexpr (VEC) {
         const int C4 = a.C >> 2;
         const int kq0 = blockIdx.y * NT;
@@ -673,24 +549,16 @@ __global__ void __launch_bounds__(NT) bn_bwd_apply_kernel(BnBwdArgs a) {
         for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < nvec; i += gs) {
             const size_t row = i / CV;
             const int c = (int)(i - row * CV);
-            float g = a.dout[i];
-            if (a.alpha >= 0.f) {
-                const float o = a.out ? a.out[i] : fmaf(a.x[i] - a.mean[c], a.gamma[c] * (1.0f / sqrtf(a.var[c] + a.eps)), a.beta[c]);
-                g = o > 0.f ? g : g * a.alpha;
-            }
+            BnCoef k = bn_coef(a.mean, a.var, a.eps, c, false);
+            bn_coef_scale(k, a.gamma, c, false);
+            if (resign) k.b[0] = a.beta[c];
+            if (a.training) bn_coef_sums(k, a.dgamma, a.dbeta, invP, c, false);
+            const float g = bn_gated(a.dout[i], a.out, (a.alpha >= 0.f && a.out) ? a.out[i] : 0.f, a.x[i], k, 0, a.alpha);
+            const float r = bn_bwd_elem(a, k, 0, a.x[i], g, (uint32_t)i, dkey);
             if (a.dshortcut) {
                 const int cs = c - cpad;
                 if (cs >= 0 && cs < a.Cs) a.dshortcut[row * a.Cs + cs] = g;
             }
-            float rs = 1.0f / sqrtf(a.var[c] + a.eps);
-            float r;
-            if (a.training) {
-                float xh = (a.x[i] - a.mean[c]) * rs;
-                r = (a.gamma[c] * rs) * fmaf(-xh, a.dgamma[c] * invP, g - a.dbeta[c] * invP);
-            } else {
-                r = a.gamma[c] * rs * g;
-            }
-            if (a.do_drop) r = pnp_drop_keep((uint32_t)i, dkey, a.drop_thresh) ? r / a.drop_keep : 0.f;
             if (a.dx) a.dx[i] = r;
             if (a.dxh) a.dxh[i] = (__bf16)r;
         }
@@ -1264,7 +1132,7 @@ extern "C" {
 
 size_t pnp_bn_workspace_bytes(int64_t P, int32_t C) {
     int nblk, rpb;
-    colreduce_plan(P, C, &nblk, &rpb);
+    colreduce_plan(P, &nblk, &rpb);
     return (size_t)nblk * 2 * C * sizeof(float);
 }
 

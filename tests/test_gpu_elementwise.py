@@ -119,19 +119,47 @@ def test_bn_reductions_with_long_partial_lists(dev, P, C):
     assert bool(torch.isfinite(dx).all())
 
 
-def test_one_launch_combine_rearms_its_tickets(dev):
-    """round 5 (opt-in, PNP_BN_ONE_LAUNCH=1 — off by default: slower, profiles/r05_bn_one_launch_ab.txt): the column reductions sum their
-    partial rows inside the reduction launch (last workgroup of a slab, then last slab; tickets in a library-owned counter buffer that
-    every launch leaves zeroed).  In a process of its own with the switch on (the library reads it once): 640 launches of mixed shapes —
-    more than the buffer has slots — must each finish (outputs pre-poisoned with NaN) with bit-identical results per shape and the
-    float64 statistics: a counter left armed would make a later launch on its slot finish early (a wrong sum) or never (NaN)"""
-    import os
-    import subprocess
-    import sys
-    env = dict(os.environ, PNP_BN_ONE_LAUNCH="1")
-    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "bn_ticket_worker.py")], env=env,
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "TICKETS OK" in r.stdout, (r.stdout[-2000:], r.stderr[-2000:])
+def test_bn_reductions_interleaved_on_one_workspace(dev):
+    """pnp_bn_stats and pnp_bn_bwd_reduce (the activation's sign recomputed from x) through the C ABI, three rounds over four shapes that
+    share ONE workspace buffer: 625 / 256 / 5 / 1024 partial rows, so two lists are compacted in place and two are not, and every launch
+    finds the buffer as another shape left it.  Outputs are pre-poisoned with NaN and must come out finite, bit-identical per shape in
+    every round, and in the first round equal to the float64 sums of the same tensors (the sign taken from the device's own mean and
+    variance, through bn_apply's output)"""
+    import ctypes
+    K, L = pkg("kernels"), pkg("_lib")
+    lib = L.load()
+    rng = np.random.default_rng(9)
+    shapes = [(40000, 512), (16384, 64), (300, 32), (65536, 128)]
+    data, first = {}, {}
+    for (P, C) in shapes:
+        x = torch.from_numpy((rng.standard_normal((P, C)) + 0.3).astype(np.float32)).to(dev)
+        d = torch.from_numpy(rng.standard_normal((P, C)).astype(np.float32)).to(dev)
+        data[(P, C)] = (x, d, torch.ones(C, device=dev), torch.zeros(C, device=dev))
+    ws = torch.empty(max(lib.pnp_bn_workspace_bytes(P, C) for P, C in shapes), dtype=torch.uint8, device=dev)
+    wsp = ctypes.c_void_p(ws.data_ptr())
+    for rnd in range(3):
+        for (P, C) in shapes:
+            x, d, gamma, beta = data[(P, C)]
+            mean, var, dg, db = (torch.full((C,), float("nan"), device=dev) for _ in range(4))
+            L.check(lib.pnp_bn_stats(K._p(x), K._p(mean), K._p(var), P, C, wsp, ws.numel(), K._stream()), "pnp_bn_stats")
+            L.check(lib.pnp_bn_bwd_reduce(K._p(d), None, K._p(x), K._p(mean), K._p(var), K._p(gamma), K._p(beta), K._p(dg), K._p(db), P, C, 1e-3, 0.2,
+                                          wsp, ws.numel(), K._stream()), "pnp_bn_bwd_reduce")
+            got = torch.stack([mean, var, dg, db])
+            assert bool(torch.isfinite(got).all()), (rnd, P, C)
+            if (P, C) in first:
+                assert torch.equal(got, first[(P, C)]), (rnd, P, C)
+                continue
+            first[(P, C)] = got
+            x64 = x.double()
+            e_mean, e_var = float((mean.double() - x64.mean(0)).abs().max()), float((var.double() - x64.var(0, unbiased=False)).abs().max())
+            out = K.bn_apply(x.view(1, 1, P, C), mean, var, gamma, beta, None, 1e-3, 0.2).view(P, C)
+            g = torch.where(out > 0, d, d * 0.2).double()
+            xh = (x64 - mean.double()) / torch.sqrt(var.double() + 1e-3)
+            db64, dg64 = g.sum(0), (g * xh).sum(0)
+            e_db, e_dg = float((db.double() - db64).abs().max() / db64.abs().max()), float((dg.double() - dg64).abs().max() / dg64.abs().max())
+            print("bn interleaved P=%d C=%d: mean %.2e var %.2e dbeta %.2e dgamma %.2e" % (P, C, e_mean, e_var, e_db, e_dg))
+            assert e_mean < 1e-6 and e_var < 1e-5, (P, C, e_mean, e_var)
+            assert e_db < 1e-4 and e_dg < 1e-4, (P, C, e_db, e_dg)
 
 
 def test_bn_statistics_of_an_overflowing_tensor_stay_infinite_not_nan(dev):
