@@ -870,20 +870,11 @@ class Trainer(object):
     def predict_volumes(self, nii_list, output_path, label_list=None, ensemble=None, tiles=None, tile_overlap=0.25, **options):
         """volume_predict.predict_volumes with this trainer's net (no counterpart in the reference): every image ->
         <output_path>/pred_<basename>, a uint8 label volume on the image's own grid with its affine; with label_list also the
-        dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  options: volume_predict.segment_volume's (edge, crop [a box, or "body" /
-        ("body", margin): the label-free body crop of DESIGN.md §24], axis,
-        flip_correction, batch_size [default: the net's], percentile, out_size; tta, prob, entropy: DESIGN.md §15, which also write prob_* /
-        entropy_* files; keep_largest, component_stats: the connected-component filter of DESIGN.md §16; fill_holes, hole_stats: the hole filling of DESIGN.md §26;
-        sample_mm: the millimetre grid of DESIGN.md §17, with each file's voxel size read from its affine; prefilter: the anti-alias prefilter of DESIGN.md §19;
-        tiles, tile_overlap: with sample_mm, overlapping planes that cover the whole crop box, blended by pnp_paste_tiles: DESIGN.md §20;
-        axes, axis_weights: multi-planar fusion, one prediction per listed slicing axis fused by pnp_fuse_views: DESIGN.md §21).  ensemble: further nets of this class, averaged with this trainer's.  Returns the pred_* paths.  test_eval is untouched."""
+        dense_pred_* / gth_dense_pred_* pair of `evaluate --pred-dir`.  volume_predict.trainer_predict_volumes with adapted_logits (the CT
+        path): see there and volume_predict.segment_volume for ensemble and the options.  Returns the pred_* paths.  test_eval is untouched."""
         from . import volume_predict as vp
-        options.setdefault("batch_size", self.net.batch_size)
-        if tiles is not None:              # entered only when given: without it segment_volume takes the path it took before
-            options.update(tiles=tiles, tile_overlap=tile_overlap)
-        fn = vp.adapted_logits(self.net) if not ensemble else [vp.adapted_logits(n) for n in [self.net] + list(ensemble)]
-        return vp.predict_volumes(fn, nii_list, output_path, label_list=label_list, num_cls=self.num_cls,
-                                  device=self.net.device, **options)
+        return vp.trainer_predict_volumes(self, vp.adapted_logits, nii_list, output_path, label_list=label_list, ensemble=ensemble, tiles=tiles,
+                                          tile_overlap=tile_overlap, **options)
 
     def test_model(self, this_model, output_path):
         """adversarial.py:1097-1108: restore a checkpoint (.npz of this package), then test_eval"""

@@ -4,10 +4,15 @@ truth, predicts every frame and keeps the volume on the device from upload to th
 
   segment_volume(logits_fn, image, ...)   one volume: orientation and crop like volume_source.prepare_pair, pnp_volume_preprocess, then per
                                           batch of ascending frames the gather (pnp_aug_slices with the un-augmented compose_matrix map),
-                                          logits_fn, and pnp_paste_labels with the inverse map straight into the file's array order
+                                          logits_fn, and pnp_paste_labels with the inverse map straight into the file's array order.
+                                          It composes the three below, which tests and tools read as well:
+  parse_request(n_callables, ...)         the options, checked once: everything that needs no image (host)
+  plan_view(request, shape, axis, box, spacing)   the geometry of one view: layout, maps, member order, frames, coverage (host, numpy only)
+  run_view(plan, fns, volume, out, ...)   the device work of one view from its plan
   invert_matrix(m)                        the inverse of a compose_matrix map: source voxel (x, y) -> output-plane coordinates
   segmenter_logits / adapted_logits       the logits_fn of source_segmenter.Full_DRN and of the CT path of adversarial.Full_DRN
-  predict_volumes(...)                    files in, pred_<basename> files out (what both trainers' predict_volumes call)
+  predict_volumes(...)                    files in, pred_<basename> files out
+  trainer_predict_volumes(...)            the body of both trainers' predict_volumes
 
 The label of a voxel is the argmax of the bilinearly interpolated LOGITS (not probabilities): no exp, and for an identity map exactly
 argmax(logits).
@@ -17,9 +22,8 @@ segment_volume gathers once per distinct map, runs one forward per member and ma
 interpolates every member's logits through that member's own inverse map, averages the softmax and writes the label, the mean
 probabilities and the normalised entropy in the file's array order.  With the defaults nothing of this is reached.
 
-Hole filling (opt-in): fill_holes= runs components.fill_holes on the finished label volume, on the device, after keep_largest.
-Connected-component filtering (opt-in): keep_largest= runs components.keep_largest on the finished label volume, on the
-device, before it is returned.
+Post-processing (opt-in): keep_largest= runs components.keep_largest and then fill_holes= components.fill_holes on the
+finished label volume, on the device, before it is returned.
 
 Millimetre grid (opt-in): with sample_mm= the plane has a fixed pixel size and is centred on the (cropped) volume, the
 outer channels lie frame_mm from the centre frame (pnp_aug_slices_z; its clamp is the edge replication, so nothing is padded) and the
@@ -32,9 +36,9 @@ Tiles (opt-in, needs sample_mm): with tiles= the crop box is cov
 grid (tile_plan), every plane is predicted, and ONE pnp_paste_tiles launch per batch blends them over their union with a window that
 trusts a plane's centre more than its border.  Without the option nothing of this is reached.
 
-Multi-planar fusion (opt-in): with axes= the scan is predicted once per listed slicing axis by the single-axis path above
-(every other option applies to each view), and ONE pnp_fuse_views launch averages the views' probability volumes over the views that
-cover a voxel (check_axes, view_box, fuse_views).  Without the option nothing of this is reached.
+Multi-planar fusion (opt-in): with axes= the scan gets one plan and one run per listed slicing axis (every other option
+applies to each view), and ONE pnp_fuse_views launch averages the views' probability volumes over the views that cover a voxel
+(check_axes, view_box, fuse_views).  Without the option nothing of this is reached.
 """
 import collections
 import logging
@@ -270,110 +274,40 @@ def ensemble_members(logits_fn, tta, limit=MAX_MEMBERS):
     return fns, entries
 
 
-def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
-                   out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None,
-                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25, axes=None, axis_weights=None, crop_box=None,
-                   fill_holes=None, hole_stats=None):
-    """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's).
-      logits_fn  x [B, H, W, 3] -> logits [B, H, W, num_cls] (device tensors; segmenter_logits / adapted_logits); a list of them is a
-                 checkpoint ensemble
-      tta        None, "default" (DEFAULT_TTA) or a list of dicts of compose_matrix's keywords: the views of every slice
-      prob, entropy   also return the mean class probabilities [num_cls, *image.shape] / the entropy normalised by log(num_cls) (float32)
-    With a list of callables, tta, prob or entropy the result is Ensemble(label, prob, entropy) (a field not asked for is None; outside the
-    crop box all three are 0) and every batch ends in one pnp_paste_ensemble launch; with the defaults it is the label
-    tensor alone, through pnp_paste_labels.
-      label      optional ground truth of the same shape: only its bounding box is used (crop = a margin in voxels)
-      crop       None, a margin around the label's bounding box, or a box ((x0, x1), (y0, y1), (z0, z1)) in slicing order; outside it: 0.
-                 "body" or ("body", margin): the label-free body crop of DESIGN.md §24 — the prepared full volume is uploaded,
-                 body.body_box finds the patient's bounding box on the device (two host synchronisations), the crop is taken on the device
-                 and everything after that is the path of an explicit box: the result equals crop=<that box> bit for bit.  With axes the
-                 box is found once, in the default axis's order, and handed to the views through view_box.
-      crop_box   optional list: the box used, ((x0, x1), (y0, y1), (z0, z1)) in slicing order (with axes: of the default axis), is appended
-      keep_largest   None, an int K (keep the K largest 3-D components of every class) or a dict of components.keep_largest's keywords
-                 (keep, min_size, connectivity, classes): applied in place to the finished label volume on the device.  On
-                 the ensemble path only Ensemble.label is filtered: prob and entropy are returned as computed, also where the label became 0.
-      component_stats   optional list: the filter's int64 [num_cls, 4] stats tensor is appended to it
-      fill_holes     None / False, True (holes of any size), a positive int (the largest hole filled, in voxels) or a dict of
-                 components.fill_holes' keywords (max_size, classes): every enclosed background hole of the finished label volume takes
-                 the class that touches it most, in place on the device, after keep_largest.  On the ensemble and tiles
-                 paths only Ensemble.label changes; with axes it runs once, on the fused label.
-      hole_stats     optional list: the fill's int64 [num_cls, 4] stats tensor is appended to it
-      sample_mm  None, or a number / (pi_mm, pj_mm, frame_mm): sample on that millimetre grid.  Needs `spacing`, the voxel
-                 size in mm per ARRAY axis of `image` (surface.spacing_of(affine)).  The plane is centred on the crop box; a voxel column
-                 outside its field of view (for any member) stays 0 in label, prob and entropy, like outside the crop box; tta
-                 entries' translate is in mm; the edge frames are replicated by the gather's clamp, nothing is padded
-      fov_stats  optional list: with sample_mm the share of the box's voxel columns inside the field of view is appended (coverage)
-      prefilter  None / "off", "auto" or sigmas in voxels (a number or (sx, sy, sz), slicing order): the anti-alias prefilter of DESIGN.md
-                 §19.  The normalised box is smoothed in place (pnp_volume_smooth) after pnp_volume_preprocess and before the edge frames
-                 are padded (the padding copies smoothed frames), with volume_source.prefilter_sigmas' sigmas from the box extents,
-                 out_size, spacing and sample_mm; tta scales are ignored.  "auto" with spacing but without sample_mm is the plain resize's
-                 rule.  The fill stays the unsmoothed minimum.  Use the setting the network was trained with.
-      tiles      None, "auto" or (ni, nj): cover the crop box with ni x nj overlapping planes of the millimetre grid (needs
-                 sample_mm) instead of the one centred plane.  tile_plan places them (tile_overlap in [0, 0.5]: the least share of a plane
-                 that its neighbour repeats); every batch gathers once per (tile, view), a tile's offset added in mm to the entry's
-                 translate, runs every callable on every gather and ends in ONE pnp_paste_tiles launch, which writes the columns that at
-                 least one member covers and blends the covering members' softmax with a window that rises over the planes' overlap.
-                 Members = callables x tiles x tta entries (in that order, callable-major), at most 64.  The result is the Ensemble tuple
-                 with the ensemble path's rules for prob, entropy, keep_largest and the short last batch; fov_stats gets the share of the
-                 columns that at least one member covers.  ALL members' logits of a batch are alive at once: members x 4 B H W num_cls
-                 bytes — 21 MB per member at the defaults, 1.3 GB at the limit of 64 members — beside one forward's activations.  On an
-                 MI355X (288 GB) no member count needs a smaller batch_size; where that product nears the free memory, halve batch_size.
-      axes       None, or a sequence of distinct slicing axes from 0, 1, 2 (check_axes): multi-planar fusion.  `axis` must
-                 then be left at its default.  Every listed axis is predicted by the single-axis path with prob=True and every other option
-                 unchanged (tta, lists of callables, tiles, sample_mm, prefilter, edge, batch_size; the member limits hold per view), and
-                 ONE pnp_fuse_views launch averages the views into the first view's probability buffer: per voxel over the views that
-                 wrote it (a view leaves 0 outside its field of view, on the edge frames it skips and outside the crop box), weighted by
-                 axis_weights (None: all 1).  The result is always the Ensemble tuple (prob / entropy None unless asked for);
-                 keep_largest runs once, on the fused label, never on a view; fov_stats gets one share per view, in axes order.  crop: None
-                 and a margin work as they are (a label's bounding box is the same voxel set in every orientation); an explicit box is
-                 given in the slicing order of the default axis (2) and re-expressed per view (view_box).  sample_mm and spacing keep their
-                 meaning per view (slicing_order moves each view's axis last): with an anisotropic scan a single number — an isotropic
-                 grid — is the sensible sample_mm.  Peak memory is len(axes) probability volumes: 262 MB per view at 256 x 256 x 200 x 5.
-      edge       "replicate": the normalised volume is padded with a copy of its first and last frame, every frame is predicted;
-                 "skip": frames 1 .. Z - 2 only (the reference's frame set), the two edge frames stay 0
-    Frames run in ascending order, batch_size at a time; the last, short batch repeats its last frame and pastes nb < B slices.  Nothing
-    synchronises between batches; the gather's error counter is read once at the end."""
-    import torch
-    from . import kernels as K
+Request = collections.namedtuple("Request", (
+    "edge", "B", "H", "W", "num_cls", "percentile", "flip_correction", "axis", "crop", "body_margin", "sample_mm", "prefilter", "tiles",
+    "tile_overlap", "entries", "n_callables", "member_limit", "ensemble", "prob", "entropy", "keep_largest", "fill_holes", "axes", "axis_weights"))
+ViewPlan = collections.namedtuple("ViewPlan", (
+    "request", "axis", "box", "origin", "strides", "dims", "vox", "geom", "counts", "offsets", "ramp", "entries", "maps", "invs", "kind", "fov",
+    "coverage", "frames", "padded", "min_frames", "rec_dtype", "dz", "sigmas", "taps", "members", "logits_bytes"))
+
+
+def parse_request(n_callables=None, *, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98, out_size=(256, 256),
+                  num_cls=5, tta=None, prob=False, entropy=False, keep_largest=None, spacing=None, sample_mm=None, prefilter=None, tiles=None,
+                  tile_overlap=0.25, axes=None, axis_weights=None, fill_holes=None):
+    """segment_volume's options, checked once -> Request: everything about a prediction that needs no image and no device.  n_callables:
+    None for a bare logits_fn, the length of a list of them (a list, also of one, is a checkpoint ensemble).  Every ValueError an option can
+    earn on its own is raised here, in this order: edge, keep_largest, fill_holes, crop, axes / axis_weights, batch_size, sample_mm,
+    prefilter, spacing, tiles / tile_overlap, the members.
+      ensemble      a list of callables, tta, prob, entropy, tiles or axes: the result is the Ensemble tuple
+      entries       tta_entries(tta): the views of every slice; members = callables x entries, at most member_limit (MAX_MEMBERS, with
+                    tiles MAX_TILE_MEMBERS and then counted again with the planes, by plan_view)
+      keep_largest, fill_holes   components.parse_option / parse_fill_option's keywords, or None
+      body_margin   the margin of crop="body" / ("body", margin), None for every other crop
+      sample_mm     check_sample_mm's triple or None; it needs `spacing`, which is checked here and ordered per view by plan_view
+      axes, axis_weights   check_axes' tuples, or None: `axis` must then be left at its default"""
+    from . import components
     if edge not in EDGES:
         raise ValueError("edge must be one of %s, got %r" % (EDGES, edge))
-    from . import components
     post = components.parse_option(keep_largest, num_cls)
     holes = components.parse_fill_option(fill_holes, num_cls)
-    body_margin = _body_margin(crop)                            # None unless crop is "body" / ("body", margin)
+    body_margin = _body_margin(crop)
     if axes is not None or axis_weights is not None:
         if axes is None:
             raise ValueError("axis_weights %r goes with axes" % (axis_weights,))
         if axis != 2:
             raise ValueError("axes=%r and axis=%r exclude each other: leave axis at its default" % (axes, axis))
         axes, axis_weights = check_axes(axes, axis_weights)
-        if body_margin is not None:                             # found once, in the slicing order of axis 2; the views get it as a box
-            full = _upload_prepared(image, flip_correction, 2, device)
-            from . import body
-            crop = body.body_box(full, percentile=int(percentile), margin=body_margin)
-            del full
-        explicit = crop is not None and not isinstance(crop, (int, np.integer))          # a box, in the slicing order of axis 2
-        if crop_box is not None:
-            if explicit:
-                crop_box.append(tuple((int(a), int(b)) for a, b in crop))
-            else:
-                lab2 = None if label is None else prepare_pair(image, label, flip_correction, 2, None)[1]
-                crop_box.append(_box_of(crop, lab2, file_layout(np.shape(image), flip_correction, 2)[2]))
-        views = []
-        for a in axes:
-            one = segment_volume(logits_fn, image, label=label, flip_correction=flip_correction, axis=a,
-                                 crop=view_box(crop, a) if explicit else crop, edge=edge, batch_size=batch_size, percentile=percentile,
-                                 out_size=out_size, num_cls=num_cls, device=device, tta=tta, prob=True, spacing=spacing, sample_mm=sample_mm,
-                                 fov_stats=fov_stats, prefilter=prefilter, tiles=tiles, tile_overlap=tile_overlap)
-            views.append(one.prob)
-            if len(views) == 1:
-                fused = one.label                       # the first view's label buffer takes the fused labels
-            del one
-        _, out_p, out_e = K.fuse_views(views, axis_weights, label=fused, prob=views[0] if prob else None, entropy=bool(entropy))
-        del views
-        _filter_components(fused, post, num_cls, component_stats)
-        _fill_holes(fused, holes, num_cls, hole_stats)
-        return Ensemble(fused, out_p, out_e)
     B, H, W = int(batch_size), int(out_size[0]), int(out_size[1])
     if B < 1:
         raise ValueError("batch_size must be at least 1")
@@ -382,114 +316,217 @@ def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2
     if mm is not None:
         if spacing is None:
             raise ValueError("sample_mm needs spacing: the voxel size in mm per array axis of the image (surface.spacing_of(affine))")
-        vox = slicing_order(spacing, axis, "spacing")          # as prepare_pair moves `axis` last
-        geom = {"spacing_xy": vox[:2], "pixel_mm": mm[:2]}
-    else:
-        geom = {}
+        slicing_order(spacing, axis, "spacing")
     tiles = check_tiles(tiles)
     if tiles is not None:
         if mm is None:
             raise ValueError("tiles needs sample_mm: the planes of a tiled prediction share one millimetre grid")
         if not 0.0 <= float(tile_overlap) <= 0.5:
             raise ValueError("tile overlap %r outside [0, 0.5]" % (tile_overlap,))
-    ensemble = tiles is not None or isinstance(logits_fn, (list, tuple)) or tta is not None or bool(prob) or bool(entropy)
-    if ensemble:
-        fns, entries = ensemble_members(logits_fn, tta, MAX_MEMBERS if tiles is None else MAX_TILE_MEMBERS)
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.PnpError("segment_volume: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (device,))
-    image = np.asarray(image)
-    img, lab = prepare_pair(image, np.zeros(image.shape, np.uint8) if label is None else label, flip_correction, axis, None)
-    full = None
-    if body_margin is not None:
-        from . import body
-        full = torch.from_numpy(img).to(device)
-        box = body.body_box(full, percentile=int(percentile), margin=body_margin)
-    else:
-        box = _box_of(crop, None if label is None else lab, img.shape)
-    if crop_box is not None:
-        crop_box.append(box)
-    origin, strides, (X, Y, Z) = file_layout(image.shape, flip_correction, axis, box)
-    if edge == "skip" and Z < 3:
-        raise ValueError("edge='skip' needs at least 3 frames, the box has %d" % Z)
-    ramp = None
-    if tiles is not None:                               # the plan, before any device work: tile-major, then view
-        extent, plane_mm = (X * vox[0], Y * vox[1]), (H * mm[0], W * mm[1])
-        offsets, counts = tile_plan(extent, plane_mm, tiles, tile_overlap)
-        if len(fns) * len(offsets) * len(entries) > MAX_TILE_MEMBERS:
-            raise ValueError("%d callables x %d x %d tiles x %d tta entries = %d members, at most %d" % (
-                len(fns), counts[0], counts[1], len(entries), len(fns) * len(offsets) * len(entries), MAX_TILE_MEMBERS))
-        ramp = tile_ramp(extent, plane_mm, counts, mm[:2])
-        shifted = []
-        for ti, tj in offsets:
-            for e in entries:
-                t = e.get("translate", (0.0, 0.0))
-                shifted.append(dict(e, translate=(t[0] + ti, t[1] + tj)))
-        entries = shifted
-    out = torch.zeros(tuple(image.shape), dtype=torch.uint8, device=device)
+    ensemble = tiles is not None or n_callables is not None or tta is not None or bool(prob) or bool(entropy) or axes is not None
+    limit = MAX_MEMBERS if tiles is None else MAX_TILE_MEMBERS
+    n = 1 if n_callables is None else int(n_callables)
+    entries = ensemble_members([None] * n, tta, limit)[1]                 # the rule counts the callables: it does not call them
+    return Request(edge, B, H, W, int(num_cls), percentile, flip_correction, axis, crop, body_margin, mm, pre, tiles, tile_overlap, tuple(entries), n,
+                   limit, ensemble, bool(prob), bool(entropy), post, holes, axes, axis_weights)
 
-    if full is not None:                                # the body crop, taken on the device
-        v = full[tuple(slice(a, b) for a, b in box)].contiguous()
-        del full
-    else:
-        v = torch.from_numpy(np.ascontiguousarray(img[tuple(slice(a, b) for a, b in box)])).to(device)
-    _, stats = K.volume_preprocess(v, int(percentile), out=v)
-    fill = float(stats[3].item())                       # the one read before the loop: the fill enters the gather's descriptor table
-    if pre is not None:
-        taps = [gaussian_weights(s) for s in prefilter_sigmas(pre, (X, Y, Z), (H, W), vox if mm is not None else None, mm)]
-        if any(t is not None for t in taps):
-            K.volume_smooth(v, taps, out=v)
-            K.drop_workspace("smooth")
+
+def _frozen(a):
+    a.setflags(write=False)
+    return a
+
+
+def plan_view(request, image_shape, axis, box, spacing=None):
+    """the host geometry of one view — `request` for the file array `image_shape` sliced along `axis`, inside `box` (resolved: _box_of's or
+    body.body_box's, in the slicing order of `axis`), `spacing` per array axis — as an immutable ViewPlan.  Pure numpy: nothing here
+    touches a device, and the ValueErrors that need the box (edge='skip' on fewer than 3 frames, tile counts that cannot cover it, too many
+    members with the planes counted) are raised here.
+      origin, strides, dims   file_layout's: where voxel (x, y, z) of the box lies in the file's array; dims = (X, Y, Z)
+      vox, geom     with sample_mm (DESIGN.md §17) the voxel size in slicing order and compose_matrix's spacing_xy / pixel_mm; None / {}
+      counts, offsets, ramp   with tiles tile_plan's planes and tile_ramp's rise; None otherwise
+      entries       the request's tta entries; with tiles one per (tile, view), tile-major, the tile's offset added in mm to `translate`
+      maps, invs    compose_matrix of every entry: one gather each; invs = [invert_matrix(m) for m in maps] * n_callables, one per member,
+                    callable-major (then tile, then view)
+      kind          the paste: "labels" (pnp_paste_labels: the maximum of the interpolated logits), "ensemble" (pnp_paste_ensemble: of the
+                    mean softmax) or "tiles" (pnp_paste_tiles: of the window-weighted softmax); fov: only the voxel columns
+                    inside the planes' field of view are written (with sample_mm)
+      coverage      with sample_mm the share of the box's voxel columns that the paste writes: inside every member's field of view, with
+                    tiles inside at least one; None otherwise
+      frames        (first, count, shift): centre frames first .. first + count - 1 of the gathered volume, pasted `shift` frames further.
+                    edge="skip" leaves the two edge frames out (the reference's frame set); edge="replicate" predicts every frame, through
+                    the gather's clamp with sample_mm and otherwise through a copy of the first and the last frame (`padded`)
+      min_frames, rec_dtype, dz   what VolumeSet and the gather's records need; dz = frame_mm in voxels with sample_mm
+      sigmas, taps  with prefilter prefilter_sigmas' sigmas for this box and their gaussian_weights (taps is None when no
+                    axis is filtered): the normalised box is smoothed before the edge frames are copied; tta scales are ignored
+      members, logits_bytes   len(invs), and the bytes of member logits alive per batch: members x 4 B H W num_cls — 21 MB per member at
+                    the defaults, 1.3 GB at 64 members; where that nears the free memory, halve batch_size"""
+    r = request
+    H, W, mm = r.H, r.W, r.sample_mm
+    box = tuple((int(a), int(b)) for a, b in box)
+    origin, strides, (X, Y, Z) = file_layout(image_shape, r.flip_correction, axis, box)
+    if r.edge == "skip" and Z < 3:
+        raise ValueError("edge='skip' needs at least 3 frames, the box has %d" % Z)
+    vox, geom = None, {}
     if mm is not None:
-        first, count, shift = (0, Z, 0) if edge == "replicate" else (1, Z - 2, 0)       # pnp_aug_slices_z clamps: its own replication
-    elif edge == "replicate":
-        v = torch.cat([v[:, :, :1], v, v[:, :, -1:]], dim=2).contiguous()          # statistics: of the unpadded volume, above
-        first, count, shift = 1, Z, -1                  # centre frames 1 .. Z of the padded volume are output frames 0 .. Z - 1
-    else:
-        first, count, shift = 1, Z - 2, 0
-    vs = VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=device)], ["volume"], [fill], percentile,
-                               min_frames=3 if mm is None else 1)
-    src = AugmentedSliceSource(vs, B, out_size=(H, W), augment=None, num_cls=num_cls, sample_mm=mm)
-    rec = np.zeros(B, dtype=SAMPLE_DTYPE if mm is None else SAMPLE_Z_DTYPE)
-    if mm is not None:
-        rec["dz"] = np.float32(mm[2] / vox[2])
+        vox = slicing_order(spacing, axis, "spacing")          # as prepare_pair moves `axis` last
+        geom = {"spacing_xy": vox[:2], "pixel_mm": mm[:2]}
+    counts = offsets = ramp = None
+    entries = r.entries
+    if r.tiles is not None:
+        extent, plane_mm = (X * vox[0], Y * vox[1]), (H * mm[0], W * mm[1])
+        offsets, counts = tile_plan(extent, plane_mm, r.tiles, r.tile_overlap)
+        if r.n_callables * len(offsets) * len(entries) > MAX_TILE_MEMBERS:
+            raise ValueError("%d callables x %d x %d tiles x %d tta entries = %d members, at most %d" % (
+                r.n_callables, counts[0], counts[1], len(entries), r.n_callables * len(offsets) * len(entries), MAX_TILE_MEMBERS))
+        ramp, offsets = tile_ramp(extent, plane_mm, counts, mm[:2]), tuple(offsets)
+        at = lambda e: e.get("translate", (0.0, 0.0))
+        entries = tuple(dict(e, translate=(at(e)[0] + ti, at(e)[1] + tj)) for ti, tj in offsets for e in entries)
+    maps = tuple(_frozen(compose_matrix((X, Y), (H, W), **e, **geom)) for e in entries)
+    invs = tuple(_frozen(invert_matrix(m)) for m in maps) * r.n_callables
     fov = mm is not None
-    # one batch loop for every path: the default one is one callable, one map and pnp_paste_labels[_fov] (the maximum of the interpolated
-    # logits, not the M = 1 ensemble kernel's maximum of their softmax)
-    if ensemble:
-        maps = [compose_matrix((X, Y), (H, W), **e, **geom) for e in entries]
-    else:
-        fns, maps = [logits_fn], [compose_matrix((X, Y), (H, W), **geom)]
-    invs = [invert_matrix(m) for m in maps] * len(fns)                      # callable-major, like the members
-    if fov and fov_stats is not None:
-        fov_stats.append(coverage(invs, X, Y, H, W, mode="all" if ramp is None else "any"))
-    out_p = torch.zeros((int(num_cls),) + tuple(image.shape), dtype=torch.float32, device=device) if prob else None
-    out_e = torch.zeros(tuple(image.shape), dtype=torch.float32, device=device) if entropy else None
-    if not ensemble:
-        paste = lambda members, nb, z: K.paste_labels(members[0], nb, z, invs[0], (X, Y), out, origin, strides, fov=fov)
-    elif ramp is not None:
-        paste = lambda members, nb, z: K.paste_tiles(members, nb, z, invs, ramp, (X, Y), out, origin, strides, prob=out_p, entropy=out_e)
-    else:
-        paste = lambda members, nb, z: K.paste_ensemble(members, nb, z, invs, (X, Y), out, origin, strides, prob=out_p, entropy=out_e, fov=fov)
+    sigmas = taps = None
+    if r.prefilter is not None:
+        sigmas = prefilter_sigmas(r.prefilter, (X, Y, Z), (H, W), vox, mm)
+        taps = tuple(gaussian_weights(s) for s in sigmas)
+        taps = taps if any(t is not None for t in taps) else None
+    # without sample_mm and with edge="replicate", centre frames 1 .. Z of the padded volume are output frames 0 .. Z - 1
+    frames = (1, Z - 2, 0) if r.edge == "skip" else (0, Z, 0) if fov else (1, Z, -1)
+    return ViewPlan(request=r, axis=axis, box=box, origin=origin, strides=strides, dims=(X, Y, Z), vox=vox, geom=geom, counts=counts, offsets=offsets,
+                    ramp=ramp, entries=entries, maps=maps, invs=invs, kind="tiles" if ramp is not None else "ensemble" if r.ensemble else "labels",
+                    fov=fov, coverage=coverage(invs, X, Y, H, W, mode="all" if ramp is None else "any") if fov else None, frames=frames,
+                    padded=not fov and r.edge == "replicate", min_frames=1 if fov else 3, rec_dtype=SAMPLE_Z_DTYPE if fov else SAMPLE_DTYPE,
+                    dz=np.float32(mm[2] / vox[2]) if fov else None, sigmas=sigmas, taps=taps, members=len(invs),
+                    logits_bytes=len(invs) * 4 * r.B * H * W * r.num_cls)
+
+
+def plan_views(request, image_shape, box, spacing=None):
+    """one ViewPlan per view: for `axis` alone, or per entry of `axes`, which get the box — given in the slicing order of
+    the default axis — re-expressed in their own order by view_box"""
+    if request.axes is None:
+        return [plan_view(request, image_shape, request.axis, box, spacing)]
+    return [plan_view(request, image_shape, a, view_box(box, a), spacing) for a in request.axes]
+
+
+def run_view(plan, fns, volume, out, out_p=None, out_e=None):
+    """the device work of one view: `volume`, the raw float32 box [X, Y, Z] on the device, is normalised in place (pnp_volume_preprocess),
+    smoothed (plan.taps) and padded (plan.padded); then per batch of ascending frames one gather per map of the plan (pnp_aug_slices[_z]),
+    one forward per callable and gather, and ONE paste of all members' logits through their inverse maps into out / out_p / out_e, which lie
+    in the file's array order.  The last, short batch repeats its last frame and pastes nb < B slices.  Nothing synchronises between
+    batches; the fill is read once before the loop, the gather's error counter once at the end.  Geometry and options are the plan's:
+    nothing is computed or checked here but the shape of what a logits_fn returns."""
+    import torch
+    from . import kernels as K
+    r = plan.request
+    B, H, W, num_cls, v, xy = r.B, r.H, r.W, r.num_cls, volume, plan.dims[:2]
+    _, stats = K.volume_preprocess(v, int(r.percentile), out=v)
+    fill = float(stats[3].item())                       # the one read before the loop: the fill enters the gather's descriptor table
+    if plan.taps is not None:
+        K.volume_smooth(v, list(plan.taps), out=v)
+        K.drop_workspace("smooth")
+    if plan.padded:
+        v = torch.cat([v[:, :, :1], v, v[:, :, -1:]], dim=2).contiguous()          # statistics: of the unpadded volume, above
+    vs = VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=v.device)], ["volume"], [fill], r.percentile,
+                               min_frames=plan.min_frames)
+    src = AugmentedSliceSource(vs, B, out_size=(H, W), augment=None, num_cls=num_cls, sample_mm=r.sample_mm)
+    rec = np.zeros(B, dtype=plan.rec_dtype)
+    if plan.dz is not None:
+        rec["dz"] = plan.dz
+    first, count, shift = plan.frames
     for k in range(0, count, B):
         nb = min(B, count - k)
         rec["frame"] = np.minimum(first + k + np.arange(B), first + k + nb - 1)
         xs = []
-        for m in maps:                                                      # one gather per distinct map, shared by the callables
+        for m in plan.maps:                                                 # one gather per distinct map, shared by the callables
             rec["m"][:] = m
             xs.append(src.gather_records(rec, num_cls, want_onehot=False)[0])
         members = []
         for fn in fns:
             for x in xs:
                 logits = fn(x)
-                if tuple(logits.shape) != (B, H, W, int(num_cls)):
-                    raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, int(num_cls))))
+                if tuple(logits.shape) != (B, H, W, num_cls):
+                    raise ValueError("logits_fn returned %s, expected %s" % (tuple(logits.shape), (B, H, W, num_cls)))
                 members.append(logits.detach().contiguous())
-        paste(members, nb, first + k + shift)
+        z = first + k + shift
+        if plan.kind == "labels":
+            K.paste_labels(members[0], nb, z, plan.invs[0], xy, out, plan.origin, plan.strides, fov=plan.fov)
+        elif plan.kind == "tiles":
+            K.paste_tiles(members, nb, z, plan.invs, plan.ramp, xy, out, plan.origin, plan.strides, prob=out_p, entropy=out_e)
+        else:
+            K.paste_ensemble(members, nb, z, plan.invs, xy, out, plan.origin, plan.strides, prob=out_p, entropy=out_e, fov=plan.fov)
     src.close()
-    _filter_components(out, post, num_cls, component_stats)
-    _fill_holes(out, holes, num_cls, hole_stats)
-    return Ensemble(out, out_p, out_e) if ensemble else out
+
+
+def segment_volume(logits_fn, image, *, label=None, flip_correction=True, axis=2, crop=None, edge="replicate", batch_size=16, percentile=98,
+                   out_size=(256, 256), num_cls=5, device="cuda", tta=None, prob=False, entropy=False, keep_largest=None, component_stats=None,
+                   spacing=None, sample_mm=None, fov_stats=None, prefilter=None, tiles=None, tile_overlap=0.25, axes=None, axis_weights=None, crop_box=None,
+                   fill_holes=None, hole_stats=None):
+    """-> uint8 label volume of `image`'s shape and axis order, a device tensor (`.cpu().numpy()` is the caller's); with a list of
+    callables, tta, prob, entropy, tiles or axes the Ensemble(label, prob, entropy) tuple (a field not asked for is None; outside the crop
+    box and the field of view all three are 0).  The composition of the functions above, where each option's rule is written down:
+      1. parse_request   every option but the four lists, checked before the device is looked at; logits_fn: x [B, H, W, 3] -> logits
+                         [B, H, W, num_cls] (segmenter_logits / adapted_logits), or a list of them
+      2. the box         crop: None, a margin around `label`'s bounding box, a box ((x0, x1), (y0, y1), (z0, z1)) in slicing order (with
+                         axes: of the default axis), or "body" / ("body", margin): the prepared volume is uploaded whole and
+                         body.body_box finds the box on the device (two host synchronisations; the result equals crop=<that box>).
+                         crop_box: optional list, the box is appended
+      3. plan_views      one plan per view; fov_stats: optional list, with sample_mm every view's coverage is appended, in axes order
+      4. run_view        per view, on its box of the prepared volume
+      5. with axes ONE pnp_fuse_views launch averages the views' probabilities into the first view's buffers, per voxel over the views
+         that wrote it, weighted by axis_weights; peak memory is len(axes) probability volumes
+      6. components.keep_largest, 7. components.fill_holes (DESIGN.md §16, §26): once, in place on the finished (fused) label only;
+         component_stats / hole_stats: optional lists, each pass's int64 [num_cls, 4] stats tensor is appended
+    DESIGN.md §14–§26 is the long form."""
+    import torch
+    from . import kernels as K
+    is_list = isinstance(logits_fn, (list, tuple))
+    fns = list(logits_fn) if is_list else [logits_fn]
+    req = parse_request(len(fns) if is_list else None, flip_correction=flip_correction, axis=axis, crop=crop, edge=edge, batch_size=batch_size,
+                        percentile=percentile, out_size=out_size, num_cls=num_cls, tta=tta, prob=prob, entropy=entropy, keep_largest=keep_largest,
+                        spacing=spacing, sample_mm=sample_mm, prefilter=prefilter, tiles=tiles, tile_overlap=tile_overlap, axes=axes,
+                        axis_weights=axis_weights, fill_holes=fill_holes)
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.PnpError("segment_volume: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (device,))
+    image = np.asarray(image)
+    blank = np.zeros(image.shape, np.uint8)
+    img, lab = prepare_pair(image, blank if label is None else label, flip_correction, axis, None)
+    full = None
+    if req.body_margin is not None:
+        from . import body
+        full = torch.from_numpy(img).to(device)
+        box = body.body_box(full, percentile=int(percentile), margin=req.body_margin)
+    else:
+        box = _box_of(crop, None if label is None else lab, img.shape)
+    if crop_box is not None:
+        crop_box.append(box)
+    plans = plan_views(req, image.shape, box, spacing)
+    if fov_stats is not None:
+        fov_stats.extend(p.coverage for p in plans if p.coverage is not None)
+    multi, shape = req.axes is not None, tuple(image.shape)
+    labels, probs = [], []
+    for plan in plans:
+        where = tuple(slice(a, b) for a, b in plan.box)
+        labels.append(torch.zeros(shape, dtype=torch.uint8, device=device))
+        # one view's body crop is taken on the device; several views take their boxes from the host, each in its own order
+        view = full if full is not None and not multi else img if plan.axis == axis else prepare_pair(image, blank, flip_correction, plan.axis, None)[0]
+        full = None
+        v = view[where].contiguous() if torch.is_tensor(view) else torch.from_numpy(np.ascontiguousarray(view[where])).to(device)
+        del view
+        probs.append(torch.zeros((req.num_cls,) + shape, dtype=torch.float32, device=device) if req.prob or multi else None)
+        out_e = torch.zeros(shape, dtype=torch.float32, device=device) if req.entropy and not multi else None
+        run_view(plan, fns, v, labels[-1], probs[-1], out_e)
+        del v, labels[1:]
+    out, out_p = labels[0], probs[0]                        # the first view's buffers take the fused result
+    if multi:
+        _, out_p, out_e = K.fuse_views(probs, req.axis_weights, label=out, prob=out_p if req.prob else None, entropy=req.entropy)
+    del probs
+    from . import components
+    for opts, run, stats in ((req.keep_largest, components.keep_largest, component_stats), (req.fill_holes, components.fill_holes, hole_stats)):
+        if opts is not None:                                # in place, on the finished label alone: prob and entropy stay as computed
+            got = run(out, num_cls=req.num_cls, out=out, **opts)[1]
+            if stats is not None:
+                stats.append(got)
+    return Ensemble(out, out_p, out_e) if req.ensemble else out
 
 
 def _body_margin(crop):
@@ -498,36 +535,6 @@ def _body_margin(crop):
         from . import body
         return body.parse_crop(crop)[1]
     return None
-
-
-def _upload_prepared(image, flip_correction, axis, device):
-    """prepare_pair's image (flips, `axis` last, finite check) on the device, whole"""
-    import torch
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.PnpError("segment_volume: pnp kernels need a CUDA/HIP device (got %s) — there is no CPU fallback" % (device,))
-    image = np.asarray(image)
-    return torch.from_numpy(prepare_pair(image, np.zeros(image.shape, np.uint8), flip_correction, axis, None)[0]).to(device)
-
-
-def _filter_components(label, post, num_cls, component_stats):
-    """components.keep_largest on the finished label volume, in place; post: components.parse_option's keywords or None (nothing runs)"""
-    if post is None:
-        return
-    from . import components
-    _, stats = components.keep_largest(label, num_cls=num_cls, out=label, **post)
-    if component_stats is not None:
-        component_stats.append(stats)
-
-
-def _fill_holes(label, holes, num_cls, hole_stats):
-    """components.fill_holes on the finished label volume, in place; holes: components.parse_fill_option's keywords or None (nothing runs)"""
-    if holes is None:
-        return
-    from . import components
-    _, stats = components.fill_holes(label, num_cls=num_cls, out=label, **holes)
-    if hole_stats is not None:
-        hole_stats.append(stats)
 
 
 def segmenter_logits(net):
@@ -548,6 +555,17 @@ def adapted_logits(net):
         with torch.no_grad():
             return net._graph(None, x, 1.0, mr_front_bn=False, joint_bn=False, ct_front_bn=False, critics=False)["ct_logits"]
     return fn
+
+
+def trainer_predict_volumes(trainer, adapter, nii_list, output_path, label_list=None, ensemble=None, tiles=None, tile_overlap=0.25, **options):
+    """Trainer.predict_volumes of both trainers: predict_volumes with the trainer's net behind `adapter` (segmenter_logits /
+    adapted_logits), its num_cls and device, and batch_size defaulting to the net's.  ensemble: further nets of the same class, averaged
+    with the trainer's (a checkpoint ensemble).  options: segment_volume's.  Returns the pred_* paths."""
+    options.setdefault("batch_size", trainer.net.batch_size)
+    if tiles is not None:              # entered only when given: without it segment_volume takes the path it took before
+        options.update(tiles=tiles, tile_overlap=tile_overlap)
+    fn = adapter(trainer.net) if not ensemble else [adapter(n) for n in [trainer.net] + list(ensemble)]
+    return predict_volumes(fn, nii_list, output_path, label_list=label_list, num_cls=trainer.num_cls, device=trainer.net.device, **options)
 
 
 def predict_volumes(logits_fn, nii_list, output_path, label_list=None, num_cls=5, device="cuda", **options):

@@ -315,6 +315,11 @@ def test_prediction_reads_the_smoothed_volume(dev, with_mm):
     else:
         m = vs.compose_matrix((X, Y), (H, W))
         dz, vol, shift = np.float32(1.0), np.concatenate([smooth[:, :, :1], smooth, smooth[:, :, -1:]], axis=2), 1
+    # the map, the frame step, the frames and the padding stated here by hand are the ones of the plan that ran
+    plan = vp.plan_view(vp.parse_request(flip_correction=False, batch_size=B, out_size=(H, W), prefilter="auto", **opts), image.shape, 2,
+                        ((0, X), (0, Y), (0, Z)), opts.get("spacing"))
+    assert len(plan.maps) == 1 and np.array_equal(plan.maps[0], m) and plan.padded == (not with_mm) and plan.frames == (shift, Z, -shift)
+    assert (plan.dz == dz if with_mm else plan.dz is None) and (plan.taps[2] is not None) == with_mm and plan.taps[0] is not None
     sx, sy = A.coords(m, H, W)
     top = float(np.abs(norm).max())
     # the normalised volume itself is the device's float32 (§13: 4 u max|v| against the float64 restatement); smoothing and gather are Lipschitz 1

@@ -399,6 +399,10 @@ def test_voxels_outside_the_field_of_view_stay_zero(dev):
     assert S.border_margin(inv, 48, 40, 16, 16) >= 1e-3
     cov = S.covered(inv, 48, 40, 16, 16)
     assert stats == [cov.mean()] and 0.2 < stats[0] < 0.6
+    # the plan of this request knows both before anything runs
+    req = vp.parse_request(spacing=(0.5, 0.5, 2.0), sample_mm=(1.0, 1.0, 2.0), out_size=(16, 16), batch_size=3, prob=True, entropy=True)
+    plan = vp.plan_view(req, image.shape, 2, ((0, 48), (0, 40), (0, 4)), (0.5, 0.5, 2.0))
+    assert len(plan.invs) == 1 and np.array_equal(plan.invs[0], inv) and plan.coverage == stats[0] and plan.frames == (0, 4, 0) and not plan.padded
     cov_file = np.flip(np.flip(cov, 0), 1)[:, :, None]                       # slicing order -> the file's (the double flip)
     label, prob, ent = res.label.cpu().numpy(), res.prob.cpu().numpy(), res.entropy.cpu().numpy()
     assert np.array_equal(label, np.where(cov_file, 3, 0) * np.ones((1, 1, 4), np.uint8))

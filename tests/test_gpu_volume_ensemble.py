@@ -163,6 +163,14 @@ def test_a_net_listed_twice_is_the_net_listed_once(dev, seg):
             assert torch.equal(a, b), "listed %d times: %s differs" % (n, name)
 
 
+def _the_plan_has(n_callables, options, shape, invs):
+    """the hand-built inverse maps are the ones segment_volume's plan holds for these options (axis 1, batches of B), member for member"""
+    vp = pkg("volume_predict")
+    plan = vp.plan_view(vp.parse_request(n_callables, axis=1, batch_size=B, **options), shape, 1, ((0, 200), (0, 232), (0, 5)), None)
+    assert plan.dims == (200, 232, 5) and plan.kind == "ensemble" and plan.members == len(invs)
+    assert all(np.array_equal(a, b) for a, b in zip(plan.invs, invs))
+
+
 def test_three_member_tta_against_the_restatement(dev, seg):
     """200 x 232 x 5 in slicing order, stored with the slicing axis in the middle and flipped: batches of 2, 2 and 1 frames"""
     vp, vs = pkg("volume_predict"), pkg("volume_source")
@@ -173,6 +181,7 @@ def test_three_member_tta_against_the_restatement(dev, seg):
                             tta=tta, prob=True, entropy=True)
     assert len(captured) == 9 and tuple(res.prob.shape) == (5, 200, 5, 232) and tuple(res.entropy.shape) == image.shape
     invs = [vp.invert_matrix(vs.compose_matrix((200, 232), (256, 256), **e)) for e in tta]
+    _the_plan_has(None, dict(tta=tta, prob=True, entropy=True), image.shape, invs)
     _against_the_restatement(res, captured, 3, invs, (200, 232, 5), True, 1, "three-member tta, 200 x 232 x 5")
 
 
@@ -185,6 +194,7 @@ def test_two_nets_against_the_restatement(dev, seg, seg2):
     assert len(captured) == 6
     assert not torch.equal(captured[0], captured[1]), "two seeds, two nets"
     inv = vp.invert_matrix(vs.compose_matrix((200, 232), (256, 256)))
+    _the_plan_has(2, dict(prob=True, entropy=True), image.shape, [inv, inv])
     _against_the_restatement(res, captured, 2, [inv, inv], (200, 232, 5), True, 1, "two nets, 200 x 232 x 5")
 
 

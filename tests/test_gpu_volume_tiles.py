@@ -54,7 +54,8 @@ def _bands(captured=None):
 
 
 def _plan(entries=({},), tiles="auto", overlap=0.25):
-    """the maps segment_volume builds for the box XYZ: (inverse maps in member order for one callable, ramp, counts)"""
+    """the maps of the box XYZ, built by hand: (inverse maps in member order for one callable, ramp, counts) — and held equal to the plan
+    that segment_volume runs (parse_request + plan_view), so the restatement below is driven through the maps the device got"""
     vp, vs = pkg("volume_predict"), pkg("volume_source")
     (X, Y), (H, W) = XYZ[:2], HW
     extent, plane = (X * VOX, Y * VOX), (H * MM, W * MM)
@@ -65,6 +66,10 @@ def _plan(entries=({},), tiles="auto", overlap=0.25):
         for e in entries:
             t = e.get("translate", (0.0, 0.0))
             invs.append(vp.invert_matrix(vs.compose_matrix((X, Y), (H, W), **dict(e, translate=(t[0] + ti, t[1] + tj)), spacing_xy=(VOX, VOX), pixel_mm=(MM, MM))))
+    req = vp.parse_request(tta=list(entries), tiles=tiles, tile_overlap=overlap, out_size=HW, spacing=_spacing(2), sample_mm=MM)
+    plan = vp.plan_view(req, XYZ, 2, tuple((0, n) for n in XYZ), _spacing(2))
+    assert plan.counts == counts and plan.ramp == ramp and plan.kind == "tiles" and plan.members == len(invs)
+    assert all(np.array_equal(a, b) for a, b in zip(plan.invs, invs))
     return invs, ramp, counts
 
 

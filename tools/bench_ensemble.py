@@ -77,8 +77,8 @@ def main():
     kw = dict(batch_size=B, num_cls=ncls, device=dev)
     vp.segment_volume(fn, scan((X, Y, 16), 2), tta="default", prob=True, entropy=True, **kw)          # warm-up: 1 batch
     torch.cuda.synchronize()
-    entries = vp.tta_entries("default")
-    M = len(entries)
+    plan = vp.plan_view(vp.parse_request(tta="default", batch_size=B, num_cls=ncls), (X, Y, Z), 2, ((0, X), (0, Y), (0, Z)))  # of the call above
+    entries, M, maps, invs = [dict(e) for e in plan.entries], plan.members, plan.maps, plan.invs
     # one fixed batch: M gathers, M forwards
     v = torch.from_numpy(big.astype(np.float32)).to(dev)
     _, st = K.volume_preprocess(v, 98, out=v)
@@ -86,13 +86,11 @@ def main():
     src = vs.AugmentedSliceSource(vset, B, augment=None, num_cls=ncls)
     rec = np.zeros(B, dtype=vs.SAMPLE_DTYPE)
     rec["frame"] = 50 + np.arange(B)
-    maps = [vs.compose_matrix((X, Y), (256, 256), **e) for e in entries]
-    invs = [vp.invert_matrix(m) for m in maps]
     members = []
     for m in maps:
         rec["m"][:] = m
         members.append(fn(src.gather_records(rec, ncls, want_onehot=False)[0]).contiguous())
-    origin, strides, _ = vp.file_layout((X, Y, Z), True, 2, None)
+    origin, strides = plan.origin, plan.strides
     if a.profile_step:
         vp.segment_volume(fn, big, tta="default", **kw)                                  # 13 batches, labels only
         vp.segment_volume(fn, big, tta="default", prob=True, entropy=True, **kw)         # 13 batches, all three outputs

@@ -83,6 +83,9 @@ def main():
     kw = dict(batch_size=B, num_cls=ncls, device=dev)
     if sample_mm is not None:
         kw.update(sample_mm=sample_mm, spacing=(1.0, 1.0, 1.0))
+    # the plan of segment_volume(big): the fixed batches below gather and paste through its maps and layout
+    whole, host = ((0, 256), (0, 256), (0, 200)), {k: v for k, v in kw.items() if k != "device"}
+    plan = vp.plan_view(vp.parse_request(**host), (256, 256, 200), 2, whole, kw.get("spacing"))
     vp.segment_volume(fn, scan((256, 256, 16), 2), **kw)          # warm-up: 1 batch
     torch.cuda.synchronize()
     if a.profile_step:
@@ -106,16 +109,14 @@ def main():
         vset = vs.VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=dev)], ["v"], [float(st[3].item())])
         src = vs.AugmentedSliceSource(vset, B, augment=None, num_cls=ncls, sample_mm=sample_mm)
         rec = np.zeros(B, dtype=vs.SAMPLE_Z_DTYPE)
-        geom = dict(spacing_xy=(1.0, 1.0), pixel_mm=sample_mm[:2])
-        rec["frame"], rec["dz"], rec["m"][:] = 50 + np.arange(B), sample_mm[2], vs.compose_matrix((256, 256), (256, 256), **geom)
+        rec["frame"], rec["dz"], rec["m"][:] = 50 + np.arange(B), plan.dz, plan.maps[0]
         logits = fn(src.gather_records(rec, ncls, want_onehot=False)[0]).contiguous()
         res["gather_ms_incl_upload_and_allocation"] = events(lambda: src.gather_records(rec, ncls, want_onehot=False), 50)
-        inv = vp.invert_matrix(vs.compose_matrix((256, 256), (256, 256), **geom))
-        origin, strides, _ = vp.file_layout((256, 256, 200), True, 2, None)
+        inv, origin, strides = plan.invs[0], plan.origin, plan.strides
         out = torch.zeros((256, 256, 200), dtype=torch.uint8, device=dev)
         for name, fov in (("paste_labels", False), ("paste_labels_fov", True)):
             res[name + "_256x256_z_fastest_ms_back_to_back"] = events(lambda: K.paste_labels(logits, B, 50, inv, (256, 256), out, origin, strides, fov=fov), 50)
-        res["coverage_256x256"] = vp.coverage(inv, 256, 256, 256, 256)
+        res["coverage_256x256"] = plan.coverage
         src.close()
         print(json.dumps(res))
         if a.out:
@@ -149,16 +150,16 @@ def main():
     vset = vs.VolumeSet.from_device([v], [torch.zeros(tuple(v.shape), dtype=torch.uint8, device=dev)], ["v"], [float(st[3].item())])
     src = vs.AugmentedSliceSource(vset, B, augment=None, num_cls=ncls)
     rec = np.zeros(B, dtype=vs.SAMPLE_DTYPE)
-    rec["frame"], rec["m"][:] = 50 + np.arange(B), vs.compose_matrix((256, 256), (256, 256))
+    rec["frame"], rec["m"][:] = 50 + np.arange(B), plan.maps[0]
     x = src.gather_records(rec, ncls, want_onehot=False)[0]
     logits = fn(x).contiguous()
     res["gather_ms_incl_upload_and_allocation"] = events(lambda: src.gather_records(rec, ncls, want_onehot=False), 50)
     res["forward_ms"] = events(lambda: fn(x), 20)
     # 3. the paste alone, both stride patterns (identity map and the 180 x 210 resize)
     for name, (X, Y, Z) in (("256x256", (256, 256, 200)), ("180x210", (180, 210, 160))):
-        inv = vp.invert_matrix(vs.compose_matrix((X, Y), (256, 256)))
         for pattern, shape, axis in (("z_fastest", (X, Y, Z), 2), ("z_slowest", (Z, X, Y), 0)):
-            origin, strides, _ = vp.file_layout(shape, True, axis, None)
+            view = vp.plan_view(plan.request, shape, axis, ((0, X), (0, Y), (0, Z)))
+            inv, origin, strides = view.invs[0], view.origin, view.strides
             out = torch.zeros(shape, dtype=torch.uint8, device=dev)
             ms = events(lambda: K.paste_labels(logits, B, 50, inv, (X, Y), out, origin, strides), 50)
             nbytes = B * 256 * 256 * ncls * 4 + B * X * Y
