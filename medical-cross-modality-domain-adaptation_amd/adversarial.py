@@ -717,7 +717,6 @@ class Trainer(object):
         g = self._captured("dis", dropout, {"mr": mr_batch.shape, "ct": ct_batch.shape})
         if g is not None:
             self.global_step += 1
-            K.weights_changed()
             return g.replay(seed, mr_batch, ct_batch)
         loss = self.net.dis_loss_and_grads(mr_batch, ct_batch, dropout, drop_seed=seed)
         if self.reducer is not None:
@@ -733,7 +732,6 @@ class Trainer(object):
         g = self._captured("gen", dropout, {"ct": ct_batch.shape})
         if g is not None:
             self.global_step += 1
-            K.weights_changed()
             return g.replay(seed, ct_batch)
         loss = self.net.gen_loss_and_grads(ct_batch, dropout, drop_seed=seed)
         if self.reducer is not None:

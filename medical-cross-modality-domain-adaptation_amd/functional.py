@@ -343,7 +343,7 @@ class ConvBNActFn(Function):
         # contract of the recomputed sign: gamma / beta / statistics are NOT written between this forward and its backward.  The
         # optimiser and clip kernels write the arena in place without bumping tensor versions — the weight epoch (bumped by every
         # weight-writing kernel wrapper) stands in for them and is checked in backward
-        ctx.wepoch = K._WEIGHT_EPOCH[0]
+        ctx.wepoch = K.weight_epoch()
         ctx.save_for_backward(x, w_, xc, beta if ctx.resign else out, mean, var, gamma)
         return out
 
@@ -352,7 +352,7 @@ class ConvBNActFn(Function):
         x, w, xc, out, mean, var, gamma = ctx.saved_tensors
         beta = None
         if getattr(ctx, "resign", False):
-            if ctx.wepoch != K._WEIGHT_EPOCH[0]:
+            if ctx.wepoch != K.weight_epoch():
                 raise RuntimeError("parameters were updated (optimiser / clip / load) between a forward pass and its backward pass: the "
                                    "BN backward recomputes the activation's sign from gamma / beta and would use the NEW values "
                                    "(set PNP_BN_RECOMPUTE_SIGN=0 for flows that step between forward and backward)")

@@ -6,11 +6,11 @@ reference's layouts (layers.py).  Each function names the reference op it stands
 """
 import ctypes
 import os
-import weakref
 
 import torch
 
 from . import _lib
+from . import weight_cache as _wc
 from ._lib import ConvGeom, PAD_SYMMETRIC, PAD_ZERO, check
 
 _ws_cache = {}
@@ -64,7 +64,7 @@ def workspace(nbytes, device, slot="main"):
     key = (device.index if isinstance(device, torch.device) else str(device), slot, _stream_ptr())
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
-        if buf is not None and (PINNED[0] > 0 or torch.cuda.is_current_stream_capturing()):
+        if buf is not None and (_wc.CACHE.pins > 0 or torch.cuda.is_current_stream_capturing()):
             _ws_retired.append(buf)
         buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
         _ws_cache[key] = buf
@@ -194,78 +194,44 @@ def conv_route(g, kind=0):
     return int(_lib.load().pnp_conv2d_route(ctypes.byref(g), int(kind)))
 
 
-# ---- transformed-filter cache of the Winograd route (pnp_conv2d_wino_filter_bind) ------------------------------------------------------
-# U = G g G^T changes only when the filter does.  Filters OWNED BY A VariableStore (variables.py marks their tensors `_pnp_var`) get one
-# buffer per pass, lent to the library; the library skips wino_filter_kernel while the entry is valid.  Validity: the library drops an
-# entry when weights_changed() names its address range (optimisers, clip, host-side loads); here an entry is tied to the tensor OBJECT it
-# was made for (weakref: a new tensor at a recycled address starts over) and to its torch version counter (an in-place torch op on the
-# filter or on the arena it is a view of).  Ad-hoc filters (tests, tools) are never cached.  PNP_WINOGRAD_UCACHE=0: off.
+# ---- what is kept per filter between launches (weight_cache.py) -------------------------------------------------------------------------
+# U = G g G^T of the Winograd route changes only when the filter does.  Filters OWNED BY A VariableStore (variables.py marks their tensors
+# `_pnp_var`) get one buffer per pass, lent to the library; the library skips wino_filter_kernel while the entry is valid.  Who a filter
+# is and when what was derived from it is stale: weight_cache.py, once, for U and for the bf16 shadows below.  Ad-hoc filters (tests,
+# tools) are never bound.  PNP_WINOGRAD_UCACHE=0: off.
 U_CACHE = os.environ.get("PNP_WINOGRAD_UCACHE", "1") != "0"
-_u_cache = {}
-
-
-def _u_drop(key, ref=None):
-    """withdraw the binding of `key` (its filter tensor died, or an ad-hoc filter now sits on its address)"""
-    ent = _u_cache.get(key)
-    if ent is None or (ref is not None and ent[0] is not ref):
-        return
-    del _u_cache[key]
-    if ent[1] is not None:
-        try:
-            _lib.load().pnp_conv2d_wino_filter_bind(ctypes.c_void_p(key[0]), int(key[1]), None, 0)
-        except Exception:          # interpreter shutdown: the library may be gone already
-            pass
 
 
 def _wino_u(w, g, kind):
-    if not U_CACHE:
-        return
-    key = (w.data_ptr(), kind)
-    ent = _u_cache.get(key)
-    if not getattr(w, "_pnp_var", False):
-        if ent is not None:                  # an ad-hoc filter on the address of a cached one: the library must not serve the old U
-            _u_drop(key)
-        return
-    if ent is not None and ent[0]() is w:
-        if ent[2] != w._version:             # written by a torch op since the entry was filled
-            if ent[1] is not None:
-                _lib.load().pnp_weights_changed(ctypes.c_void_p(w.data_ptr()), ctypes.c_void_p(w.data_ptr() + 4 * w.numel()))
-            ent[2] = w._version
-        if ent[1] is not None or not (g.R == 3 and g.S == 3 and wino_chosen(g, kind)):
-            return
-        # no buffer was bound when this filter was first seen (a small-batch forward the planner declined, a policy change): the route
-        # takes it NOW — bind one instead of leaving the cache silently off for the lifetime of the tensor (ADVICE r5)
-    lib = _lib.load()
-    if ent is not None and not (ent[0]() is w and ent[1] is None):
-        _u_drop(key)
-    U = None
-    if g.R == 3 and g.S == 3 and wino_chosen(g, kind):          # (decided once per filter and pass: a later policy change runs un-cached)
-        nbytes = int(lib.pnp_conv2d_wino_filter_bytes(int(w.shape[2]), int(w.shape[3])))
-        if nbytes:
-            U = torch.empty(nbytes // 4, dtype=torch.float32, device=w.device)
-            check(lib.pnp_conv2d_wino_filter_bind(ctypes.c_void_p(w.data_ptr()), int(kind), ctypes.c_void_p(U.data_ptr()), nbytes),
-                  "pnp_conv2d_wino_filter_bind")
-    # the binding goes when the tensor object does (CPython frees it, and with it the arena it may keep alive, deterministically): nothing
-    # allocated later on the same address can meet a valid entry
-    _u_cache[key] = [weakref.ref(w, lambda r, k=key: _u_drop(k, r)), U, w._version]
+    if U_CACHE:
+        _wc.CACHE.bind_u(w, g, kind, _lib.load())
 
 
 def wino_u_cache_clear():
     """withdraw every transformed-filter buffer (tests; a store that goes away)"""
-    if _u_cache:
-        _lib.load().pnp_conv2d_wino_filter_bind(None, 0, None, 0)
-        _u_cache.clear()
+    _wc.CACHE.clear_u()
+
+
+def weights_changed(ranges=None):
+    """weights were (or are queued to be) written.  ranges: [(first byte address, end address), ...] of what changed — the library drops
+    the transformed filters (Winograd route) of exactly those; None: everything.  The bf16 shadows follow the same ranges (round 6: one
+    global epoch re-built the shadows of every FROZEN filter after every optimiser step — 102 filter_bf16_kernel launches per joint step)."""
+    _wc.CACHE.report(ranges)
+
+
+def weight_epoch():
+    """count of weight-write reports so far (functional: nothing may write parameters between a forward pass and its backward pass)"""
+    return _wc.CACHE.log.epoch
 
 
 def memory_report():
     """bytes of device memory the host side of the library holds on to between steps (nothing reported it):
     grow-only workspaces per (slot, stream), workspaces retired under a recorded step, transformed filters of the Winograd route,
     bf16 filter shadows"""
-    nb = lambda t: 0 if t is None else int(t.numel()) * int(t.element_size())
+    nb = lambda t: int(t.numel()) * int(t.element_size())
     rep = {"workspaces": sum(nb(b) for b in _ws_cache.values()), "workspace_buffers": len(_ws_cache),
-           "workspaces_retired": sum(nb(b) for b in _ws_retired), "recorded_steps_alive": int(PINNED[0]),
-           "winograd_filters": sum(nb(e[1]) for e in _u_cache.values()), "winograd_filter_entries": len(_u_cache),
-           "bf16_filter_shadows": sum(nb(e[1]) + nb(e[2]) for e in _filter_cache.values()), "bf16_filter_entries": len(_filter_cache)}
+           "workspaces_retired": sum(nb(b) for b in _ws_retired)}
+    rep.update(_wc.CACHE.memory())
     rep["total"] = rep["workspaces"] + rep["workspaces_retired"] + rep["winograd_filters"] + rep["bf16_filter_shadows"]
     return rep
 
@@ -349,40 +315,9 @@ def filter_bf16(w, want_io=True, want_oi=True):
 
 # bf16 copies ("shadows") of tensors the resident convolutions read.  An activation's shadow is written by its producer (yh / dxh side
 # outputs) and travels as an attribute of the tensor OBJECT; a tensor that arrives without one (re-wrapped by a view, produced by a
-# kernel without a bf16 output) is cast on demand.  Filter shadows are cached per filter and weight epoch: every kernel that writes
-# weights (optimisers, clip) and every host-side load bumps the epoch.
-_WEIGHT_EPOCH = [0]
-_CHANGES = []              # (epoch, ((lo, hi), ...)) of the range-limited weight writes since _CHANGE_FLOOR, oldest first
-_CHANGE_FLOOR = [0]        # a write of unknown extent happened at this epoch: everything older is stale
-_filter_cache = {}
+# kernel without a bf16 output) is cast on demand.  Filter shadows are kept per filter (weight_cache.py): every kernel that writes
+# weights (optimisers, clip) and every host-side load reports what it wrote (weights_changed).
 CAST_COUNT = [0]          # on-demand casts since the last reset (tests / profiling: how many producers still lack a bf16 output)
-
-
-RECORDING = [None]        # token of the hipGraph recording in progress (step_capture.CapturedStep): filter_shadows casts once per recording
-PINNED = [0]              # live CapturedStep objects: their hipGraphs hold the ADDRESSES of filter shadows — nothing may be freed under them
-
-
-def weights_changed(ranges=None):
-    """weights were (or are queued to be) written.  ranges: [(first byte address, end address), ...] of what changed — the library drops
-    the transformed filters (Winograd route) of exactly those; None: everything.  The bf16 shadows follow the same ranges (round 6: one
-    global epoch re-built the shadows of every FROZEN filter after every optimiser step — 102 filter_bf16_kernel launches per joint step)."""
-    _WEIGHT_EPOCH[0] += 1
-    if ranges is None or len(_CHANGES) >= 64:
-        _CHANGES.clear()
-        _CHANGE_FLOOR[0] = _WEIGHT_EPOCH[0]         # everything filled before this epoch is stale
-    else:
-        _CHANGES.append((_WEIGHT_EPOCH[0], tuple((int(lo), int(hi)) for lo, hi in ranges)))
-    if len(_filter_cache) > 1024 and not PINNED[0]:      # shadows of filters of stores that no longer exist (test suites): start over
-        _filter_cache.clear()
-    if _u_cache:
-        lib = _lib.load()
-        if ranges is None and len(_u_cache) > 4096 and not PINNED[0]:    # buffers of stores that no longer exist (test suites): start over
-            wino_u_cache_clear()
-        elif ranges is None:
-            lib.pnp_weights_changed(None, None)
-        else:
-            for lo, hi in ranges:
-                lib.pnp_weights_changed(ctypes.c_void_p(lo), ctypes.c_void_p(hi))
 
 
 class HalfOnly(object):
@@ -418,43 +353,18 @@ def set_bf16(t, h):
     return t
 
 
-def _changed_since(epoch, lo, hi):
-    """has a reported weight write touched [lo, hi) after `epoch`"""
-    if epoch < _CHANGE_FLOOR[0]:
-        return True
-    for ep, rs in reversed(_CHANGES):
-        if ep <= epoch:
-            break
-        for a, b in rs:
-            if a < hi and lo < b:
-                return True
-    return False
+def _filter_cast(w, into=None):
+    """the shadows of `w`: a new pair, or `into` = (w_io, w_oi) written again"""
+    if into is None:
+        return filter_bf16(w)
+    R, S, C, Kc = w.shape
+    check(_lib.load().pnp_filter_bf16(_p(w), _ph(into[0]), _ph(into[1]), R, S, C, Kc, _stream()), "pnp_filter_bf16")
+    return into
 
 
 def filter_shadows(w):
     """(w_io, w_oi) of an fp32 filter [R,S,C,K], refreshed when a reported weight write has touched the filter since they were made"""
-    key = (w.data_ptr(), tuple(w.shape))
-    ent = _filter_cache.get(key)
-    # valid: same weight epoch (kernels that write weights), same torch version counter (an in-place torch op on the filter or the arena
-    # it is a view of), same owner object (a new tensor on a recycled address is another filter)
-    owner = w._base if w._base is not None else w
-    # While a hipGraph is being recorded the refresh is ALWAYS taken once per recording (as bf16_of does): a shadow that happens to be
-    # fresh at capture time would leave its cast out of the graph, and every replay would then read the copy of whatever the filter held
-    # when it was recorded — the filters another graph updates (the generator's, read by the dis graph) or a state_dict loaded after the
-    # recording.  (Once: RECORDING names the recording; a second read of the same filter in it follows the ordinary staleness rule.)
-    # The other way round, a cast that was only RECORDED has not run: outside that recording its entry counts as stale.
-    rec = (RECORDING[0] if RECORDING[0] is not None else object()) if torch.cuda.is_current_stream_capturing() else None
-    if ent is None or ent[5] is not rec or ent[3] != w._version or ent[4]() is not owner or \
-            (ent[0] != _WEIGHT_EPOCH[0] and _changed_since(ent[0], key[0], key[0] + 4 * w.numel())):
-        if ent is None:
-            w_io, w_oi = filter_bf16(w)
-        else:                   # refresh in place: same buffers, no allocation in the steady state
-            w_io, w_oi = ent[1], ent[2]
-            R, S, C, Kc = w.shape
-            check(_lib.load().pnp_filter_bf16(_p(w), _ph(w_io), _ph(w_oi), R, S, C, Kc, _stream()), "pnp_filter_bf16")
-        ent = (_WEIGHT_EPOCH[0], w_io, w_oi, w._version, weakref.ref(owner), rec)
-        _filter_cache[key] = ent
-    return ent[1], ent[2]
+    return _wc.CACHE.shadows(w, _filter_cast)
 
 
 _served_cache = {}

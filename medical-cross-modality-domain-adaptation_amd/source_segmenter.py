@@ -513,7 +513,6 @@ class Trainer(object):
         cap = getattr(self, "_cap", None)
         if cap is not None and cap["dropout"] == float(dropout) and cap["x"] == tuple(batch_x.shape) and cap["y"] == tuple(batch_y.shape):
             self.global_step += 1
-            K.weights_changed()
             return cap["step"].replay(step + 1 + self.seed_offset, batch_x, batch_y)
         loss = net.loss_and_grads(batch_x, batch_y, dropout, main_bn=True, adapt_bn=True, drop_seed=step + 1 + self.seed_offset)
         if self.reducer is not None:

@@ -25,12 +25,12 @@ import torch
 
 from . import _lib
 from . import kernels as K
+from . import weight_cache
 import weakref
 
 
-def _unpin():
-    K.PINNED[0] -= 1
-    if K.PINNED[0] <= 0:
+def _unpin(cache):
+    if cache.unpin() <= 0:
         del K._ws_retired[:]         # no recording left that could replay their addresses
 
 
@@ -57,18 +57,17 @@ class CapturedStep(object):
         self.graph = torch.cuda.CUDAGraph()
         _lib.check(lib.pnp_step_params_bind(self._bp), "pnp_step_params_bind")
         t0 = adam.t if adam is not None else 0
-        K.RECORDING[0] = object()                        # every filter shadow the step reads is cast inside the recording, once
+        cache = weight_cache.CACHE
         try:
-            with torch.cuda.graph(self.graph):
+            with cache.recording(), torch.cuda.graph(self.graph):        # every filter shadow the step reads is cast inside the recording, once
                 self.out = fn(*self.static)
         finally:
-            K.RECORDING[0] = None
             _lib.check(lib.pnp_step_params_bind(None), "pnp_step_params_bind")
             if adam is not None:
                 adam.t = t0                              # recording executes nothing: the counter moved, the weights did not
         self.replays = 0
-        K.PINNED[0] += 1                                  # the graph holds addresses of cached filter shadows: nothing may be freed under it
-        weakref.finalize(self, _unpin)
+        cache.pin()                                       # the graph holds addresses of cached filter shadows: nothing may be freed under it
+        weakref.finalize(self, _unpin, cache)
 
     def _lr_t(self):
         a = self.adam

@@ -247,3 +247,55 @@ def test_training_graph_runs_on_the_resident_kernels(dev):
     print("resident vs staged-rounding path (1 - cosine): out %.2e dx %.2e parameter gradients %.2e; casts %d; symbols %s" % (
         d + (casts1, sorted(set(names1)))))
     assert d[0] < 1e-5 and d[1] < 2e-3 and d[2] < 2e-3, d
+
+
+def test_joint_step_casts_filter_shadows_only_where_weights_were_written(dev, monkeypatch):
+    """eager dis + gen updates of the B = 2, 256 x 256 joint step (test_gpu_wino.py::test_joint_steps_with_and_without_the_filter_cache) in
+    bf16: pnp_filter_bf16 runs for a filter exactly when an optimiser or the clip has reported a write over its bytes since its shadows
+    were made — the same count every pair from the second on, one cast per written filter and pass that first reads it after the
+    write, none for frozen filters.  Expected from the reads of each step and the trainer's own written_ranges, not typed in."""
+    adv, K, F, WC = pkg("adversarial"), pkg("kernels"), pkg("functional"), pkg("weight_cache")
+    from test_gpu_adversarial import he_state
+    B = 2
+    rng = np.random.default_rng(4)
+    mr = torch.from_numpy(rng.standard_normal((B, 256, 256, 3)).astype(np.float32)).to(dev)
+    ct = torch.from_numpy(rng.standard_normal((B, 256, 256, 3)).astype(np.float32)).to(dev)
+    reads, counts = [], []
+    real = K.filter_shadows
+    monkeypatch.setattr(K, "filter_shadows", lambda w: (reads[-1].append((w.data_ptr(), w.data_ptr() + 4 * w.numel())), real(w))[1])
+    F.set_conv_dtype("bf16")
+    try:
+        net = adv.Full_DRN(channels=3, n_class=5, batch_size=B, device=dev, seed=0,
+                           cost_kwargs={"regularizer": 1e-4, "gan_regularizer": 1e-4, "miu_gen": 0.002, "miu_dis": 0.002, "lambda_mask_loss": 0.3},
+                           network_config={"mr_front_trainable": False, "joint_trainable": False, "ct_front_trainable": True, "cls_trainable": True,
+                                           "m_cls_trainable": True})
+        net.store.load_state_dict(he_state(net, 9))
+        tr = adv.Trainer(net, None, None, None, None, num_cls=5, batch_size=B, opt_kwargs={"learning_rate": 3e-4},
+                         train_config={"dis_sub_iter": 1, "gen_sub_iter": 1})
+        tr._get_optimizer()
+        for i in range(3):
+            n0 = WC.CACHE.casts
+            reads.append([])
+            tr.dis_step(mr, ct, 0.75, 2 * i + 1)
+            reads.append([])
+            tr.gen_step(ct, 0.75, 2 * i + 2)
+            counts.append(WC.CACHE.casts - n0)
+        torch.cuda.synchronize()
+    finally:
+        F.set_conv_dtype("f32")
+    written = [list(tr.dis_optimizer._ranges) + list(tr._clip_ranges), list(tr.gen_optimizer._ranges)]       # by a dis step, by a gen step
+    hit = lambda r, ranges: any(a < r[1] and r[0] < b for a, b in ranges)
+    fresh, expected = set(), [0, 0, 0]
+    for s, rd in enumerate(reads):
+        for r in rd:
+            if r not in fresh:
+                expected[s // 2] += 1
+                fresh.add(r)
+        fresh = set(r for r in fresh if not hit(r, written[s % 2]))
+    filters = set(r for rd in reads for r in rd)
+    trained = set(r for r in filters if hit(r, written[0] + written[1]))
+    print("filter casts per dis + gen pair %s, expected %s; %d filters read through shadows, %d of them written by an optimiser" % (
+        counts, expected, len(filters), len(trained)))
+    assert counts[1] == counts[2]
+    assert counts == expected             # (the first pair also makes every shadow once, and casts again what its dis step then wrote)
+    assert 0 < counts[1] <= 2 * len(trained) and len(trained) < len(filters)          # frozen filters are read, and add nothing

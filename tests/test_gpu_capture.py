@@ -134,7 +134,7 @@ def _gan_capture_case(dev, dtype):
     # stream's buffer, hand every cached block back to the driver, overwrite what the allocator gives out next.
     K, F = pkg("kernels"), pkg("functional")
     side = F.wgrad_side_stream()
-    assert side is not None and K.PINNED[0] >= 2
+    assert side is not None and K.memory_report()["recorded_steps_alive"] >= 2
     old = K._ws_cache[(dev.index, "main", side.cuda_stream)]
     p_old, n_old = old.data_ptr(), old.numel()
     del old

@@ -308,7 +308,7 @@ def test_transformed_filter_cache(dev, wino):
     # block straight back) is transformed afresh — never served the dead filter's U
     addr = w.data_ptr()
     del w
-    assert not any(k[0] == addr for k in K._u_cache)
+    assert pkg("weight_cache").CACHE.bound(addr) == []
     w3 = torch.from_numpy((rng.standard_normal((3, 3, C, Kf)) * 0.05).astype(np.float32)).to(dev)
     y3 = K.conv2d_fwd(x, w3, g)
     wino(0)

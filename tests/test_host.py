@@ -698,12 +698,12 @@ def test_written_ranges_of_an_optimiser_mask():
 
 
 def test_transformed_filter_cache_rules_on_the_host(monkeypatch):
-    """kernels._wino_u (the Python side of pnp_conv2d_wino_filter_bind) against a recording stand-in for the library: a store-owned filter
+    """kernels._wino_u -> weight_cache.bind_u (the Python side of pnp_conv2d_wino_filter_bind) against a recording stand-in for the library: a store-owned filter
     gets ONE binding per pass; a torch in-place write (version counter) reports the filter's byte range; the binding is withdrawn when the
     tensor object dies and when an ad-hoc filter turns up on a cached address; ad-hoc filters are never bound; weights_changed hands
     ranges through"""
     import ctypes
-    K = pkg("kernels")
+    K, WC = pkg("kernels"), pkg("weight_cache")
     calls = []
 
     class FakeLib(object):
@@ -722,20 +722,22 @@ def test_transformed_filter_cache_rules_on_the_host(monkeypatch):
 
     monkeypatch.setattr(K._lib, "load", lambda: FakeLib())
     monkeypatch.setattr(ctypes, "byref", lambda g: g)
-    monkeypatch.setattr(K, "_u_cache", {})
+    cache = WC.WeightCache()
+    monkeypatch.setattr(WC, "CACHE", cache)
     monkeypatch.setattr(K, "U_CACHE", True)
+    entries = lambda: K.memory_report()["winograd_filter_entries"]
 
     class G(object):
         R = S = 3
 
     w = torch.zeros(3, 3, 32, 32)
     K._wino_u(w, G(), 0)                                  # ad-hoc: nothing
-    assert calls == [] and not K._u_cache
+    assert calls == [] and not entries() and not cache.records
     w._pnp_var = True
     K._wino_u(w, G(), 0)
     K._wino_u(w, G(), 0)
     K._wino_u(w, G(), 1)
-    assert calls == [("bind", w.data_ptr(), 0), ("bind", w.data_ptr(), 1)] and len(K._u_cache) == 2
+    assert calls == [("bind", w.data_ptr(), 0), ("bind", w.data_ptr(), 1)] and entries() == 2 and cache.bound(w.data_ptr()) == [0, 1]
     w.add_(1.0)                                           # a torch op on the filter
     K._wino_u(w, G(), 0)
     assert calls[-1] == ("changed", w.data_ptr(), w.data_ptr() + 4 * w.numel())
@@ -745,14 +747,14 @@ def test_transformed_filter_cache_rules_on_the_host(monkeypatch):
     assert calls[-1] == ("changed", None, None)
     ptr = w.data_ptr()
     del w                                                 # the tensor goes: both bindings with it
-    assert not K._u_cache and sorted(calls[-2:]) == [("unbind", ptr, 0), ("unbind", ptr, 1)]
+    assert not entries() and not cache.bound(ptr) and sorted(calls[-2:]) == [("unbind", ptr, 0), ("unbind", ptr, 1)]
     w2 = torch.zeros(3, 3, 32, 32)
     w2._pnp_var = True
     K._wino_u(w2, G(), 1)
-    v = torch.zeros(3, 3, 32, 32)                         # an ad-hoc filter "on the same address": move the entry under its key
-    K._u_cache[(v.data_ptr(), 1)] = K._u_cache.pop((w2.data_ptr(), 1))
+    v = w2.view(3, 3, 32, 32)                             # an ad-hoc filter on the same address: another tensor object, not marked
+    assert v is not w2 and v.data_ptr() == w2.data_ptr() and cache.bound(v.data_ptr()) == [1]
     K._wino_u(v, G(), 1)
-    assert calls[-1] == ("unbind", v.data_ptr(), 1) and not K._u_cache
+    assert calls[-1] == ("unbind", v.data_ptr(), 1) and not entries() and not cache.bound(v.data_ptr())
 
 
 def test_captured_gan_steps_fall_back_to_eager_when_the_learning_rate_moved():
@@ -778,7 +780,7 @@ def test_captured_gan_steps_fall_back_to_eager_when_the_learning_rate_moved():
 def test_filter_shadows_are_cast_inside_every_recording(monkeypatch):
     """kernels.filter_shadows: a hipGraph recording must hold the cast of every bf16 filter shadow it reads, fresh or not —
     once per filter and recording; a cast that was only recorded has not run, so the next eager reader casts again"""
-    K = pkg("kernels")
+    K, WC = pkg("kernels"), pkg("weight_cache")
     casts = []
 
     class FakeLib(object):
@@ -792,24 +794,24 @@ def test_filter_shadows_are_cast_inside_every_recording(monkeypatch):
     monkeypatch.setattr(K, "_ph", lambda t: t)
     monkeypatch.setattr(K, "_stream", lambda: None)
     monkeypatch.setattr(K, "filter_bf16", lambda w: (casts.append("new"), torch.zeros(1), torch.zeros(1))[1:])
-    monkeypatch.setattr(K, "_filter_cache", {})
-    monkeypatch.setattr(K, "_u_cache", {})
-    monkeypatch.setattr(K, "RECORDING", [None])
+    cache = WC.WeightCache()
+    monkeypatch.setattr(WC, "CACHE", cache)
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: capturing[0])
     w = torch.zeros(3, 3, 32, 64)
     K.filter_shadows(w)
     K.filter_shadows(w)
     assert casts == ["new"]                               # eager: fresh shadows are reused
     for _ in range(2):                                    # two recordings: each holds the cast, once
-        capturing[0], K.RECORDING[0] = True, object()
-        del casts[:]
-        K.filter_shadows(w)
-        K.filter_shadows(w)
-        assert casts == ["refresh"]
-        K.weights_changed([(w.data_ptr(), w.data_ptr() + 4 * w.numel())])     # an optimiser node in the middle of the recording
-        K.filter_shadows(w)
-        assert casts == ["refresh", "refresh"]
-    capturing[0], K.RECORDING[0] = False, None
+        capturing[0] = True
+        with cache.recording():
+            del casts[:]
+            K.filter_shadows(w)
+            K.filter_shadows(w)
+            assert casts == ["refresh"]
+            K.weights_changed([(w.data_ptr(), w.data_ptr() + 4 * w.numel())])     # an optimiser node in the middle of the recording
+            K.filter_shadows(w)
+            assert casts == ["refresh", "refresh"]
+    capturing[0] = False
     del casts[:]
     K.filter_shadows(w)                                   # the recorded cast has not run
     K.filter_shadows(w)
