@@ -803,7 +803,8 @@ int pnp_filter_components(const uint8_t* vol, const int32_t* roots, int64_t D0, 
  * rounded up to 256.  Its first two uint32 are the labelling's and the size count's error counters (see above), the uint32 at byte 1 024
  * counts cavities without a contact and cavity voxels on a face (neither can happen); all are zeroed by the call and read by the caller.
  * Refused on the host before any HIP call: null pointers; an extent outside [1, 4096]; n >= 2^31; ncls outside [2, 8]; class_mask with bit 0
- * or a bit >= ncls; max_size < 0; a short workspace. */
+ * or a bit >= ncls; max_size < 0; a short workspace; a workspace address that is no multiple of 16 (the kernels read it in 16-byte loads and
+ * keep 64-bit sums in it); an out that is neither vol itself nor disjoint from vol's n bytes (a partial overlap). */
 size_t pnp_fill_holes_workspace_bytes(int64_t D0, int64_t D1, int64_t D2, int32_t ncls);
 int pnp_fill_holes(const uint8_t* vol, int64_t D0, int64_t D1, int64_t D2, int32_t ncls, uint32_t class_mask, int64_t max_size, uint8_t* out,
                    int64_t* stats, void* workspace, size_t workspace_bytes, void* stream);

@@ -626,6 +626,11 @@ int pnp_fill_holes(const uint8_t* vol, int64_t D0, int64_t D1, int64_t D2, int32
     PNP_REQUIRE((class_mask & 1u) == 0 && (class_mask >> ncls) == 0, "pnp_fill_holes: class_mask 0x%x selects class 0 or a class >= ncls = %d",
                 (unsigned)class_mask, (int)ncls);
     PNP_REQUIRE(max_size >= 0, "pnp_fill_holes: max_size %lld is negative", (long long)max_size);
+    // cc_count_kernel reads roots as int4 and FillHeader holds 64-bit atomics: every block starts at a multiple of 256 bytes from ws
+    PNP_REQUIRE((uintptr_t)ws % 16 == 0, "pnp_fill_holes: ws must be 16-byte aligned");
+    // fh_apply_kernel reads and writes a lane's own voxel only: out is vol itself or shares no byte with it
+    const uintptr_t v0 = (uintptr_t)vol, v1 = v0 + (uintptr_t)n, o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n;
+    PNP_REQUIRE(o0 == v0 || o1 <= v0 || v1 <= o0, "pnp_fill_holes: out overlaps vol");
     PNP_REQUIRE(ws_bytes >= fill_ws_bytes_of(n, (int)ncls), "pnp_fill_holes: workspace too small (%zu < %zu bytes)", ws_bytes,
                 fill_ws_bytes_of(n, (int)ncls));
     hipStream_t st = (hipStream_t)stream;

@@ -7,8 +7,8 @@ at index 0 or D - 1 of any axis; its contacts with class c are the pairs (v in t
 winner the class with the most contacts (ties: the lower class).  It is filled with its winner when the winner is in `classes` (None: all)
 and max_size == 0 or its size <= max_size.  out = the winner on filled cavities, 0 on all other background, vol elsewhere.  stats: row c
 >= 1 = cavities filled with c, voxels filled with c, largest cavity filled with c, cavities won by c and left; row 0 = cavities found,
-their voxels, cavities left, voxels left.  info: {"cavities", "ties", "multi", "root", "size", "winner", "filled"} for the tests' own
-assertions.  tests/test_holes_host.py pins the set of filled voxels to scipy.ndimage.binary_fill_holes.
+their voxels, cavities left, voxels left.  info: {"cavities", "ties", "multi", "root", "size", "winner", "filled", "contacts" (int64 [cavities, ncls])} for the
+tests' own assertions.  tests/test_holes_host.py pins the set of filled voxels to scipy.ndimage.binary_fill_holes.
 
 The background is labelled by components_ref.roots (the background as the one class of a 2-class volume, connectivity 1)."""
 import numpy as np
@@ -55,7 +55,8 @@ def fill_holes(vol, ncls, max_size=0, classes=None):
     stats[0] = len(root), size[root].sum(), int((~filled).sum()), size[root[~filled]].sum()
     best = cc[:, 1:].max(axis=1) if len(root) else np.zeros(0, np.int64)
     info = {"cavities": len(root), "ties": int(((cc[:, 1:] == best[:, None]).sum(axis=1) > 1).sum()),
-            "multi": int(((cc[:, 1:] > 0).sum(axis=1) > 1).sum()), "root": root, "size": size[root], "winner": winner, "filled": filled}
+            "multi": int(((cc[:, 1:] > 0).sum(axis=1) > 1).sum()), "root": root, "size": size[root], "winner": winner, "filled": filled,
+            "contacts": cc}
     return out.reshape(v.shape), stats, info
 
 

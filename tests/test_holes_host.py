@@ -82,8 +82,8 @@ def test_restatement_options(volumes):
 
 
 def _buffers():
-    buf = ctypes.create_string_buffer(1 << 16)
-    return buf, ctypes.c_void_p(ctypes.addressof(buf))
+    buf = ctypes.create_string_buffer((1 << 16) + 16)
+    return buf, ctypes.c_void_p((ctypes.addressof(buf) + 15) // 16 * 16)       # pnp_fill_holes wants a 16-byte aligned workspace
 
 
 def test_workspace_query(built):
